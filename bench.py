@@ -13,6 +13,13 @@ data-path collective is the SUM of the two ConClave score vectors (RCCL).
 torch.distributed.run child, before this process touches the GPU); under a
 launcher (RANK / WORLD_SIZE in the environment) it is one of the ranks.
 
+A plain run sets up, warms up, times --steps steps and prints the headline.
+Everything else it can measure or check (strong scaling at N > 1, the
+counter-enabled launches and the roofline, the oracle parity sample, the
+paired-end / whole-pipeline / C4 / default-mode / file-to-file legs, the CPU
+baselines) runs only with --full.  --dump-outputs DIR writes what the timed
+path computed in its last step as DIR/<name>.npy (see dump_outputs).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -57,6 +64,12 @@ def parse():
     ap.add_argument("--pe-pairs", type=int, default=10_000_000, help="pairs of the extra BASELINE config C3 legs (resident step and file to file); 0: skip")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: --reads per rank; strong: --reads in total, sharded over the ranks")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: strong scaling beside a weak "
+                    "N > 1 run, the counter-enabled launches and the roofline, and on one GPU the parity sample and the extra legs "
+                    "(--cpu-sample, --parity-sample, --no-cpu, --c4-*, --e2e-*, --pe-pairs apply only then)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs to DIR/<name>.npy (float32 / float64, a fixed "
+                         "seeded sample of the per-read arrays; rank 0's shard at N > 1)")
     return ap.parse_args()
 
 
@@ -671,6 +684,48 @@ def parity_sample(prefix, codes, got_scan, got_hits):
     return bool(ok)
 
 
+DUMP_SAMPLE_READS = 1 << 18
+DUMP_SEED = 20240607
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(path, dev, rc_flag, flag, T_off, T, n_hits, best, oflag, h_t, h_sc, h_s, h_e, aln, uniq):
+    """--dump-outputs: what the timed step hands its caller, as DIR/<name>.npy.  The per-read arrays at a fixed, seeded sample
+    of DUMP_SAMPLE_READS reads (ascending; `sample_read` holds their indices); of the CSR arrays the sampled reads' slices, in
+    read order: the candidates T[T_off[i], T_off[i+1]) and the hits' first n_hits[i] entries of that slice (the rest of it is
+    the path's scratch); the two ConClave score vectors whole.  int32 fields as float32 (exact: all below 2^24), int64 ones
+    (offsets, score sums) as float64.  About 53 MB at most when the sample holds no more than the 8 candidates per read the
+    step's T has room for on average; more than DUMP_MAX_BYTES in all is an error."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n = int(n_hits.numel())
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_SAMPLE_READS), replace=False))
+    it = torch.from_numpy(idx).to(dev)
+    off = T_off[it].cpu().numpy()
+    n_cand = (T_off[it + 1] - T_off[it]).cpu().numpy()
+    nh = n_hits[it].clamp(min=0).cpu().numpy().astype(np.int64)
+
+    def slices(starts, counts):
+        tot = int(counts.sum())
+        return np.repeat(starts, counts) + (np.arange(tot, dtype=np.int64) - np.repeat(np.cumsum(counts) - counts, counts))
+
+    ic = torch.from_numpy(slices(off, n_cand)).to(dev)
+    ih = torch.from_numpy(slices(off, nh)).to(dev)
+    arrays = {
+        "sample_read": (idx, np.float64), "T_off": (off, np.float64), "n_cand": (n_cand, np.float32),
+        "rc_flag": (rc_flag[it], np.float32), "flag": (flag[it], np.float32), "T": (T[ic], np.float32),
+        "n_hits": (n_hits[it], np.float32), "best_score": (best[it], np.float32), "out_flag": (oflag[it], np.float32),
+        "hit_tmpl": (h_t[ih], np.float32), "hit_score": (h_sc[ih], np.float32), "hit_start": (h_s[ih], np.float32),
+        "hit_end": (h_e[ih], np.float32), "alignment_scores": (aln, np.float64), "uniq_alignment_scores": (uniq, np.float64),
+    }
+    arrays = {name: (x.cpu().numpy() if isinstance(x, torch.Tensor) else x).astype(dt) for name, (x, dt) in arrays.items()}
+    size = sum(x.nbytes for x in arrays.values())
+    if size > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {size} bytes, more than {DUMP_MAX_BYTES}")
+    for name, x in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), x)
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "RANK" not in os.environ:
@@ -708,7 +763,7 @@ def main():
             from kma_amd.dist import shard_bounds
             lo, hi = shard_bounds(a.reads, rank, world)
             n = hi - lo
-        keep = min(n, a.cpu_sample) if rank == 0 else 0
+        keep = min(n, a.cpu_sample) if rank == 0 and a.full else 0
         rd = synth_dev.make_packed_reads(seqs, n, seed=1000 + rank, device=dev, keep_codes=keep,
                                          random_frac=0.02 if a.hard else 0.0, junk_frac=0.02 if a.hard else 0.0)
         rc_flag = torch.empty(n, dtype=torch.int32, device=dev)
@@ -749,18 +804,20 @@ def main():
         for _ in range(a.warmup):
             step()
         db.status(stream)
-        db.set_timing(True)
+        if a.full:
+            db.set_timing(True)           # per-kernel HIP events for the roofline
         fence()
         t0 = time.perf_counter()
         for _ in range(a.steps):
             step()
         fence()
         dt = time.perf_counter() - t0
-        scan_ms, scan_n = db.get_timing(0)
-        aln_ms, aln_n = db.get_timing(1)
-        pre_ms, pre_n = db.get_timing(2)
-        seed_ms, seed_n = db.get_timing(3)
-        db.set_timing(False)
+        if a.full:
+            scan_ms, scan_n = db.get_timing(0)
+            aln_ms, aln_n = db.get_timing(1)
+            pre_ms, pre_n = db.get_timing(2)
+            seed_ms, seed_n = db.get_timing(3)
+            db.set_timing(False)
         db.status(stream)
 
         def max_over_ranks(x):
@@ -770,9 +827,16 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             return float(t.item())
         dt = max_over_ranks(dt)
+        # the last timed step's outputs, before anything below launches into the same buffers
+        cand = int((T_off[1:] > T_off[:-1]).sum().item())
+        mapped = int((n_hits > 0).sum().item())
+        ties = int((n_hits < 0).sum().item())
+        total_T = int(T_off[-1].item())
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, dev, rc_flag, flag, T_off, T, n_hits, best, oflag, h_t, h_sc, h_s, h_e, aln, uniq)
         # strong scaling beside the weak figure: the same K steps on this rank's share of ONE batch of a.reads reads
         strong = None
-        if a.scaling == "weak" and world > 1:
+        if a.full and a.scaling == "weak" and world > 1:
             from kma_amd.dist import shard_bounds
             lo, hi = shard_bounds(a.reads, rank, world)
             m = hi - lo
@@ -786,56 +850,53 @@ def main():
             strong = {"reads_total": a.reads, "reads_per_gpu": m, "ms_per_step": dts / a.steps * 1e3, "value": a.reads * a.steps / dts,
                       "unit": "reads/s", "note": "same timed loop with the fixed batch sharded over the ranks (max over ranks)"}
 
-        # algorithmic work of one launch (separate, untimed, counter-enabled launches)
-        db.set_stats(True)
-        db.scan_se_dev(rd["seq"], rd["seq_off"], rd["length"], rd["N"], rd["N_off"], rc_flag, flag, T_off, T, stream=stream)
-        st = db.get_stats(stream)
-        db.align_se_dev(rd["seq"], rd["seq_off"], rd["length"], rd["N"], rd["N_off"], 150, rc_flag, flag, T_off, T,
-                        n_hits, best, oflag, h_t, h_sc, h_s, h_e, aln, uniq, stream=stream)
-        ast = db.get_align_stats(stream)
-        db.set_stats(False)
-        cand = int((T_off[1:] > T_off[:-1]).sum().item())
-        mapped = int((n_hits > 0).sum().item())
-        ties = int((n_hits < 0).sum().item())
-        total_T = int(T_off[-1].item())
-        W = (150 + 31) // 32
-        scan_s = scan_ms / 1e3 / max(1, scan_n)
-        aln_s = aln_ms / 1e3 / max(1, aln_n)
-        pre_s = pre_ms / 1e3 / max(1, pre_n)
-        seed_s = seed_ms / 1e3 / max(1, seed_n)
-        # SURVEY §8(d) algorithmic bytes.  scan: 12 B per probe (4 B directory + 4 B key + 4 B value index in the
-        # reference layout) + 2 B per value-list element + packed read in + S2 fields out.
-        # Stage 2 runs as two kernels: scan_prefilter_kernel (every k-th k-mer of both strands; reads in, active list
-        # out) and scan_se_kernel (all k-mer starts of the surviving strands; the rest of the bytes).
-        pre_bytes = 12 * st.prefilter_probes + n * (8 * W + 4 + 8) + 8 * st.active_strands
-        scan_bytes = (12 * (st.probes - st.prefilter_probes) + 2 * st.value_elems + st.active_strands * (8 * W + 4 + 8 + 8)
-                      + n * (4 + 4 + 8) + 4 * total_T)
-        # align: 12 B per position-index lookup (4 B index + 8 B template word), 2 bits per MEM base on both
-        # sequences, packed read in per task, 24 B out per task; DP cells move no HBM bytes (no E matrix)
-        # Stage 3a runs as seed_tasks_kernel (the MEM search: lookups + MEM bases + packed read in, 4 + 32 B handed over per
-        # task) and align_tasks_kernel (chain, stitch, DP: hand-over + packed read in, 24 B out per task)
-        seed_bytes = 12 * ast.lookups + ast.mem_bases // 2 + ast.tasks * (8 * W + 36)
-        aln_bytes = ast.tasks * (8 * W + 36 + 24) + n * 12
-        if aln_s >= scan_s:
-            dom = dict(kernel="align_tasks_kernel", kernel_ms=aln_s * 1e3, achieved=aln_bytes / aln_s / 1e9,
-                       algorithmic_bytes_per_launch=aln_bytes)
-        else:
-            dom = dict(kernel="scan_se_kernel", kernel_ms=scan_s * 1e3, achieved=scan_bytes / scan_s / 1e9,
-                       algorithmic_bytes_per_launch=scan_bytes)
+        if a.full:
+            # algorithmic work of one launch (separate, untimed, counter-enabled launches)
+            db.set_stats(True)
+            db.scan_se_dev(rd["seq"], rd["seq_off"], rd["length"], rd["N"], rd["N_off"], rc_flag, flag, T_off, T, stream=stream)
+            st = db.get_stats(stream)
+            db.align_se_dev(rd["seq"], rd["seq_off"], rd["length"], rd["N"], rd["N_off"], 150, rc_flag, flag, T_off, T,
+                            n_hits, best, oflag, h_t, h_sc, h_s, h_e, aln, uniq, stream=stream)
+            ast = db.get_align_stats(stream)
+            db.set_stats(False)
+            W = (150 + 31) // 32
+            scan_s = scan_ms / 1e3 / max(1, scan_n)
+            aln_s = aln_ms / 1e3 / max(1, aln_n)
+            pre_s = pre_ms / 1e3 / max(1, pre_n)
+            seed_s = seed_ms / 1e3 / max(1, seed_n)
+            # SURVEY §8(d) algorithmic bytes.  scan: 12 B per probe (4 B directory + 4 B key + 4 B value index in the
+            # reference layout) + 2 B per value-list element + packed read in + S2 fields out.
+            # Stage 2 runs as two kernels: scan_prefilter_kernel (every k-th k-mer of both strands; reads in, active list
+            # out) and scan_se_kernel (all k-mer starts of the surviving strands; the rest of the bytes).
+            pre_bytes = 12 * st.prefilter_probes + n * (8 * W + 4 + 8) + 8 * st.active_strands
+            scan_bytes = (12 * (st.probes - st.prefilter_probes) + 2 * st.value_elems + st.active_strands * (8 * W + 4 + 8 + 8)
+                          + n * (4 + 4 + 8) + 4 * total_T)
+            # align: 12 B per position-index lookup (4 B index + 8 B template word), 2 bits per MEM base on both
+            # sequences, packed read in per task, 24 B out per task; DP cells move no HBM bytes (no E matrix)
+            # Stage 3a runs as seed_tasks_kernel (the MEM search: lookups + MEM bases + packed read in, 4 + 32 B handed over per
+            # task) and align_tasks_kernel (chain, stitch, DP: hand-over + packed read in, 24 B out per task)
+            seed_bytes = 12 * ast.lookups + ast.mem_bases // 2 + ast.tasks * (8 * W + 36)
+            aln_bytes = ast.tasks * (8 * W + 36 + 24) + n * 12
+            if aln_s >= scan_s:
+                dom = dict(kernel="align_tasks_kernel", kernel_ms=aln_s * 1e3, achieved=aln_bytes / aln_s / 1e9,
+                           algorithmic_bytes_per_launch=aln_bytes)
+            else:
+                dom = dict(kernel="scan_se_kernel", kernel_ms=scan_s * 1e3, achieved=scan_bytes / scan_s / 1e9,
+                           algorithmic_bytes_per_launch=scan_bytes)
 
-        # HBM-side traffic of the dominant kernel: PMC counters cannot be read from inside this process; the committed rocprofv3
-        # --pmc summary of this same command supplies it -- but only while the kernel sources are the ones it was taken on
-        # (tools/collect_profiles.py stores their hash); a stale figure is dropped, not reported
-        traffic, traffic_src = None, None
-        for prof in ("r4_pmc_traffic.json", "r3_pmc_traffic.json", "r2_pmc_traffic.json", "r1_pmc_traffic.json"):
-            try:
-                pmc = json.load(open(os.path.join(ROOT, "profiles", prof)))
-                if dom["kernel"] in pmc and n == 10_000_000 and a.families == 1000 and pmc.get("_kernel_src_sha256") == kernel_src_sha():
-                    traffic = pmc[dom["kernel"]]["corrected_bytes"]
-                    traffic_src = f"profiles/{prof}: (2*FETCH_SIZE + WRITE_SIZE)*1024 per launch, separate --pmc passes, kernel sources {pmc['_kernel_src_sha256'][:12]}"
-                    break
-            except (OSError, ValueError, KeyError):
-                pass
+            # HBM-side traffic of the dominant kernel: PMC counters cannot be read from inside this process; the committed rocprofv3
+            # --pmc summary of this same command supplies it -- but only while the kernel sources are the ones it was taken on
+            # (tools/collect_profiles.py stores their hash); a stale figure is dropped, not reported
+            traffic, traffic_src = None, None
+            for prof in ("r4_pmc_traffic.json", "r3_pmc_traffic.json", "r2_pmc_traffic.json", "r1_pmc_traffic.json"):
+                try:
+                    pmc = json.load(open(os.path.join(ROOT, "profiles", prof)))
+                    if dom["kernel"] in pmc and n == 10_000_000 and a.families == 1000 and pmc.get("_kernel_src_sha256") == kernel_src_sha():
+                        traffic = pmc[dom["kernel"]]["corrected_bytes"]
+                        traffic_src = f"profiles/{prof}: (2*FETCH_SIZE + WRITE_SIZE)*1024 per launch, separate --pmc passes, kernel sources {pmc['_kernel_src_sha256'][:12]}"
+                        break
+                except (OSError, ValueError, KeyError):
+                    pass
 
         out = {
             "metric": "mapped reads/sec (whole node), 10M×150bp vs 5k-gene DB, 1/2/4/8 GPU",
@@ -860,7 +921,9 @@ def main():
                 "stage2_candidate_fraction": cand / n, "mapped_fraction": mapped / n, "strand_tie_reads": ties,
                 "align_tasks": total_T, "parallelism": f"read-shard x{world}",
             },
-            "roofline": {
+        }
+        if a.full:
+            out["roofline"] = {
                 "bound": "hbm", "achieved": dom["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": dom["achieved"] / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                 "achieved_kind": "effective: SURVEY 8(d) algorithmic bytes of the REFERENCE layout (12 B per resolved k-mer start, ...) / "
@@ -877,8 +940,7 @@ def main():
                 "align": {"kernel_ms": aln_s * 1e3, "lookups": int(ast.lookups), "dp_cells": int(ast.dp_cells),
                           "GCUPS": ast.dp_cells / aln_s / 1e9, "GB/s": aln_bytes / aln_s / 1e9,
                           "tasks_per_s": ast.tasks / aln_s},
-            },
-        }
+            }
         # what carried the step's one exchange, as the transport reports it (a SCALE line can be checked for "RCCL saw N ranks")
         comm = {"backend": "none", "nranks": 1}
         if world > 1:
@@ -894,7 +956,7 @@ def main():
                 dist.all_reduce(one)
                 comm["ranks_counted_by_allreduce"] = int(one.item())
         out["config"]["comm"] = comm
-        if rank == 0 and world == 1 and not a.no_cpu and keep:
+        if rank == 0 and world == 1 and a.full and not a.no_cpu and keep:
             codes = rd["codes"][:keep]
             k = min(a.parity_sample, keep)
             got = [x.cpu().numpy() for x in (rc_flag[:k], flag[:k], T_off[:k + 1])]

@@ -64,7 +64,7 @@ def test_bench_with_two_ranks_reports_two_gpus_and_both_scalings():
     e = dict(os.environ)
     e.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--reads", "400000",
-                        "--steps", "2", "--warmup", "1", "--no-cpu"], env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                        "--steps", "2", "--warmup", "1", "--no-cpu", "--full"], env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["value"] > 0

@@ -8,7 +8,7 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-python3 bench.py --steps 5 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --steps 5 --warmup 1 --full > $OUT/bench.json 2> $OUT/bench.err
 PCMD="python3 $REPO/bench.py --steps 3 --warmup 1 --no-cpu"
 echo "python3 bench.py --steps 3 --warmup 1 --no-cpu  (PMC passes: --steps 1 --warmup 0)" > $OUT/cmd.txt
 cd /tmp
