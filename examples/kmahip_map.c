@@ -120,24 +120,51 @@ typedef struct stream_job {
 	kmahip_ingest *ing; kmahip_read_batch b;
 	int state, rc; char err[512]; double t_done;
 	pthread_mutex_t mu; pthread_cond_t cv;
+	/* -s1dev: stage 1 on the device (kmahip_ingest_dev_*) for the files it covers; b_dev says where the batch handed over lives */
+	int s1dev, device, b_dev;
+	kmahip_ingest_dev *dev;
+	long long dev_records, dev_handed;
 } stream_job;
+/* the reader of one input file (or couple of mate files): the device reader where -s1dev asks for it and the file is one it covers
+ * (plain FASTQ; KMAHIP_EFORMAT from its open, before it touches the device, says it is not), the host reader otherwise */
+static int stream_open(stream_job *j, const char *p1, const char *p2) {
+	int whole = 0;
+	j->dev = NULL; j->ing = NULL;
+	if(j->s1dev && !(p2 && !p2[0])) {
+		int rc = kmahip_init(j->device);          /* (this thread's device; the main thread brings the runtime up at the same time) */
+		if(!rc) rc = kmahip_ingest_dev_open(p1, p2, &j->trim, &j->dev);
+		if(rc != KMAHIP_EFORMAT) return rc;
+		j->dev = NULL;
+	}
+	int rc = kmahip_ingest_open_part(p1, p2, &j->trim, 0, 1, &j->ing, &whole);
+	if(!rc && j->batch_bases > 0) rc = kmahip_ingest_set_batch_bases(j->ing, j->batch_bases);
+	return rc;
+}
+static void stream_close(stream_job *j) {
+	if(j->dev) {
+		int64_t rd = 0, kept = 0;
+		kmahip_ingest_dev_counts(j->dev, &rd, &kept);
+		j->dev_records += rd; j->dev_handed += kmahip_ingest_dev_handed_back(j->dev);
+		kmahip_ingest_dev_close(j->dev); j->dev = NULL;
+	}
+	if(j->ing) { kmahip_ingest_close(j->ing); j->ing = NULL; }
+}
 static void *stream_main(void *arg) {
 	stream_job *j = (stream_job *) arg;
-	int whole = 0, file = 0;
-	int rc = kmahip_ingest_open_part(j->in1, j->in2, &j->trim, 0, 1, &j->ing, &whole);
-	if(!rc && j->batch_bases > 0) rc = kmahip_ingest_set_batch_bases(j->ing, j->batch_bases);
+	int file = 0;
+	int rc = stream_open(j, j->in1, j->in2);
 	for(;;) {
-		if(!rc) rc = kmahip_ingest_next(j->ing, j->batch_reads, &j->b);
+		if(!rc) rc = j->dev ? kmahip_ingest_dev_next(j->dev, j->batch_reads, &j->b) : kmahip_ingest_next(j->ing, j->batch_reads, &j->b);
+		j->b_dev = j->dev != NULL;
 		if(!rc && j->rc_mates) rc_second_mates(&j->b);
 		int end = rc || j->b.reads.n_reads == 0;
-		if(end && !rc) rc = kmahip_ingest_status(j->ing);
+		if(end && !rc) rc = j->dev ? kmahip_ingest_dev_status(j->dev) : kmahip_ingest_status(j->ing);
 		if(end && !rc && file + 1 < j->n_files) {
 			/* the next file of the list (its own phred scale, like the reference's loop over the files; a batch never spans two files).
 			 * The batch handed over last has been given back (state 0), so nothing points into this reader any more */
 			++file;
-			kmahip_ingest_close(j->ing); j->ing = NULL;
-			rc = kmahip_ingest_open_part(j->list1[file], j->in2 ? (j->in2[0] ? j->list2[file] : "") : NULL, &j->trim, 0, 1, &j->ing, &whole);
-			if(!rc && j->batch_bases > 0) rc = kmahip_ingest_set_batch_bases(j->ing, j->batch_bases);
+			stream_close(j);
+			rc = stream_open(j, j->list1[file], j->in2 ? (j->in2[0] ? j->list2[file] : "") : NULL);
 			if(!rc) continue;
 			end = 1;
 		}
@@ -188,8 +215,10 @@ static void *xcalloc(size_t n, size_t sz) { void *p = calloc(n ? n : 1, sz); if(
 static void usage(void) {
 	fprintf(stderr, "usage: kmahip_map (-i reads.fq[.gz] | -ipe r1.fq[.gz] r2.fq[.gz] [-apm p|u] | -int interleaved.fq[.gz] [-apm p|u]) -t_db <index prefix> -o <output prefix> [-1t1] [-Mt1 <template>] [-bcNano] [-bc90] [-bc <support>] [-bcg] [-ref_fsa [n]] [-dense]\n"
 	                "       [-t threads] [-nc] [-na] [-nf] [-mf fragments] [-ml len] [-xl len] [-mp phred] [-mi phred] [-eq q] [-mq q] [-ts bases] [-mrs f] [-mrc f] [-mct f]\n"
-	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N]\n"
+	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev]\n"
 	                "       [-reward n] [-gapopen n] [-gapextend n] [-localopen n] [-Npenalty n] [-per n] [-transition n] [-transversion n] [-penalty n] [-cge]\n"
+	                "       (-s1dev, like -gpus not an option of kma: stage 1 of plain FASTQ input on the device; one rank, -1t1 only; its batches close at a quarter\n"
+	                "        of a gigabase of their own accord, KMAHIP_MAP_BATCH_BASES does not apply to them)\n"
 	                "(the options of kma 1.5.1 this path implements; -apm takes p or u; everything else is refused)\n");
 }
 
@@ -269,7 +298,7 @@ int main(int argc, char **argv) {
 	int cmp_mode = 0, lc = 0, mem_mode = 0;      /* -and / -oa, -lc, -mem_mode */
 	int pm = 0, fpm = 0;           /* -pm / -fpm (1 p, 2 u; 0: not given) */
 	char *list1[256], *list2[256]; int n_files = 0;          /* the input files (mate files side by side) */
-	int mt1 = 0, one2one = 0, chain = 0, apm = 0, no_cons = 0, no_frag = 0, no_aln = 0, gpus = 0, threads = 0, bcd = 1;
+	int mt1 = 0, one2one = 0, chain = 0, apm = 0, no_cons = 0, no_frag = 0, no_aln = 0, gpus = 0, threads = 0, bcd = 1, s1dev = 0;
 	int base_call = 0, sig_mode = 0, ref_fsa = 0, dense = 0;      /* as kmahip_assemble_opts.caller (0-2 here) / .sig90; printconsensus.c's ref_fsa */
 	double support = 0;
 	long long max_frag = 0;
@@ -371,6 +400,7 @@ int main(int argc, char **argv) {
 		else if(!strcmp(o, "-transversion")) Tv = -abs((int) need_int(argc, argv, &a, o));
 		else if(!strcmp(o, "-cge")) { par.scoreT = 0.5; cp.mrs = 0.5; par.rw.M = 1; par.rw.W1 = -5; par.rw.U = -1; par.rw.PE = 17; }      /* (its MM = -3 does not survive kma.c:1308) */
 		else if(!strcmp(o, "-gpus")) gpus = (int) need_int(argc, argv, &a, o);
+		else if(!strcmp(o, "-s1dev")) s1dev = 1;                                                /* (our own: kmahip_ingest_dev_* + kmahip_session_upload_dev) */
 		else { fprintf(stderr, "kmahip_map: option %s is not one this program implements\n", o); usage(); return 2; }
 	}
 	if(!prefix || !input || !out) { fprintf(stderr, "kmahip_map: -i (or -ipe / -int), -t_db and -o are required\n"); usage(); return 2; }
@@ -415,6 +445,12 @@ int main(int argc, char **argv) {
 	const char *reader2 = input2;
 	const int rc_mates = mt1 && input2;
 	if(mt1) input2 = NULL;
+	/* stage 1 on the device feeds the -1t1 sessions of one rank; everything else needs the batches' host arrays */
+	if(s1dev && (gpus > 1 || getenv("KMAHIP_RANK") || getenv("RANK") || chain || pe_chain || mt1 || getenv("KMAHIP_MAP_ONE_BATCH") ||
+	             (getenv("KMAHIP_COMM_FORCE_RCCL") && getenv("KMAHIP_COMM_FORCE_RCCL")[0] == '1'))) {
+		fprintf(stderr, "kmahip_map: -s1dev serves a single-rank -1t1 run (not -gpus N, the default mode without -1t1, or -Mt1)\n");
+		return 2;
+	}
 	if(threads) {
 		char v[16];
 		snprintf(v, sizeof v, "%d", threads);
@@ -470,6 +506,7 @@ int main(int argc, char **argv) {
 		memset(&sj, 0, sizeof sj);
 		sj.in1 = input; sj.in2 = reader2; sj.rc_mates = rc_mates; sj.trim = trim;
 		sj.list1 = list1; sj.list2 = list2; sj.n_files = n_files;
+		sj.s1dev = s1dev; sj.device = local;
 		sj.batch_reads = getenv("KMAHIP_MAP_BATCH") ? atoll(getenv("KMAHIP_MAP_BATCH")) : 1000000;
 		if(sj.batch_reads < 1) sj.batch_reads = 1;
 		sj.batch_bases = getenv("KMAHIP_MAP_BATCH_BASES") ? atoll(getenv("KMAHIP_MAP_BATCH_BASES")) : (256ll << 20);
@@ -512,7 +549,7 @@ int main(int argc, char **argv) {
 				int64_t c = 0;
 				if(!kmahip_chain_unpinned_reads(sj.b.reads.len, sj.b.reads.N, sj.b.reads.N_off, sj.b.reads.n_reads, (int) sinfo.kmersize, longest, &longest, &c)) unpinned += c;
 			}
-			if(kmahip_session_upload(ses, &sj.b)) die("upload");
+			if(sj.b_dev ? kmahip_session_upload_dev(ses, &sj.b) : kmahip_session_upload(ses, &sj.b)) die("upload");
 			pthread_mutex_lock(&sj.mu);
 			sj.state = 0;
 			pthread_cond_broadcast(&sj.cv);
@@ -526,6 +563,10 @@ int main(int argc, char **argv) {
 		double ms[8];
 		int64_t n_reads = 0, n_rows = 0;
 		if(kmahip_session_finish(ses, out, !no_cons, !no_frag, &n_reads, &n_rows, ms)) die("finish");
+		if(s1dev) {
+			stream_close(&sj);
+			fprintf(stderr, "# kmahip_map: stage 1 on the device: %lld input records, %lld bytes of input left to the host reader\n", sj.dev_records, sj.dev_handed);
+		}
 		if(unpinned) fprintf(stderr, "# kmahip_map: %lld reads carry an N among their first k - 1 bases behind a longer read: the reference's records for them depend on what its buffer held\n", (long long) unpinned);
 		fprintf(stderr, "# kmahip_map: %lld reads in %d batches, %lld fragment rows; wall: open %.2f s, ingest done after %.2f, mapped after %.2f, finish %.2f | uploads %.1f ms, stages 2+3a %.1f, "
 		        "ConClave %.1f, traceback %.1f, pile-up + consensus %.1f, .res + .fsa %.1f, .frag.gz %.1f (+ %.1f beside the batches) (main entered %.2f s after process start; peak RSS %.0f MB)\n", (long long) n_reads, batches,
@@ -538,7 +579,7 @@ int main(int argc, char **argv) {
 			const double t2 = now_s();
 			kmahip_db_close(db);
 			const double t3 = now_s();
-			kmahip_ingest_close(sj.ing);
+			stream_close(&sj);
 			const double t4 = now_s();
 			fprintf(stderr, "# kmahip_map: teardown: session %.3f s, workspace %.3f, index %.3f, reader %.3f\n", t1 - t0, t2 - t1, t3 - t2, t4 - t3);
 		}

@@ -522,6 +522,37 @@ int kmahip_ingest_phred_scale(const kmahip_ingest *in);
 void kmahip_ingest_counts(const kmahip_ingest *in, int64_t *records_read, int64_t *records_kept);
 void kmahip_ingest_close(kmahip_ingest *in);
 
+/* ---- stage 1 on the device: the same batches, born in HBM ------------------------------------------------------------
+ * A second reader for plain (uncompressed) FASTQ in regular files, single end or two mate files in lockstep: the host only
+ * reads file bytes into pinned buffers and copies them up; locating the records (FileBuffgetFq, seqparse.c:241-403), quality
+ * trimming and the length gate (phredStat runinput.c:127-313, run_input / run_input_PE :370-606) and the 2-bit packing
+ * (compDNA, compdna.c:99-127) are HIP kernels. Read for read its batches are those of kmahip_ingest_next on the same
+ * input; where a batch ends is the reader's own business (a batch never ends inside a couple). The first record that is
+ * not four well-formed lines ends the device's part: from there on -- and for the bytes behind the last complete record
+ * of the input -- the host reader above does the work inside this one, so odd files and "Malformed input." behave as ever.
+ * NOT covered: .gz, FASTA, interleaved input, byte-range parts. kmahip_ingest_dev_open refuses those with KMAHIP_EFORMAT
+ * (kmahip_last_error names the reason) before it makes any HIP call: take kmahip_ingest_open for them. */
+typedef struct kmahip_ingest_dev kmahip_ingest_dev;
+/* run_input / run_input_PE (runinput.c:370-606) over plain FASTQ; the device current at the call is the reader's */
+int kmahip_ingest_dev_open(const char *path1, const char *path2, const kmahip_trim *trim, kmahip_ingest_dev **out);
+/* up to max_records further S1 records (printFsa / printFsa_pair, runinput.c:765-830). batch->reads.*, names, name_off:
+ * DEVICE pointers; batch->pair: HOST; the scalar fields filled. All valid until the next call on the reader. */
+int kmahip_ingest_dev_next(kmahip_ingest_dev *in, int64_t max_records, kmahip_read_batch *batch);
+/* as kmahip_ingest_status ("Malformed input.", seqparse.c:256-260), kmahip_ingest_phred_scale (getPhredFileBuff,
+ * seqparse.c:551-589) and kmahip_ingest_counts */
+int kmahip_ingest_dev_status(kmahip_ingest_dev *in);
+int kmahip_ingest_dev_phred_scale(const kmahip_ingest_dev *in);
+void kmahip_ingest_dev_counts(const kmahip_ingest_dev *in, int64_t *records_read, int64_t *records_kept);
+/* bytes of input that were left to the host reader inside this one, from an odd record or the unfinished end of the input on
+ * (0: the device delivered every record itself) */
+int64_t kmahip_ingest_dev_handed_back(const kmahip_ingest_dev *in);
+/* where the device part's time went so far, ms: [0] reading the files into pinned memory, [1] waiting for the copies,
+ * [2] kernels, scans and the figures that come back; *bytes: input bytes copied up */
+void kmahip_ingest_dev_timing(const kmahip_ingest_dev *in, double ms[3], int64_t *bytes);
+/* for callers without a HIP runtime of their own (the Python binding): bytes of a batch's device arrays copied to host memory */
+int kmahip_ingest_dev_copy_out(void *host_dst, const void *dev_src, size_t bytes);
+void kmahip_ingest_dev_close(kmahip_ingest_dev *in);
+
 /* `.frag.gz` (updateFrags, assembly.c:49-83): one row per read that passed the stage-3c filter -- the read as aligned, the
  * number of equally good templates, score, start, end, template name (from <prefix>.name), read header -- in the order a
  * single-threaded assemble_KMA writes them: templates ascending, inside a template the pile-up order (see kmahip_assemble).
@@ -711,6 +742,11 @@ int kmahip_session_add(kmahip_session *s, const kmahip_read_batch *batch);
  * batch's host arrays are free again, _map runs stages 2 and 3a on what has been uploaded since the last call */
 int kmahip_session_upload(kmahip_session *s, const kmahip_read_batch *batch);
 int kmahip_session_map(kmahip_session *s);
+/* kmahip_session_upload for a batch that is on the device already (kmahip_ingest_dev_next: what the reference's stage 1 writes into
+ * its pipe, kmapipe.c:55-146, never leaves HBM): device-to-device placement behind the batches before it; the batch's arrays are free
+ * when it returns. For the `-1t1` single-end and paired sessions; KMAHIP_EINVAL for a session in the default mode or `-Mt1`, whose
+ * hosts need the host arrays. A failing call leaves the session as it was. */
+int kmahip_session_upload_dev(kmahip_session *s, const kmahip_read_batch *dev_batch);
 int kmahip_session_finish(kmahip_session *s, const char *out_prefix, int write_fsa, int write_frag, int64_t *n_reads, int64_t *n_rows, double ms[8]);
 void kmahip_session_close(kmahip_session *s);
 

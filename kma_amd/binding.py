@@ -219,6 +219,19 @@ def lib():
         L.kmahip_ingest_status.argtypes = [C.c_void_p]
         L.kmahip_ingest_set_batch_bases.argtypes = [C.c_void_p, C.c_int64]
         L.kmahip_ingest_close.restype = None
+        L.kmahip_ingest_dev_open.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Trim), C.POINTER(C.c_void_p)]
+        L.kmahip_ingest_dev_next.argtypes = [C.c_void_p, C.c_int64, C.POINTER(ReadBatchC)]
+        L.kmahip_ingest_dev_status.argtypes = [C.c_void_p]
+        L.kmahip_ingest_dev_phred_scale.argtypes = [C.c_void_p]
+        L.kmahip_ingest_dev_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.kmahip_ingest_dev_counts.restype = None
+        L.kmahip_ingest_dev_handed_back.argtypes = [C.c_void_p]
+        L.kmahip_ingest_dev_handed_back.restype = C.c_int64
+        L.kmahip_ingest_dev_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        L.kmahip_ingest_dev_timing.restype = None
+        L.kmahip_ingest_dev_copy_out.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.kmahip_ingest_dev_close.argtypes = [C.c_void_p]
+        L.kmahip_ingest_dev_close.restype = None
         _lib = L
     return _lib
 
@@ -306,6 +319,79 @@ class Ingest:
     def close(self):
         if self._h:
             lib().kmahip_ingest_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class IngestDev:
+    """Stage 1 on the device (kmahip_ingest_dev_*): plain FASTQ file(s) -> the batches of Ingest, made by HIP kernels and resident in HBM.
+    Inputs it does not cover (.gz, FASTA) raise KmaHipError from the constructor, before any HIP call: use Ingest for them."""
+
+    def __init__(self, path1, path2=None, min_phred=20, min_q=0, hardmask_q=0, min_len=16, max_len=2**31 - 1):
+        L = lib()
+        t = Trim(min_phred, min_q, hardmask_q, min_len, max_len)
+        self._h = C.c_void_p()
+        _check(L.kmahip_ingest_dev_open(os.fsencode(path1), os.fsencode(path2) if path2 else None, C.byref(t), C.byref(self._h)))
+
+    @property
+    def phred_scale(self):
+        return lib().kmahip_ingest_dev_phred_scale(self._h)
+
+    @property
+    def handed_back(self):
+        """bytes of input that were left to the host reader (0: the device delivered every record itself)"""
+        return int(lib().kmahip_ingest_dev_handed_back(self._h))
+
+    def counts(self):
+        a, b = C.c_int64(), C.c_int64()
+        lib().kmahip_ingest_dev_counts(self._h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def timing(self):
+        """-> (ms reading the files, ms waiting for the copies, ms kernels and scans, input bytes copied up)"""
+        ms, n = (C.c_double * 3)(), C.c_int64()
+        lib().kmahip_ingest_dev_timing(self._h, ms, C.byref(n))
+        return ms[0], ms[1], ms[2], n.value
+
+    def next_dev(self, max_records=1 << 20):
+        """the batch as the library hands it out (ReadBatchC with device pointers; valid until the next call), or None at the end"""
+        b = ReadBatchC()
+        _check(lib().kmahip_ingest_dev_next(self._h, max_records, C.byref(b)))
+        return b if b.reads.n_reads else None
+
+    def next(self, max_records=1 << 20):
+        """-> (ReadBatch, names list[bytes], pair u8[n]) as Ingest.next, the arrays copied back from the device; None at the end"""
+        from . import formats
+        b = self.next_dev(max_records)
+        if b is None:
+            return None
+        n = b.reads.n_reads
+
+        def arr(ptr, dt, m):
+            out = np.zeros(m, dt)
+            if m:
+                _check(lib().kmahip_ingest_dev_copy_out(out.ctypes.data_as(C.c_void_p), C.cast(ptr, C.c_void_p), out.nbytes))
+            return out
+        batch = formats.ReadBatch(seq=arr(b.reads.seq, np.uint64, b.reads.seq_words), seq_off=arr(b.reads.seq_off, np.int64, n + 1),
+                                  length=arr(b.reads.len, np.int32, n), N=arr(b.reads.N, np.int32, max(1, b.reads.N_total)),
+                                  N_off=arr(b.reads.N_off, np.int64, n + 1))
+        noff = arr(b.name_off, np.int64, n + 1)
+        raw = arr(b.names, np.uint8, int(noff[-1])).tobytes()
+        names = [raw[noff[i]:noff[i + 1] - 1] for i in range(n)]
+        pair = np.ctypeslib.as_array(C.cast(b.pair, C.POINTER(C.c_uint8)), shape=(n,)).copy()
+        return batch, names, pair
+
+    def status(self):
+        _check(lib().kmahip_ingest_dev_status(self._h))
+
+    def close(self):
+        if self._h:
+            lib().kmahip_ingest_dev_close(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):

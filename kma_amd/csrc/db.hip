@@ -1,6 +1,7 @@
 // db.hip -- host side of libkmahip: reads the reference's on-disk index
 // (<prefix>.comp.b/.length.b/.seq.b; written by `kma index`,
 // hashmapkma.c:722-775) and lays the database out in HBM for the gfx950 kernels.
+#include <atomic>
 #include "kmahip_internal.h"
 #include <cstdarg>
 #include <cstdio>
@@ -40,7 +41,7 @@ extern "C" void kmahip_default_params(kmahip_params *p) {
 	p->scoreT = 0.5; p->mrc = 0.0; p->minFrac = 1.0; p->ts = 0; p->apm = 0;
 }
 
-static int g_device = 0;
+static std::atomic<int> g_device{0};          // (kmahip_init may be called by several threads, each for its own current device)
 
 extern "C" int kmahip_init(int device) {
 	int n = 0;

@@ -1011,6 +1011,30 @@ static int ingest_open_impl(const char *path1, const char *path2, bool interleav
 	return KMAHIP_OK;
 }
 
+// For the device reader (ingest_dev.hip), not part of the C ABI: the one copy of the phred-scale guess, the to2Bit table (256 codes)
+// and the 10^(-q/10) table (256 doubles, indexed by the quality itself) that both readers use
+int kmahip_ingest_guess_phred(const uint8_t *buff, size_t bytes) { return guess_phred(buff, bytes); }
+const uint8_t *kmahip_ingest_to2bit() { return g_trans.t; }
+const double *kmahip_ingest_prob() { return g_prob.p; }
+
+// For the device reader (ingest_dev.hip), not part of the C ABI: this reader over plain regular FASTQ files from given byte offsets
+// on -- each the start of a record, or the end of its file -- with the phred scale the caller guessed from the files' first bytes
+// and the counts of the records before the offsets. What follows is what kmahip_ingest_next makes of the rest of the input.
+int kmahip_ingest_open_at(const char *path1, size_t off1, const char *path2, size_t off2, const kmahip_trim *trim, int phred,
+                          int64_t n_read, int64_t n_kept, kmahip_ingest **out) {
+	const int rc = ingest_open_impl(path1, path2, false, trim, out);
+	if(rc) return rc;
+	kmahip_ingest *in = *out;
+	const size_t off[2] = {off1, off2};
+	for(int i = 0; i < (path2 ? 2 : 1); ++i) {
+		Chunk *w = in->fastq ? in->m[i].feed.whole : nullptr;
+		if(!w || (w->hi && !w->mapped)) { kmahip_ingest_close(in); *out = nullptr; kmahip_set_error("%s is not a plain regular FASTQ file", i ? path2 : path1); return KMAHIP_EFORMAT; }
+		w->lo = std::min(off[i], w->hi);
+	}
+	in->phred = phred; in->n_read = n_read; in->n_kept = n_kept;
+	return KMAHIP_OK;
+}
+
 // One rank's part of the input (see kmahip.h). Plain single-end FASTQ: the mapped file is cut at record starts -- the guess of
 // fill_wave's regions, taken from the byte part * size / parts onwards, the same on every rank -- and the reader is given
 // [start of this part, start of the next); everything else is delivered whole for the caller to slice by record number.

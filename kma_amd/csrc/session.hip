@@ -384,6 +384,56 @@ extern "C" int kmahip_session_upload(kmahip_session *S, const kmahip_read_batch 
 	return KMAHIP_OK;
 }
 
+// kmahip_session_upload for a batch that was born on the device (kmahip_ingest_dev_next; the reference's stage 1 hands its records
+// to stage 2 through a pipe, kmapipe.c:55-146): its arrays are copied device to device behind the batches before them, the offsets
+// moved like there. Nothing of the session changes before the device work has succeeded (the mate flags come last).
+extern "C" int kmahip_session_upload_dev(kmahip_session *S, const kmahip_read_batch *batch) {
+	if(!S || !batch) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(S->chain || S->mt1) { kmahip_set_error("kmahip_session_upload_dev serves the -1t1 sessions only: the default mode and -Mt1 need the batch's host arrays"); return KMAHIP_EINVAL; }
+	const kmahip_reads &R = batch->reads;
+	const int64_t nb = R.n_reads;
+	if(nb < 0 || R.seq_words < 0 || R.N_total < 0) { kmahip_set_error("negative size"); return KMAHIP_EINVAL; }
+	if(nb == 0) return KMAHIP_OK;
+	if(!batch->names || !batch->name_off) { kmahip_set_error("the batch carries no read names"); return KMAHIP_EINVAL; }
+	if(S->pe) {
+		if(!batch->pair) { kmahip_set_error("a paired session needs the batch's mate flags"); return KMAHIP_EINVAL; }
+		if(batch->pair[nb - 1] == 1) { kmahip_set_error("a batch of a paired session ends inside a couple"); return KMAHIP_EINVAL; }
+	}
+	hipStream_t s = 0;
+	auto t = std::chrono::steady_clock::now();
+	int rc;
+	int64_t nbytes = 0;
+	HIP_TRY(hipMemcpy(&nbytes, batch->name_off + nb, 8, hipMemcpyDeviceToHost));
+	if(nbytes < 0) { kmahip_set_error("negative size"); return KMAHIP_EINVAL; }
+	if((rc = S->seq.ensure((size_t) (S->words + R.seq_words + 2) * 8, (size_t) S->words * 8, s)) || (rc = S->seq_off.ensure((size_t) (S->n + nb + 1) * 8, (size_t) (S->n + 1) * 8, s)) ||
+	   (rc = S->len.ensure((size_t) (S->n + nb + 1) * 4, (size_t) S->n * 4, s)) || (rc = S->N.ensure((size_t) (S->nN + R.N_total + 1) * 4, (size_t) S->nN * 4, s)) ||
+	   (rc = S->N_off.ensure((size_t) (S->n + nb + 1) * 8, (size_t) (S->n + 1) * 8, s)) || (rc = S->names.ensure((size_t) (S->name_bytes + nbytes + 1), (size_t) S->name_bytes, s)) ||
+	   (rc = S->name_off.ensure((size_t) (S->n + nb + 1) * 8, (size_t) (S->n + 1) * 8, s))) return rc;
+	const hipMemcpyKind DD = hipMemcpyDeviceToDevice;
+	if(R.seq_words) HIP_TRY(hipMemcpyAsync(S->seq.as<uint64_t>() + S->words, R.seq, (size_t) R.seq_words * 8, DD, s));
+	HIP_TRY(hipMemsetAsync(S->seq.as<uint64_t>() + S->words + R.seq_words, 0, 16, s));
+	HIP_TRY(hipMemcpyAsync(S->len.as<int32_t>() + S->n, R.len, (size_t) nb * 4, DD, s));
+	if(R.N_total) HIP_TRY(hipMemcpyAsync(S->N.as<int32_t>() + S->nN, R.N, (size_t) R.N_total * 4, DD, s));
+	if(nbytes) HIP_TRY(hipMemcpyAsync(S->names.as<char>() + S->name_bytes, batch->names, (size_t) nbytes, DD, s));
+	HIP_TRY(hipMemcpyAsync(S->seq_off.as<int64_t>() + S->n, R.seq_off, (size_t) (nb + 1) * 8, DD, s));
+	HIP_TRY(hipMemcpyAsync(S->N_off.as<int64_t>() + S->n, R.N_off, (size_t) (nb + 1) * 8, DD, s));
+	HIP_TRY(hipMemcpyAsync(S->name_off.as<int64_t>() + S->n, batch->name_off, (size_t) (nb + 1) * 8, DD, s));
+	const unsigned g1 = (unsigned) ((nb + 1 + 255) / 256);
+	if(S->words) hipLaunchKernelGGL(add_off_kernel, dim3(g1), dim3(256), 0, s, nb + 1, S->seq_off.as<int64_t>() + S->n, S->words);
+	if(S->nN) hipLaunchKernelGGL(add_off_kernel, dim3(g1), dim3(256), 0, s, nb + 1, S->N_off.as<int64_t>() + S->n, S->nN);
+	if(S->name_bytes) hipLaunchKernelGGL(add_off_kernel, dim3(g1), dim3(256), 0, s, nb + 1, S->name_off.as<int64_t>() + S->n, S->name_bytes);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(s));          // (the reader's arrays are its own again)
+	S->ms_upload += since(t);
+	if(S->pe) S->pair.insert(S->pair.end(), batch->pair, batch->pair + nb);
+	Batch U;
+	U.r0 = S->n; U.n = nb; U.max_len = R.max_len; U.words = R.seq_words;
+	S->uploaded.push_back(std::move(U));
+	S->n += nb; S->n_reads += nb; S->words += R.seq_words; S->nN += R.N_total; S->name_bytes += nbytes;
+	S->max_len = std::max(S->max_len, R.max_len);
+	return KMAHIP_OK;
+}
+
 static int session_map_one(kmahip_session *S, Batch &B);
 static int session_warm_pe(kmahip_session *S, Batch &B);
 
