@@ -579,6 +579,11 @@ int kmahip_frag_write3(const char *path, kmahip_db *db, const kmahip_reads *read
  * and concatenate the members (RFC 1952 2.2). Exposed for tests. */
 int kmahip_gzip_member(const void *src, int64_t n, void *dst, int64_t cap, int64_t *out_bytes);
 
+/* The mapping quality the stage-3 kernels gate on with -mq (chainSeeds, chain.c:79-260: ceil(40 (1 - second / best) min(1, w / 10)
+ * log(best)) in double, 0 for best <= 0), evaluated ON THE DEVICE by the one function all of those kernels call, for n triples in HOST
+ * arrays. Exposed for tests: the device's log against the libm the reference links. */
+int kmahip_test_mapq(const int32_t *best, const int32_t *second, const int32_t *w, int64_t n, uint32_t *out);
+
 /* The single-end run in KMA's DEFAULT mode (no -1t1) on one batch: kmahip_scan_chain, then every S2 record -- a read, or its
  * reverse complement where the record prints that, with its query bounds -- goes through stage 3a, ConClave, the `.res`
  * statistics, the traceback and the pile-up like a read of kmahip_run_se (runKMA, runkma.c:104-900 with kmerScan =

@@ -254,6 +254,18 @@ def cigar_from_runs(runs, clip_start=0, clip_end=0):
     return "".join(out)
 
 
+def test_mapq(best, second, w):
+    """kmahip_test_mapq (a test hook): the device's mapQ function on arrays of (best, second, w) -> uint32 array"""
+    b, s, ww = (np.ascontiguousarray(x, np.int32) for x in (best, second, w))
+    assert b.shape == s.shape == ww.shape and b.ndim == 1
+    out = np.zeros(len(b), np.uint32)
+    L = lib()
+    L.kmahip_test_mapq.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.kmahip_test_mapq.restype = C.c_int
+    _check(L.kmahip_test_mapq(_p(b), _p(s), _p(ww), len(b), _p(out)))
+    return out
+
+
 def index_build(fasta_paths, out_prefix, k=16):
     """kmahip_index_build: the four index files from FASTA file(s) (needs a GPU: the k-mers are sorted on the device)"""
     paths = [os.fsencode(p) for p in ([fasta_paths] if isinstance(fasta_paths, (str, bytes)) else fasta_paths)]

@@ -828,10 +828,7 @@ __device__ int chain_seeds(const Lane &L, int n, int q_len, int t_len, int k, un
 			second = best;
 		}
 	}
-	if(0 < best) {
-		const double wq = fmin(1.0, MEMA(L, 4, bestPos) / 10.0);
-		*mapQ = (unsigned) ceil(40 * (1 - 1.0 * second / best) * wq * log((double) best));
-	} else *mapQ = 0;
+	*mapQ = 0 < best ? kma_mapq(best, second, MEMA(L, 4, bestPos)) : 0;
 	MEMA(L, 5, bestPos) = best;
 	return bestPos;
 }
@@ -1576,10 +1573,7 @@ __device__ __forceinline__ Aln kma_score_fast(FastCtx &C, const Lane &L, const u
 		}
 	}
 	unsigned mapQ = 0;
-	if(0 < best) {
-		const double wq = fmin(1.0, sel4(wt, bestPos) / 10.0);
-		mapQ = (unsigned) ceil(40 * (1 - 1.0 * second / best) * wq * log((double) best));
-	}
+	if(0 < best) mapQ = kma_mapq(best, second, sel4(wt, bestPos));
 	if(mapQ < (unsigned) mq || best < k) return FAIL;
 
 	// the chain from its best start: the MEM in hand in scalars (the reference's write-backs of a clipped start, align.c:694-711, are
@@ -3024,6 +3018,32 @@ extern "C" int kmahip_diag_hist(unsigned long long *out256, int reset) {
 	return 0;
 }
 #endif
+
+// test hook: kma_mapq -- the function every mapQ gate of align.hip and longtrace.hip calls -- over host arrays of triples
+static __global__ void test_mapq_kernel(const int32_t *best, const int32_t *second, const int32_t *w, int64_t n, uint32_t *out) {
+	for(int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t) gridDim.x * blockDim.x)
+		out[i] = kma_mapq(best[i], second[i], w[i]);
+}
+
+extern "C" int kmahip_test_mapq(const int32_t *best, const int32_t *second, const int32_t *w, int64_t n, uint32_t *out) {
+	if(n < 0 || (n && (!best || !second || !w || !out))) { kmahip_set_error("kmahip_test_mapq: bad argument"); return KMAHIP_EINVAL; }
+	if(!n) return KMAHIP_OK;
+	int32_t *d = nullptr;
+	if(hipMalloc((void **) &d, (size_t) n * 16) != hipSuccess) { kmahip_set_error("kmahip_test_mapq: %lld triples do not fit", (long long) n); return KMAHIP_ENOMEM; }
+	hipError_t e = hipMemcpy(d, best, (size_t) n * 4, hipMemcpyHostToDevice);
+	if(e == hipSuccess) e = hipMemcpy(d + n, second, (size_t) n * 4, hipMemcpyHostToDevice);
+	if(e == hipSuccess) e = hipMemcpy(d + 2 * n, w, (size_t) n * 4, hipMemcpyHostToDevice);
+	if(e == hipSuccess) {
+		const int64_t blocks = (n + 255) / 256;
+		const unsigned grid = (unsigned) (blocks < 65536 ? blocks : 65536);
+		hipLaunchKernelGGL(test_mapq_kernel, dim3(grid), dim3(256), 0, 0, d, d + n, d + 2 * n, n, (uint32_t *) (d + 3 * n));
+		e = hipGetLastError();
+	}
+	if(e == hipSuccess) e = hipMemcpy(out, d + 3 * n, (size_t) n * 4, hipMemcpyDeviceToHost);
+	(void) hipFree(d);
+	if(e != hipSuccess) { kmahip_set_error("kmahip_test_mapq: %s", hipGetErrorString(e)); return KMAHIP_EDEVICE; }
+	return KMAHIP_OK;
+}
 
 int kmahip_launch_align_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads, const kmahip_cands *cands,
                            const kmahip_params *p, kmahip_hits *out, hipStream_t stream) {

@@ -162,5 +162,15 @@ __device__ __forceinline__ int mism_score(int span, int k, int M, int MM) {
 	return Ms * M + MMs * MM;
 }
 
+// mapping quality of the best chain (chainSeeds, chain.c:79-260; oracle/align.c:406): best / second = the two best chain scores,
+// w = the bases the best chain's MEMs cover. The one copy of the expression: its order of operations is the reference's. For best
+// <= 2048 and w <= 10 every product that is no exact integer lies more than 4 ulp from one, so log's last bits do not matter there;
+// beyond that (best up to 2^21, sampled) the device and the host libm were only found equal on the points tried.
+__device__ __forceinline__ unsigned kma_mapq(int best, int second, int w) {
+	if(best <= 0) return 0;
+	const double wq = fmin(1.0, w / 10.0);
+	return (unsigned) ceil(40 * (1 - 1.0 * second / best) * wq * log((double) best));
+}
+
 
 } // namespace

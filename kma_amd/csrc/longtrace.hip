@@ -490,10 +490,7 @@ __device__ int lt_chain(const LtArgs &A, SeedLds &S, const MemArr &Mm, int base,
 			second = best;
 		}
 	}
-	if(0 < best) {
-		const double wq = fmin(1.0, bestW / 10.0);
-		*mapQ = (unsigned) ceil(40 * (1 - 1.0 * second / best) * wq * log((double) best));
-	} else *mapQ = 0;
+	*mapQ = 0 < best ? kma_mapq(best, second, bestW) : 0;
 	*bestScore = best;
 	return bestPos;
 }

@@ -349,6 +349,20 @@ static int mism_score(int span, int k, const orc_rewards *rw) {
 	return Ms * rw->M + MMs * rw->MM;
 }
 
+/* the mapping quality chainSeeds leaves behind (chain.c:79-260): best / second = the two best chain scores, w = bases covered by the
+ * MEMs of the best chain. Against the host libm, like the reference. */
+unsigned orc_mapq(int best, int second, int w) {
+	if(0 < best) {
+		double wq = w / 10.0; if(1 < wq) wq = 1;
+		return (unsigned) ceil(40 * (1 - 1.0 * second / best) * wq * log(best));
+	}
+	return 0;
+}
+
+void orc_mapq_batch(const int32_t *best, const int32_t *second, const int32_t *w, int64_t n, uint32_t *out) {
+	for(int64_t i = 0; i < n; ++i) out[i] = orc_mapq(best[i], second[i], w[i]);
+}
+
 static int chain_seeds(aws *w, int q_len, int t_len, int k, const orc_rewards *rw, unsigned *mapQ) {
 	const int W1 = rw->W1, U = rw->U, M = rw->M;
 	const int n = w->plen;
@@ -401,10 +415,7 @@ static int chain_seeds(aws *w, int q_len, int t_len, int k, const orc_rewards *r
 			second = best;
 		}
 	}
-	if(0 < best) {
-		double wq = w->w[bestPos] / 10.0; if(1 < wq) wq = 1;
-		*mapQ = (unsigned) ceil(40 * (1 - 1.0 * second / best) * wq * log(best));
-	} else *mapQ = 0;
+	*mapQ = orc_mapq(best, second, w->w[bestPos]);
 	w->sc[bestPos] = best;
 	return bestPos;
 }

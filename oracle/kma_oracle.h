@@ -138,6 +138,9 @@ int orc_align_trace(orc_aligner *a, const orc_rewards *rw, const orc_align_param
 /* the `-Mt1 t` form of the same: raw read, strand picked by anker_rc (align.c:780-991). See align.c. */
 int orc_align_trace_mt1(orc_aligner *a, const orc_rewards *rw, const orc_align_params *ap, uint8_t *read, int q_len, int t,
                         int one2one, int exhaustive, int *stats, char *cols, int cap, int *is_rc);
+/* mapQ of a read's best chain (chainSeeds): ceil(40 (1 - second / best) min(1, w / 10) log(best)), 0 for best <= 0 */
+unsigned orc_mapq(int best, int second, int w);
+void orc_mapq_batch(const int32_t *best, const int32_t *second, const int32_t *w, int64_t n, uint32_t *out);
 void orc_nw_tap(const uint64_t *tseq, int tlen_total, const uint8_t *q, int k, int t_s, int t_e, int q_s, int q_e,
                 int band, const orc_rewards *rw, int out[6]);
 

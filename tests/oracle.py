@@ -219,6 +219,18 @@ def conclave(n_hits, read_score, q_len, q_len2, off, tmpl, start, end, alignment
     return out
 
 
+def mapq(best, second, w):
+    """orc_mapq (oracle/align.c: the expression chain_seeds evaluates, against the host libm) on arrays -> uint32 array"""
+    b, s, ww = (np.ascontiguousarray(x, np.int32) for x in (best, second, w))
+    assert b.shape == s.shape == ww.shape and b.ndim == 1
+    out = np.zeros(len(b), np.uint32)
+    L = lib()
+    L.orc_mapq_batch.restype = None
+    L.orc_mapq_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.orc_mapq_batch(_p(b), _p(s), _p(ww), len(b), _p(out))
+    return out
+
+
 def res_stats(w_scores, tlen, evalue=0.05, scoreT=0.5):
     """-> dict(expected (as printed), q_value, p_value, significant) per template (runkma.c:765-783)."""
     D = len(tlen)

@@ -44,17 +44,17 @@ def codes_of(words, seqlen, N):
     return c
 
 
-def oracle_pe_lines(g):
+def oracle_pe_lines(g, minlen=16, mq=0, scoreT=0.5, mrc=0.0):
     import oracle
     db = oracle.OracleDB(g["prefix"])
-    al = oracle.OracleAligner(db)
+    al = oracle.OracleAligner(db, minlen=minlen, mq=mq, scoreT=scoreT, mrc=mrc)
     exp, kinds = [], collections.Counter()
 
     def se_record(r, rc, rc_flag, flag, T):
         words, N = emitted(r, rc)
         b = formats.pack_ragged([codes_of(words, r["seqlen"], N)])
         res = db.align_se(b, np.array([rc_flag], np.int32), np.array([flag & ~16], np.int32),
-                          np.array([0, len(T)], np.int64), np.asarray(T, np.int32))
+                          np.array([0, len(T)], np.int64), np.asarray(T, np.int32), minlen=minlen, mq=mq, scoreT=scoreT, mrc=mrc)
         nh = int(res["n_hits"][0])
         if nh > 0:
             exp.append((r["hdr"].rstrip(b"\0").decode(), nh, int(res["best_score"][0]), res["start"][:nh].tolist(),
@@ -95,12 +95,12 @@ def oracle_pe_lines(g):
     return exp, kinds
 
 
-def oracle_pe_conclave_records(g):
+def oracle_pe_conclave_records(g, minlen=16, mq=0, scoreT=0.5, mrc=0.0):
     """The frag_raw records of the paired run as ConClave input arrays: one record per proper pair (score negated,
     updatescores.c:470-488), one per singly written read; plus the two ConClave score vectors."""
     import oracle
     db = oracle.OracleDB(g["prefix"])
-    al = oracle.OracleAligner(db)
+    al = oracle.OracleAligner(db, minlen=minlen, mq=mq, scoreT=scoreT, mrc=mrc)
     rec = []        # (n_hits, signed score, q_len, q_len2, tmpl, start, end)
     vec = [np.zeros(len(al.alignment_scores), np.uint64), np.zeros(len(al.alignment_scores), np.uint64)]
 
@@ -108,7 +108,7 @@ def oracle_pe_conclave_records(g):
         words, N = emitted(r, rc)
         b = formats.pack_ragged([codes_of(words, r["seqlen"], N)])
         res = db.align_se(b, np.array([rc_flag], np.int32), np.array([flag & ~16], np.int32),
-                          np.array([0, len(T)], np.int64), np.asarray(T, np.int32))
+                          np.array([0, len(T)], np.int64), np.asarray(T, np.int32), minlen=minlen, mq=mq, scoreT=scoreT, mrc=mrc)
         vec[0] += res["alignment_scores"]; vec[1] += res["uniq_alignment_scores"]
         nh = int(res["n_hits"][0])
         if nh > 0:
@@ -154,9 +154,10 @@ def oracle_pe_conclave_records(g):
                 alignment_scores=vec[0], uniq_alignment_scores=vec[1])
 
 
-def hip_pe_conclave(db, g):
+def hip_pe_conclave(db, g, records_only=False):
     """Stages 2 + 3a on the device for the pairs (map_pe) and the singly emitted reads (map_se) of a paired fixture, the two
-    results merged into frag_raw records in stream order, then stage 3b over them (KmaHipDB.conclave_records)."""
+    results merged into frag_raw records in stream order, then stage 3b over them (KmaHipDB.conclave_records).
+    records_only: stop before stage 3b and return the records in the form of oracle_pe_conclave_records"""
     codes = lambda r: codes_of(r["seq"], r["seqlen"], r["N"])
     pairs = [u for u in g["units"] if u[0] == "pe"]
     singles = [u for u in g["units"] if u[0] == "se"]
@@ -168,7 +169,9 @@ def hip_pe_conclave(db, g):
     sj = {u[1]: j for j, u in enumerate(singles)}
     rec, frags = [], []      # frags[k] = fragments of record k in record order: (index into g["s1"], stage-3a flag, rc)
 
-    def add(n, score, ql, ql2, src, o, fr):
+    def add(n, score, ql, ql2, src, o, fr, keep_empty=True):
+        if records_only and n == 0 and not keep_empty:      # oracle_pe_conclave_records lists a record without a hit only for a proper pair
+            return
         rec.append((n, score, ql, ql2, src["tmpl"][o:o + n].tolist(), src["start"][o:o + n].tolist(), src["end"][o:o + n].tolist()))
         frags.append(fr)
 
@@ -190,11 +193,11 @@ def hip_pe_conclave(db, g):
                 [fg(r1), fg(r0)] if swapped else [fg(r0), fg(r1)])
         elif kind == 2:
             n0, n1 = int(h["n_hits"][r0]), int(h["n_hits"][r1])
-            add(n0, int(h["best_score"][r0]), ln(r0), 0, h, o, [fg(r0)])
-            add(n1, int(h["best_score"][r1]), ln(r1), 0, h, o + n0, [fg(r1)])
+            add(n0, int(h["best_score"][r0]), ln(r0), 0, h, o, [fg(r0)], False)
+            add(n1, int(h["best_score"][r1]), ln(r1), 0, h, o + n0, [fg(r1)], False)
         elif kind in (3, 4):
             x = r0 if kind == 3 else r1
-            add(int(h["n_hits"][x]), int(h["best_score"][x]), ln(x), 0, h, o, [fg(x)])
+            add(int(h["n_hits"][x]), int(h["best_score"][x]), ln(x), 0, h, o, [fg(x)], False)
         else:
             for x in (r0, r1):
                 if mate[x] >= 0 and h["n_hits"][x] > 0:
@@ -204,6 +207,9 @@ def hip_pe_conclave(db, g):
     col = lambda i: np.array([r[i] for r in rec], np.int32)
     AS = h["alignment_scores"] + sh["alignment_scores"]
     US = h["uniq_alignment_scores"] + sh["uniq_alignment_scores"]
+    if records_only:
+        return dict(n_hits=col(0), score=col(1), q_len=col(2), q_len2=col(3), off=off[:-1], tmpl=flat(4), start=flat(5), end=flat(6),
+                    alignment_scores=AS, uniq_alignment_scores=US)
     out = db.conclave_records(col(0), col(1), col(2), col(3), off, flat(4), flat(5), flat(6), AS, US)
     # the slot form on the pairs alone must agree with the records form over the same pairs
     vec = dict(h); vec["alignment_scores"], vec["uniq_alignment_scores"] = AS, US

@@ -199,12 +199,8 @@ def _with_env(env, fn):
                 os.environ[k] = v
 
 
-@pytest.mark.parametrize("kind", ["genome", "genes"])
-def test_long_read_route_equals_lane_kernel_and_oracle(tmp_path, kind):
-    """stage 2 of long reads: chain_long_anchor_kernel (a wavefront per read and strand) + chain_long_tail_kernel against chain_kernel
-    (KMAHIP_CHAIN=slow: a lane per read, anchors included) and the oracle -- lengths on either side of the fast route's limit and of
-    the kernel's passes of 512 k-mer starts, reads shorter than k, unrelated reads, exact copies (one anchor spanning every pass), reads
-    glued from pieces of both strands, exhaustive mode, and the pool cut into many chunks"""
+def long_route_set(kind):
+    """database and reads of test_long_read_route_equals_lane_kernel_and_oracle (tests/test_thresholds_gpu.py runs them off the defaults)"""
     rng = np.random.default_rng(11)
     if kind == "genome":
         genome = rng.integers(0, 4, 300_000, dtype=np.uint8)
@@ -212,8 +208,6 @@ def test_long_read_route_equals_lane_kernel_and_oracle(tmp_path, kind):
     else:
         names, seqs = synth.make_gene_db(40, 6, 800, 3000, 0.03, seed=77)
         genome = np.concatenate(seqs)
-    prefix = str(tmp_path / "db")
-    formats.write_index(prefix, names, seqs)
     reads = []
     for L in (15, 16, 17, 303, 304, 305, 526, 527, 528, 529, 1038, 1039, 1040, 1041, 2000, 5000, 9000, 20000):
         for err in (0.0, 0.1):
@@ -236,6 +230,18 @@ def test_long_read_route_equals_lane_kernel_and_oracle(tmp_path, kind):
             w = src[st:st + L].copy()
             parts.append(synth.revcomp_codes(w) if rng.random() < 0.5 else w)
         reads.append(np.concatenate(parts))
+    return names, seqs, reads
+
+
+@pytest.mark.parametrize("kind", ["genome", "genes"])
+def test_long_read_route_equals_lane_kernel_and_oracle(tmp_path, kind):
+    """stage 2 of long reads: chain_long_anchor_kernel (a wavefront per read and strand) + chain_long_tail_kernel against chain_kernel
+    (KMAHIP_CHAIN=slow: a lane per read, anchors included) and the oracle -- lengths on either side of the fast route's limit and of
+    the kernel's passes of 512 k-mer starts, reads shorter than k, unrelated reads, exact copies (one anchor spanning every pass), reads
+    glued from pieces of both strands, exhaustive mode, and the pool cut into many chunks"""
+    names, seqs, reads = long_route_set(kind)
+    prefix = str(tmp_path / "db")
+    formats.write_index(prefix, names, seqs)
     b = formats.pack_ragged(reads)
     odb = oracle.OracleDB(prefix)
     db = binding.KmaHipDB(prefix)
