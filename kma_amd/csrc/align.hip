@@ -87,6 +87,7 @@ struct AlignArgs {
 	int32_t *pend;           // its tasks that wait for queued problems (counters[AC_PEND]) ...
 	int *part;               // ... and their sums so far, PART_INTS per TASK
 	int per_round;           // tasks a wavefront takes per round (64; fewer over the list, whose tasks all bring DP problems for the wave's queues)
+	int seed_diag;           // seed_tasks_kernel: short reads without N's take the diagonal route (seed_view_diag)
 };
 
 constexpr int SEEDS = 4;        // MEMs per task the seeding kernel hands over (a 150 bp read has 1-3)
@@ -1140,13 +1141,144 @@ __device__ __forceinline__ int seed_view(const AlignArgs &A, int t, const QView 
 	return nm;
 }
 
+// ---- the diagonal route of the MEM search (short reads without N's and without trimmed bounds; KMAHIP_SEED_DIAG=0: off). A MEM lies
+// on one template diagonal d = (pos - 1) - j, known as soon as the position index has answered, and with it every template word the
+// read can touch: they are fetched together and compared with the read in registers ONCE, into a mask with a bit per read base that
+// differs from its template base or has none. mem_extend's answer is then two bit scans of that mask -- the same base comparisons with
+// the same bounds (lowq = 0 and segstop = L on this route), without its serial 32-base steps. A later lookup on the same diagonal (a
+// substitution, then a hit one base on) costs no template access at all; another diagonal (an indel, a repeat) gets its own mask.
+struct DiagMask { uint32_t m0, m1, m2, m3, m4; };
+
+// tp = the word of the template store that holds template position d (d < 0: a word before the template's first). The six words
+// from there on are read whatever the template's extent -- the caller has checked that they lie inside the store -- since a word of a
+// neighbouring template is compared with read bases that lie off this one, and those are marked by the bounds whatever the compare says.
+__device__ __forceinline__ DiagMask diag_mask(const uint64_t *tp, int t_len, const RegRead &R, int L, int d) {
+	const uint64_t t0 = tp[0], t1 = tp[1], t2 = tp[2], t3 = tp[3], t4 = tp[4], t5 = tp[5];
+	const int sh = (d & 31) << 1;
+	const int lo = max(0, -d), hi = min(L, t_len - d);      // read bases [lo, hi) have a template base
+	DiagMask D;
+	D.m0 = diff_bits(funnel2(t0, t1, sh) ^ R.r0) | bits_before(lo) | ~bits_before(hi);
+	D.m1 = diff_bits(funnel2(t1, t2, sh) ^ R.r1) | bits_before(lo - 32) | ~bits_before(hi - 32);
+	D.m2 = diff_bits(funnel2(t2, t3, sh) ^ R.r2) | bits_before(lo - 64) | ~bits_before(hi - 64);
+	D.m3 = diff_bits(funnel2(t3, t4, sh) ^ R.r3) | bits_before(lo - 96) | ~bits_before(hi - 96);
+	D.m4 = diff_bits(funnel2(t4, t5, sh) ^ R.r4) | bits_before(lo - 128) | ~bits_before(hi - 128);
+	return D;
+}
+// one past the last marked base below j (0: none)
+__device__ __forceinline__ int diag_start(const DiagMask &D, int j) {
+	int s = 0;
+	uint32_t x;
+	x = D.m0 & bits_before(j);       if(x) s = 32 - (__ffs((int) x) - 1);
+	x = D.m1 & bits_before(j - 32);  if(x) s = 64 - (__ffs((int) x) - 1);
+	x = D.m2 & bits_before(j - 64);  if(x) s = 96 - (__ffs((int) x) - 1);
+	x = D.m3 & bits_before(j - 96);  if(x) s = 128 - (__ffs((int) x) - 1);
+	x = D.m4 & bits_before(j - 128); if(x) s = 160 - (__ffs((int) x) - 1);
+	return s;
+}
+// the first marked base at or after a (L: none; every base from the read end on is marked, so the answer never exceeds L)
+__device__ __forceinline__ int diag_end(const DiagMask &D, int a, int L) {
+	int e = L;
+	uint32_t x;
+	x = D.m4 & ~bits_before(a - 128); if(x) e = 128 + __clz((int) x);
+	x = D.m3 & ~bits_before(a - 96);  if(x) e = 96 + __clz((int) x);
+	x = D.m2 & ~bits_before(a - 64);  if(x) e = 64 + __clz((int) x);
+	x = D.m1 & ~bits_before(a - 32);  if(x) e = 32 + __clz((int) x);
+	x = D.m0 & ~bits_before(a);       if(x) e = __clz((int) x);
+	return e;
+}
+
+// seed_view for a read of k <= L <= RR_MAXLEN bases without N's and with the whole read as its bounds: the same lookups on the same
+// (j, j + 1) pairs, the same MEMs. They go to the slot as they are found, not through registers (the kernel has none to spare): a
+// slot's MEMs beyond its count are never read. -2: not served (a diagonal at an end of the store); what was written is not read.
+__device__ __forceinline__ int seed_view_diag(const AlignArgs &A, int t, const QView &q, int k, int64_t slot) {
+	const int L = q.L;
+	const uint4 ma = A.db.tmeta[2 * (size_t) t], mb = A.db.tmeta[2 * (size_t) t + 1];
+	const int t_len = (int) mb.x;
+	const int64_t toff = (int64_t) (((uint64_t) ma.y << 32) | ma.x);
+	const uint2 *tab = A.db.tpos_slots + (((uint64_t) ma.w << 32) | ma.z);
+	const uint32_t tsh = mb.y;
+	const RegRead R = rr_load(q);
+	const int end = L - k + 1;
+	DiagMask D = {0u, 0u, 0u, 0u, 0u};
+	int nm = 0, j = 0, dcur = INT_MIN;      // no diagonal compared yet (a real one is above -L)
+	while(j < end) {
+		int v, v2;
+		const uint64_t w = rr_win(R, j);
+		const uint32_t km1 = (uint32_t) (w >> (64 - 2 * k)), km2 = (uint32_t) ((w << 2) >> (64 - 2 * k));
+		tpos_get2(tab, tsh, km1, km2, j + 1 < end, v, v2);
+		if(v == 0) {
+			if(v2 == 0) { j += 2; continue; }
+			++j; v = v2;
+		}
+		if(v < 0 || nm >= SEEDS) return -1;
+		const int d = v - 1 - j;
+		if(d != dcur) {
+			// the six words from the diagonal's first must lie inside the store, which ends in two pad words (db.hip): not so when the
+			// read hangs off the start of the first template or lies in the last words of the last one -- the view is left to seed_view
+			const int64_t w0 = toff + (d >> 5);
+			if(w0 < 0 || w0 + 5 > A.db.tseq_off[A.db.DB_size] + 1) return -2;      // read here, not held: no register to spare
+			D = diag_mask(A.db.tseq + w0, t_len, R, L, d); dcur = d;
+		}
+		const int qS = diag_start(D, j), qE = diag_end(D, j + k, L);
+		A.seed_mem[slot * SEEDS + nm++] = make_uint2((uint32_t) (qS + d + 1), (uint32_t) qS | ((uint32_t) (qE - qS) << 16));
+		j = qE;
+	}
+	return nm;
+}
+
+// The kernel is one or two walks of a lane over its tasks. With KMAHIP_SEED_DIAG=0 one walk, seed_view for every view, as before.
+// Otherwise the first walk takes the diagonal route for the views it serves and leaves -2 in the slot of every other view, and the
+// second is seed_view for the tasks with a marked slot (a lane reads only marks it wrote itself). The two routes are two walks, not
+// two arms of one branch, because a lane's registers are the larger of the walks' needs but MORE than the larger of two arms' needs:
+// what one arm reads stays live while the other runs. For a short-read sample the second walk reads the marks (4 bytes per slot,
+// coalesced) and finds next to none.
+// The first walk takes the first slot of all its tasks, then the second (paired records), and works the task's views out per slot:
+// nothing of the task is held across the search but its number.
+__device__ __forceinline__ void seed_walk_diag(const AlignArgs &A, const int64_t n_tasks) {
+	const int k = (int) A.db.kmersize;
+	const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+	const int slots = A.seed_slots;
+	for(int m = 0; m < slots; ++m) for(int64_t task = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; task < n_tasks; task += stride) {
+		const int64_t slot = task * slots + m;
+		const int64_t r = A.t_rec[task];
+		// the reads this task aligns and their orientation: exactly the choices of align_tasks_kernel's phase A
+		int views = 0, rcstate = 0;
+		int64_t rd = r;
+		int rc = 0;
+		if(!A.pe_mode) {
+			if(A.rc_flag[r] > 0 && !long_routed(A, r)) { views = 1; rc = (A.flag[r] & 16) ? 1 : 0; }
+		} else {
+			const int64_t p0 = r & ~1ll;
+			const bool couple = (r & 1) && A.rec_mate[p0] >= 0 && A.rec_mate[r] >= 0 && A.T_off[p0 + 1] == A.T_off[p0];
+			if(couple) {
+				views = 2;
+				for(int64_t j = A.T_off[r]; j <= task; ++j) if(A.T[j] < 0) { rcstate = 1; break; }
+				rd = p0 + A.rec_mate[p0 + m]; rc = A.rec_rc[p0 + m] ^ rcstate;
+			} else if(A.rc_flag[r] > 0 && A.rec_mate[r] >= 0) { views = 1; rd = p0 + A.rec_mate[r]; rc = A.rec_rc[r]; }
+		}
+		int nm = -1;
+		if(m < views) {
+			QView q;
+			q.w = A.seq + A.seq_off[rd]; q.L = A.len[rd]; q.rc = rc;
+			q_set_bounds(q, A.q_start, A.q_end, rd);
+			q.N = A.N + A.N_off[rd]; q.nN = (int) (A.N_off[rd + 1] - A.N_off[rd]);
+			nm = -2;
+			if(q.L >= k && q.L <= RR_MAXLEN && q.nN == 0 && q.b0 == 0 && q.b1 >= q.L) nm = seed_view_diag(A, abs(A.T[task]), q, k, slot);
+		}
+		A.seed_n[slot] = nm;
+	}
+}
+
 __global__ __launch_bounds__(256, 8) void seed_tasks_kernel(const AlignArgs A) {
 	const int64_t n_tasks = A.T_off[A.n_reads];
 	if(n_tasks > A.tasks_cap) return;
 	const int k = (int) A.db.kmersize;
 	const int64_t stride = (int64_t) gridDim.x * blockDim.x;
 	const int slots = A.seed_slots;
+	const bool marked = A.seed_diag != 0;      // the second walk: only the tasks with a slot the first one marked
+	if(marked) seed_walk_diag(A, n_tasks);
 	for(int64_t task = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; task < n_tasks; task += stride) {
+		if(marked && A.seed_n[task * slots] != -2 && A.seed_n[task * slots + slots - 1] != -2) continue;
 		const int64_t r = A.t_rec[task];
 		const int t = abs(A.T[task]);
 		// the reads this task aligns and their orientation: exactly the choices of align_tasks_kernel's phase A
@@ -2854,6 +2986,9 @@ static int launch_align(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 	if(const char *e = getenv("KMAHIP_ABLATE_ALIGN")) A.ablate = atoi(e);
 #endif
 	A.tasks_cap = tasks_cap;
+	// seeding of short reads from one compare per diagonal (KMAHIP_SEED_DIAG=0: mem_extend's 32-base steps for every task)
+	A.seed_diag = 1;
+	if(const char *e = getenv("KMAHIP_SEED_DIAG")) if(!atoi(e)) A.seed_diag = 0;
 	// reads over 1 kb (single end, not the work-counting launch) go through the long-read pipeline (KMAHIP_ALIGN_LONG: another length, 0: never)
 	A.long_min = 0;
 	if(!rec_mate && !A.stats) {

@@ -97,6 +97,60 @@ __device__ __forceinline__ void q_kmer2(const QView &q, int j, int k, uint32_t &
 	km2 = (uint32_t) ((w << 2) >> (64 - 2 * k));
 }
 
+// ---- a short read held in registers (seed_tasks_kernel's diagonal route): the ORIENTED read of up to 160 bases as five 2-bit words,
+// loaded once and reverse complemented once. A word picked by a run-time index comes from a chain of selects over named members,
+// never from an indexed array: that would live in scratch.
+constexpr int RR_MAXLEN = 160;
+struct RegRead { uint64_t r0, r1, r2, r3, r4; };
+// word i of five, 0 outside [0, 5); one select per statement, so that none of them becomes a branch
+__device__ __forceinline__ uint64_t rr_word(const RegRead &R, int i) {
+	uint64_t x = 0;
+	x = i == 0 ? R.r0 : x;
+	x = i == 1 ? R.r1 : x;
+	x = i == 2 ? R.r2 : x;
+	x = i == 3 ? R.r3 : x;
+	x = i == 4 ? R.r4 : x;
+	return x;
+}
+// 32 bases from the pair of words (a, b) starting ip / 2 bases into a (ip even, 0..62): win2's shift without its loads
+__device__ __forceinline__ uint64_t funnel2(uint64_t a, uint64_t b, int ip) { return (a << ip) | ((b >> 1) >> (63 - ip)); }
+// the oriented read of q (q.L <= RR_MAXLEN); bases past the read end are garbage, as in qwin. Oriented word m of a reverse complemented
+// view mirrors the forward window at L - 32 - 32 m: the same shift for every m and the words in descending order, so the words are
+// fetched in the order the view wants them, all at once, and no word is picked at run time. Only words of the read itself are
+// touched (index clamped to [0, (L - 1) / 32]; what a clamped word stands in for is past the read end or shifted out).
+__device__ __forceinline__ RegRead rr_load(const QView &q) {
+	const int last = (q.L - 1) >> 5, hiw = q.L >> 5, ip = (q.L & 31) << 1;
+	const uint64_t g0 = q.w[min(q.rc ? hiw : 0, last)];
+	const uint64_t g1 = q.w[min(max(q.rc ? hiw - 1 : 1, 0), last)];
+	const uint64_t g2 = q.w[min(max(q.rc ? hiw - 2 : 2, 0), last)];
+	const uint64_t g3 = q.w[min(max(q.rc ? hiw - 3 : 3, 0), last)];
+	const uint64_t g4 = q.w[min(max(q.rc ? hiw - 4 : 4, 0), last)];
+	const uint64_t g5 = q.w[max(hiw - 5, 0)];      // a reverse complemented view's last word only
+	RegRead R;
+	R.r0 = q.rc ? revcomp64(funnel2(g1, g0, ip)) : g0;
+	R.r1 = q.rc ? revcomp64(funnel2(g2, g1, ip)) : g1;
+	R.r2 = q.rc ? revcomp64(funnel2(g3, g2, ip)) : g2;
+	R.r3 = q.rc ? revcomp64(funnel2(g4, g3, ip)) : g3;
+	R.r4 = q.rc ? revcomp64(funnel2(g5, g4, ip)) : g4;
+	return R;
+}
+// qwin from the registers: 32 bases of the oriented read starting at i
+__device__ __forceinline__ uint64_t rr_win(const RegRead &R, int i) {
+	const int wi = i >> 5;
+	return funnel2(rr_word(R, wi), rr_word(R, wi + 1), (i & 31) << 1);
+}
+// XOR of two 2-bit words -> one bit per base that differs, base p of the word at bit 31 - p
+__device__ __forceinline__ uint32_t diff_bits(uint64_t x) {
+	x = (x | (x >> 1)) & 0x5555555555555555ull;
+	x = (x | (x >> 1)) & 0x3333333333333333ull;
+	x = (x | (x >> 2)) & 0x0f0f0f0f0f0f0f0full;
+	x = (x | (x >> 4)) & 0x00ff00ff00ff00ffull;
+	x = (x | (x >> 8)) & 0x0000ffff0000ffffull;
+	return (uint32_t) (x | (x >> 16));
+}
+// the bits of the bases before local position n of a 32-base mask word (base p at bit 31 - p); any n
+__device__ __forceinline__ uint32_t bits_before(int n) { return (uint32_t) ~(0xFFFFFFFFull >> min(max(n, 0), 32)); }
+
 // Query codes of a DP problem without a global load per cell: a cached 32-base window of the oriented
 // read, reloaded when the column index leaves it (columns are walked in descending order).
 struct QCursor {
