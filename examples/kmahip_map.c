@@ -215,7 +215,7 @@ static void *xcalloc(size_t n, size_t sz) { void *p = calloc(n ? n : 1, sz); if(
 static void usage(void) {
 	fprintf(stderr, "usage: kmahip_map (-i reads.fq[.gz] | -ipe r1.fq[.gz] r2.fq[.gz] [-apm p|u] | -int interleaved.fq[.gz] [-apm p|u]) -t_db <index prefix> -o <output prefix> [-1t1] [-Mt1 <template>] [-bcNano] [-bc90] [-bc <support>] [-bcg] [-ref_fsa [n]] [-dense]\n"
 	                "       [-t threads] [-nc] [-na] [-nf] [-mf fragments] [-ml len] [-xl len] [-mp phred] [-mi phred] [-eq q] [-mq q] [-ts bases] [-mrs f] [-mrc f] [-mct f]\n"
-	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev]\n"
+	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev] [-sam n]\n"
 	                "       [-reward n] [-gapopen n] [-gapextend n] [-localopen n] [-Npenalty n] [-per n] [-transition n] [-transversion n] [-penalty n] [-cge]\n"
 	                "       (-s1dev, like -gpus not an option of kma: stage 1 of plain FASTQ input on the device; one rank, -1t1 only; its batches close at a quarter\n"
 	                "        of a gigabase of their own accord, KMAHIP_MAP_BATCH_BASES does not apply to them)\n"
@@ -299,6 +299,7 @@ int main(int argc, char **argv) {
 	int pm = 0, fpm = 0;           /* -pm / -fpm (1 p, 2 u; 0: not given) */
 	char *list1[256], *list2[256]; int n_files = 0;          /* the input files (mate files side by side) */
 	int mt1 = 0, one2one = 0, chain = 0, apm = 0, no_cons = 0, no_frag = 0, no_aln = 0, gpus = 0, threads = 0, bcd = 1, s1dev = 0;
+	int sam = 0, sam_bare = 0, status_opt = 0;   /* -sam [n] (kma.c:1005-1017); -status, which the reference refuses beside it (kma.c:1254) */
 	int base_call = 0, sig_mode = 0, ref_fsa = 0, dense = 0;      /* as kmahip_assemble_opts.caller (0-2 here) / .sig90; printconsensus.c's ref_fsa */
 	double support = 0;
 	long long max_frag = 0;
@@ -380,7 +381,17 @@ int main(int argc, char **argv) {
 		else if(!strcmp(o, "-ex_mode")) par.exhaustive = 1;
 		/* switches of the reference that change nothing in its result files: how the index is held (-mmap / -swap, kma.c:526), where its
 		 * temporary files go (-tmp [dir/], kma.c:1031-1050: this program writes none), what it says on stderr (-status, -verbose [n]) */
-		else if(!strcmp(o, "-mmap") || !strcmp(o, "-swap") || !strcmp(o, "-status")) { }
+		else if(!strcmp(o, "-mmap") || !strcmp(o, "-swap")) { }
+		else if(!strcmp(o, "-status")) status_opt = 1;
+		else if(!strcmp(o, "-sam")) {                                                           /* kma.c:1005-1017: a value is optional */
+			sam = 1; sam_bare = 1;
+			if(a + 1 < argc && argv[a + 1][0] != '-') {
+				sam_bare = 0;
+				char *end = NULL;
+				sam = (int) strtol(argv[++a], &end, 10);
+				if(*end) { fprintf(stderr, "Invalid argument at \"-sam\".\n"); return 1; }
+			}
+		}
 		else if(!strcmp(o, "-tmp") || !strcmp(o, "-verbose")) { if(a + 1 < argc && argv[a + 1][0] != '-') ++a; }
 		else if(!strcmp(o, "-mem_mode")) mem_mode = 1;                                           /* kma.c:547 */
 		else if(!strcmp(o, "-lc")) lc = 1;                                                      /* kma.c:694-701 */
@@ -450,6 +461,23 @@ int main(int argc, char **argv) {
 	             (getenv("KMAHIP_COMM_FORCE_RCCL") && getenv("KMAHIP_COMM_FORCE_RCCL")[0] == '1'))) {
 		fprintf(stderr, "kmahip_map: -s1dev serves a single-rank -1t1 run (not -gpus N, the default mode without -1t1, or -Mt1)\n");
 		return 2;
+	}
+	if(sam) {
+		/* SAM records go to standard output like the reference's; they are built for the single-end -1t1 run of one rank, batch by batch */
+		const char *why = NULL;
+		if(status_opt) { fprintf(stderr, "\"-sam\" and \"-status\" cannot coincide.\n"); return 2; }
+		if(sam < 0) why = "a negative value";
+		/* the level is given in full: `-sam 1` for what the reference prints for a bare -sam (the unmapped reads as well), `-sam 4`, `-sam 16`, ... */
+		else if(sam_bare) why = "an option without its value (give the level: -sam 1 for every record, -sam 4 or -sam 16 for those of filed fragments)";
+		else if(input2 && sam == 1) why = "paired input at -sam 1 (the unmapped-mate flags of stage 2 and stage 3a are not built)";
+		else if(input2 && input2[0] == 0) why = "interleaved input (-int)";
+		else if(mt1) why = "-Mt1";
+		else if(chain || pe_chain) why = "the default mode without -1t1 (its records carry query bounds)";
+		else if(gpus > 1 || getenv("KMAHIP_RANK") || getenv("RANK")) why = "-gpus N (several ranks)";
+		else if(getenv("KMAHIP_MAP_ONE_BATCH")) why = "KMAHIP_MAP_ONE_BATCH";
+		else if(getenv("KMAHIP_COMM_FORCE_RCCL") && getenv("KMAHIP_COMM_FORCE_RCCL")[0] == '1') why = "KMAHIP_COMM_FORCE_RCCL";
+		else if(mem_mode) why = "-mem_mode";
+		if(why) { fprintf(stderr, "kmahip_map: -sam is not built for %s: it serves the -1t1 run of one rank: -sam n on single-end input, -sam n with n != 1 on -ipe input\n", why); return 2; }
 	}
 	if(threads) {
 		char v[16];
@@ -534,6 +562,16 @@ int main(int argc, char **argv) {
 		if(reader2) hint *= 2;
 		if(kmahip_session_open(db, ws, &par, &so, hint, &ses) || (chain && kmahip_session_set_chain(ses, &cp)) || (mt1 && kmahip_session_set_mt1(ses, mt1, one2one, no_frag ? NULL : mt1_frag)) ||
 		   (input2 && kmahip_session_set_pe(ses))) die("session");
+		if(sam) {	/* @PG ... CL: the arguments joined by blanks (strjoin, kma.c:1599) */
+			size_t cl = 1;
+			for(int a = 0; a < argc; ++a) cl += strlen(argv[a]) + 1;
+			char *cmdline = malloc(cl);
+			if(!cmdline) fail("out of memory");
+			cmdline[0] = 0;
+			for(int a = 0; a < argc; ++a) { if(a) strcat(cmdline, " "); strcat(cmdline, argv[a]); }
+			if(kmahip_session_set_sam(ses, sam, "-", "kmahip_map", cmdline)) die("session");
+			free(cmdline);
+		}
 		int batches = 0;
 		kmahip_db_info sinfo;
 		int64_t unpinned = 0;
@@ -569,7 +607,7 @@ int main(int argc, char **argv) {
 		}
 		if(unpinned) fprintf(stderr, "# kmahip_map: %lld reads carry an N among their first k - 1 bases behind a longer read: the reference's records for them depend on what its buffer held\n", (long long) unpinned);
 		fprintf(stderr, "# kmahip_map: %lld reads in %d batches, %lld fragment rows; wall: open %.2f s, ingest done after %.2f, mapped after %.2f, finish %.2f | uploads %.1f ms, stages 2+3a %.1f, "
-		        "ConClave %.1f, traceback %.1f, pile-up + consensus %.1f, .res + .fsa %.1f, .frag.gz %.1f (+ %.1f beside the batches) (main entered %.2f s after process start; peak RSS %.0f MB)\n", (long long) n_reads, batches,
+		        "ConClave %.1f, traceback %.1f, pile-up + consensus %.1f, .res + .fsa %.1f, .frag.gz %.1f (+ %.1f beside the batches, or for the SAM records) (main entered %.2f s after process start; peak RSS %.0f MB)\n", (long long) n_reads, batches,
 		        (long long) n_rows, t_open - t_start, sj.t_done - t_start, t_mapped - t_start, now_s() - t_mapped, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], ms[6], ms[7], t_before_main, peak_rss_mb());
 		if(getenv("KMAHIP_MAP_TEARDOWN")) {	/* what the process gives back, piece by piece and timed (the exit does the same in one go) */
 			double t0 = now_s();

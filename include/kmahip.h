@@ -316,6 +316,19 @@ int kmahip_align_trace_dev(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *rea
 int kmahip_align_trace(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads, const int32_t *rc, const int32_t *tmpl,
                        const uint8_t *tmpl_ok, const kmahip_params *p, kmahip_traces *out, int64_t *ops_needed);
 
+/* What the read filter dropped, kept on request (the `-sam` rows of assembly.c:1995-2002: an alignment that fails the filter with a read
+ * score other than 0 is still printed as an aligned record). With a record set on the workspace, every trace call on it (kmahip_align_trace_dev,
+ * the sessions) fills, per read: stats[6 * i ..] = read_score (which may be negative), start, end, clip_start, clip_end, mapQ, and the read's
+ * runs as n_ops[i] entries at ops_off[i] of the SAME run pool (kmahip_traces.ops; they count towards ops_cap) -- for a read with a template that
+ * the filter dropped with read_score != 0; all zero for every other read. The read's kmahip_traces entry stays all zero either way, so the
+ * pile-up and the fragment rows see no change. DEVICE pointers, n_reads entries as the traces'; NULL (the default) switches it off. */
+typedef struct kmahip_trace_drops {
+	int32_t *stats;     /* 6 * n_reads */
+	int64_t *ops_off;   /* n_reads */
+	int32_t *n_ops;     /* n_reads */
+} kmahip_trace_drops;
+int kmahip_ws_set_trace_drops(kmahip_ws *ws, const kmahip_trace_drops *drops);
+
 /* `-Mt1 t` (runKMA_Mt1, mt1.c:86-500 -> assemble_KMA with read_score == 0, assembly.c:1917-1965): raw reads go straight to
  * stage 3c against ONE template, no stage 2 and no ConClave. Per read: anker_rc (align.c:780-991) seeds both strands against
  * the template's position index and keeps the strand with the larger MEM coverage (forward on equality; the forward strand is
@@ -579,6 +592,45 @@ int kmahip_frag_write3(const char *path, kmahip_db *db, const kmahip_reads *read
  * and concatenate the members (RFC 1952 2.2). Exposed for tests. */
 int kmahip_gzip_member(const void *src, int64_t n, void *dst, int64_t cap, int64_t *out_bytes);
 
+/* ---- SAM records (`-sam [n]`, kma.c:1005-1012; saminit / samwrite / makeCigar, sam.c:30-211) ------------------------------------------
+ * One row per record: QNAME FLAG RNAME POS MAPQ CIGAR * 0 TLEN SEQ * ET:i:<equally good templates> AS:i:<score>, QNAME = the read header up
+ * to its first TAB, MAPQ = min(254, mapQ), POS = start + 1, TLEN = end - POS, SEQ = the fragment as filed (N's restored). Which records, with
+ * `level` = the option's value (1 for a bare -sam):
+ *   1  reads stage 2 passed nothing on for (n_hits 0, tmpl 0, flag & 4 clear), only when level == 1 (kmers.c:70, savekmers.c:205-248):
+ *      FLAG 20, RNAME *, POS 0, MAPQ 0, CIGAR *, TLEN 0, ET 0, AS 0, SEQ = the read as stage 1 packed it
+ *   2  reads stage 3a rejected (tmpl 0, flag & 4), only when level == 1 (runkma.c:348, alnfrags.c:2262-2273): FLAG = flag, otherwise as
+ *      above, SEQ = the read as stage 2 passed it on (rc bit 0)
+ *   3  the filed fragments (tmpl != 0) of every template, templates ascending, in assemble_KMA's order (that of the fragment rows, counted
+ *      over ALL filed fragments): 3a kept by the read filter (the rows of `.frag.gz`): FLAG = flag | 16 for a template of negative sign;
+ *      3b dropped with read_score != 0 (kmahip_trace_drops): an aligned record all the same, AS = read_score; 3c / 3d everything else that
+ *      was filed (read_score 0, nothing to align, or a template the significance gate skips: tmpl_ok 0): FLAG | 4, RNAME = the template,
+ *      POS 0, MAPQ 0, CIGAR *, TLEN 0, AS 0. 3b - 3d only when !(level & 2096) (assembly.c:1995-2015; the reference's own test, kept).
+ * Order: class 1 in stream order, class 2 in stream order, class 3 (the reference's stages 2 and 3a run beside each other under -sam and
+ * interleave their rows differently from run to run; what it prints with a template name comes in this order every time).
+ *
+ * kmahip_sam_cigar: the CIGAR of one record (makeCigar: <clip_start>S, the runs as =XID, <clip_end>S), 0-terminated, into out[cap]; returns
+ * its length or KMAHIP_EOVERFLOW. kmahip_sam_row_host: one whole row from host values (rname NULL = "*", runs NULL = CIGAR "*", seq = the
+ * bases as text); returns its length (no terminator is written) or KMAHIP_EOVERFLOW. Pure host code: the checkers of the device's text. */
+#define KMAHIP_VERSION "0.9.0"
+const char *kmahip_version(void);
+int64_t kmahip_sam_cigar(const uint32_t *runs, int64_t n, int32_t clip_start, int32_t clip_end, char *out, int64_t cap);
+int64_t kmahip_sam_row_host(const char *header, int32_t flag, const char *rname, int32_t pos, int32_t mapq, const uint32_t *runs, int64_t n_runs,
+                            int32_t clip_start, int32_t clip_end, int32_t tlen, const char *seq, int32_t et, int32_t as, char *out, int64_t cap);
+/* The header (saminit): @HD, one @PG line ("@PG\tID:KMA\tPN:<program>\tVN:<KMAHIP_VERSION>\tCL:<cmdline>", CL left out for a NULL cmdline),
+ * @SQ for every template in index order. path: a file (created or emptied), or "-" = standard output. */
+int kmahip_sam_header(kmahip_db *db, const char *program, const char *cmdline, const char *path);
+/* The rows of one batch that is the whole stream, APPENDED to path ("-" = standard output). HOST buffers in the mould of kmahip_frag_write3:
+ * the reads, kmahip_hits.rc / kmahip_conclave.tmpl / kmahip_hits.n_hits / kmahip_hits.flag per read, the traces of kmahip_align_trace (stats,
+ * ops_off, n_ops, and ops_cap entries of ops), the drop record with HOST arrays (NULL: no rows of class 3b), tmpl_ok per template (NULL =
+ * all), frag_rank as in kmahip_assemble_opts, the read headers. Classified, ordered, measured and formatted on the device -- a lane per row,
+ * or a wavefront per row for long reads (KMAHIP_SAM_GROUP=1 / 64 forces one) --, brought back as text a chunk at a time (KMAHIP_SAM_CHUNK
+ * bytes, 64 MiB by default; a longer row gets a buffer of its own size) and written in order, uncompressed.
+ * class_rows (may be NULL): rows of classes 1, 2, 3a, 3b, 3c + 3d. */
+int kmahip_sam_write(const char *path, kmahip_db *db, const kmahip_reads *reads, const int32_t *rc, const int32_t *tmpl, const int32_t *n_hits,
+                     const int32_t *flag, const kmahip_traces *traces, const kmahip_trace_drops *drops, const uint8_t *tmpl_ok, int64_t max_frag,
+                     int order, const int64_t *frag_rank, const char *read_names, const int64_t *read_name_off, int level, int64_t *rows,
+                     int64_t class_rows[5]);
+
 /* The mapping quality the stage-3 kernels gate on with -mq (chainSeeds, chain.c:79-260: ceil(40 (1 - second / best) min(1, w / 10)
  * log(best)) in double, 0 for best <= 0), evaluated ON THE DEVICE by the one function all of those kernels call, for n triples in HOST
  * arrays. Exposed for tests: the device's log against the libm the reference links. */
@@ -742,6 +794,14 @@ int kmahip_session_set_chain(kmahip_session *s, const kmahip_chain_params *cp);
  * the finish as <out_prefix>.frag.gz). ms[] of kmahip_session_finish: [1] the tracebacks, [3] nothing, [7] the fragment rows made
  * beside the batches. */
 int kmahip_session_set_mt1(kmahip_session *s, int32_t tmpl, int one2one, const char *frag_path);
+/* SAM records of the run (`-sam [n]`; kmahip_sam_write has the record classes and their order): call before the first batch. level = the
+ * option's value (1 for a bare -sam), path = where header and rows go ("-" = standard output), program / cmdline = the @PG line's PN and CL.
+ * The session then keeps every read's stage-3a flag, lets its traceback keep what the read filter drops (kmahip_trace_drops, when the level
+ * prints such rows) and kmahip_session_finish writes the SAM beside `.res` / `.fsa` / `.frag.gz`, which stay byte for byte what they are
+ * without it. Serves the single-end `-1t1` session at every level and the paired one (kmahip_session_set_pe) at levels other than 1: the
+ * filed fragments of kmahip_run_pe's records, each with its record's flag, in the fragment rows' order. KMAHIP_EINVAL, naming the mode,
+ * for a session in the default mode, `-Mt1`, or with paired input at level 1 (the unmapped-mate flags of stages 2 and 3a are not built). */
+int kmahip_session_set_sam(kmahip_session *s, int level, const char *path, const char *program, const char *cmdline);
 int kmahip_session_add(kmahip_session *s, const kmahip_read_batch *batch);
 /* kmahip_session_add in two steps, for a caller whose reader thread is to go on while the device works: _upload returns when the
  * batch's host arrays are free again, _map runs stages 2 and 3a on what has been uploaded since the last call */

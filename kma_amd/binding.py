@@ -113,6 +113,15 @@ class TraceStats(C.Structure):
     _fields_ = [("problems", C.c_uint64), ("dp_cells", C.c_uint64), ("mems", C.c_uint64), ("reads", C.c_uint64)]
 
 
+class TraceDrops(C.Structure):
+    _fields_ = [("stats", C.c_void_p), ("ops_off", C.c_void_p), ("n_ops", C.c_void_p)]
+
+
+class ShardOpts(C.Structure):
+    _fields_ = [("evalue", C.c_double), ("bcd", C.c_int32), ("caller", C.c_int32), ("sig90", C.c_int32), ("max_frag", C.c_int64),
+                ("ID_t", C.c_double), ("Depth_t", C.c_double), ("support", C.c_double), ("ref_fsa", C.c_int32), ("write_aln", C.c_int32)]
+
+
 class KmaHipError(RuntimeError):
     pass
 
@@ -232,6 +241,24 @@ def lib():
         L.kmahip_ingest_dev_copy_out.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.kmahip_ingest_dev_close.argtypes = [C.c_void_p]
         L.kmahip_ingest_dev_close.restype = None
+        L.kmahip_version.restype = C.c_char_p
+        L.kmahip_sam_cigar.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_char_p, C.c_int64]
+        L.kmahip_sam_cigar.restype = C.c_int64
+        L.kmahip_sam_row_host.argtypes = [C.c_char_p, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_char_p, C.c_int32, C.c_int32, C.c_char_p, C.c_int64]
+        L.kmahip_sam_row_host.restype = C.c_int64
+        L.kmahip_sam_header.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p]
+        L.kmahip_sam_write.argtypes = [C.c_char_p, C.c_void_p, C.POINTER(Reads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Traces),
+                                       C.POINTER(TraceDrops), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_char_p, C.c_void_p, C.c_int,
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.kmahip_ws_set_trace_drops.argtypes = [C.c_void_p, C.POINTER(TraceDrops)]
+        L.kmahip_session_open.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Params), C.POINTER(ShardOpts), C.c_int64, C.POINTER(C.c_void_p)]
+        L.kmahip_session_set_sam.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p]
+        L.kmahip_session_set_chain.argtypes = [C.c_void_p, C.POINTER(ChainParams)]
+        L.kmahip_session_set_mt1.argtypes = [C.c_void_p, C.c_int32, C.c_int, C.c_char_p]
+        L.kmahip_session_set_pe.argtypes = [C.c_void_p]
+        L.kmahip_session_close.argtypes = [C.c_void_p]
+        L.kmahip_session_close.restype = None
         _lib = L
     return _lib
 
@@ -252,6 +279,33 @@ def cigar_from_runs(runs, clip_start=0, clip_end=0):
     if clip_end:
         out.append(f"{clip_end}S")
     return "".join(out)
+
+
+def sam_cigar(runs, clip_start=0, clip_end=0, cap=None):
+    """kmahip_sam_cigar (host code): the CIGAR text of one record; KmaHipError (-6) when `cap` bytes do not hold it"""
+    r = np.ascontiguousarray(runs, np.uint32)
+    cap = int(cap) if cap is not None else 12 * len(r) + 32
+    buf = C.create_string_buffer(max(1, cap))
+    n = lib().kmahip_sam_cigar(_p(r) if len(r) else None, len(r), int(clip_start), int(clip_end), buf, cap)
+    if n < 0:
+        _check(int(n))
+    return buf.raw[:n].decode()
+
+
+def sam_row_host(header, flag, rname, pos, mapq, runs, clip_start, clip_end, tlen, seq, et, as_, cap=None):
+    """kmahip_sam_row_host (host code): one SAM row from host values -> bytes. rname None = "*", runs None = CIGAR "*"."""
+    r = None if runs is None else np.ascontiguousarray(runs, np.uint32)
+    header, seq = (x.encode() if isinstance(x, str) else bytes(x) for x in (header, seq))
+    rn = None if rname is None else (rname.encode() if isinstance(rname, str) else bytes(rname))
+    cap = int(cap) if cap is not None else len(header) + len(seq) + (0 if r is None else 12 * len(r)) + 256 + (len(rn) if rn else 0)
+    buf = C.create_string_buffer(max(1, cap))
+    # (an empty run list is still a list: a pointer that is not NULL)
+    keep = np.zeros(1, np.uint32) if r is not None and not len(r) else r
+    n = lib().kmahip_sam_row_host(header, int(flag), rn, int(pos), int(mapq), None if keep is None else _p(keep), 0 if r is None else len(r),
+                                  int(clip_start), int(clip_end), int(tlen), seq, int(et), int(as_), buf, cap)
+    if n < 0:
+        _check(int(n))
+    return buf.raw[:n]
 
 
 def test_mapq(best, second, w):
@@ -404,6 +458,41 @@ class IngestDev:
     def close(self):
         if self._h:
             lib().kmahip_ingest_dev_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Session:
+    """A kmahip_session on a database, as far as choosing its mode goes: set_sam (kmahip_session_set_sam) beside set_chain / set_mt1 /
+    set_pe, each before the first batch. Feeding batches and finishing the run is the host program's (examples/kmahip_map.c)."""
+
+    def __init__(self, db, evalue=0.05, bcd=1, max_frag=0, reads_hint=0):
+        self._db = db
+        self._h = C.c_void_p()
+        so = ShardOpts(evalue, bcd, 0, 0, int(max_frag), 1.0, 0.0, 0.0, 0, 1)
+        p = Params.from_buffer_copy(db.params)
+        _check(lib().kmahip_session_open(db.h, db.ws, C.byref(p), C.byref(so), int(reads_hint), C.byref(self._h)))
+
+    def set_sam(self, level=1, path="-", program="kmahip", cmdline=None):
+        _check(lib().kmahip_session_set_sam(self._h, int(level), os.fsencode(path), program.encode(), None if cmdline is None else cmdline.encode()))
+
+    def set_chain(self):
+        _check(lib().kmahip_session_set_chain(self._h, None))
+
+    def set_mt1(self, tmpl, one2one=0, frag_path=None):
+        _check(lib().kmahip_session_set_mt1(self._h, int(tmpl), int(one2one), None if frag_path is None else os.fsencode(frag_path)))
+
+    def set_pe(self):
+        _check(lib().kmahip_session_set_pe(self._h))
+
+    def close(self):
+        if self._h:
+            lib().kmahip_session_close(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):
@@ -870,6 +959,50 @@ class KmaHipDB:
         _check(lib().kmahip_frag_write3(os.fsencode(path), self.h, C.byref(r), _p(fl), _p(tm), _p(nh), _p(st), int(max_frag), int(order),
                                         None if fr is None else _p(fr), blob, _p(noff), C.byref(rows)))
         return rows.value
+
+    def sam_header(self, path, program="kmahip", cmdline=None):
+        """kmahip_sam_header: @HD, @PG and the @SQ lines into `path` (created or emptied; "-" = standard output)"""
+        _check(lib().kmahip_sam_header(self.h, program.encode(), None if cmdline is None else cmdline.encode(), os.fsencode(path)))
+
+    def sam_write(self, path, batch, rc, tmpl, n_hits, flag, traces, read_names, drops=None, tmpl_ok=None, level=1, order=0, max_frag=0,
+                  frag_rank=None):
+        """kmahip_sam_write: the SAM rows of a batch (host arrays) appended to `path`, made on the device. traces = (stats [n, 10],
+        ops_off, n_ops, ops) as align_trace returns them, drops = (stats [n, 6], ops_off, n_ops) or None.
+        -> (rows, [rows of classes 1, 2, 3a, 3b, 3c + 3d])"""
+        n = batch.n
+        seq = np.ascontiguousarray(batch.seq, np.uint64)
+        Nn = np.ascontiguousarray(batch.N if len(batch.N) else np.zeros(1, np.int32), np.int32)
+        r = Reads(n, _p(seq), _p(batch.seq_off), _p(batch.length), _p(Nn), _p(batch.N_off), len(seq), len(batch.N),
+                  int(batch.length.max()) if n else 0)
+        i32 = lambda a: np.ascontiguousarray(a if n else np.zeros(1, np.int32), np.int32)  # noqa: E731
+        fl, tm, nh, fg = i32(rc), i32(tmpl), i32(n_hits), i32(flag)
+        st = np.ascontiguousarray(traces[0] if n else np.zeros((1, 10), np.int32), np.int32)
+        off = np.ascontiguousarray(traces[1] if n else np.zeros(1, np.int64), np.int64)
+        nops = i32(traces[2])
+        ops = np.ascontiguousarray(traces[3], np.uint32)
+        tr = Traces(_p(st), _p(off), _p(nops), _p(ops) if len(ops) else None, len(ops))
+        dr = None
+        if drops is not None:
+            dst = np.ascontiguousarray(drops[0] if n else np.zeros((1, 6), np.int32), np.int32)
+            doff = np.ascontiguousarray(drops[1] if n else np.zeros(1, np.int64), np.int64)
+            dn = i32(drops[2])
+            dr = TraceDrops(_p(dst), _p(doff), _p(dn))
+        ok = None if tmpl_ok is None else np.ascontiguousarray(tmpl_ok, np.uint8)
+        fr = None if frag_rank is None else np.ascontiguousarray(frag_rank if n else np.zeros(1, np.int64), np.int64)
+        blob = b"".join(nm + b"\0" for nm in read_names) + b"\0"
+        noff = np.zeros(n + 1, np.int64)
+        if n:
+            noff[1:] = np.cumsum([len(nm) + 1 for nm in read_names])
+        rows = C.c_int64()
+        per = (C.c_int64 * 5)()
+        _check(lib().kmahip_sam_write(os.fsencode(path), self.h, C.byref(r), _p(fl), _p(tm), _p(nh), _p(fg), C.byref(tr),
+                                      None if dr is None else C.byref(dr), None if ok is None else _p(ok), int(max_frag), int(order),
+                                      None if fr is None else _p(fr), blob, _p(noff), int(level), C.byref(rows), per))
+        return rows.value, list(per)
+
+    def session(self, evalue=0.05, bcd=1, max_frag=0, reads_hint=0):
+        """a kmahip_session on this database and workspace, for choosing its mode (Session)"""
+        return Session(self, evalue, bcd, max_frag, reads_hint)
 
     def set_pe_chain(self, on=True, minlen=16, coverT=0.1, mrs=0.5):
         """Paired runs on this workspace in the reference's default mode (no -1t1): records that lost their mate go to the chain

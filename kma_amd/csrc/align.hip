@@ -2315,6 +2315,11 @@ struct TraceArgs {
 	int32_t *o_nops;
 	uint32_t *ops;               // runs: (length << 2) | class, class 0 '=' 1 'X' 2 'I' 3 'D'
 	int64_t ops_pool_cap;
+	// what the read filter drops with read_score != 0, kept on request (kmahip_trace_drops; all NULL: off): 6 figures per read and its
+	// runs in the same pool
+	int32_t *d_stats;
+	int64_t *d_off;
+	int32_t *d_nops;
 	unsigned long long *counters;   // [0] run pool top, [1] status, [3] reads put off
 	// Two passes. fast != 0: a read whose DP problems all have a provably ungapped answer (see diag_proof) is finished without
 	// a move matrix; any other read is put off -- its index goes to q_out -- so that no lane of a wave sits through another
@@ -2755,7 +2760,7 @@ __global__ __launch_bounds__(256) void trace_kernel(const TraceArgs A) {      //
 	for(int64_t it = gtid; __any(it < n_items); it += n_threads) {
 		const int64_t r = it < n_items ? (A.q_in ? (int64_t) A.q_in[it] : it) : A.n_reads;
 		// what the read contributes: nothing (keep = false) or its figures + T.em.n alignment runs
-		bool keep = false;
+		bool keep = false, drop = false;
 		int32_t *st = nullptr;
 		int read_score = 0, start = 0, end = 0, aln_len = 0, cs = 0, ce = 0, t_len = 0;
 		unsigned mapQ = 0;
@@ -2764,6 +2769,7 @@ __global__ __launch_bounds__(256) void trace_kernel(const TraceArgs A) {      //
 			st = A.o_stats + 10 * r;
 			for(int x = 0; x < 10; ++x) st[x] = 0;
 			A.o_off[r] = 0; A.o_nops[r] = 0;
+			if(A.d_stats) { for(int x = 0; x < 6; ++x) A.d_stats[6 * r + x] = 0; A.d_off[r] = 0; A.d_nops[r] = 0; }
 			const int tt = A.tmpl[r], t = abs(tt);
 			if(!(t == 0 || (A.tmpl_ok && !A.tmpl_ok[t]))) {
 				QView q;
@@ -2788,22 +2794,29 @@ __global__ __launch_bounds__(256) void trace_kernel(const TraceArgs A) {      //
 					if(A.minlen <= aln_len && ((A.mrc * q.L <= S.len - S.qGaps) || (A.mrc * t_len <= S.len - S.tGaps))) score = 1.0 * read_score / aln_len;
 					else read_score = 0;
 					keep = 0 < read_score && A.scoreT <= score;
+					drop = !keep && read_score != 0 && A.d_stats != nullptr;          // (still a SAM record, assembly.c:1995-2002)
 				}
 			}
 		}
 		// room in the run pool: one atomic per wavefront (a wave prefix sum of the run counts) instead of one per read on a
 		// single counter
-		const int need = keep ? T.em.n : 0;
+		const int need = (keep || drop) ? T.em.n : 0;
 		int incl = need;
 		for(int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(incl, d); if(lane >= d) incl += v; }
 		const int total = __shfl(incl, 63);
 		unsigned long long base = 0;
 		if(lane == 63 && total) base = atomicAdd(&A.counters[0], (unsigned long long) total);
 		base = __shfl(base, 63);
-		if(!keep) continue;
+		if(!keep && !drop) continue;
 		const int64_t o = (int64_t) base + incl - need;
 		if(o + T.em.n > A.ops_pool_cap) { atomicMax(&A.counters[1], 2ull); continue; }
 		for(int x = 0; x < T.em.n; ++x) A.ops[o + x] = T.em.at(x);
+		if(drop) {
+			int32_t *ds = A.d_stats + 6 * r;
+			ds[0] = read_score; ds[1] = start; ds[2] = (t_len < end) ? end - t_len : end; ds[3] = cs; ds[4] = ce; ds[5] = (int) mapQ;
+			A.d_off[r] = o; A.d_nops[r] = T.em.n;
+			continue;
+		}
 		st[0] = read_score; st[1] = start; st[2] = (t_len < end) ? end - t_len : end; st[3] = aln_len; st[4] = cs; st[5] = ce;
 		st[6] = S.match; st[7] = S.tGaps; st[8] = S.qGaps; st[9] = (int) mapQ;
 		A.o_off[r] = o; A.o_nops[r] = T.em.n;
@@ -3268,6 +3281,7 @@ int kmahip_launch_trace(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 	A.ops_s = (uint32_t *) (A.rows + (size_t) lanes * 4 * ncols);
 	A.E = ws->t_E; A.lanes = lanes; A.e_cap = e_cap; A.mem_cap = mem_cap; A.ncols = ncols; A.ops_cap = ops_cap;
 	A.o_stats = out->stats; A.o_off = out->ops_off; A.o_nops = out->n_ops; A.ops = out->ops; A.ops_pool_cap = out->ops_cap;
+	A.d_stats = ws->t_drops.stats; A.d_off = ws->t_drops.ops_off; A.d_nops = ws->t_drops.n_ops;
 	A.counters = ws->counters;
 	// pass 1 settles every read whose DP problems are provably ungapped (diag_proof above) and lists the others; pass 2 runs
 	// the listed ones with their move matrices. KMAHIP_TRACE=lanes1: everything in one pass, as before.

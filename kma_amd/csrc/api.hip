@@ -22,6 +22,13 @@ extern "C" int kmahip_ws_set_pe_chain(kmahip_ws *ws, const kmahip_chain_params *
 	return KMAHIP_OK;
 }
 
+extern "C" int kmahip_ws_set_trace_drops(kmahip_ws *ws, const kmahip_trace_drops *drops) {
+	if(!ws) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(drops && (!drops->stats || !drops->ops_off || !drops->n_ops)) { kmahip_set_error("kmahip_ws_set_trace_drops: a drop record needs its three arrays"); return KMAHIP_EINVAL; }
+	if(drops) ws->t_drops = *drops; else memset(&ws->t_drops, 0, sizeof ws->t_drops);
+	return KMAHIP_OK;
+}
+
 extern "C" void kmahip_ws_destroy(kmahip_ws *ws) {
 	if(!ws) return;
 	(void) hipFree(ws->item_score); (void) hipFree(ws->item_n); (void) hipFree(ws->item_off);

@@ -120,6 +120,8 @@ struct kmahip_ws {
 	int32_t *t_queue;            // reads the first trace pass put off
 	int64_t t_queue_cap;
 	int t_max_len, t_mem_cap;
+	// what the read filter dropped, kept on request (kmahip_ws_set_trace_drops): all NULL = off
+	kmahip_trace_drops t_drops;
 	// pile-up stage (3c) scratch and results
 	uint32_t *p_counts;
 	int32_t *p_chain, *p_seg, *p_vals;
@@ -174,6 +176,24 @@ struct KmaFragSink;
 KmaFragSink *kmahip_frag_sink_open(const char *path);
 int kmahip_frag_sink_close(KmaFragSink *sink);
 
+// the SAM rows of a run whose items and headers are in HBM (samout.hip): classified, ordered, measured and formatted on the device, written
+// to `fd` in order as the chunks of text come back. Everything in KmaSamIn is a DEVICE pointer; W->n_reads items.
+struct KmaSamIn {
+	const kmahip_reads *W;
+	const char *d_names;
+	const int64_t *d_name_off, *d_name_idx;          // d_name_idx (or NULL): the header an item carries
+	const int32_t *d_rc, *d_tmpl, *d_nhits, *d_flag;
+	const kmahip_traces *tr;
+	const kmahip_trace_drops *drops;                 // NULL: no rows of class 3b
+	const uint8_t *d_ok;                             // per template, NULL = all
+	const int64_t *d_rank;                           // position among the filed items of the whole stream, NULL = counted here
+	int64_t max_frag;
+	int order, level;
+};
+int kmahip_sam_write_dev(kmahip_db *db, const KmaSamIn *in, int fd, int64_t text_chunk, char **pinned, int64_t *rows_out, int64_t class_rows[5]);
+int kmahip_sam_open(const char *path, bool append);          // a descriptor for kmahip_sam_write_dev ("-": standard output), -1 on failure
+int kmahip_sam_close(int fd);
+
 // stage 2 of the default mode on a batch that is in HBM, its records as a batch of their own in stream order (pipeline.hip). The
 // arrays live in a block of their own until kmahip_chain_records_free.
 struct KmaChainRecs {
@@ -204,6 +224,7 @@ struct KmaPeDev {
 	char **h_text;
 	int64_t text_chunk;
 	int64_t *frag_rows;       // out: rows written to the fragment file (may be NULL)
+	int sam_level, sam_fd;    // SAM records of the filed fragments: the value of -sam (0: none) and the descriptor they go to
 };
 int kmahip_run_pe_resident(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *batch, const KmaPeDev *pd, const kmahip_params *p, double evalue, int bcd,
                            int64_t max_frag, const char *frag_path, kmahip_run *out);

@@ -139,6 +139,9 @@ struct LtArgs {
 	int64_t ops_cap;
 	unsigned long long *ops_top;   // the batch's run pool top (shared by the passes)
 	int32_t *o_rc;
+	int32_t *d_stats;         // what the read filter drops with read_score != 0, kept on request (kmahip_trace_drops; NULL: off)
+	int64_t *d_off;
+	int32_t *d_nops;
 	volatile uint32_t *rec;   // bring-up flight recorder in host memory (KMAHIP_DEBUG_TIMING): 16 words per workgroup, NULL = off
 };
 #define LT_REC(slot, val) do { if(A.rec && blockIdx.x < 2048) A.rec[(size_t) blockIdx.x * 16 + (slot)] = (uint32_t) (val); } while(0)
@@ -2103,6 +2106,7 @@ __global__ __launch_bounds__(64) void lt_finish_kernel(const LtArgs A) {
 			for(int x = 0; x < 10; ++x) A.o_stats[10 * r + x] = 0;
 			A.o_off[r] = 0; A.o_nops[r] = 0;
 			if(A.o_rc) A.o_rc[r] = H.rc;
+			if(A.d_stats) { for(int x = 0; x < 6; ++x) A.d_stats[6 * r + x] = 0; A.d_off[r] = 0; A.d_nops[r] = 0; }
 		}
 		if(!H.status) { if(A.score_mode && lane == 0) A.o_stats[10 * r + 3] = 1; continue; }          // (KMA_score's failure value: len 1)
 		const int q_len = A.len[r];
@@ -2174,7 +2178,8 @@ __global__ __launch_bounds__(64) void lt_finish_kernel(const LtArgs A) {
 		double norm = 0;
 		if(A.minlen <= aln_len && ((A.mrc * q_len <= aln_len - qGaps) || (A.mrc * t_len <= aln_len - tGaps))) norm = 1.0 * read_score / aln_len;
 		else read_score = 0;
-		if(!(0 < read_score && A.scoreT <= norm)) continue;
+		const bool keep = 0 < read_score && A.scoreT <= norm;
+		if(!keep && !(A.d_stats && read_score != 0)) continue;          // (dropped with a score: still a SAM record, assembly.c:1995-2002)
 		unsigned long long ob = 0;
 		if(lane == 0) ob = atomicAdd(A.ops_top, (unsigned long long) n_merged);
 		ob = __shfl(ob, 0);
@@ -2210,7 +2215,13 @@ __global__ __launch_bounds__(64) void lt_finish_kernel(const LtArgs A) {
 			} else carry_len += total;
 		}
 		if(lane == 0 && carry_cls >= 0) out[w] = ((uint32_t) carry_len << 2) | (uint32_t) carry_cls;
-		if(lane == 0) {
+		if(lane == 0 && !keep) {
+			int32_t *ds = A.d_stats + 6 * r;
+			ds[0] = read_score; ds[1] = start; ds[2] = (t_len < end) ? end - t_len : end;
+			ds[3] = H.clip0 + lead_clip; ds[4] = q_len - H.qe_trail + trail_clip; ds[5] = H.mapQ;
+			A.d_off[r] = (int64_t) ob; A.d_nops[r] = n_merged;
+		}
+		if(lane == 0 && keep) {
 			int32_t *st = A.o_stats + 10 * r;
 			st[0] = read_score; st[1] = start; st[2] = (t_len < end) ? end - t_len : end; st[3] = aln_len;
 			st[4] = H.clip0 + lead_clip; st[5] = q_len - H.qe_trail + trail_clip;
@@ -2366,6 +2377,9 @@ int kmahip_launch_longtrace(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *re
 	A.counters = counters;
 	A.o_stats = out->stats; A.o_off = out->ops_off; A.o_nops = out->n_ops; A.ops = out->ops; A.ops_cap = out->ops_cap;
 	A.ops_top = counters + LCI(LC_OUT); A.o_rc = rc_out;
+	// (not for KMA_score's figures, and not for -Mt1, whose reads have no filed template)
+	const bool drops = !score_mode && tmpl != nullptr && ws->t_drops.stats != nullptr;
+	A.d_stats = drops ? ws->t_drops.stats : nullptr; A.d_off = drops ? ws->t_drops.ops_off : nullptr; A.d_nops = drops ? ws->t_drops.n_ops : nullptr;
 	A.rec = nullptr;
 	A.stop = getenv("KMAHIP_LT_STOP") ? atoi(getenv("KMAHIP_LT_STOP")) : 0;
 	if(getenv("KMAHIP_DEBUG_TIMING")) {

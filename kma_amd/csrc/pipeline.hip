@@ -449,6 +449,8 @@ struct RecArgs {
 	int32_t *r_n, *r_score, *r_ql, *r_ql2;
 	int64_t *r_off;
 	int32_t *fr_read, *fr_rc;            // 2 per slot (-1: none)
+	const int32_t *p_flag, *s_flag;      // kmahip_hits.flag of the pairs' records / of the singles
+	int32_t *fr_flag;                    // 2 per slot: the SAM flag of the fragment's record (stats[4] of frag_raw)
 };
 
 __global__ __launch_bounds__(256) void pe_records_kernel(const RecArgs A) {
@@ -458,6 +460,7 @@ __global__ __launch_bounds__(256) void pe_records_kernel(const RecArgs A) {
 	for(int x = 0; x < 2; ++x) {
 		A.r_n[s0 + x] = 0; A.r_score[s0 + x] = 0; A.r_ql[s0 + x] = 0; A.r_ql2[s0 + x] = 0; A.r_off[s0 + x] = 0;
 		A.fr_read[2 * (s0 + x)] = -1; A.fr_read[2 * (s0 + x) + 1] = -1; A.fr_rc[2 * (s0 + x)] = 0; A.fr_rc[2 * (s0 + x) + 1] = 0;
+		A.fr_flag[2 * (s0 + x)] = 0; A.fr_flag[2 * (s0 + x) + 1] = 0;
 	}
 	auto rec = [&](int64_t slot, int n, int score, int ql, int ql2, int64_t off) {
 		A.r_n[slot] = n; A.r_score[slot] = score; A.r_ql[slot] = ql; A.r_ql2[slot] = ql2; A.r_off[slot] = off;
@@ -467,13 +470,13 @@ __global__ __launch_bounds__(256) void pe_records_kernel(const RecArgs A) {
 		const int64_t j = -(int64_t) A.u_idx[u] - 1;
 		if(A.s_n[j] > 0) {
 			rec(s0, A.s_n[j], A.s_best[j], A.s_len[j], 0, A.s_base + A.T_off[j]);
-			A.fr_read[2 * s0] = first; A.fr_rc[2 * s0] = A.s_rc[j];
+			A.fr_read[2 * s0] = first; A.fr_rc[2 * s0] = A.s_rc[j]; A.fr_flag[2 * s0] = A.s_flag[j];
 		}
 		return;
 	}
 	const int64_t j = A.u_idx[u], r0 = 2 * j, r1 = 2 * j + 1;
 	auto ln = [&](int64_t x) { return A.p_len[2 * j + A.mate[x]]; };
-	auto frag = [&](int64_t slot, int at, int64_t x) { A.fr_read[2 * slot + at] = first + A.mate[x]; A.fr_rc[2 * slot + at] = A.p_rc[x] & 1; };
+	auto frag = [&](int64_t slot, int at, int64_t x) { A.fr_read[2 * slot + at] = first + A.mate[x]; A.fr_rc[2 * slot + at] = A.p_rc[x] & 1; A.fr_flag[2 * slot + at] = A.p_flag[x]; };
 	const int64_t o = A.R_off[r1];
 	const int kd = A.kind[j];
 	if(kd == 1) {
@@ -509,7 +512,7 @@ __global__ __launch_bounds__(256) void pe_frag_count_kernel(int64_t n_slots, con
 // pile-up and the writer divide by.
 __global__ __launch_bounds__(256) void pe_frag_fill_kernel(int64_t n_slots, const int32_t *c_tmpl, const int32_t *r_n, const int32_t *fr_read, const int32_t *fr_rc,
                                                            const int64_t *f_off, const int64_t *starts, int n_starts, int64_t mf, int64_t chunk_base, int64_t *f_src, int32_t *f_rc,
-                                                           int32_t *f_t, int32_t *f_nh, int64_t *f_rank) {
+                                                           int32_t *f_t, int32_t *f_nh, int64_t *f_rank, const int32_t *fr_flag, int32_t *f_flag) {
 	const int64_t s = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
 	if(s >= n_slots) return;
 	const int tt = c_tmpl[s];
@@ -520,6 +523,7 @@ __global__ __launch_bounds__(256) void pe_frag_fill_kernel(int64_t n_slots, cons
 		int lo = 0, hi = n_starts;          // last chunk that starts at or before g
 		while(hi - lo > 1) { const int mid = (lo + hi) >> 1; if(starts[mid] <= g) lo = mid; else hi = mid; }
 		f_src[g] = fr_read[2 * s + x]; f_rc[g] = fr_rc[2 * s + x]; f_t[g] = x == 0 ? tt : abs(tt); f_nh[g] = r_n[s];
+		f_flag[g] = fr_flag[2 * s + x];
 		f_rank[g] = (chunk_base + lo) * (mf + 1) + (g - starts[lo]);
 		++g;
 	}
@@ -772,7 +776,8 @@ static int run_pe_impl(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *ba
 	A.s_n = sh.n_hits; A.s_best = sh.best_score; A.s_rc = sh.rc; A.T_off = cd.T_off; A.s_base = s_base;
 	if((rc = B.get((size_t) n_slots + 1, &A.r_n)) || (rc = B.get((size_t) n_slots + 1, &A.r_score)) || (rc = B.get((size_t) n_slots + 1, &A.r_ql)) ||
 	   (rc = B.get((size_t) n_slots + 1, &A.r_ql2)) || (rc = B.get((size_t) n_slots + 1, &A.r_off)) || (rc = B.get((size_t) 2 * n_slots + 2, &A.fr_read)) ||
-	   (rc = B.get((size_t) 2 * n_slots + 2, &A.fr_rc))) return rc;
+	   (rc = B.get((size_t) 2 * n_slots + 2, &A.fr_rc)) || (rc = B.get((size_t) 2 * n_slots + 2, &A.fr_flag))) return rc;
+	A.p_flag = ph.flag; A.s_flag = sh.flag;
 	kmahip_conclave cc;
 	if((rc = B.get((size_t) n_slots + 1, &cc.tmpl, true)) || (rc = B.get((size_t) n_slots + 1, &cc.start, true)) || (rc = B.get((size_t) n_slots + 1, &cc.end, true)) ||
 	   (rc = B.get(D, &cc.w_scores, true))) return rc;
@@ -853,15 +858,19 @@ static int run_pe_impl(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *ba
 	const int64_t *d_starts = nullptr;
 	if((rc = B.up(starts.data(), starts.size(), 1, &d_starts))) return rc;
 	int64_t *f_src, *f_rank, *f_name = nullptr;
-	int32_t *f_rc, *f_t, *f_nh;
+	int32_t *f_rc, *f_t, *f_nh, *f_flag;
+	// (SAM records of the filed fragments: the session asks through pd; the alignments the read filter drops are kept for them)
+	const int sam_level = pd ? pd->sam_level : 0;
+	kmahip_trace_drops drops{};
+	struct DropsOff { kmahip_ws *ws; ~DropsOff() { (void) kmahip_ws_set_trace_drops(ws, nullptr); } } drops_off{ws};
 	if((rc = B.get((size_t) nf + 1, &f_src)) || (rc = B.get((size_t) nf + 1, &f_rank)) || (rc = B.get((size_t) nf + 1, &f_rc)) || (rc = B.get((size_t) nf + 1, &f_t)) ||
-	   (rc = B.get((size_t) nf + 1, &f_nh))) return rc;
+	   (rc = B.get((size_t) nf + 1, &f_nh)) || (rc = B.get((size_t) nf + 1, &f_flag))) return rc;
 	kmahip_reads dF{};
 	kmahip_traces tr;
 	memset(&tr, 0, sizeof tr);
 	if(nf > 0) {
 		hipLaunchKernelGGL(pe_frag_fill_kernel, dim3((unsigned) ((n_slots + 255) / 256)), dim3(256), 0, s, n_slots, cc.tmpl, A.r_n, A.fr_read, A.fr_rc, f_off, d_starts,
-		                   (int) starts.size(), mf, chunk_base, f_src, f_rc, f_t, f_nh, f_rank);
+		                   (int) starts.size(), mf, chunk_base, f_src, f_rc, f_t, f_nh, f_rank, A.fr_flag, f_flag);
 		HIP_TRY(hipGetLastError());
 		if((rc = cp ? gather_batch2(B, dR, n, CR.d, f_src, nf, &dF, s) : gather_batch(B, dR, f_src, nf, &dF, s))) return rc;
 		if(cp) {          // (the headers: a record's is its read's)
@@ -873,6 +882,10 @@ static int run_pe_impl(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *ba
 		// stage 3c per fragment; the run pool is sized for a handful of runs per read and grown on demand
 		if((rc = B.get((size_t) 10 * nf + 10, &tr.stats)) || (rc = B.get((size_t) nf + 1, &tr.ops_off)) || (rc = B.get((size_t) nf + 1, &tr.n_ops))) return rc;
 		tr.ops_cap = 6 * nf + (1 << 20);
+		if(sam_level && !(sam_level & 2096)) {
+			if((rc = B.get((size_t) 6 * nf + 6, &drops.stats, true)) || (rc = B.get((size_t) nf + 1, &drops.ops_off, true)) || (rc = B.get((size_t) nf + 1, &drops.n_ops, true)) ||
+			   (rc = kmahip_ws_set_trace_drops(ws, &drops))) return rc;
+		}
 		for(int attempt = 0;; ++attempt) {
 			if((rc = B.get((size_t) tr.ops_cap, &tr.ops))) return rc;
 			if((rc = kmahip_launch_trace(db, ws, &dF, f_rc, f_t, d_ok, p, &tr, s))) return rc;
@@ -944,6 +957,13 @@ static int run_pe_impl(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *ba
 		const int32_t none[4] = {0, 0, 0, 0};
 		int64_t rows = 0;
 		if((rc = kmahip_frag_write_src(frag_path, db, &R, 0, &none64, none, none, none, none, 4, mf + 1, 0, &none64, "", &none64, &rows))) return rc;
+	}
+	if(sam_level && nf > 0) {
+		// the SAM records of the filed fragments, in the fragment rows' order (samout.hip); a fragment carries its record's flag
+		KmaSamIn in{};
+		in.W = &dF; in.d_names = pd->d_names; in.d_name_off = pd->d_name_off; in.d_name_idx = f_name ? f_name : f_src; in.d_rc = f_rc; in.d_tmpl = f_t; in.d_nhits = f_nh;
+		in.d_flag = f_flag; in.tr = &tr; in.drops = drops.stats ? &drops : nullptr; in.d_ok = d_ok; in.d_rank = f_rank; in.max_frag = mf + 1; in.order = 0; in.level = sam_level;
+		if((rc = kmahip_sam_write_dev(db, &in, pd->sam_fd, pd->text_chunk, pd->h_text, nullptr, nullptr))) return rc;
 	}
 	out->ms[5] = since(t);
 	return KMAHIP_OK;

@@ -240,6 +240,10 @@ struct kmahip_session {
 	char *h_text[NBUF] = {nullptr, nullptr, nullptr};
 	int64_t text_chunk = 0;
 	double ms_upload = 0, ms_map = 0;
+	// SAM records (kmahip_session_set_sam): the option's value (0: none), where they go, the @PG line's program and command line
+	int sam_level = 0;
+	std::string sam_path, sam_program, sam_cmdline;
+	bool sam_cl = false;
 	~kmahip_session() {
 		for(Batch &b : batches) b.release();
 		for(Batch &b : uploaded) b.release();
@@ -278,6 +282,7 @@ extern "C" void kmahip_session_close(kmahip_session *S) { delete S; }
 extern "C" int kmahip_session_set_mt1(kmahip_session *S, int32_t tmpl, int one2one, const char *frag_path) {
 	if(!S) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	if(S->n || S->n_reads || !S->uploaded.empty() || S->chain || S->mt1 || S->pe) { kmahip_set_error("the mode of a session is chosen before its first batch"); return KMAHIP_EINVAL; }
+	if(S->sam_level) { kmahip_set_error("SAM records (kmahip_session_set_sam) are not built for a -Mt1 session"); return KMAHIP_EINVAL; }
 	if(tmpl < 1 || (size_t) tmpl >= S->db->info.DB_size) { kmahip_set_error("template %d out of range", tmpl); return KMAHIP_EINVAL; }
 	if(hipMalloc((void **) &S->mt1_sum, 8) != hipSuccess || hipMemset(S->mt1_sum, 0, 8) != hipSuccess) { kmahip_set_error("hipMalloc failed"); return KMAHIP_ENOMEM; }
 	if(frag_path) {
@@ -293,6 +298,7 @@ extern "C" int kmahip_session_set_mt1(kmahip_session *S, int32_t tmpl, int one2o
 extern "C" int kmahip_session_set_pe(kmahip_session *S) {
 	if(!S) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	if(S->n || S->n_reads || !S->uploaded.empty() || S->chain || S->mt1) { kmahip_set_error("the mode of a session is chosen before its first batch"); return KMAHIP_EINVAL; }
+	if(S->sam_level == 1) { kmahip_set_error("SAM records at level 1 are not built for a session with paired input: the unmapped-mate flags of stages 2 and 3a"); return KMAHIP_EINVAL; }
 	S->pe = true;
 	return KMAHIP_OK;
 }
@@ -300,8 +306,20 @@ extern "C" int kmahip_session_set_pe(kmahip_session *S) {
 extern "C" int kmahip_session_set_chain(kmahip_session *S, const kmahip_chain_params *cp) {
 	if(!S) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	if(S->n || S->n_reads || !S->uploaded.empty() || S->mt1 || S->pe) { kmahip_set_error("the mode of a session is chosen before its first batch"); return KMAHIP_EINVAL; }
+	if(S->sam_level) { kmahip_set_error("SAM records (kmahip_session_set_sam) are not built for a session in the default mode (without -1t1)"); return KMAHIP_EINVAL; }
 	S->chain = true;
 	if(cp) S->cp = *cp; else { S->cp.minlen = 16; S->cp.pad_ = 0; S->cp.coverT = 0.1; S->cp.mrs = 0.5; }
+	return KMAHIP_OK;
+}
+
+extern "C" int kmahip_session_set_sam(kmahip_session *S, int level, const char *path, const char *program, const char *cmdline) {
+	if(!S || !path) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(level < 1) { kmahip_set_error("kmahip_session_set_sam: level %d (the value of -sam) must be positive", level); return KMAHIP_EINVAL; }
+	if(S->n || S->n_reads || !S->uploaded.empty()) { kmahip_set_error("the mode of a session is chosen before its first batch"); return KMAHIP_EINVAL; }
+	if(S->chain) { kmahip_set_error("SAM records are not built for a session in the default mode (without -1t1): its records carry query bounds"); return KMAHIP_EINVAL; }
+	if(S->mt1) { kmahip_set_error("SAM records are not built for a -Mt1 session"); return KMAHIP_EINVAL; }
+	if(S->pe && level == 1) { kmahip_set_error("SAM records at level 1 are not built for a session with paired input: the unmapped-mate flags of stages 2 and 3a"); return KMAHIP_EINVAL; }
+	S->sam_level = level; S->sam_path = path; S->sam_program = program ? program : "kmahip"; S->sam_cl = cmdline != nullptr; S->sam_cmdline = cmdline ? cmdline : "";
 	return KMAHIP_OK;
 }
 
@@ -831,7 +849,7 @@ int kmahip_frag_write_dev(kmahip_db *db, const kmahip_reads *W, const char *d_na
 }
 
 // ConClave, statistics, traceback, pile-up, consensus and the three files. ms[8]: uploads (summed over the batches), stages 2 + 3a
-// (summed), ConClave + statistics, traceback, pile-up + consensus, .res + .fsa, fragment rows, (unused).
+// (summed), ConClave + statistics, traceback, pile-up + consensus, .res + .fsa, fragment rows, SAM records (-Mt1: fragment rows made beside the batches).
 extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, int write_fsa, int write_frag, int64_t *n_reads, int64_t *n_rows_out, double ms[8]) {
 	if(!S || !out_prefix || !ms) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	kmahip_db *db = S->db;
@@ -868,7 +886,14 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 		kmahip_read_batch hb;
 		session_pe_view(S, 0, n, &hb);
 		int64_t n_frag_rows = 0;
-		KmaPeDev pd{S->names.as<char>(), S->name_off.as<int64_t>(), S->h_text, S->text_chunk, &n_frag_rows};
+		KmaPeDev pd{S->names.as<char>(), S->name_off.as<int64_t>(), S->h_text, S->text_chunk, &n_frag_rows, 0, -1};
+		struct SamFd { int fd = -1; ~SamFd() { (void) kmahip_sam_close(fd); } } sam_fd;
+		if(S->sam_level) {
+			if(ws->pe_chain_on) { kmahip_set_error("SAM records are not built for paired input in the default mode (without -1t1)"); return KMAHIP_EINVAL; }
+			if((rc = kmahip_sam_header(db, S->sam_program.c_str(), S->sam_cl ? S->sam_cmdline.c_str() : nullptr, S->sam_path.c_str()))) return rc;
+			if((sam_fd.fd = kmahip_sam_open(S->sam_path.c_str(), true)) < 0) return KMAHIP_EIO;
+			pd.sam_level = S->sam_level; pd.sam_fd = sam_fd.fd;
+		}
 		std::vector<kmahip_res_row> rows(D);
 		std::vector<int64_t> a_cover(D, 0), a_len(D, 0), a_depth(D, 0), a_asm(D, 0), c_off(D, -1);
 		int64_t tbases = 0;
@@ -944,7 +969,8 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 
 	// stage 3b per batch on the finished vectors, the `.res` statistics
 	kmahip_conclave cc{};
-	int32_t *rc_all = nullptr, *nh_all = nullptr;
+	int32_t *rc_all = nullptr, *nh_all = nullptr, *fl_all = nullptr;
+	if(S->sam_level && (rc = B.get((size_t) n + 1, &fl_all, true))) return rc;
 	if((rc = B.get((size_t) n + 1, &cc.tmpl, true)) || (rc = B.get((size_t) n + 1, &cc.start, true)) || (rc = B.get((size_t) n + 1, &cc.end, true)) || (rc = B.get(D, &cc.w_scores, true)) ||
 	   (rc = B.get((size_t) n + 1, &rc_all, true)) || (rc = B.get((size_t) n + 1, &nh_all, true))) return rc;
 	for(Batch &b : S->batches) {
@@ -957,6 +983,7 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 		if((rc = kmahip_conclave_se_dev(db, ws, &d, &b.c, &b.h, &cb, s))) return rc;
 		HIP_TRY(hipMemcpyAsync(rc_all + b.r0, b.h.rc, (size_t) b.n * 4, hipMemcpyDeviceToDevice, s));
 		HIP_TRY(hipMemcpyAsync(nh_all + b.r0, b.h.n_hits, (size_t) b.n * 4, hipMemcpyDeviceToDevice, s));
+		if(fl_all) HIP_TRY(hipMemcpyAsync(fl_all + b.r0, b.h.flag, (size_t) b.n * 4, hipMemcpyDeviceToDevice, s));
 	}
 	std::vector<uint64_t> w(D);
 	HIP_TRY(hipMemcpy(w.data(), cc.w_scores, D * 8, hipMemcpyDeviceToHost));
@@ -973,6 +1000,15 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 	kmahip_traces tr{};
 	if((rc = B.get((size_t) 10 * n + 10, &tr.stats, true)) || (rc = B.get((size_t) n + 1, &tr.ops_off, true)) || (rc = B.get((size_t) n + 1, &tr.n_ops, true))) return rc;
 	for(Batch &b : S->batches) b.release();
+	// (SAM rows of what the read filter drops: the traceback keeps those alignments too -- their runs go into the same pool and count
+	// towards its size, the retry below included)
+	kmahip_trace_drops drops{};
+	const bool want_drops = S->sam_level && !(S->sam_level & 2096);
+	if(want_drops) {
+		if((rc = B.get((size_t) 6 * n + 6, &drops.stats, true)) || (rc = B.get((size_t) n + 1, &drops.ops_off, true)) || (rc = B.get((size_t) n + 1, &drops.n_ops, true)) ||
+		   (rc = kmahip_ws_set_trace_drops(ws, &drops))) return rc;
+	}
+	struct DropsOff { kmahip_ws *ws; ~DropsOff() { (void) kmahip_ws_set_trace_drops(ws, nullptr); } } drops_off{ws};
 	DevArr pool;
 	// (runs: a handful per short read; long reads with their errors leave one every few bases)
 	if((rc = pool.ensure((size_t) (6 * n + (1 << 20) + (S->max_len > 1024 ? S->words * 32 / 3 : 0)) * 4, 0, s))) return rc;
@@ -1027,9 +1063,26 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 		                               (prefix + ".frag.gz").c_str(), S->text_chunk, S->h_text, &n_frag_rows))) return rc;
 		if(n_rows_out) *n_rows_out = n_frag_rows;
 	}
+	double ms_rows = -1;
+	if(S->sam_level) {
+		// ---- the SAM records: header from the host, rows classified, ordered and formatted on the device (samout.hip)
+		ms_rows = since(t);
+		auto ts = std::chrono::steady_clock::now();
+		if((rc = kmahip_sam_header(db, S->sam_program.c_str(), S->sam_cl ? S->sam_cmdline.c_str() : nullptr, S->sam_path.c_str()))) return rc;
+		const int fd = kmahip_sam_open(S->sam_path.c_str(), true);
+		if(fd < 0) return KMAHIP_EIO;
+		KmaSamIn in{};
+		in.W = &W; in.d_names = S->names.as<char>(); in.d_name_off = S->name_off.as<int64_t>(); in.d_rc = rc_all; in.d_tmpl = cc.tmpl; in.d_nhits = nh_all; in.d_flag = fl_all;
+		in.tr = &tr; in.drops = want_drops ? &drops : nullptr; in.d_ok = d_ok; in.max_frag = mf; in.order = 0; in.level = S->sam_level;
+		int64_t sam_rows = 0;
+		rc = kmahip_sam_write_dev(db, &in, fd, S->text_chunk, S->h_text, &sam_rows, nullptr);
+		const int rc2 = kmahip_sam_close(fd);
+		if(rc || rc2) return rc ? rc : rc2;
+		ms[7] = since(ts);
+	}
 	text.join();
 	if(rc_text) { kmahip_set_error("%s", err_text.c_str()); return rc_text; }
 	ms[5] = ms_text;
-	ms[6] = since(t);
+	ms[6] = ms_rows >= 0 ? ms_rows : since(t);
 	return KMAHIP_OK;
 }
