@@ -850,6 +850,10 @@ int kmahip_align_get_stats(kmahip_ws *ws, kmahip_align_stats *st, void *stream);
 /* counting costs atomics in the kernel: off by default */
 int kmahip_scan_set_stats(kmahip_ws *ws, int on);
 int kmahip_scan_get_stats(kmahip_ws *ws, kmahip_scan_stats *st, void *stream);
+/* How the last scan launch on this workspace handed its live strand items to the first tier: out[0] as self-contained
+ * records (reads without N's of at most 192 bases, outside the exhaustive mode), out[1] as bare list entries (everything else,
+ * and every item with KMAHIP_SCAN_REC=0 in the environment). Read it before another stage is launched on the workspace. */
+int kmahip_ws_scan_routes(kmahip_ws *ws, void *stream, unsigned long long out[2]);
 
 /* work figures of the last long-read trace call on this workspace (kmahip_align_trace_mt1*, kmahip_run_mt1, or the trace stage
  * on reads over 1 kb): DP problems solved, their cells (rows x columns; rows x (band + 1) for banded ones), MEMs of the chained

@@ -33,6 +33,7 @@ extern "C" void kmahip_ws_destroy(kmahip_ws *ws) {
 	if(!ws) return;
 	(void) hipFree(ws->item_score); (void) hipFree(ws->item_n); (void) hipFree(ws->item_off);
 	(void) hipFree(ws->pool); (void) hipFree(ws->counters); (void) hipFree(ws->overflow_items); (void) hipFree(ws->active_items);
+	(void) hipFree(ws->recs);
 	(void) hipFree(ws->dense); (void) hipFree(ws->blk_sums);
 	for(int i = 0; i < 8; ++i) (void) hipFree(ws->stage[i]);
 	for(auto *ev : {ws->events, ws->events2, ws->events3, ws->events4}) {
@@ -99,6 +100,18 @@ extern "C" int kmahip_scan_get_stats(kmahip_ws *ws, kmahip_scan_stats *st, void 
 	HIP_TRY(hipMemcpyAsync(c, ws->counters, sizeof c, hipMemcpyDeviceToHost, (hipStream_t) stream));
 	HIP_TRY(hipStreamSynchronize((hipStream_t) stream));
 	st->probes = c[3]; st->value_elems = c[4]; st->active_strands = c[5]; st->hash_probes = c[6]; st->prefilter_probes = c[9];
+	return KMAHIP_OK;
+}
+
+// items the last scan launch took by record and from the bare list (KMAHIP_C_NREC, KMAHIP_C_NACT)
+extern "C" int kmahip_ws_scan_routes(kmahip_ws *ws, void *stream, unsigned long long out[2]) {
+	if(!ws || !out || !ws->counters) return KMAHIP_EINVAL;
+	unsigned long long c[KMAHIP_N_COUNTERS];
+	HIP_TRY(hipMemcpyAsync(c, ws->counters, sizeof c, hipMemcpyDeviceToHost, (hipStream_t) stream));
+	HIP_TRY(hipStreamSynchronize((hipStream_t) stream));
+	const unsigned long long cap = ws->rec_cap > 0 ? (unsigned long long) ws->rec_cap : 0ull;
+	out[0] = c[KMAHIP_C_NREC] < cap ? c[KMAHIP_C_NREC] : cap;
+	out[1] = c[KMAHIP_C_NACT];
 	return KMAHIP_OK;
 }
 

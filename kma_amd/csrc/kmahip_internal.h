@@ -10,6 +10,9 @@
 #define KMAHIP_EMPTY_VI 0xFFFFFFFFu
 #define KMAHIP_BUCKET_SLOTS 4
 #define KMAHIP_N_COUNTERS 24
+// slots of kmahip_ws::counters that scan.hip and api.hip both name: live strand items on the bare list, and as records
+#define KMAHIP_C_NACT 8
+#define KMAHIP_C_NREC 21
 #define KMAHIP_KBITS_MUL 0x85EBCA6Bu      // device counter words per workspace
 
 // Probe table in HBM: open hashing over 32-byte buckets of 4 (key, position)
@@ -82,11 +85,13 @@ struct kmahip_ws {
 	int64_t pool_scale;       // pool = cap_reads * 16 * pool_scale ints; doubled after an overflow
 	int mem_scale;            // MEM slots per (read, template) = the usual 64 (reads up to 1 kb) x this; raised by the runs when a read
 	                          // full of repeats carries more (status 3), 0 = 1
-	// counters (16): [0] pool top, [1] status, [2] n_overflow, [3] probes, [4] value elems, [5] active strands,
-	// [6] hash probes, [7] pair pool top, [8] active strand items, [9] prefilter probes
+	// counters (KMAHIP_N_COUNTERS): [0] pool top, [1] status, [2] n_overflow, [3] probes, [4] value elems, [5] active strands,
+	// [6] hash probes, [7] pair pool top, [8] live strand items on the bare list, [9] prefilter probes, [21] records
 	unsigned long long *counters;
 	int64_t *overflow_items;
 	int64_t *active_items;    // strand items that passed the prefilter (device-wide compaction)
+	uint64_t *recs;           // the live items the scan takes as 64-byte records (scan.hip: REC_WORDS), counters[21] of them
+	int64_t rec_cap;          // records the prefilter may write: cap_reads, or KMAHIP_SCAN_REC_CAP if that is less
 	int stats_on;
 	int timing_on;
 	std::vector<std::pair<hipEvent_t, hipEvent_t>> *events;

@@ -94,12 +94,20 @@ struct ScanArgs {
 	int64_t cat_bases;   // > 0: the prefilter files the template diagonal of its hit with every live strand item (bits 33.. of the
 	                     // list entry: position in `cat` minus strand position of the hit k-mer, + DIAG_BIAS; DIAG_NONE: none) and the
 	                     // scan's lanes try that diagonal before they probe
+	uint64_t *recs;      // the prefilter's records of the plain live items (counters[C_NREC] of them, at most rec_cap); NULL: every
+	int64_t rec_cap;     // live item goes to active_items
 };
 
 constexpr int64_t ITEM_MASK = (1ll << 33) - 1;          // a strand item: (read << 1) | strand, reads < 2^31
 constexpr int64_t DIAG_BIAS = 1ll << 20, DIAG_NONE = 0x7FFFFFFFll;      // (reads are at most 2^20 bases, `cat` below 2^30 when diagonals are filed)
+// A live item of a read without N's that is staged once (at most (SW - 1) * 32 bases) is handed to the scan as a self-contained
+// record of REC_WORDS words, 64 bytes: [0] the list entry above, [1] the read length, [2 .. 7] the six words of the read in
+// STRAND orientation that the scan's staging loop would put into its row of w_lds (zero past the read's last word). The scan reads
+// it in ONE round trip where the bare entry costs three dependent ones (entry -> len / seq_off / N_off -> words).
+constexpr int REC_WORDS = 8;
+static_assert(REC_WORDS - 2 == SW - 1, "a record carries the staged row but its last, always zero, word");
 
-enum { C_POOL = 0, C_STATUS = 1, C_NOVER = 2, C_PROBES = 3, C_VALS = 4, C_ACTIVE = 5, C_HASH = 6, C_PPOOL = 7, C_NACT = 8, C_PREF = 9, C_NOVER2 = 10, N_COUNTERS = KMAHIP_N_COUNTERS };
+enum { C_POOL = 0, C_STATUS = 1, C_NOVER = 2, C_PROBES = 3, C_VALS = 4, C_ACTIVE = 5, C_HASH = 6, C_PPOOL = 7, C_NACT = KMAHIP_C_NACT, C_PREF = 9, C_NOVER2 = 10, C_NREC = KMAHIP_C_NREC, N_COUNTERS = KMAHIP_N_COUNTERS };
 
 // two probes whose home buckets travel together (used after a miss: the k-mer starts behind a mismatch miss in a row)
 __device__ __forceinline__ void probe2(const DevDB &db, uint32_t key1, uint32_t key2, uint32_t &r1, uint32_t &r2) {
@@ -276,20 +284,21 @@ constexpr int PF_ITEMS = PF_BLOCK * PF_ROUNDS;             // items per workgrou
 
 template <bool STATS>
 __global__ __launch_bounds__(THREADS) void scan_prefilter_kernel(const ScanArgs A) {
-	__shared__ int64_t s_list[PF_ITEMS];
-	__shared__ uint32_t s_n, s_np, s_nt;
-	__shared__ unsigned long long s_base;
+	__shared__ int64_t s_list[PF_ITEMS];      // the bare entries from the front, the entries that become records from the back
+	__shared__ uint32_t s_n, s_nr, s_np, s_nt;
+	__shared__ unsigned long long s_base, s_rbase;
+	__shared__ uint32_t s_room;
 	const DevDB &db = A.db;
 	const int tid = threadIdx.x;
 	const int k = (int) db.kmersize;
 	const int plane = tid & (PF_PLANES - 1);
-	if(tid == 0) { s_n = 0; s_np = 0; s_nt = 0; }
+	if(tid == 0) { s_n = 0; s_nr = 0; s_np = 0; s_nt = 0; }
 	__syncthreads();
 	uint32_t nprobe = 0, ntable = 0;      // k-mers resolved / of them by a gather into the probe table
 	for(int rd = 0; rd < PF_ROUNDS; ++rd) {
 		const int64_t item = (int64_t) blockIdx.x * PF_ITEMS + rd * PF_BLOCK + (tid / PF_PLANES);
 		const int64_t r = item >> 1;
-		bool hit = false;
+		bool hit = false, plain = false;   // plain: the scan can take the item from a record
 		int64_t diag = DIAG_NONE;          // template diagonal of the hit: its position in `cat` minus its strand position in the read
 		if(r < A.n_reads) {
 			const int L = A.len[r], strand = (int) (item & 1), npos = L - k + 1;
@@ -297,6 +306,7 @@ __global__ __launch_bounds__(THREADS) void scan_prefilter_kernel(const ScanArgs 
 				const uint64_t *rs = A.seq + A.seq_off[r];
 				const int64_t no = A.N_off[r];
 				const int nN = (int) (A.N_off[r + 1] - no);
+				plain = A.recs && nN == 0 && L <= (SW - 1) * 32 && !A.exhaustive;
 #ifdef KMAHIP_DIAG
 				if(A.exhaustive || (A.ablate & 4)) {
 #else
@@ -379,24 +389,59 @@ __global__ __launch_bounds__(THREADS) void scan_prefilter_kernel(const ScanArgs 
 		const unsigned long long bal = __ballot(hit);
 		const bool any = ((bal >> ((tid & 63) & ~(PF_PLANES - 1))) & ((1ull << PF_PLANES) - 1ull)) != 0ull;
 		if(plane == 0 && r < A.n_reads) {
-			if(any) s_list[atomicAdd(&s_n, 1u)] = item | ((A.cat_bases > 0 && diag != DIAG_NONE ? diag + DIAG_BIAS : DIAG_NONE) << 33);
+			if(any) {
+				const int64_t ent = item | ((A.cat_bases > 0 && diag != DIAG_NONE ? diag + DIAG_BIAS : DIAG_NONE) << 33);
+				if(plain) s_list[PF_ITEMS - 1 - atomicAdd(&s_nr, 1u)] = ent;
+				else s_list[atomicAdd(&s_n, 1u)] = ent;
+			}
 			else { A.item_score[item] = 0; A.item_n[item] = 0; A.item_off[item] = 0; }
 		}
 	}
 	if(STATS && nprobe) { atomicAdd(&s_np, nprobe); atomicAdd(&s_nt, ntable); }
 	__syncthreads();
-	const uint32_t nact = s_n;
+	const uint32_t nact = s_n, nrec = s_nr;
 	if(tid == 0) {
-		s_base = nact ? atomicAdd(&A.counters[C_NACT], (unsigned long long) nact) : 0ull;
+		// one atomic per list. The records that the buffer has no room for (every place below rec_cap has ONE owner, who fills it:
+		// the scan reads min(counter, rec_cap) records) go behind the workgroup's bare entries
+		uint32_t room = 0;
+		if(nrec) {
+			const unsigned long long rb = atomicAdd(&A.counters[C_NREC], (unsigned long long) nrec);
+			s_rbase = rb;
+			room = rb >= (unsigned long long) A.rec_cap ? 0u : (uint32_t) min((unsigned long long) nrec, (unsigned long long) A.rec_cap - rb);
+		}
+		s_room = room;
+		const uint32_t nbare = nact + (nrec - room);
+		s_base = nbare ? atomicAdd(&A.counters[C_NACT], (unsigned long long) nbare) : 0ull;
 		if(STATS) {
 			atomicAdd(&A.counters[C_PROBES], (unsigned long long) s_np);
 			atomicAdd(&A.counters[C_HASH], (unsigned long long) s_nt);
 			atomicAdd(&A.counters[C_PREF], (unsigned long long) s_np);
-			atomicAdd(&A.counters[C_ACTIVE], (unsigned long long) nact);
+			atomicAdd(&A.counters[C_ACTIVE], (unsigned long long) (nact + nrec));
 		}
 	}
 	__syncthreads();
 	for(uint32_t i = tid; i < nact; i += THREADS) A.active_items[s_base + i] = s_list[i];
+	// the records, one lane each: the six words by the arithmetic of the scan's staging loop, then 64 contiguous bytes in 16-byte
+	// stores (the read's words were fetched by this workgroup a moment ago: they come from the caches)
+	const uint32_t room = s_room;
+	for(uint32_t i = tid; i < nrec; i += THREADS) {
+		const int64_t ent = s_list[PF_ITEMS - 1 - i];
+		if(i >= room) { A.active_items[s_base + nact + (i - room)] = ent; continue; }
+		const int64_t it = ent & ITEM_MASK, r = it >> 1;
+		const int L = A.len[r], nw = (L + 31) >> 5;
+		const uint64_t *rs = A.seq + A.seq_off[r];
+		uint64_t w[REC_WORDS];
+		w[0] = (uint64_t) ent; w[1] = (uint64_t) (uint32_t) L;
+#pragma unroll
+		for(int x = 0; x < SW - 1; ++x) {
+			uint64_t v = 0;
+			if(x < nw) v = (it & 1) ? strand_win(rs, L, 1, x << 5) : rs[x];
+			w[2 + x] = v;
+		}
+		ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(A.recs + (s_rbase + i) * REC_WORDS);
+#pragma unroll
+		for(int x = 0; x < REC_WORDS / 2; ++x) dst[x] = make_ulonglong2(w[2 * x], w[2 * x + 1]);
+	}
 }
 
 // ---- scan: one workgroup = GROUP active strand items, 16 lanes each ----------------------------------------
@@ -416,8 +461,12 @@ __device__ __forceinline__ int compact_threads(bool flag, int tid, int32_t *wcnt
 	return total;
 }
 
-template <bool STATS, int MODE, int TSLOTS>
+// REC: the items are the prefilter's records (A.recs), not list entries: only the front of the kernel differs -- no read has an
+// N and every read is staged once, both known to the compiler. LOOP: a fixed grid that loops over the groups (the second tier,
+// and the first tier's launch over the bare list, which is short whenever records are written).
+template <bool STATS, int MODE, int TSLOTS, bool REC = false, bool LOOP = (TSLOTS != TS1)>
 __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHREADS == 256 ? 2 : 3)) void scan_se_kernel(const ScanArgs A) {
+	static_assert(!REC || TSLOTS == TS1, "records feed the first tier only");
 	__shared__ uint32_t v_id[VSLOTS * SG];              // value-list offset per slot (MISS = free)
 	__shared__ uint32_t v_mask[MW * VSLOTS * SG];       // positions of the pass whose k-mer carries that value list
 	// forward words: if every read of the group fits in SW-1 words they are staged ONCE and serve all passes;
@@ -444,13 +493,42 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 	const DevDB &db = A.db;
 	const int tid = threadIdx.x;
 	const int k = (int) db.kmersize;
-	const int64_t n_active = (int64_t) A.counters[A.in_count];
-	// first tier: one group of items per workgroup; second tier: a fixed grid that loops over the (usually few) groups
+	const int64_t n_active = REC ? min((int64_t) A.counters[C_NREC], A.rec_cap) : (int64_t) A.counters[A.in_count];
+	// all-candidates mode: the first tier's two launches share the fixed places of the pool (see the finish), the records first
+	int64_t place0 = 0, n_places = n_active;
+	if(MODE && TSLOTS == TS1 && A.recs) {
+		if(REC) n_places += (int64_t) A.counters[C_NACT];
+		else { place0 = min((int64_t) A.counters[C_NREC], A.rec_cap); n_places += place0; }
+	}
+	// first tier: one group of items per workgroup; LOOP: a fixed grid that loops over the (usually few) groups
 	int64_t first = (int64_t) blockIdx.x * SG;
 	if(first >= n_active) return;
 	do {
 	const int ng = (int) min((int64_t) SG, n_active - first);
 
+	if(REC) {
+		// one round trip: lane sl of item g fetches word sl of the item's row, lane 0 the header as well
+		const int g = tid & (SG - 1), sl = tid / SG;
+		const uint64_t *rec = A.recs + (first + g) * REC_WORDS;
+		uint64_t wv = 0;
+		ulonglong2 hd = make_ulonglong2(0ull, 0ull);
+		if(g < ng) {
+			if(sl == 0) hd = *reinterpret_cast<const ulonglong2 *>(rec);
+			if(sl < SW - 1) wv = rec[2 + sl];
+		}
+		if(sl < SW) w_lds[g * SW + sl] = wv;
+		if(tid < SG) {
+			const int64_t raw = (int64_t) hd.x;
+			const int L = (int) (uint32_t) hd.y;
+			int dg = (int) DIAG_NONE;
+			if(tid < ng && A.cat_bases > 0 && (raw >> 33) != 0) dg = (int) (raw >> 33);
+			s_len[tid] = L; s_item[tid] = raw & ITEM_MASK; s_diag[tid] = dg;
+			int mx = L;
+#pragma unroll
+			for(int d = SG / 2; d; d >>= 1) mx = max(mx, __shfl_xor(mx, d, SG));
+			if(tid == 0) { s_gmax = mx - k + 1; s_qn = 0; }
+		}
+	} else
 	if(tid < SG) {
 		int L = 0, nN = 0; int64_t so = 0, no = 0, it = 0;
 		int dg = (int) DIAG_NONE;
@@ -470,11 +548,11 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 	}
 	if(tid < 3) s_stats[tid] = 0;
 	__syncthreads();
-	const bool staged_once = !s_anylong;
+	const bool staged_once = REC || !s_anylong;
 	const int gmax = s_gmax;
 	// the words are staged in STRAND orientation (word w = strand bases 32w .. 32w+31: for the reverse strand the reverse
 	// complement of the forward words), so the passes below never reverse-complement a k-mer or a walk window
-	if(staged_once) {
+	if(!REC && staged_once) {
 		for(int idx = tid; idx < SG * SW; idx += STHREADS) {
 			const int g = idx / SW, w = idx - g * SW;
 			const int L = s_len[g];
@@ -553,7 +631,7 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 			};
 			// one k-mer start on its own (position jj of the pass, item g): probe, and a run of one position when it hits
 			auto resolve = [&](int g, int jj) {
-				const int L = s_len[g], strand = (int) (s_item[g] & 1), nN = s_nN[g];
+				const int L = s_len[g], strand = (int) (s_item[g] & 1), nN = REC ? 0 : s_nN[g];
 				const int p = c0 + jj;
 				const int q = strand ? (L - k - p) : p;
 				if(nN && window_has_N(A.N + s_noff[g], nN, q, k)) return;
@@ -586,7 +664,7 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 				// waiting for five dependent gathers (profiles/r3_scan_phase_counters.md: phase 1 was 28 % of the instructions
 				// and 47 % of the time).
 				if(g < ng && c0 + j0 < s_len[g] - k + 1) {
-					const int L = s_len[g], npos = L - k + 1, strand = (int) (s_item[g] & 1), nN = s_nN[g];
+					const int L = s_len[g], npos = L - k + 1, strand = (int) (s_item[g] & 1), nN = REC ? 0 : s_nN[g];
 					const int32_t *Nl = A.N + s_noff[g];
 					const uint64_t *wsrc = &w_lds[g * SW];
 					const int wb = staged_once ? 0 : (c0 >> 5);
@@ -859,9 +937,9 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 			// 6 ns a workgroup -- as long as the whole scan took. The lists take fixed places instead (the item's place in the active
 			// list x the most a first-tier table holds) whenever the pool has the room; the second tier and the best-templates mode
 			// (a list longer than the inline slots is rare there) keep the counter.
-			const bool fixed = MODE && TSLOTS == TS1 && n_active * (int64_t) (TSLOTS - 2) <= A.pool_cap - A.pool_tail0;
+			const bool fixed = MODE && TSLOTS == TS1 && n_places * (int64_t) (TSLOTS - 2) <= A.pool_cap - A.pool_tail0;
 			if(fixed) {
-				pbase = (unsigned long long) first * (TSLOTS - 2); incl = tid * (TSLOTS - 2) + want;
+				pbase = (unsigned long long) (place0 + first) * (TSLOTS - 2); incl = tid * (TSLOTS - 2) + want;
 				if(first == 0 && tid == 0) atomicAdd(&A.counters[C_POOL], (unsigned long long) (n_active * (int64_t) (TSLOTS - 2)));      // (the later tiers allocate behind the fixed places)
 			}
 			else if(tid == 0 && tot) pbase = atomicAdd(&A.counters[C_POOL], (unsigned long long) tot);
@@ -872,7 +950,9 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 			if(over) { A.out_over[obase + (unsigned long long) (oincl - 1)] = item; s_off[g] = -1; }
 			else if(mine) {
 				if(nb) off = want ? A.pool_tail0 + (int64_t) pbase + (incl - want) : item * INL;
-				if(nb && off + nb > A.pool_cap) { atomicMax(&A.counters[C_STATUS], 1ull); s_off[g] = -1; }
+				// (pool exhausted: the host repeats the call with a larger one; the item is left without a list, so that nothing
+				// downstream follows an offset behind the pool)
+				if(nb && off + nb > A.pool_cap) { atomicMax(&A.counters[C_STATUS], 1ull); s_off[g] = -1; nb = 0; off = 0; }
 				else s_off[g] = nb ? off : -1;
 			}
 			if(mine) {
@@ -911,7 +991,7 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 		}
 		__syncthreads();
 	}
-	if(TSLOTS == TS1) break;          // (straight-line code in the first tier)
+	if(!LOOP) break;          // (straight-line code in the first tier)
 	first += (int64_t) gridDim.x * SG;
 	} while(first < n_active);
 }
@@ -1009,7 +1089,7 @@ __global__ __launch_bounds__(64) void scan_dense_kernel(const ScanArgs A) {
 			off = __shfl(off, 0);
 			if(off + nb <= A.pool_cap) {
 				for(int e = lane; e < nlist; e += 64) { A.pool[off + e] = list[e]; A.pool_sc[off + e] = max(0, (int) score[list[e]]); }
-			} else if(lane == 0) atomicMax(&A.counters[C_STATUS], 1ull);
+			} else { if(lane == 0) atomicMax(&A.counters[C_STATUS], 1ull); nb = 0; off = 0; }
 		} else if(hits) {
 			for(int e = lane; e < nlist; e += 64) best = max(best, max(0, (int) score[list[e]]));
 			for(int d = 32; d; d >>= 1) best = max(best, __shfl_xor(best, d));
@@ -1027,7 +1107,7 @@ __global__ __launch_bounds__(64) void scan_dense_kernel(const ScanArgs A) {
 						if(is) A.pool[off + w + __popcll(m & below)] = list[e];
 						w += __popcll(m);
 					}
-				} else if(lane == 0) atomicMax(&A.counters[C_STATUS], 1ull);
+				} else { if(lane == 0) atomicMax(&A.counters[C_STATUS], 1ull); nb = 0; off = 0; }
 			} else nb = 0;
 		}
 		for(int e = lane; e < nlist; e += 64) { const int t = list[e]; score[t] = 0; ext[t] = -1; }
@@ -1720,9 +1800,49 @@ static int64_t diag_cat_bases(const kmahip_db *db) {
 	return total > 0 && total < (1ll << 30) ? total : 0;
 }
 
+// Does the prefilter write records for this batch? KMAHIP_SCAN_REC=0 (read per launch): never. Nor in the exhaustive mode, nor for
+// a batch whose caller declares a read beyond the record's 192 bases (kmahip_reads::max_len; 0 = not told): the bare list's
+// looping launch is for a short list -- with 35 spilled dwords it takes 3.8 ms more per 10 M reads than the straight-line kernel
+// when every item goes through it -- so a batch of long reads keeps the one launch.
+static bool scan_records_on(const kmahip_ws *ws, const kmahip_reads *reads, const kmahip_params *p) {
+	if(const char *e = getenv("KMAHIP_SCAN_REC")) if(!atoi(e)) return false;
+	return !p->exhaustive && ws->rec_cap > 0 && reads->max_len <= (SW - 1) * 32;
+}
+
+// the first tier's launch over the bare list: a fixed grid that loops, every wave slot of the device taken once
+static unsigned bare_grid() {
+	static unsigned grid = 0;
+	if(!grid) {
+		int dev = 0, cus = 0;
+		if(hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+		grid = (unsigned) cus * 4u * KMAHIP_SCAN_WAVES / (STHREADS / 64);      // 4 SIMDs per CU
+	}
+	return grid;
+}
+
+// first tier: the records (one group per workgroup), then the bare list on the looping grid; without records the bare list holds
+// every live item and gets one group per workgroup (an upper bound: the workgroups past the live count exit)
+template <int MODE>
+static void launch_first_tier(const ScanArgs &A, bool stats, hipStream_t stream) {
+	if(!A.recs) {
+		const unsigned grid = (unsigned) ((2 * A.n_reads + SG - 1) / SG);
+		if(stats) hipLaunchKernelGGL((scan_se_kernel<true, MODE, TS1>), dim3(grid), dim3(STHREADS), 0, stream, A);
+		else hipLaunchKernelGGL((scan_se_kernel<false, MODE, TS1>), dim3(grid), dim3(STHREADS), 0, stream, A);
+		return;
+	}
+	{
+		const unsigned rgrid = (unsigned) ((std::min(A.rec_cap, 2 * A.n_reads) + SG - 1) / SG);
+		if(stats) hipLaunchKernelGGL((scan_se_kernel<true, MODE, TS1, true>), dim3(rgrid), dim3(STHREADS), 0, stream, A);
+		else hipLaunchKernelGGL((scan_se_kernel<false, MODE, TS1, true>), dim3(rgrid), dim3(STHREADS), 0, stream, A);
+	}
+	if(stats) hipLaunchKernelGGL((scan_se_kernel<true, MODE, TS1, false, true>), dim3(bare_grid()), dim3(STHREADS), 0, stream, A);
+	else hipLaunchKernelGGL((scan_se_kernel<false, MODE, TS1, false, true>), dim3(bare_grid()), dim3(STHREADS), 0, stream, A);
+}
+
 static int ws_reserve(kmahip_ws *ws, int64_t n_reads) {
 	kmahip_db *db = ws->db;
 	if(n_reads > ws->cap_reads) {
+		(void) hipFree(ws->recs); ws->recs = nullptr;
 		(void) hipFree(ws->item_score); (void) hipFree(ws->item_n); (void) hipFree(ws->item_off);
 		(void) hipFree(ws->pool); (void) hipFree(ws->overflow_items); (void) hipFree(ws->blk_sums); (void) hipFree(ws->active_items);
 		ws->item_score = ws->item_n = nullptr; ws->item_off = nullptr; ws->pool = nullptr;
@@ -1736,10 +1856,14 @@ static int ws_reserve(kmahip_ws *ws, int64_t n_reads) {
 		HIP_TRY(hipMalloc((void **) &ws->pool, ws->pool_cap * sizeof(int32_t)));
 		HIP_TRY(hipMalloc((void **) &ws->overflow_items, cap * 4 * sizeof(int64_t)));       // first-tier list + second-tier list
 		HIP_TRY(hipMalloc((void **) &ws->active_items, cap * 2 * sizeof(int64_t)));
+		HIP_TRY(hipMalloc((void **) &ws->recs, cap * REC_WORDS * sizeof(uint64_t)));
 		ws->blk_cap = (cap + CB - 1) / CB + 1;
 		HIP_TRY(hipMalloc((void **) &ws->blk_sums, ws->blk_cap * sizeof(int64_t)));
 		ws->cap_reads = cap;
 	}
+	// (KMAHIP_SCAN_REC_CAP: fewer records than the buffer holds, for the tests of the spill to the bare list)
+	ws->rec_cap = ws->cap_reads;
+	if(const char *e = getenv("KMAHIP_SCAN_REC_CAP")) ws->rec_cap = std::max<int64_t>(0, std::min<int64_t>(ws->cap_reads, atoll(e)));
 	if(!ws->counters) { HIP_TRY(hipMalloc((void **) &ws->counters, N_COUNTERS * sizeof(unsigned long long))); HIP_TRY(hipMemset(ws->counters, 0, N_COUNTERS * sizeof(unsigned long long))); }
 	if(!ws->dense) {
 		// overflow scratch: up to 4096 concurrent items, bounded to 1 GiB
@@ -1768,6 +1892,7 @@ int kmahip_launch_scan_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	A.pool = ws->pool; A.pool_cap = ws->pool_cap; A.counters = ws->counters; A.overflow_items = ws->overflow_items;
 	A.dense = ws->dense; A.dense_slots = ws->dense_slots; A.active_items = ws->active_items;
 	A.mode = 0; A.pool_sc = nullptr; A.pool_tail0 = 2 * n * INL; A.cat_bases = diag_cat_bases(db);
+	A.recs = scan_records_on(ws, reads, p) ? ws->recs : nullptr; A.rec_cap = ws->rec_cap;
 	A.ablate = 0;
 #ifdef KMAHIP_DIAG
 	if(const char *e = getenv("KMAHIP_ABLATE_SCAN")) A.ablate = atoi(e);
@@ -1781,7 +1906,6 @@ int kmahip_launch_scan_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	}
 	const int64_t items = 2 * n;
 	const unsigned pgrid = (unsigned) ((items + PF_ITEMS - 1) / PF_ITEMS);
-	const unsigned grid = (unsigned) ((items + SG - 1) / SG);      // scan: upper bound; workgroups past the active count exit
 	hipEvent_t ev0 = nullptr, ev1 = nullptr, evp = nullptr, evq = nullptr;
 	if(ws->timing_on) {
 		HIP_TRY(hipEventCreate(&ev0)); HIP_TRY(hipEventCreate(&ev1)); HIP_TRY(hipEventCreate(&evp)); HIP_TRY(hipEventCreate(&evq));
@@ -1792,8 +1916,7 @@ int kmahip_launch_scan_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	if(ws->timing_on) { HIP_TRY(hipEventRecord(evq, stream)); HIP_TRY(hipEventRecord(ev0, stream)); }
 	int64_t *over1 = ws->overflow_items, *over2 = ws->overflow_items + 2 * ws->cap_reads;
 	A.in_items = ws->active_items; A.in_count = C_NACT; A.out_over = over1; A.out_count = C_NOVER;
-	if(ws->stats_on) hipLaunchKernelGGL((scan_se_kernel<true, 0, TS1>), dim3(grid), dim3(STHREADS), 0, stream, A);
-	else hipLaunchKernelGGL((scan_se_kernel<false, 0, TS1>), dim3(grid), dim3(STHREADS), 0, stream, A);
+	launch_first_tier<0>(A, ws->stats_on != 0, stream);
 	if(ws->timing_on) {
 		HIP_TRY(hipEventRecord(ev1, stream));
 		if(!ws->events) ws->events = new std::vector<std::pair<hipEvent_t, hipEvent_t>>();
@@ -1832,6 +1955,7 @@ int kmahip_launch_chain_anchors(kmahip_db *db, kmahip_ws *ws, const kmahip_reads
 	S.pool = ws->pool; S.pool_cap = ws->pool_cap; S.counters = ws->counters; S.overflow_items = ws->overflow_items;
 	S.dense = ws->dense; S.dense_slots = ws->dense_slots; S.active_items = ws->active_items;
 	S.mode = 0; S.pool_sc = nullptr; S.pool_tail0 = 2 * n * INL; S.ablate = 0; S.cat_bases = 0;
+	S.recs = nullptr; S.rec_cap = 0;          // (the anchor kernel takes every live item from the bare list)
 	S.in_items = ws->active_items; S.in_count = C_NACT; S.out_over = ws->overflow_items; S.out_count = C_NOVER;
 	A.pool = pool; A.pool_cap = pool_cap; A.a_off = a_off; A.a_n = a_n; A.slow = slow; A.cnt = cnt;
 	HIP_TRY(hipMemsetAsync(ws->counters, 0, sizeof(unsigned long long), stream));
@@ -1870,6 +1994,7 @@ int kmahip_launch_scan_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	A.pool = ws->pool; A.pool_cap = ws->pool_cap; A.counters = ws->counters; A.overflow_items = ws->overflow_items;
 	A.dense = ws->dense; A.dense_slots = ws->dense_slots; A.active_items = ws->active_items;
 	A.ablate = 0; A.mode = 1; A.pool_sc = ws->pool_sc; A.pool_tail0 = 0; A.cat_bases = diag_cat_bases(db);
+	A.recs = scan_records_on(ws, reads, p) ? ws->recs : nullptr; A.rec_cap = ws->rec_cap;
 #ifdef KMAHIP_DIAG
 	if(const char *e = getenv("KMAHIP_ABLATE_SCAN")) A.ablate = atoi(e);
 #endif
@@ -1884,11 +2009,9 @@ int kmahip_launch_scan_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	if(ws->stats_on) hipLaunchKernelGGL((scan_prefilter_kernel<true>), dim3((unsigned) ((2 * n + PF_ITEMS - 1) / PF_ITEMS)), dim3(THREADS), 0, stream, A);
 	else hipLaunchKernelGGL((scan_prefilter_kernel<false>), dim3((unsigned) ((2 * n + PF_ITEMS - 1) / PF_ITEMS)), dim3(THREADS), 0, stream, A);
 	if(ws->timing_on) { HIP_TRY(hipEventRecord(evq, stream)); HIP_TRY(hipEventRecord(ev0, stream)); }
-	const unsigned grid = (unsigned) ((2 * n + SG - 1) / SG);
 	int64_t *over1 = ws->overflow_items, *over2 = ws->overflow_items + 2 * ws->cap_reads;
 	A.in_items = ws->active_items; A.in_count = C_NACT; A.out_over = over1; A.out_count = C_NOVER;
-	if(ws->stats_on) hipLaunchKernelGGL((scan_se_kernel<true, 1, TS1>), dim3(grid), dim3(STHREADS), 0, stream, A);
-	else hipLaunchKernelGGL((scan_se_kernel<false, 1, TS1>), dim3(grid), dim3(STHREADS), 0, stream, A);
+	launch_first_tier<1>(A, ws->stats_on != 0, stream);
 	if(ws->timing_on) {
 		HIP_TRY(hipEventRecord(ev1, stream));
 		if(!ws->events) ws->events = new std::vector<std::pair<hipEvent_t, hipEvent_t>>();
