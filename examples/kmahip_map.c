@@ -215,7 +215,7 @@ static void *xcalloc(size_t n, size_t sz) { void *p = calloc(n ? n : 1, sz); if(
 static void usage(void) {
 	fprintf(stderr, "usage: kmahip_map (-i reads.fq[.gz] | -ipe r1.fq[.gz] r2.fq[.gz] [-apm p|u] | -int interleaved.fq[.gz] [-apm p|u]) -t_db <index prefix> -o <output prefix> [-1t1] [-Mt1 <template>] [-bcNano] [-bc90] [-bc <support>] [-bcg] [-ref_fsa [n]] [-dense]\n"
 	                "       [-t threads] [-nc] [-na] [-nf] [-mf fragments] [-ml len] [-xl len] [-mp phred] [-mi phred] [-eq q] [-mq q] [-ts bases] [-mrs f] [-mrc f] [-mct f]\n"
-	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev] [-sam n]\n"
+	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev] [-sam n] [-ef [n]]\n"
 	                "       [-reward n] [-gapopen n] [-gapextend n] [-localopen n] [-Npenalty n] [-per n] [-transition n] [-transversion n] [-penalty n] [-cge]\n"
 	                "       (-s1dev, like -gpus not an option of kma: stage 1 of plain FASTQ input on the device; one rank, -1t1 only; its batches close at a quarter\n"
 	                "        of a gigabase of their own accord, KMAHIP_MAP_BATCH_BASES does not apply to them)\n"
@@ -300,6 +300,7 @@ int main(int argc, char **argv) {
 	char *list1[256], *list2[256]; int n_files = 0;          /* the input files (mate files side by side) */
 	int mt1 = 0, one2one = 0, chain = 0, apm = 0, no_cons = 0, no_frag = 0, no_aln = 0, gpus = 0, threads = 0, bcd = 1, s1dev = 0;
 	int sam = 0, sam_bare = 0, status_opt = 0;   /* -sam [n] (kma.c:1005-1017); -status, which the reference refuses beside it (kma.c:1254) */
+	int ef = 0;                                  /* -ef [n] (kma.c:938-948): the extended-features file <out>.mapstat */
 	int base_call = 0, sig_mode = 0, ref_fsa = 0, dense = 0;      /* as kmahip_assemble_opts.caller (0-2 here) / .sig90; printconsensus.c's ref_fsa */
 	double support = 0;
 	long long max_frag = 0;
@@ -392,6 +393,14 @@ int main(int argc, char **argv) {
 				if(*end) { fprintf(stderr, "Invalid argument at \"-sam\".\n"); return 1; }
 			}
 		}
+		else if(!strcmp(o, "-ef")) {                                                            /* kma.c:938-948: a value is optional, every non-zero one means the same to runKMA */
+			ef = 1;
+			if(a + 1 < argc && argv[a + 1][0] != '-') {
+				char *end = NULL;
+				ef = (int) strtol(argv[++a], &end, 10);
+				if(*end) { fprintf(stderr, "Invalid argument at \"-ef\".\n"); return 1; }
+			}
+		}
 		else if(!strcmp(o, "-tmp") || !strcmp(o, "-verbose")) { if(a + 1 < argc && argv[a + 1][0] != '-') ++a; }
 		else if(!strcmp(o, "-mem_mode")) mem_mode = 1;                                           /* kma.c:547 */
 		else if(!strcmp(o, "-lc")) lc = 1;                                                      /* kma.c:694-701 */
@@ -478,6 +487,15 @@ int main(int argc, char **argv) {
 		else if(getenv("KMAHIP_COMM_FORCE_RCCL") && getenv("KMAHIP_COMM_FORCE_RCCL")[0] == '1') why = "KMAHIP_COMM_FORCE_RCCL";
 		else if(mem_mode) why = "-mem_mode";
 		if(why) { fprintf(stderr, "kmahip_map: -sam is not built for %s: it serves the -1t1 run of one rank: -sam n on single-end input, -sam n with n != 1 on -ipe input\n", why); return 2; }
+	}
+	if(ef && !mt1) {
+		/* the extended features are summed behind the pile-up of one rank's session; runKMA_Mt1 writes no such file (mt1.c:313, 378), so
+		 * -Mt1 -ef is taken and leaves none, like there */
+		const char *why = NULL;
+		if(gpus > 1 || getenv("KMAHIP_RANK") || getenv("RANK")) why = "-gpus N (several ranks)";
+		else if(getenv("KMAHIP_MAP_ONE_BATCH")) why = "KMAHIP_MAP_ONE_BATCH";
+		else if(getenv("KMAHIP_COMM_FORCE_RCCL") && getenv("KMAHIP_COMM_FORCE_RCCL")[0] == '1') why = "KMAHIP_COMM_FORCE_RCCL";
+		if(why) { fprintf(stderr, "kmahip_map: -ef is not built for %s: the .mapstat file is written by the run of one rank, batch by batch\n", why); return 2; }
 	}
 	if(threads) {
 		char v[16];
@@ -572,7 +590,18 @@ int main(int argc, char **argv) {
 			if(kmahip_session_set_sam(ses, sam, "-", "kmahip_map", cmdline)) die("session");
 			free(cmdline);
 		}
+		if(ef && !mt1) {	/* ## command: the arguments joined by blanks (strjoin, kma.c:1614); ## database: -t_db without its folder */
+			size_t cl = 1;
+			for(int a = 0; a < argc; ++a) cl += strlen(argv[a]) + 1;
+			char *cmdline = malloc(cl);
+			if(!cmdline) fail("out of memory");
+			cmdline[0] = 0;
+			for(int a = 0; a < argc; ++a) { if(a) strcat(cmdline, " "); strcat(cmdline, argv[a]); }
+			if(kmahip_session_set_ef(ses, cmdline, prefix)) die("session");
+			free(cmdline);
+		}
 		int batches = 0;
+		int64_t s1_records = 0;          /* what stage 1 passed on, a couple counting once: the ## fragmentCount of -ef (ankers.c:163-216) */
 		kmahip_db_info sinfo;
 		int64_t unpinned = 0;
 		int32_t longest = 0;
@@ -587,6 +616,7 @@ int main(int argc, char **argv) {
 				int64_t c = 0;
 				if(!kmahip_chain_unpinned_reads(sj.b.reads.len, sj.b.reads.N, sj.b.reads.N_off, sj.b.reads.n_reads, (int) sinfo.kmersize, longest, &longest, &c)) unpinned += c;
 			}
+			s1_records += sj.b.records;
 			if(sj.b_dev ? kmahip_session_upload_dev(ses, &sj.b) : kmahip_session_upload(ses, &sj.b)) die("upload");
 			pthread_mutex_lock(&sj.mu);
 			sj.state = 0;
@@ -600,6 +630,7 @@ int main(int argc, char **argv) {
 		const double t_mapped = now_s();
 		double ms[8];
 		int64_t n_reads = 0, n_rows = 0;
+		if(ef && !mt1 && kmahip_session_set_ef_fragments(ses, s1_records)) die("session");
 		if(kmahip_session_finish(ses, out, !no_cons, !no_frag, &n_reads, &n_rows, ms)) die("finish");
 		if(s1dev) {
 			stream_close(&sj);

@@ -436,6 +436,59 @@ int kmahip_run_mt1(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads, int3
 int kmahip_res_line(const char *template_name, const kmahip_res_row *row, int64_t cover, int64_t aln_len, int64_t depth_sum,
                     double ID_t, double Depth_t, char *line, int64_t cap);
 
+/* ---- extended features (`-ef [n]`, kma.c:938-948; the `<out>.mapstat` file) -----------------------------------------------------
+ * Per template, what the reference gathers beside the `.res` columns while it assembles (HOST vectors of DB_size entries each, zero
+ * where nothing was piled up):
+ *   depth_var            sum of depth^2 over the columns the consensus calls as something other than '-', insertion columns included
+ *                        (callConsensus, assembly.c:1598-1601)
+ *   snp_sum, deletion_sum   over the template positions: the bases that differ from the template's, the gaps (ef.c:94-96)
+ *   insert_sum           the bases on the insertion columns (ef.c:97-99)
+ *   max_depth            the deepest column, gaps counted (ef.c:101-105)
+ *   nuc_high_var         the columns deeper than depth / t_len + 3 sqrt(var) (ef.c:65, 106-108)
+ *   score_sum, read_count_aln, fragment_count_aln   over the reads the stage-3c filter kept (alnToMat, assembly.c:1334-1338): their
+ *                        alignment scores without the end bonus, their number, and the number of those that are not the second mate of
+ *                        a proper pair (`!(flag & 2) || (flag & 64)`), raised to half the reads (ef.c:71)
+ *   var                  depth_var / t_len - (depth / t_len)^2 in long double, stored when it is not negative (assembly.c:2067-2081);
+ *                        else fixVarOverflow's sum over the template positions (assembly.c:1633-1687)
+ * Counts are read as the reference's 16-bit counters hold them. */
+typedef struct kmahip_assembly_ef {
+	uint64_t *depth_var;
+	uint64_t *snp_sum, *insert_sum, *deletion_sum;
+	uint32_t *max_depth, *nuc_high_var;
+	uint64_t *score_sum;
+	uint32_t *read_count_aln, *fragment_count_aln;
+	double *var;
+} kmahip_assembly_ef;
+/* Valid directly after a kmahip_assemble2 / kmahip_assemble2_dev call on the same workspace, before anything else uses it: the sums
+ * are made over the pile-up that call left in HBM, by kernels of their own behind it. n_reads, tmpl, traces (only `stats` is read)
+ * and `assembly` are those of that call; flag: per read the frag_raw flag (kmahip_hits.flag; for the fragments of a paired run their
+ * record's), NULL = every read is a fragment; p: rw.Wl, the end bonus the scores carry. KMAHIP_EINVAL with a message when the
+ * pile-up is not there (no such call before, or its columns were called on the host: KMAHIP_HOST_CONSENSUS).
+ * _dev: tmpl, traces->stats and flag are DEVICE pointers; the other form takes them on the host. `out` is the host's in both. */
+int kmahip_assemble_ef_dev(kmahip_db *db, kmahip_ws *ws, int64_t n_reads, const int32_t *tmpl, const kmahip_traces *traces, const int32_t *flag,
+                           const kmahip_params *p, const kmahip_assembly *assembly, kmahip_assembly_ef *out);
+int kmahip_assemble_ef(kmahip_db *db, kmahip_ws *ws, int64_t n_reads, const int32_t *tmpl, const kmahip_traces *traces, const int32_t *flag,
+                       const kmahip_params *p, const kmahip_assembly *assembly, kmahip_assembly_ef *out);
+
+/* The text of `<out>.mapstat`. Header (initExtendedFeatures, ef.c:30-46): `## method`, `## version` (that of the reference whose file
+ * this is: KMAHIP_MAPSTAT_VERSION), `## database` (t_db without its folder), `## fragmentCount` (the records stage 1 passed on, a couple
+ * counting once: kmahip_read_batch.records summed; ankers.c:163-216), `## date`, `## command`, the column line. Returns the
+ * characters written, 0 when cap is too small. */
+#define KMAHIP_MAPSTAT_VERSION "1.5.1"
+int64_t kmahip_mapstat_header(const char *t_db, uint32_t fragment_count, const char *cmdline, char *text, int64_t cap);
+/* One row (printExtendedFeatures, ef.c:129-136), printed exactly where the `.res` row is (runkma.c:814-829): the first seven arguments
+ * are kmahip_res_line's, and the result is 0 where that function's is. read_count / fragment_count: ConClave's (kmahip_conclave). */
+typedef struct kmahip_mapstat_row {
+	uint32_t read_count, fragment_count;
+	uint64_t score_sum;
+	double var;
+	uint32_t nuc_high_var, max_depth;
+	uint64_t snp_sum, insert_sum, deletion_sum;
+	uint32_t read_count_aln, fragment_count_aln;
+} kmahip_mapstat_row;
+int kmahip_mapstat_line(const char *template_name, const kmahip_res_row *row, int64_t cover, int64_t aln_len, int64_t depth_sum,
+                        double ID_t, double Depth_t, const kmahip_mapstat_row *ef, char *line, int64_t cap);
+
 /* ---- stage 2 of the DEFAULT mode (no -1t1) -------------------------------------------------------------------
  * kmerScan = save_kmers_chain (savekmers.c:5127-5945, the reference's default, savekmers.c:40) with the default helpers of
  * kmeranker.c:25-30. A read yields zero or more S2 records, one per accepted chain of anchors: rc_flag = the chain's score
@@ -802,6 +855,15 @@ int kmahip_session_set_mt1(kmahip_session *s, int32_t tmpl, int one2one, const c
  * filed fragments of kmahip_run_pe's records, each with its record's flag, in the fragment rows' order. KMAHIP_EINVAL, naming the mode,
  * for a session in the default mode, `-Mt1`, or with paired input at level 1 (the unmapped-mate flags of stages 2 and 3a are not built). */
 int kmahip_session_set_sam(kmahip_session *s, int level, const char *path, const char *program, const char *cmdline);
+/* The extended-features file (`-ef`): call before the first batch. The session then asks ConClave for its read and fragment counts,
+ * runs kmahip_assemble_ef_dev behind the pile-up and writes <out_prefix>.mapstat beside `.res`, from the same loop over the rows: a
+ * template is in both files or in neither. cmdline: the `## command` line (NULL: empty). t_db: the `## database` value (NULL: the
+ * prefix the index was opened with). Served by the -1t1 sessions (single end and paired) and the default mode; a -Mt1 session writes no
+ * such file, as runKMA_Mt1 writes none (mt1.c:313, 378). */
+int kmahip_session_set_ef(kmahip_session *s, const char *cmdline, const char *t_db);
+/* ... its `## fragmentCount`: the records stage 1 passed on (kmahip_read_batch.records summed over the batches, a couple counting
+ * once). Only the reader knows it, and only when the input has ended: call before kmahip_session_finish. */
+int kmahip_session_set_ef_fragments(kmahip_session *s, int64_t records);
 int kmahip_session_add(kmahip_session *s, const kmahip_read_batch *batch);
 /* kmahip_session_add in two steps, for a caller whose reader thread is to go on while the device works: _upload returns when the
  * batch's host arrays are free again, _map runs stages 2 and 3a on what has been uploaded since the last call */

@@ -70,6 +70,17 @@ class Assembly(C.Structure):
                 ("consensus", C.c_void_p), ("consensus_off", C.c_void_p), ("consensus_cap", C.c_int64), ("consensus_used", C.c_int64)]
 
 
+class AssemblyEf(C.Structure):
+    _fields_ = [("depth_var", C.c_void_p), ("snp_sum", C.c_void_p), ("insert_sum", C.c_void_p), ("deletion_sum", C.c_void_p), ("max_depth", C.c_void_p),
+                ("nuc_high_var", C.c_void_p), ("score_sum", C.c_void_p), ("read_count_aln", C.c_void_p), ("fragment_count_aln", C.c_void_p), ("var", C.c_void_p)]
+
+
+class MapstatRow(C.Structure):
+    _fields_ = [("read_count", C.c_uint32), ("fragment_count", C.c_uint32), ("score_sum", C.c_uint64), ("var", C.c_double), ("nuc_high_var", C.c_uint32),
+                ("max_depth", C.c_uint32), ("snp_sum", C.c_uint64), ("insert_sum", C.c_uint64), ("deletion_sum", C.c_uint64), ("read_count_aln", C.c_uint32),
+                ("fragment_count_aln", C.c_uint32)]
+
+
 class Trim(C.Structure):
     _fields_ = [("min_phred", C.c_int32), ("min_q", C.c_int32), ("hardmask_q", C.c_int32), ("min_len", C.c_int32),
                 ("max_len", C.c_int32)]
@@ -261,6 +272,15 @@ def lib():
         L.kmahip_session_set_pe.argtypes = [C.c_void_p]
         L.kmahip_session_close.argtypes = [C.c_void_p]
         L.kmahip_session_close.restype = None
+        if hasattr(L, "kmahip_assemble_ef"):          # (KMAHIP_LIB may name an older library, for side-by-side timing)
+            L.kmahip_assemble_ef.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(Traces), C.c_void_p, C.POINTER(Params), C.POINTER(Assembly),
+                                             C.POINTER(AssemblyEf)]
+            L.kmahip_mapstat_header.argtypes = [C.c_char_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_int64]
+            L.kmahip_mapstat_header.restype = C.c_int64
+            L.kmahip_mapstat_line.argtypes = [C.c_char_p, C.POINTER(ResRow), C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, C.POINTER(MapstatRow),
+                                              C.c_char_p, C.c_int64]
+            L.kmahip_session_set_ef.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+            L.kmahip_session_set_ef_fragments.argtypes = [C.c_void_p, C.c_int64]
         _lib = L
     return _lib
 
@@ -482,6 +502,12 @@ class Session:
 
     def set_sam(self, level=1, path="-", program="kmahip", cmdline=None):
         _check(lib().kmahip_session_set_sam(self._h, int(level), os.fsencode(path), program.encode(), None if cmdline is None else cmdline.encode()))
+
+    def set_ef(self, cmdline=None, t_db=None):
+        _check(lib().kmahip_session_set_ef(self._h, None if cmdline is None else cmdline.encode(), None if t_db is None else os.fsencode(t_db)))
+
+    def set_ef_fragments(self, records):
+        _check(lib().kmahip_session_set_ef_fragments(self._h, int(records)))
 
     def set_chain(self):
         _check(lib().kmahip_session_set_chain(self._h, None))
@@ -1067,6 +1093,42 @@ class KmaHipDB:
         _check(lib().kmahip_frag_write(os.fsencode(path), self.h, C.byref(r), _p(fl), _p(tm), _p(nh), _p(st), int(max_frag), blob,
                                        _p(noff), C.byref(rows)))
         return rows.value
+
+    def assemble_ef(self, tmpl, traces, asm, flag=None):
+        """The extended features of the pile-up the last assemble() call on this database left in HBM (kmahip_assemble_ef; host arrays):
+        tmpl and traces as given there, asm = what it returned (its depth is read), flag = the frag_raw flag per read or None.
+        -> dict(depth_var, snp_sum, insert_sum, deletion_sum, score_sum [u64], max_depth, nuc_high_var, read_count_aln, fragment_count_aln
+        [u32], var [f64]), DB_size entries each"""
+        n = len(tmpl)
+        tm = np.ascontiguousarray(tmpl if n else np.zeros(1, np.int32), np.int32)
+        st = np.ascontiguousarray(traces[0] if n else np.zeros((1, 10), np.int32), np.int32)
+        fl = None if flag is None else np.ascontiguousarray(flag if n else np.zeros(1, np.int32), np.int32)
+        tr = Traces(_p(st), None, None, None, 0)
+        D = int(self.info.DB_size)
+        depth = np.ascontiguousarray(asm["depth"], np.int64)
+        a = Assembly(None, None, _p(depth), None, None, None, 0, 0)
+        o = {k: np.zeros(D, np.uint64) for k in ("depth_var", "snp_sum", "insert_sum", "deletion_sum", "score_sum")}
+        o.update({k: np.zeros(D, np.uint32) for k in ("max_depth", "nuc_high_var", "read_count_aln", "fragment_count_aln")})
+        o["var"] = np.zeros(D, np.float64)
+        e = AssemblyEf(*[_p(o[k]) for k in ("depth_var", "snp_sum", "insert_sum", "deletion_sum", "max_depth", "nuc_high_var", "score_sum", "read_count_aln",
+                                            "fragment_count_aln", "var")])
+        p = Params.from_buffer_copy(self.params)
+        _check(lib().kmahip_assemble_ef(self.h, self.ws, n, _p(tm), C.byref(tr), None if fl is None else _p(fl), C.byref(p), C.byref(a), C.byref(e)))
+        return o
+
+    @staticmethod
+    def mapstat_header(t_db, fragment_count, cmdline=None):
+        """The header lines of `<out>.mapstat` (kmahip_mapstat_header) as bytes"""
+        buf = C.create_string_buffer(4096 + len(t_db) + len(cmdline or ""))
+        n = lib().kmahip_mapstat_header(os.fsencode(t_db), int(fragment_count), None if cmdline is None else cmdline.encode(), buf, len(buf))
+        return buf.raw[:n]
+
+    @staticmethod
+    def mapstat_line(name, row, cover, aln_len, depth, ef, ID_t=1.0, Depth_t=0.0):
+        """The `.mapstat` row (kmahip_mapstat_line; ef: a MapstatRow), or None where res_line gives None"""
+        buf = C.create_string_buffer(4096 + len(name))
+        n = lib().kmahip_mapstat_line(name.encode(), C.byref(row), int(cover), int(aln_len), int(depth), ID_t, Depth_t, C.byref(ef), buf, len(buf))
+        return buf.raw[:n].decode() if n else None
 
     @staticmethod
     def res_line(name, row, cover, aln_len, depth, ID_t=1.0, Depth_t=0.0):

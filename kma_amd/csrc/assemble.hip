@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <chrono>
 #include <cstdlib>
+#include <ctime>
 
 namespace {
 
@@ -1359,7 +1360,9 @@ extern "C" int kmahip_assemble2_dev(kmahip_db *db, kmahip_ws *ws, const kmahip_r
 	if(db->h_cat_off.empty()) { kmahip_set_error("index has no .length.b/.seq.b: stage 3c unavailable"); return KMAHIP_EINVAL; }
 	const int64_t D = db->info.DB_size;
 	for(int64_t t = 0; t < D; ++t) { out->cover[t] = 0; out->aln_len[t] = 0; out->depth[t] = 0; out->asm_len[t] = 0; }
-	if(reads->n_reads == 0) return KMAHIP_OK;
+	// (what kmahip_assemble_ef_dev may rely on: 0 no pile-up, 1 piled up and called on the device, 2 nothing to pile up, 3 called on the host)
+	ws->ef_state = 0;
+	if(reads->n_reads == 0) { ws->ef_state = 2; return KMAHIP_OK; }
 	int rc;
 	const kmahip_reads &d = *reads;
 	const kmahip_traces &dt = *traces;
@@ -1370,7 +1373,7 @@ extern "C" int kmahip_assemble2_dev(kmahip_db *db, kmahip_ws *ws, const kmahip_r
 	if((opts->caller & 16) ? (rc = pileup_dense_device(db, ws, &d, d_flag, d_tmpl, &dt, 0)) : (rc = pileup_device(db, ws, &d, d_flag, d_tmpl, &dt, max_frag, opts->order, opts->frag_rank, 0))) return rc;
 	const auto t1 = now();
 	if(dbg) fprintf(stderr, "[kmahip] assemble: pile-up on device %.1f ms\n", ms(t0, t1));
-	if(!ws->p_kept) return KMAHIP_OK;
+	if(!ws->p_kept) { ws->ef_state = 2; return KMAHIP_OK; }
 
 	// consensus on the device (two passes: figures + lengths, then the characters at their offsets); the host version below is
 	// kept as the arithmetic reference -- KMAHIP_HOST_CONSENSUS=1 selects it, and it takes over if p_chisqr is not monotone
@@ -1467,6 +1470,7 @@ extern "C" int kmahip_assemble2_dev(kmahip_db *db, kmahip_ws *ws, const kmahip_r
 			}
 			HIP_TRY(hipGetLastError());
 			if(dbg) fprintf(stderr, "[kmahip] assemble: consensus on device %.1f ms (q* = %.17g)\n", ms(t1, now()), qstar);
+			ws->ef_state = 1; ws->ef_bcd = bcd; ws->ef_caller = caller; ws->ef_sig90 = sig90; ws->ef_support = support; ws->ef_qstar = qstar;
 			return KMAHIP_OK;
 		}
 	}
@@ -1522,6 +1526,7 @@ extern "C" int kmahip_assemble2_dev(kmahip_db *db, kmahip_ws *ws, const kmahip_r
 		}
 	}
 	if(dbg) fprintf(stderr, "[kmahip] assemble: consensus on host %.1f ms\n", ms(t2, now()));
+	ws->ef_state = 3;
 	return KMAHIP_OK;
 }
 
@@ -1542,5 +1547,340 @@ extern "C" int kmahip_res_line(const char *template_name, const kmahip_res_row *
 	// runkma.c:141: expected / q_value are long double and printed as (unsigned) / (double)
 	const int w = snprintf(line, (size_t) cap, "%s\t%8ld\t%8u\t%8d\t%8.2f\t%8.2f\t%8.2f\t%8.2f\t%8.2f\t%8.2f\t%4.1e\n", template_name,
 	                       (long) row->score, row->expected, t_len, id, cov, q_id, q_cover, (double) depth, row->q_value, row->p_value);
+	return (w > 0 && w < cap) ? w : 0;
+}
+
+// ---- extended features (`-ef`, the `.mapstat` file): what getExtendedFeatures (ef.c:48-127), callConsensus' depthVar
+// (assembly.c:1598-1601) and alnToMat's per-read counts (assembly.c:1334-1338) sum over a template, made where the pile-up lies.
+// Sibling kernels of consensus_kernel<false> over the same segment list (cs_t / cs_lo, CONS_SEG positions each) and the same walk --
+// template position p, then the insertion columns chained in front of p + 1 --, so a run without -ef launches what it always did.
+namespace {
+
+struct EfArgs {
+	DevDB db;
+	const uint32_t *counts;
+	const int32_t *chain_head;
+	const InsNode *nodes;
+	const int32_t *seg_start;
+	int64_t n_kept;
+	int bcd, caller, sig90;
+	double support, qstar;
+	const int32_t *cs_t, *cs_lo;
+	int64_t n_cs;
+	const double *high_var;      // per template (ef_high_kernel)
+	unsigned long long *depth_var, *snp, *ins, *del;      // per template
+	unsigned int *max_depth, *n_high;
+	uint32_t *pos_depth;         // ef_depth_kernel: the depth of every template position of template `one_t`
+	int one_t;
+};
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+	for(int d = 32; d; d >>= 1) v += __shfl_down(v, d);
+	return v;
+}
+__device__ __forceinline__ unsigned wave_max(unsigned v) {
+	for(int d = 32; d; d >>= 1) v = max(v, (unsigned) __shfl_down(v, d));
+	return v;
+}
+
+// one column as getExtendedFeatures reads it: the five base counts, the gaps, 16-bit counters
+struct EfCol { unsigned bases, gaps, tcount; };
+__device__ __forceinline__ EfCol ef_col(const uint32_t *c, int tnuc) {
+	EfCol e;
+	e.bases = 0;
+	for(int j = 0; j < 5; ++j) e.bases += min(c[j], 65535u);
+	e.gaps = min(c[5], 65535u);
+	e.tcount = tnuc < 5 ? min(c[tnuc], 65535u) : 0u;
+	return e;
+}
+
+// depthVar over the called columns, snpSum / deletionSum over the template positions, insertSum over the insertion columns, the
+// deepest column: per-thread sums, reduced per wavefront, LDS partials per workgroup, one global atomic per workgroup and quantity
+__global__ __launch_bounds__(CONS_THREADS) void ef_sums_kernel(const EfArgs E) {
+	__shared__ unsigned long long s_sum[4];
+	__shared__ unsigned s_max;
+	const int tid = threadIdx.x, lane = tid & 63;
+	for(int64_t g = blockIdx.x; g < E.n_cs; g += gridDim.x) {
+		const int t = E.cs_t[g];
+		if(E.seg_start[t] >= E.n_kept) continue;           // uniform per workgroup
+		const int t_len = E.db.tlen[t];
+		const int lo = E.cs_lo[g], hi = min(lo + CONS_SEG, t_len);
+		const int64_t base = E.db.cat_off[t];
+		const uint64_t *ts = E.db.tseq + E.db.tseq_off[t];
+		if(tid < 4) s_sum[tid] = 0;
+		if(tid == 0) s_max = 0;
+		__syncthreads();
+		unsigned long long dvar = 0, snp = 0, ins = 0, del = 0;
+		unsigned mx = 0;
+		for(int p = lo + tid; p < hi; p += CONS_THREADS) {
+			const int tnuc = (int) ((ts[p >> 5] >> (62 - ((p & 31) << 1))) & 3ull);
+			const uint32_t *c = E.counts + (size_t) (base + p) * 6;
+			long long dep = 0;
+			unsigned char call = call_column_dev(c, tnuc, E.bcd, E.qstar, E.caller, E.sig90, E.support, &dep);
+			if(call != '-') dvar += (unsigned long long) dep * (unsigned long long) dep;
+			EfCol e = ef_col(c, tnuc);
+			del += e.gaps; snp += e.bases - e.tcount;
+			mx = max(mx, e.bases + e.gaps);
+			const int np = (p + 1 == t_len) ? 0 : p + 1;
+			for(int h = E.chain_head[base + np]; h; h = E.nodes[h - 1].next) {
+				call = call_column_dev(E.nodes[h - 1].c, 5, E.bcd, E.qstar, E.caller, E.sig90, E.support, &dep);
+				if(call != '-') dvar += (unsigned long long) dep * (unsigned long long) dep;
+				e = ef_col(E.nodes[h - 1].c, 5);
+				ins += e.bases;
+				mx = max(mx, e.bases + e.gaps);
+			}
+		}
+		dvar = wave_sum(dvar); snp = wave_sum(snp); ins = wave_sum(ins); del = wave_sum(del); mx = wave_max(mx);
+		if(lane == 0) {
+			if(dvar) atomicAdd(&s_sum[0], dvar);
+			if(snp) atomicAdd(&s_sum[1], snp);
+			if(ins) atomicAdd(&s_sum[2], ins);
+			if(del) atomicAdd(&s_sum[3], del);
+			if(mx) atomicMax(&s_max, mx);
+		}
+		__syncthreads();
+		if(tid == 0) {
+			if(s_sum[0]) atomicAdd(&E.depth_var[t], s_sum[0]);
+			if(s_sum[1]) atomicAdd(&E.snp[t], s_sum[1]);
+			if(s_sum[2]) atomicAdd(&E.ins[t], s_sum[2]);
+			if(s_sum[3]) atomicAdd(&E.del[t], s_sum[3]);
+			if(s_max) atomicMax(&E.max_depth[t], s_max);
+		}
+		__syncthreads();
+	}
+}
+
+// nucHighVar: the columns deeper than highVar = depth / t_len + 3 sqrt(var), which the host worked out (ef.c:65, 106-108)
+__global__ __launch_bounds__(CONS_THREADS) void ef_high_kernel(const EfArgs E) {
+	__shared__ unsigned s_n;
+	const int tid = threadIdx.x, lane = tid & 63;
+	for(int64_t g = blockIdx.x; g < E.n_cs; g += gridDim.x) {
+		const int t = E.cs_t[g];
+		if(E.seg_start[t] >= E.n_kept) continue;
+		const int t_len = E.db.tlen[t];
+		const int lo = E.cs_lo[g], hi = min(lo + CONS_SEG, t_len);
+		const int64_t base = E.db.cat_off[t];
+		const double high = E.high_var[t];
+		if(tid == 0) s_n = 0;
+		__syncthreads();
+		unsigned long long n = 0;
+		for(int p = lo + tid; p < hi; p += CONS_THREADS) {
+			EfCol e = ef_col(E.counts + (size_t) (base + p) * 6, 5);
+			if(high < (double) (e.bases + e.gaps)) ++n;
+			const int np = (p + 1 == t_len) ? 0 : p + 1;
+			for(int h = E.chain_head[base + np]; h; h = E.nodes[h - 1].next) {
+				e = ef_col(E.nodes[h - 1].c, 5);
+				if(high < (double) (e.bases + e.gaps)) ++n;
+			}
+		}
+		n = wave_sum(n);
+		if(lane == 0 && n) atomicAdd(&s_n, (unsigned) n);
+		__syncthreads();
+		if(tid == 0 && s_n) atomicAdd(&E.n_high[t], s_n);
+		__syncthreads();
+	}
+}
+
+// fixVarOverflow (assembly.c:1633-1687) sums over the template positions in order, in double: their depths for the host
+__global__ __launch_bounds__(256) void ef_depth_kernel(const EfArgs E) {
+	const int t_len = E.db.tlen[E.one_t];
+	const int64_t base = E.db.cat_off[E.one_t];
+	for(int p = blockIdx.x * blockDim.x + threadIdx.x; p < t_len; p += gridDim.x * blockDim.x) {
+		const EfCol e = ef_col(E.counts + (size_t) (base + p) * 6, 5);
+		E.pos_depth[p] = e.bases + e.gaps;
+	}
+}
+
+// alnToMat's counts over the kept reads (assembly.c:1334-1338): score without the end bonus the read filter added, a read, and a
+// fragment unless the read is the second mate of a proper pair. Lanes of a wavefront whose reads lie on the same template go
+// together: the counts from ballots, the score by a reduction, one lane adds (a same-address atomic per read serialises).
+__global__ __launch_bounds__(256) void ef_reads_kernel(int64_t n, const int32_t *tmpl, const int32_t *stats, const int32_t *flag, const int32_t *tlen, int Wl,
+                                                       unsigned long long *score, unsigned int *reads, unsigned int *frags) {
+	const int64_t r = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	const int lane = threadIdx.x & 63;
+	int t = 0;
+	long long sc = 0;
+	bool frag = false;
+	if(r < n && stats[10 * r + 3] != 0 && tmpl[r] != 0) {
+		t = abs(tmpl[r]);
+		const int32_t *st = stats + 10 * r;
+		sc = (long long) st[0] - (long long) Wl * ((st[1] == 0) + (st[2] == tlen[t]));
+		const int f = flag ? flag[r] : 0;
+		frag = !(f & 2) || (f & 64);
+	}
+	unsigned long long todo = __ballot(t != 0);
+	while(todo) {
+		const int leader = __ffsll((long long) todo) - 1;
+		const int tl = __shfl(t, leader);
+		const unsigned long long grp = __ballot(t == tl) & todo;
+		const unsigned long long fr = __ballot(t == tl && frag) & todo;
+		const unsigned long long sum = wave_sum((unsigned long long) (t == tl && ((todo >> lane) & 1ull) ? sc : 0));
+		if(lane == 0) {
+			atomicAdd(&score[tl], sum);
+			atomicAdd(&reads[tl], (unsigned) __popcll(grp));
+			if(fr) atomicAdd(&frags[tl], (unsigned) __popcll(fr));
+		}
+		todo &= ~grp;
+	}
+}
+
+}  // namespace
+
+// The host's part, as the reference does it (assembly.c:2067-2081 in long double; ef.c:65, 71): var, highVar, the fragment fix-up.
+extern "C" int kmahip_assemble_ef_dev(kmahip_db *db, kmahip_ws *ws, int64_t n_reads, const int32_t *d_tmpl, const kmahip_traces *traces, const int32_t *d_flag,
+                                      const kmahip_params *p, const kmahip_assembly *assembly, kmahip_assembly_ef *out) {
+	if(!db || !ws || !p || !assembly || !assembly->depth || !out || !out->depth_var || !out->snp_sum || !out->insert_sum || !out->deletion_sum || !out->max_depth ||
+	   !out->nuc_high_var || !out->score_sum || !out->read_count_aln || !out->fragment_count_aln || !out->var) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(n_reads < 0 || (n_reads > 0 && (!d_tmpl || !traces || !traces->stats))) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(!ws->ef_state) { kmahip_set_error("extended features: the pile-up is not there (call kmahip_assemble2 / kmahip_assemble2_dev on this workspace first)"); return KMAHIP_EINVAL; }
+	if(ws->ef_state == 3) { kmahip_set_error("extended features: the pile-up was called on the host (KMAHIP_HOST_CONSENSUS, or a libm whose p_chisqr is not monotone); its threshold is not on the device"); return KMAHIP_EINVAL; }
+	const int64_t D = db->info.DB_size;
+	for(int64_t t = 0; t < D; ++t) {
+		out->depth_var[t] = 0; out->snp_sum[t] = 0; out->insert_sum[t] = 0; out->deletion_sum[t] = 0; out->max_depth[t] = 0; out->nuc_high_var[t] = 0;
+		out->score_sum[t] = 0; out->read_count_aln[t] = 0; out->fragment_count_aln[t] = 0; out->var[t] = 0;
+	}
+	if(ws->ef_state == 2 || n_reads == 0 || !ws->p_kept) return KMAHIP_OK;          // (nothing was piled up)
+	hipStream_t s = 0;
+	DevGuard G;
+	// 4 x u64 sums + score | 4 x u32 | high_var
+	unsigned long long *d64 = nullptr;
+	HIP_TRY(hipMalloc((void **) &d64, (size_t) D * (5 * 8 + 4 * 4 + 8)));
+	G.v.push_back(d64);
+	HIP_TRY(hipMemsetAsync(d64, 0, (size_t) D * (5 * 8 + 4 * 4 + 8), s));
+	double *d_high = (double *) (d64 + 5 * D);
+	unsigned int *d32 = (unsigned int *) (d_high + D);
+	std::vector<int32_t> cs;
+	for(int64_t t = 1; t < D; ++t) for(int lo = 0; lo < db->h_tlen[(size_t) t]; lo += CONS_SEG) cs.push_back((int32_t) t);
+	const int64_t n_cs = (int64_t) cs.size();
+	for(int64_t t = 1; t < D; ++t) for(int lo = 0; lo < db->h_tlen[(size_t) t]; lo += CONS_SEG) cs.push_back(lo);
+	int32_t *d_cs = nullptr;
+	HIP_TRY(hipMalloc((void **) &d_cs, (size_t) (2 * n_cs + 2) * 4));
+	G.v.push_back(d_cs);
+	if(n_cs) HIP_TRY(hipMemcpyAsync(d_cs, cs.data(), (size_t) 2 * n_cs * 4, hipMemcpyHostToDevice, s));
+	EfArgs E;
+	memset((void *) &E, 0, sizeof E);
+	E.db = db->dev; E.counts = ws->p_counts; E.chain_head = ws->p_chain; E.nodes = (const InsNode *) ws->p_nodes; E.seg_start = ws->p_seg; E.n_kept = ws->p_kept;
+	E.bcd = ws->ef_bcd; E.caller = ws->ef_caller; E.sig90 = ws->ef_sig90; E.support = ws->ef_support; E.qstar = ws->ef_qstar;
+	E.cs_t = d_cs; E.cs_lo = d_cs + n_cs; E.n_cs = n_cs; E.high_var = d_high;
+	E.depth_var = d64; E.snp = d64 + D; E.ins = d64 + 2 * D; E.del = d64 + 3 * D;
+	E.max_depth = d32; E.n_high = d32 + D;
+	unsigned long long *d_score = d64 + 4 * D;
+	unsigned int *d_reads = d32 + 2 * D, *d_frags = d32 + 3 * D;
+	const unsigned blocks = (unsigned) std::min<int64_t>(std::max<int64_t>(n_cs, 1), 256 * 16);
+	const bool timing = getenv("KMAHIP_DEBUG_TIMING") != nullptr;
+	hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+	struct Ev { hipEvent_t *e; ~Ev() { for(int x = 0; x < 5; ++x) if(e[x]) (void) hipEventDestroy(e[x]); } } ev_guard{ev};
+	if(timing) { for(int x = 0; x < 5; ++x) HIP_TRY(hipEventCreate(&ev[x])); HIP_TRY(hipEventRecord(ev[0], s)); }
+	hipLaunchKernelGGL(ef_sums_kernel, dim3(blocks), dim3(CONS_THREADS), 0, s, E);
+	if(timing) HIP_TRY(hipEventRecord(ev[1], s));
+	hipLaunchKernelGGL(ef_reads_kernel, dim3((unsigned) ((n_reads + 255) / 256)), dim3(256), 0, s, n_reads, d_tmpl, traces->stats, d_flag, db->dev.tlen, p->rw.Wl, d_score, d_reads, d_frags);
+	if(timing) HIP_TRY(hipEventRecord(ev[2], s));
+	HIP_TRY(hipGetLastError());
+	std::vector<unsigned long long> h64((size_t) 5 * D);
+	std::vector<unsigned int> h32((size_t) 4 * D);
+	HIP_TRY(hipMemcpyAsync(h64.data(), d64, h64.size() * 8, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipMemcpyAsync(h32.data(), d32, h32.size() * 4, hipMemcpyDeviceToHost, s));
+	HIP_TRY(hipStreamSynchronize(s));
+	std::vector<int32_t> seg((size_t) D + 1);
+	HIP_TRY(hipMemcpy(seg.data(), ws->p_seg, seg.size() * 4, hipMemcpyDeviceToHost));
+	std::vector<double> high((size_t) D, 0.0);
+	for(int64_t t = 1; t < D; ++t) {
+		if(seg[(size_t) t] >= ws->p_kept) continue;
+		const int t_len = db->h_tlen[(size_t) t];
+		out->depth_var[t] = h64[(size_t) t]; out->snp_sum[t] = h64[(size_t) (D + t)]; out->insert_sum[t] = h64[(size_t) (2 * D + t)]; out->deletion_sum[t] = h64[(size_t) (3 * D + t)];
+		out->score_sum[t] = h64[(size_t) (4 * D + t)];
+		out->max_depth[t] = h32[(size_t) t];
+		const unsigned rca = h32[(size_t) (2 * D + t)], fca = h32[(size_t) (3 * D + t)];
+		out->read_count_aln[t] = rca;
+		out->fragment_count_aln[t] = std::max(fca, (rca >> 1) + (rca & 1));          // ef.c:71
+		// assembly.c:2070-2077
+		long double mean = (long double) (unsigned long) assembly->depth[t];
+		mean /= t_len;
+		long double var = (long double) (unsigned long) out->depth_var[t];
+		var /= t_len;
+		var -= (mean * mean);
+		if(0 <= var) out->var[t] = (double) var;
+		else {
+			// fixVarOverflow, assembly.c:1633-1687 (one thread's order: the positions ascending)
+			uint32_t *d_dep = nullptr;
+			HIP_TRY(hipMalloc((void **) &d_dep, (size_t) t_len * 4));
+			G.v.push_back(d_dep);
+			E.pos_depth = d_dep; E.one_t = (int) t;
+			hipLaunchKernelGGL(ef_depth_kernel, dim3((unsigned) std::min(1024, (t_len + 255) / 256)), dim3(256), 0, s, E);
+			HIP_TRY(hipGetLastError());
+			std::vector<uint32_t> dep((size_t) t_len);
+			HIP_TRY(hipMemcpy(dep.data(), d_dep, dep.size() * 4, hipMemcpyDeviceToHost));
+			double v = 0;
+			const double depth = (double) ((long double) (unsigned long) assembly->depth[t] / t_len);
+			for(int pos = 0; pos < t_len; ++pos) { const double tmp = ((int) dep[(size_t) pos] - depth); v += tmp * tmp / t_len; }
+			out->var[t] = v;
+		}
+		high[(size_t) t] = (double) ((long double) (unsigned long) assembly->depth[t] / t_len + 3 * sqrt(out->var[t]));          // ef.c:65
+	}
+	HIP_TRY(hipMemcpyAsync(d_high, high.data(), (size_t) D * 8, hipMemcpyHostToDevice, s));
+	if(timing) HIP_TRY(hipEventRecord(ev[3], s));
+	hipLaunchKernelGGL(ef_high_kernel, dim3(blocks), dim3(CONS_THREADS), 0, s, E);
+	if(timing) HIP_TRY(hipEventRecord(ev[4], s));
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpy(h32.data(), d32 + D, (size_t) D * 4, hipMemcpyDeviceToHost));
+	for(int64_t t = 1; t < D; ++t) if(seg[(size_t) t] < ws->p_kept) out->nuc_high_var[t] = h32[(size_t) t];
+	if(timing) {
+		float a = 0, b = 0, c = 0;
+		(void) hipEventElapsedTime(&a, ev[0], ev[1]); (void) hipEventElapsedTime(&b, ev[1], ev[2]); (void) hipEventElapsedTime(&c, ev[3], ev[4]);
+		fprintf(stderr, "[kmahip] extended features: %lld segments, %lld reads; ef_sums_kernel %.3f ms, ef_reads_kernel %.3f ms, ef_high_kernel %.3f ms (HIP events)\n",
+		        (long long) n_cs, (long long) n_reads, a, b, c);
+	}
+	return KMAHIP_OK;
+}
+
+// the same with the per-read inputs on the host (tmpl, traces->stats, flag or NULL: n_reads entries each)
+extern "C" int kmahip_assemble_ef(kmahip_db *db, kmahip_ws *ws, int64_t n_reads, const int32_t *tmpl, const kmahip_traces *traces, const int32_t *flag,
+                                  const kmahip_params *p, const kmahip_assembly *assembly, kmahip_assembly_ef *out) {
+	if(!ws) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(!ws->ef_state || n_reads <= 0) return kmahip_assemble_ef_dev(db, ws, n_reads < 0 ? n_reads : 0, nullptr, nullptr, nullptr, p, assembly, out);
+	if(!tmpl || !traces || !traces->stats) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	DevGuard G;
+	int32_t *d = nullptr;
+	HIP_TRY(hipMalloc((void **) &d, (size_t) n_reads * 12 * 4));
+	G.v.push_back(d);
+	HIP_TRY(hipMemcpy(d, tmpl, (size_t) n_reads * 4, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(d + n_reads, traces->stats, (size_t) n_reads * 40, hipMemcpyHostToDevice));
+	if(flag) HIP_TRY(hipMemcpy(d + 11 * n_reads, flag, (size_t) n_reads * 4, hipMemcpyHostToDevice));
+	kmahip_traces dt = *traces;
+	dt.stats = d + n_reads;
+	return kmahip_assemble_ef_dev(db, ws, n_reads, d, &dt, flag ? d + 11 * n_reads : nullptr, p, assembly, out);
+}
+
+// `<out>.mapstat`, the header lines (initExtendedFeatures, ef.c:30-46): database = the -t_db value without its folder, fragment_count =
+// the records stage 1 passed on (a couple counts once), the date of today. Returns the characters written, 0 if cap is too small.
+extern "C" int64_t kmahip_mapstat_header(const char *t_db, uint32_t fragment_count, const char *cmdline, char *text, int64_t cap) {
+	if(!t_db || !text || cap <= 0) return 0;
+	const char *base = strrchr(t_db, '/');
+	base = base ? base + 1 : t_db;
+	char date[11] = "";
+	time_t t1;
+	time(&t1);
+	struct tm tmv;
+	if(localtime_r(&t1, &tmv)) strftime(date, sizeof date, "%Y-%m-%d", &tmv);
+	const int w = snprintf(text, (size_t) cap, "## method\tKMA\n## version\t%s\n## database\t%s\n## fragmentCount\t%u\n## date\t%s\n## command\t%s\n"
+	                       "# refSequence\treadCount\tfragmentCount\tmapScoreSum\trefCoveredPositions\trefConsensusSum\tbpTotal\tdepthVariance\tnucHighDepthVariance\tdepthMax\tsnpSum\tinsertSum\tdeletionSum\treadCountAln\tfragmentCountAln\n",
+	                       KMAHIP_MAPSTAT_VERSION, base, fragment_count, date, cmdline ? cmdline : "");
+	return (w > 0 && w < cap) ? w : 0;
+}
+
+// one row (printExtendedFeatures, ef.c:129-136), written exactly where the `.res` row is (runkma.c:814-829): 0 where kmahip_res_line
+// gives 0 for the same template
+extern "C" int kmahip_mapstat_line(const char *template_name, const kmahip_res_row *row, int64_t cover, int64_t aln_len, int64_t depth_sum, double ID_t, double Depth_t,
+                                   const kmahip_mapstat_row *ef, char *line, int64_t cap) {
+	if(!template_name || !row || !ef || !line || cap <= 0) return 0;
+	if(!(cover > 0)) return 0;
+	const int t_len = row->template_length;
+	long double depth = depth_sum;
+	depth /= t_len;
+	const double id = 100.0 * cover / t_len;
+	if(!(ID_t <= id && 0 < id && Depth_t <= depth)) return 0;
+	const int w = snprintf(line, (size_t) cap, "%s\t%u\t%u\t%lu\t%u\t%u\t%lu\t%f\t%u\t%u\t%lu\t%lu\t%lu\t%u\t%u\n", template_name, ef->read_count, ef->fragment_count,
+	                       (unsigned long) ef->score_sum, (unsigned) aln_len, (unsigned) cover, (unsigned long) depth_sum, ef->var, ef->nuc_high_var, ef->max_depth,
+	                       (unsigned long) ef->snp_sum, (unsigned long) ef->insert_sum, (unsigned long) ef->deletion_sum, ef->read_count_aln, ef->fragment_count_aln);
 	return (w > 0 && w < cap) ? w : 0;
 }

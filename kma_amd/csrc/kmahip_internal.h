@@ -134,6 +134,9 @@ struct kmahip_ws {
 	uint64_t *p_keys;
 	int64_t *p_rank;
 	int64_t p_total, p_node_cap, p_reads_cap, p_kept, p_nodes_used, p_ent_cap;
+	// what the last kmahip_assemble2_dev left for kmahip_assemble_ef_dev (assemble.hip): 0 = no pile-up, else how its columns were called
+	int ef_state, ef_bcd, ef_caller, ef_sig90;
+	double ef_support, ef_qstar;
 	// long-read trace pipeline (longtrace.hip): per-wavefront MEM arrays, per-pass pools, queues, scratch, counters
 	void *lt_buf[20];
 	size_t lt_bytes[20];
@@ -230,6 +233,19 @@ struct KmaPeDev {
 	int64_t text_chunk;
 	int64_t *frag_rows;       // out: rows written to the fragment file (may be NULL)
 	int sam_level, sam_fd;    // SAM records of the filed fragments: the value of -sam (0: none) and the descriptor they go to
+	struct KmaEfReq *ef;      // the extended features of the run (or NULL): filled behind the pile-up
+};
+// what a run gathers for the `.mapstat` file: HOST vectors of DB_size entries, ConClave's two counts and kmahip_assemble_ef_dev's figures
+struct KmaEfReq {
+	uint32_t *read_counts, *frag_counts;
+	kmahip_assembly_ef *out;
+};
+// ... and what the writer of `.res` needs to write the file beside it, a row where it writes one (kmahip_write_res_fsa)
+struct KmaMapstat {
+	const char *path, *t_db, *cmdline;
+	uint32_t fragments;          // `## fragmentCount`
+	const uint32_t *read_counts, *frag_counts;
+	const kmahip_assembly_ef *ef;
 };
 int kmahip_run_pe_resident(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *batch, const KmaPeDev *pd, const kmahip_params *p, double evalue, int bcd,
                            int64_t max_frag, const char *frag_path, kmahip_run *out);

@@ -783,6 +783,8 @@ static int run_pe_impl(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *ba
 	   (rc = B.get(D, &cc.w_scores, true))) return rc;
 	cc.fragment_counts = nullptr; cc.read_counts = nullptr; cc.depth = nullptr;
 	if(sc && (rc = B.get(D, &cc.fragment_counts, true))) return rc;
+	KmaEfReq *ef = pd ? pd->ef : nullptr;          // (-ef: ConClave's two counts, readCounts / fragmentCounts of conclave.c:148-151, 170-172)
+	if(ef && ((rc = B.get(D, &cc.fragment_counts, true)) || (rc = B.get(D, &cc.read_counts, true)))) return rc;
 	{
 		if(U > 0) hipLaunchKernelGGL(pe_records_kernel, dim3((unsigned) ((U + 255) / 256)), dim3(256), 0, s, A);
 		HIP_TRY(hipGetLastError());
@@ -811,6 +813,10 @@ static int run_pe_impl(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *ba
 	}
 	std::vector<uint64_t> w(D);
 	HIP_TRY(hipMemcpy(w.data(), cc.w_scores, D * 8, hipMemcpyDeviceToHost));
+	if(ef) {
+		HIP_TRY(hipMemcpy(ef->frag_counts, cc.fragment_counts, D * 4, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(ef->read_counts, cc.read_counts, D * 4, hipMemcpyDeviceToHost));
+	}
 	if((rc = kmahip_res_rows(db, w.data(), evalue, p->scoreT, out->rows, out->rows_cap, &out->n_rows))) return rc;
 	std::vector<uint8_t> ok(D + 8, 0);
 	for(int64_t r = 0; r < out->n_rows; ++r) ok[(size_t) out->rows[r].template_id] = (uint8_t) out->rows[r].significant;
@@ -920,6 +926,8 @@ static int run_pe_impl(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *ba
 	if(nf > 0) {
 		kmahip_assemble_opts ao = {mf + 1, evalue, bcd, 0, out->caller, out->sig90, f_rank, out->support};
 		if((rc = kmahip_assemble2_dev(db, ws, &dF, f_rc, f_t, &tr, &ao, &out->assembly))) return rc;
+		// (the extended features behind the pile-up, before anything else uses the workspace; a fragment carries its record's flag)
+		if(ef && (rc = kmahip_assemble_ef_dev(db, ws, nf, f_t, &tr, f_flag, p, &out->assembly, ef->out))) return rc;
 	} else for(size_t i = 0; i < D; ++i) { out->assembly.cover[i] = 0; out->assembly.aln_len[i] = 0; out->assembly.depth[i] = 0; out->assembly.asm_len[i] = 0; }
 	out->ms[4] = since(t);
 
@@ -1429,11 +1437,19 @@ extern "C" int64_t kmahip_aln_entry(kmahip_db *db, int32_t tmpl, const char *nam
 // `rank`. fsa_path NULL: no consensus file (-nc); aln_path NULL: no alignment file (-na).
 int kmahip_write_res_fsa(kmahip_db *db, const char *res_path, const char *fsa_path, bool header, const kmahip_res_row *rows, int64_t n_rows,
                          const int32_t *owner, int rank, const int64_t *cover, const int64_t *aln_len, const int64_t *depth, const char *cons,
-                         const int64_t *cons_off, double ID_t, double Depth_t, int ref_fsa, const char *aln_path) {
+                         const int64_t *cons_off, double ID_t, double Depth_t, int ref_fsa, const char *aln_path, const KmaMapstat *mapstat = nullptr) {
 	int rc = kmahip_db_load_names(db);
 	if(rc) return rc;
 	FILE *res = fopen(res_path, "w"), *fsa = fsa_path ? fopen(fsa_path, "w") : nullptr, *aln = aln_path ? fopen(aln_path, "w") : nullptr;
 	if(!res || (fsa_path && !fsa) || (aln_path && !aln)) { if(res) fclose(res); if(fsa) fclose(fsa); if(aln) fclose(aln); kmahip_set_error("cannot create %s", !res ? res_path : (fsa_path && !fsa) ? fsa_path : aln_path); return KMAHIP_EIO; }
+	// the extended-features file (-ef): its rows come from this loop, so that a template is in both files or in neither
+	FILE *mst = mapstat ? fopen(mapstat->path, "w") : nullptr;
+	struct CloseMst { FILE *&f; ~CloseMst() { if(f) fclose(f); } } close_mst{mst};
+	if(mapstat) {
+		std::vector<char> head(4096 + strlen(mapstat->cmdline ? mapstat->cmdline : "") + strlen(mapstat->t_db));
+		const int64_t hl = mst ? kmahip_mapstat_header(mapstat->t_db, mapstat->fragments, mapstat->cmdline, head.data(), (int64_t) head.size()) : 0;
+		if(!hl || fwrite(head.data(), 1, (size_t) hl, mst) != (size_t) hl) { fclose(res); if(fsa) fclose(fsa); if(aln) fclose(aln); kmahip_set_error("cannot create %s", mapstat->path); return KMAHIP_EIO; }
+	}
 	if(header) fputs("#Template\tScore\tExpected\tTemplate_length\tTemplate_Identity\tTemplate_Coverage\tQuery_Identity\tQuery_Coverage\tDepth\tq_value\tp_value\n", res);
 	std::vector<char> line((1 << 16) + 512), block;
 	std::string entry;
@@ -1444,6 +1460,12 @@ int kmahip_write_res_fsa(kmahip_db *db, const char *res_path, const char *fsa_pa
 		const std::string &name = db->h_names[tt - 1];
 		if(!kmahip_res_line(name.c_str(), &row, cover[tt], aln_len[tt], depth[tt], ID_t, Depth_t, line.data(), (int64_t) line.size())) continue;
 		fputs(line.data(), res);
+		if(mst) {
+			const kmahip_assembly_ef &e = *mapstat->ef;
+			const kmahip_mapstat_row m = {mapstat->read_counts[tt], mapstat->frag_counts[tt], e.score_sum[tt], e.var[tt], e.nuc_high_var[tt], e.max_depth[tt], e.snp_sum[tt], e.insert_sum[tt],
+			                              e.deletion_sum[tt], e.read_count_aln[tt], e.fragment_count_aln[tt]};
+			if(kmahip_mapstat_line(name.c_str(), &row, cover[tt], aln_len[tt], depth[tt], ID_t, Depth_t, &m, line.data(), (int64_t) line.size())) fputs(line.data(), mst);
+		}
 		const char *q0 = cons_off[tt] >= 0 ? cons + cons_off[tt] : "";
 		if(aln) {
 			const size_t len = strlen(q0);
@@ -1471,7 +1493,10 @@ int kmahip_write_res_fsa(kmahip_db *db, const char *res_path, const char *fsa_pa
 	}
 	const bool bad = fclose(res) != 0;
 	const bool bad2 = fsa && fclose(fsa) != 0, bad3 = aln && fclose(aln) != 0;
+	bool bad4 = false;
+	if(mst) { bad4 = fclose(mst) != 0; mst = nullptr; }
 	if(rc) return rc;
+	if(bad4) { kmahip_set_error("write to %s failed", mapstat->path); return KMAHIP_EIO; }
 	if(bad || bad2 || bad3) { kmahip_set_error("write to %s failed", res_path); return KMAHIP_EIO; }
 	return KMAHIP_OK;
 }

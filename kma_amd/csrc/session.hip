@@ -22,7 +22,7 @@ void kmahip_gzstream_submit(kmahip_gzstream *g, const char *text, size_t bytes, 
 int kmahip_gzstream_close(kmahip_gzstream *g);
 int kmahip_write_res_fsa(kmahip_db *db, const char *res_path, const char *fsa_path, bool header, const kmahip_res_row *rows, int64_t n_rows,
                          const int32_t *owner, int rank, const int64_t *cover, const int64_t *aln_len, const int64_t *depth, const char *cons,
-                         const int64_t *cons_off, double ID_t, double Depth_t, int ref_fsa, const char *aln_path);                                    // pipeline.hip
+                         const int64_t *cons_off, double ID_t, double Depth_t, int ref_fsa, const char *aln_path, const KmaMapstat *mapstat = nullptr);       // pipeline.hip
 
 namespace {
 
@@ -244,6 +244,10 @@ struct kmahip_session {
 	int sam_level = 0;
 	std::string sam_path, sam_program, sam_cmdline;
 	bool sam_cl = false;
+	// the extended-features file (kmahip_session_set_ef): the `## command` and `## database` values, stage 1's record count
+	bool ef = false;
+	std::string ef_cmdline, ef_tdb;
+	int64_t ef_frags = 0;
 	~kmahip_session() {
 		for(Batch &b : batches) b.release();
 		for(Batch &b : uploaded) b.release();
@@ -320,6 +324,19 @@ extern "C" int kmahip_session_set_sam(kmahip_session *S, int level, const char *
 	if(S->mt1) { kmahip_set_error("SAM records are not built for a -Mt1 session"); return KMAHIP_EINVAL; }
 	if(S->pe && level == 1) { kmahip_set_error("SAM records at level 1 are not built for a session with paired input: the unmapped-mate flags of stages 2 and 3a"); return KMAHIP_EINVAL; }
 	S->sam_level = level; S->sam_path = path; S->sam_program = program ? program : "kmahip"; S->sam_cl = cmdline != nullptr; S->sam_cmdline = cmdline ? cmdline : "";
+	return KMAHIP_OK;
+}
+
+extern "C" int kmahip_session_set_ef(kmahip_session *S, const char *cmdline, const char *t_db) {
+	if(!S) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(S->n || S->n_reads || !S->uploaded.empty()) { kmahip_set_error("the mode of a session is chosen before its first batch"); return KMAHIP_EINVAL; }
+	S->ef = true; S->ef_cmdline = cmdline ? cmdline : ""; S->ef_tdb = t_db ? t_db : S->db->prefix;
+	return KMAHIP_OK;
+}
+
+extern "C" int kmahip_session_set_ef_fragments(kmahip_session *S, int64_t records) {
+	if(!S || records < 0) { kmahip_set_error("kmahip_session_set_ef_fragments: a session and a count that is not negative"); return KMAHIP_EINVAL; }
+	S->ef_frags = records;
 	return KMAHIP_OK;
 }
 
@@ -878,6 +895,24 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 	W.n_reads = n; W.seq = S->seq.as<uint64_t>(); W.seq_off = S->seq_off.as<int64_t>(); W.len = S->len.as<int32_t>(); W.N = S->N.as<int32_t>(); W.N_off = S->N_off.as<int64_t>();
 	W.seq_words = S->words; W.N_total = S->nN; W.max_len = S->max_len;
 	if(S->chain && n) { W.q_start = S->qs.as<int32_t>(); W.q_end = S->qe.as<int32_t>(); }
+	// the extended features (-ef; a -Mt1 session writes none, like runKMA_Mt1): host vectors per template, and what the writer takes
+	const bool ef_on = S->ef && !S->mt1;
+	std::vector<uint64_t> ef64(ef_on ? 5 * D : 0, 0);
+	std::vector<uint32_t> ef32(ef_on ? 6 * D : 0, 0);
+	std::vector<double> ef_var(ef_on ? D : 0, 0.0);
+	kmahip_assembly_ef efo{};
+	KmaEfReq ef_req{};
+	KmaMapstat mapstat{};
+	const std::string mapstat_path = std::string(out_prefix) + ".mapstat";
+	if(ef_on) {
+		efo.depth_var = ef64.data(); efo.snp_sum = ef64.data() + D; efo.insert_sum = ef64.data() + 2 * D; efo.deletion_sum = ef64.data() + 3 * D; efo.score_sum = ef64.data() + 4 * D;
+		efo.max_depth = ef32.data(); efo.nuc_high_var = ef32.data() + D; efo.read_count_aln = ef32.data() + 2 * D; efo.fragment_count_aln = ef32.data() + 3 * D;
+		efo.var = ef_var.data();
+		ef_req.read_counts = ef32.data() + 4 * D; ef_req.frag_counts = ef32.data() + 5 * D; ef_req.out = &efo;
+		mapstat.path = mapstat_path.c_str(); mapstat.t_db = S->ef_tdb.c_str(); mapstat.cmdline = S->ef_cmdline.c_str(); mapstat.fragments = (uint32_t) S->ef_frags;
+		mapstat.read_counts = ef_req.read_counts; mapstat.frag_counts = ef_req.frag_counts; mapstat.ef = &efo;
+	}
+	const KmaMapstat *mapstat_p = ef_on ? &mapstat : nullptr;
 
 	if(S->pe) {
 		// paired input: the whole run on what the batches left in HBM (kmahip_run_pe's stages; pipeline.hip), then the text files
@@ -886,7 +921,7 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 		kmahip_read_batch hb;
 		session_pe_view(S, 0, n, &hb);
 		int64_t n_frag_rows = 0;
-		KmaPeDev pd{S->names.as<char>(), S->name_off.as<int64_t>(), S->h_text, S->text_chunk, &n_frag_rows, 0, -1};
+		KmaPeDev pd{S->names.as<char>(), S->name_off.as<int64_t>(), S->h_text, S->text_chunk, &n_frag_rows, 0, -1, ef_on ? &ef_req : nullptr};
 		struct SamFd { int fd = -1; ~SamFd() { (void) kmahip_sam_close(fd); } } sam_fd;
 		if(S->sam_level) {
 			if(ws->pe_chain_on) { kmahip_set_error("SAM records are not built for paired input in the default mode (without -1t1)"); return KMAHIP_EINVAL; }
@@ -909,7 +944,7 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 		(void) since(t);
 		ms[1] += run.ms[0] + run.ms[1]; ms[2] = run.ms[2]; ms[3] = run.ms[3]; ms[4] = run.ms[4]; ms[6] = run.ms[5];
 		if((rc = kmahip_write_res_fsa(db, (prefix + ".res").c_str(), write_fsa ? (prefix + ".fsa").c_str() : nullptr, true, rows.data(), run.n_rows, nullptr, 0, a_cover.data(), a_len.data(),
-		                              a_depth.data(), cons.data(), c_off.data(), S->opts.ID_t > 0 ? S->opts.ID_t : 1.0, S->opts.Depth_t, S->opts.ref_fsa, S->opts.write_aln ? (prefix + ".aln").c_str() : nullptr))) return rc;
+		                              a_depth.data(), cons.data(), c_off.data(), S->opts.ID_t > 0 ? S->opts.ID_t : 1.0, S->opts.Depth_t, S->opts.ref_fsa, S->opts.write_aln ? (prefix + ".aln").c_str() : nullptr, mapstat_p))) return rc;
 		ms[5] = since(t);
 		if(n_rows_out) *n_rows_out = n_frag_rows;
 		return KMAHIP_OK;
@@ -971,6 +1006,8 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 	kmahip_conclave cc{};
 	int32_t *rc_all = nullptr, *nh_all = nullptr, *fl_all = nullptr;
 	if(S->sam_level && (rc = B.get((size_t) n + 1, &fl_all, true))) return rc;
+	// (-ef: readCounts / fragmentCounts, conclave.c:148-151, 170-172 -- the batches' calls add into the same two vectors)
+	if(ef_on && ((rc = B.get(D, &cc.fragment_counts, true)) || (rc = B.get(D, &cc.read_counts, true)))) return rc;
 	if((rc = B.get((size_t) n + 1, &cc.tmpl, true)) || (rc = B.get((size_t) n + 1, &cc.start, true)) || (rc = B.get((size_t) n + 1, &cc.end, true)) || (rc = B.get(D, &cc.w_scores, true)) ||
 	   (rc = B.get((size_t) n + 1, &rc_all, true)) || (rc = B.get((size_t) n + 1, &nh_all, true))) return rc;
 	for(Batch &b : S->batches) {
@@ -987,6 +1024,10 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 	}
 	std::vector<uint64_t> w(D);
 	HIP_TRY(hipMemcpy(w.data(), cc.w_scores, D * 8, hipMemcpyDeviceToHost));
+	if(ef_on) {
+		HIP_TRY(hipMemcpy(ef_req.frag_counts, cc.fragment_counts, D * 4, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(ef_req.read_counts, cc.read_counts, D * 4, hipMemcpyDeviceToHost));
+	}
 	std::vector<kmahip_res_row> rows(D);
 	int64_t n_rows = 0;
 	if((rc = kmahip_res_rows(db, w.data(), S->opts.evalue, p->scoreT, rows.data(), (int64_t) D, &n_rows))) return rc;
@@ -1041,6 +1082,8 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 	if(n) {
 		kmahip_assemble_opts ao = {mf, S->opts.evalue, S->opts.bcd, 0, S->opts.caller | (S->opts.ref_fsa == 2 ? 8 : 0) | (S->opts.write_aln ? 32 : 0), S->opts.sig90, nullptr, S->opts.support};
 		if((rc = kmahip_assemble2_dev(db, ws, &W, rc_all, cc.tmpl, &tr, &ao, &asmb))) return rc;
+		// (the extended features behind the pile-up, before anything else uses the workspace; single-end records are fragments all)
+		if(ef_on && (rc = kmahip_assemble_ef_dev(db, ws, n, cc.tmpl, &tr, nullptr, p, &asmb, &efo))) return rc;
 	}
 	ms[4] = since(t);
 	const std::string prefix(out_prefix);
@@ -1051,7 +1094,7 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 	std::thread text([&]() {
 		auto tt = std::chrono::steady_clock::now();
 		rc_text = kmahip_write_res_fsa(db, (prefix + ".res").c_str(), write_fsa ? (prefix + ".fsa").c_str() : nullptr, true, rows.data(), n_rows, nullptr, 0, a_cover.data(), a_len.data(),
-		                               a_depth.data(), cons.data(), c_off.data(), S->opts.ID_t > 0 ? S->opts.ID_t : 1.0, S->opts.Depth_t, S->opts.ref_fsa, S->opts.write_aln ? (prefix + ".aln").c_str() : nullptr);
+		                               a_depth.data(), cons.data(), c_off.data(), S->opts.ID_t > 0 ? S->opts.ID_t : 1.0, S->opts.Depth_t, S->opts.ref_fsa, S->opts.write_aln ? (prefix + ".aln").c_str() : nullptr, mapstat_p);
 		if(rc_text) err_text = kmahip_last_error();          // (the message is the thread's)
 		ms_text = since(tt);
 	});
