@@ -215,7 +215,7 @@ static void *xcalloc(size_t n, size_t sz) { void *p = calloc(n ? n : 1, sz); if(
 static void usage(void) {
 	fprintf(stderr, "usage: kmahip_map (-i reads.fq[.gz] | -ipe r1.fq[.gz] r2.fq[.gz] [-apm p|u] | -int interleaved.fq[.gz] [-apm p|u]) -t_db <index prefix> -o <output prefix> [-1t1] [-Mt1 <template>] [-bcNano] [-bc90] [-bc <support>] [-bcg] [-ref_fsa [n]] [-dense]\n"
 	                "       [-t threads] [-nc] [-na] [-nf] [-mf fragments] [-ml len] [-xl len] [-mp phred] [-mi phred] [-eq q] [-mq q] [-ts bases] [-mrs f] [-mrc f] [-mct f]\n"
-	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev] [-sam n] [-ef [n]]\n"
+	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev] [-sam n] [-ef [n]] [-matrix] [-vcf [n]]\n"
 	                "       [-reward n] [-gapopen n] [-gapextend n] [-localopen n] [-Npenalty n] [-per n] [-transition n] [-transversion n] [-penalty n] [-cge]\n"
 	                "       (-s1dev, like -gpus not an option of kma: stage 1 of plain FASTQ input on the device; one rank, -1t1 only; its batches close at a quarter\n"
 	                "        of a gigabase of their own accord, KMAHIP_MAP_BATCH_BASES does not apply to them)\n"
@@ -301,6 +301,7 @@ int main(int argc, char **argv) {
 	int mt1 = 0, one2one = 0, chain = 0, apm = 0, no_cons = 0, no_frag = 0, no_aln = 0, gpus = 0, threads = 0, bcd = 1, s1dev = 0;
 	int sam = 0, sam_bare = 0, status_opt = 0;   /* -sam [n] (kma.c:1005-1017); -status, which the reference refuses beside it (kma.c:1254) */
 	int ef = 0;                                  /* -ef [n] (kma.c:938-948): the extended-features file <out>.mapstat */
+	int matrix = 0, vcf = 0;                     /* -matrix (kma.c:667): <out>.mat.gz; -vcf [n] (kma.c:949-961): <out>.vcf.gz, n = 2 fills its FILTER column */
 	int base_call = 0, sig_mode = 0, ref_fsa = 0, dense = 0;      /* as kmahip_assemble_opts.caller (0-2 here) / .sig90; printconsensus.c's ref_fsa */
 	double support = 0;
 	long long max_frag = 0;
@@ -401,6 +402,15 @@ int main(int argc, char **argv) {
 				if(*end) { fprintf(stderr, "Invalid argument at \"-ef\".\n"); return 1; }
 			}
 		}
+		else if(!strcmp(o, "-matrix")) matrix = 1;                                              /* kma.c:667 */
+		else if(!strcmp(o, "-vcf")) {                                                           /* kma.c:949-961: a value is optional */
+			vcf = 1;
+			if(a + 1 < argc && argv[a + 1][0] != '-') {
+				char *end = NULL;
+				vcf = (int) strtol(argv[++a], &end, 10);
+				if(*end) { fprintf(stderr, "Invalid argument at \"-vcf\".\n"); return 1; }
+			}
+		}
 		else if(!strcmp(o, "-tmp") || !strcmp(o, "-verbose")) { if(a + 1 < argc && argv[a + 1][0] != '-') ++a; }
 		else if(!strcmp(o, "-mem_mode")) mem_mode = 1;                                           /* kma.c:547 */
 		else if(!strcmp(o, "-lc")) lc = 1;                                                      /* kma.c:694-701 */
@@ -496,6 +506,15 @@ int main(int argc, char **argv) {
 		else if(getenv("KMAHIP_MAP_ONE_BATCH")) why = "KMAHIP_MAP_ONE_BATCH";
 		else if(getenv("KMAHIP_COMM_FORCE_RCCL") && getenv("KMAHIP_COMM_FORCE_RCCL")[0] == '1') why = "KMAHIP_COMM_FORCE_RCCL";
 		if(why) { fprintf(stderr, "kmahip_map: -ef is not built for %s: the .mapstat file is written by the run of one rank, batch by batch\n", why); return 2; }
+	}
+	if(matrix || vcf) {
+		/* both files are made behind the pile-up of one rank's session and written by its `.res` loop */
+		const char *which = matrix && vcf ? "-matrix / -vcf" : matrix ? "-matrix" : "-vcf";
+		const char *why = NULL;
+		if(gpus > 1 || getenv("KMAHIP_RANK") || getenv("RANK")) why = "-gpus N (several ranks)";
+		else if(getenv("KMAHIP_MAP_ONE_BATCH")) why = "KMAHIP_MAP_ONE_BATCH";
+		else if(getenv("KMAHIP_COMM_FORCE_RCCL") && getenv("KMAHIP_COMM_FORCE_RCCL")[0] == '1') why = "KMAHIP_COMM_FORCE_RCCL";
+		if(why) { fprintf(stderr, "kmahip_map: %s is not built for %s: the .mat.gz and .vcf.gz files are written by the run of one rank, batch by batch\n", which, why); return 2; }
 	}
 	if(threads) {
 		char v[16];
@@ -600,6 +619,8 @@ int main(int argc, char **argv) {
 			if(kmahip_session_set_ef(ses, cmdline, prefix)) die("session");
 			free(cmdline);
 		}
+		/* (-vcf 0 is no file, like the reference's `if(vcf)`; the header's last column: -t_db without its folder) */
+		if((matrix && kmahip_session_set_matrix(ses)) || (vcf && kmahip_session_set_vcf(ses, vcf, prefix))) die("session");
 		int batches = 0;
 		int64_t s1_records = 0;          /* what stage 1 passed on, a couple counting once: the ## fragmentCount of -ef (ankers.c:163-216) */
 		kmahip_db_info sinfo;

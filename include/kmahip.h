@@ -489,6 +489,52 @@ typedef struct kmahip_mapstat_row {
 int kmahip_mapstat_line(const char *template_name, const kmahip_res_row *row, int64_t cover, int64_t aln_len, int64_t depth_sum,
                         double ID_t, double Depth_t, const kmahip_mapstat_row *ef, char *line, int64_t cap);
 
+/* ---- the count matrix and the VCF file (`-matrix`, kma.c:667; `-vcf [n]`, kma.c:949-961: `<out>.mat.gz`, `<out>.vcf.gz`) ----------------
+ * Both are made over the pile-up the last kmahip_assemble2 / kmahip_assemble2_dev call left in HBM, by kernels of their own behind it
+ * (over consensus_kernel's segment list), for the templates `mask` names: HOST bytes, DB_size of them, 1 where the `.res` row of the
+ * template passes its gate (kmahip_res_line gives a row). Valid directly after that call on the same workspace (kmahip_assemble_ef[_dev]
+ * may come between: it leaves the pile-up as it is); KMAHIP_EINVAL with a message when the pile-up is not there or its columns were
+ * called on the host (KMAHIP_HOST_CONSENSUS). Neither takes a per-read array, so there is no host-pointer form beside them.
+ *
+ * kmahip_assemble_matrix_dev replaces the row loop of updateMatrix (assembly.c:107-129; called at runkma.c:824, :1538, mt1.c:445): per
+ * column in ring order (template position p, then the insertion columns in front of p + 1) the row
+ * `<ref>\t%hu\t%hu\t%hu\t%hu\t%hu\t%hu\n`, <ref> the template's base or '-' at an insertion column, counts as the reference's 16-bit
+ * counters hold them. The rows are formatted on the device and handed to `sink` in template order, whole rows only, in pieces of at most
+ * chunk_bytes + 37 bytes (chunk_bytes <= 0: the value of KMAHIP_MAT_CHUNK, or 64 MiB); tmpl_bytes[t] (HOST, DB_size entries; filled
+ * before the first call of `sink`) is the number of bytes of template t, so the caller can put `#name\n` in front of a template's
+ * rows and the empty line behind them (assembly.c:100-105, 131-139). sink NULL: the sizes alone. A sink that returns non-zero ends the
+ * call with KMAHIP_EIO. */
+typedef int (*kmahip_text_sink)(void *user, const char *text, int64_t bytes);
+int kmahip_assemble_matrix_dev(kmahip_db *db, kmahip_ws *ws, const uint8_t *mask, int64_t chunk_bytes, int64_t *tmpl_bytes, kmahip_text_sink sink, void *user);
+
+/* kmahip_assemble_vcf_dev replaces the column loop of updateVcf (vcf.c:128-277; called at runkma.c:830, :1544, mt1.c:448) up to the
+ * decision whether a column's row is printed: one record per printed row, in ring order, templates ascending. The gates are evaluated
+ * on the device (vcf.c:195, and the all-zero row of a template position nothing was piled on, vcf.c:261-275); `evalue < P` is the test
+ * of the consensus, Q < q* in IEEE double. The text is the host's (kmahip_vcf_line): no floating-point text is made on the device.
+ *   pos          POS: the template position + 1, 0 at an insertion column
+ *   ref          the template's base ('A', 'C', 'G', 'T'), '-' at an insertion column
+ *   call         the called character ('.' in the all-zero row)
+ *   best_score   bestScore as updateVcf leaves it behind its minor-call branch (vcf.c:143-178)
+ *   counts       A, C, G, T, N, gaps, as the reference's 16-bit counters hold them
+ * tmpl_rows[t] (HOST, DB_size entries): the records of template t. recs: room for `cap` records (HOST); *n_recs: the number there is.
+ * recs NULL: the numbers alone; cap too small: KMAHIP_EOVERFLOW with *n_recs set. */
+typedef struct kmahip_vcf_rec {
+	int32_t tmpl, pos;
+	uint8_t ref, call;
+	uint16_t reserved;
+	int32_t best_score;
+	uint32_t counts[6];
+} kmahip_vcf_rec;
+int kmahip_assemble_vcf_dev(kmahip_db *db, kmahip_ws *ws, const uint8_t *mask, int64_t *tmpl_rows, kmahip_vcf_rec *recs, int64_t cap, int64_t *n_recs);
+
+/* The text of `<out>.vcf.gz`. Header (initialiseVcf, vcf.c:46-95): kmaVersion is KMAHIP_MAPSTAT_VERSION, the last column t_db without
+ * its folder. One row (vcf.c:180-275) from a record: AF, RAF and Q with %.2f, P = p_chisqr(Q) with %4.1e, QUAL from binP(DP, AD, 0.25)
+ * (stdstat.c:149-202), PASS / LowQual / FAIL (vcf.c:202-208), `<->` for a gap on either side, all in the host's libm. evalue, support,
+ * bcd: those of the run; filter: the value of -vcf (2 fills the FILTER column, else it is `.`). Both return the characters written,
+ * 0 when cap is too small. */
+int64_t kmahip_vcf_header(const char *t_db, char *text, int64_t cap);
+int kmahip_vcf_line(const char *template_name, const kmahip_vcf_rec *rec, double evalue, double support, int bcd, int filter, char *line, int64_t cap);
+
 /* ---- stage 2 of the DEFAULT mode (no -1t1) -------------------------------------------------------------------
  * kmerScan = save_kmers_chain (savekmers.c:5127-5945, the reference's default, savekmers.c:40) with the default helpers of
  * kmeranker.c:25-30. A read yields zero or more S2 records, one per accepted chain of anchors: rc_flag = the chain's score
@@ -864,6 +910,13 @@ int kmahip_session_set_ef(kmahip_session *s, const char *cmdline, const char *t_
 /* ... its `## fragmentCount`: the records stage 1 passed on (kmahip_read_batch.records summed over the batches, a couple counting
  * once). Only the reader knows it, and only when the input has ended: call before kmahip_session_finish. */
 int kmahip_session_set_ef_fragments(kmahip_session *s, int64_t records);
+/* The count matrix (`-matrix`) and the VCF file (`-vcf [n]`): call before the first batch. The session then runs
+ * kmahip_assemble_matrix_dev / kmahip_assemble_vcf_dev behind the pile-up, for the templates whose `.res` row passes its gate, and writes
+ * <out_prefix>.mat.gz / <out_prefix>.vcf.gz from the loop that writes `.res`: a template is in all files or in none. level: the value of
+ * -vcf (1, or 2 to fill the FILTER column); t_db: the last column of the header line (NULL: the prefix the index was opened with).
+ * Served by every session: -1t1 single end and paired, the default mode, -Mt1 (runKMA_Mt1 writes both, mt1.c:445-450). */
+int kmahip_session_set_matrix(kmahip_session *s);
+int kmahip_session_set_vcf(kmahip_session *s, int level, const char *t_db);
 int kmahip_session_add(kmahip_session *s, const kmahip_read_batch *batch);
 /* kmahip_session_add in two steps, for a caller whose reader thread is to go on while the device works: _upload returns when the
  * batch's host arrays are free again, _map runs stages 2 and 3a on what has been uploaded since the last call */

@@ -81,6 +81,16 @@ class MapstatRow(C.Structure):
                 ("fragment_count_aln", C.c_uint32)]
 
 
+class VcfRec(C.Structure):
+    _fields_ = [("tmpl", C.c_int32), ("pos", C.c_int32), ("ref", C.c_uint8), ("call", C.c_uint8), ("reserved", C.c_uint16), ("best_score", C.c_int32),
+                ("counts", C.c_uint32 * 6)]
+
+
+VCF_REC = np.dtype([("tmpl", np.int32), ("pos", np.int32), ("ref", np.uint8), ("call", np.uint8), ("reserved", np.uint16), ("best_score", np.int32),
+                    ("counts", np.uint32, 6)])
+TEXT_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64)
+
+
 class Trim(C.Structure):
     _fields_ = [("min_phred", C.c_int32), ("min_q", C.c_int32), ("hardmask_q", C.c_int32), ("min_len", C.c_int32),
                 ("max_len", C.c_int32)]
@@ -281,6 +291,14 @@ def lib():
                                               C.c_char_p, C.c_int64]
             L.kmahip_session_set_ef.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
             L.kmahip_session_set_ef_fragments.argtypes = [C.c_void_p, C.c_int64]
+        if hasattr(L, "kmahip_assemble_matrix_dev"):
+            L.kmahip_assemble_matrix_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, TEXT_SINK, C.c_void_p]
+            L.kmahip_assemble_vcf_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+            L.kmahip_vcf_header.argtypes = [C.c_char_p, C.c_char_p, C.c_int64]
+            L.kmahip_vcf_header.restype = C.c_int64
+            L.kmahip_vcf_line.argtypes = [C.c_char_p, C.POINTER(VcfRec), C.c_double, C.c_double, C.c_int, C.c_int, C.c_char_p, C.c_int64]
+            L.kmahip_session_set_matrix.argtypes = [C.c_void_p]
+            L.kmahip_session_set_vcf.argtypes = [C.c_void_p, C.c_int, C.c_char_p]
         _lib = L
     return _lib
 
@@ -508,6 +526,12 @@ class Session:
 
     def set_ef_fragments(self, records):
         _check(lib().kmahip_session_set_ef_fragments(self._h, int(records)))
+
+    def set_matrix(self):
+        _check(lib().kmahip_session_set_matrix(self._h))
+
+    def set_vcf(self, level=1, t_db=None):
+        _check(lib().kmahip_session_set_vcf(self._h, int(level), None if t_db is None else os.fsencode(t_db)))
 
     def set_chain(self):
         _check(lib().kmahip_session_set_chain(self._h, None))
@@ -1115,6 +1139,56 @@ class KmaHipDB:
         p = Params.from_buffer_copy(self.params)
         _check(lib().kmahip_assemble_ef(self.h, self.ws, n, _p(tm), C.byref(tr), None if fl is None else _p(fl), C.byref(p), C.byref(a), C.byref(e)))
         return o
+
+    def assemble_matrix(self, mask, chunk_bytes=0):
+        """The count-matrix rows (`-matrix`) of the pile-up the last assemble() call on this database left in HBM, for the templates with
+        mask[t] != 0 (kmahip_assemble_matrix_dev). -> (the rows of all those templates as bytes, templates ascending; bytes per template [i64])"""
+        D = int(self.info.DB_size)
+        m = np.ascontiguousarray(mask, np.uint8)
+        assert len(m) == D
+        per = np.zeros(D, np.int64)
+        parts = []
+
+        def take(user, text, n):
+            parts.append(C.string_at(text, n))
+            return 0
+        cb = TEXT_SINK(take)
+        _check(lib().kmahip_assemble_matrix_dev(self.h, self.ws, _p(m), int(chunk_bytes), _p(per), cb, None))
+        return b"".join(parts), per
+
+    def assemble_vcf(self, mask):
+        """The records of the rows `-vcf` prints, chosen on the device (kmahip_assemble_vcf_dev) -> (records [VCF_REC], records per template [i64])"""
+        D = int(self.info.DB_size)
+        m = np.ascontiguousarray(mask, np.uint8)
+        assert len(m) == D
+        per = np.zeros(D, np.int64)
+        n = C.c_int64(0)
+        _check(lib().kmahip_assemble_vcf_dev(self.h, self.ws, _p(m), _p(per), None, 0, C.byref(n)))
+        recs = np.zeros(max(n.value, 1), VCF_REC)
+        if n.value:
+            _check(lib().kmahip_assemble_vcf_dev(self.h, self.ws, _p(m), _p(per), _p(recs), n.value, C.byref(n)))
+        return recs[:n.value], per
+
+    @staticmethod
+    def vcf_header(t_db):
+        """The header lines of `<out>.vcf.gz` (kmahip_vcf_header) as bytes"""
+        buf = C.create_string_buffer(4096 + len(t_db))
+        n = lib().kmahip_vcf_header(os.fsencode(t_db), buf, len(buf))
+        return buf.raw[:n]
+
+    @staticmethod
+    def vcf_line(name, rec, evalue=0.05, support=0.0, bcd=1, filter=1, cap=None):
+        """One row of `<out>.vcf.gz` (kmahip_vcf_line) as bytes, b"" when it does not fit `cap`. rec: a VcfRec, an element of a VCF_REC
+        array, or (pos, ref, call, best_score, counts)"""
+        if isinstance(rec, tuple):
+            pos, ref, call, best, counts = rec
+            rec = VcfRec(0, int(pos), ord(ref), ord(call), 0, int(best), (C.c_uint32 * 6)(*[int(x) for x in counts]))
+        elif not isinstance(rec, VcfRec):
+            rec = VcfRec(int(rec["tmpl"]), int(rec["pos"]), int(rec["ref"]), int(rec["call"]), 0, int(rec["best_score"]), (C.c_uint32 * 6)(*[int(x) for x in rec["counts"]]))
+        cap = 4096 + len(name) if cap is None else int(cap)
+        buf = C.create_string_buffer(max(cap, 1))
+        n = lib().kmahip_vcf_line(name.encode(), C.byref(rec), float(evalue), float(support), int(bcd), int(filter), buf, cap)
+        return buf.raw[:n]
 
     @staticmethod
     def mapstat_header(t_db, fragment_count, cmdline=None):

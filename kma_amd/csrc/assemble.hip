@@ -1884,3 +1884,490 @@ extern "C" int kmahip_mapstat_line(const char *template_name, const kmahip_res_r
 	                       (unsigned long) ef->snp_sum, (unsigned long) ef->insert_sum, (unsigned long) ef->deletion_sum, ef->read_count_aln, ef->fragment_count_aln);
 	return (w > 0 && w < cap) ? w : 0;
 }
+
+// ---- the count matrix and the VCF file (`-matrix`, `-vcf`): updateMatrix's rows (assembly.c:107-129) and the columns updateVcf prints
+// (vcf.c:128-277), made where the pile-up lies. Sibling kernels of consensus_kernel<false> over the same segment list and the same walk
+// -- template position p, then the insertion columns chained in front of p + 1 --, for the templates of a mask the host gives (those
+// whose `.res` row passes its gate). A run without the options launches what it always did.
+namespace {
+
+struct ColArgs {
+	DevDB db;
+	const uint32_t *counts;
+	const int32_t *chain_head;
+	const InsNode *nodes;
+	const int32_t *seg_start;
+	int64_t n_kept;
+	int bcd, caller, sig90;
+	double support, qstar;
+	const int32_t *cs_t, *cs_lo;
+	int64_t n_cs;
+	const uint8_t *mask;                 // per template: 1 = its columns are written
+	unsigned long long *seg_size;        // pass 1 out, per segment: bytes of its matrix rows / its VCF records
+	const int64_t *seg_off;              // pass 2 in, per segment: bytes / records in front of it in the whole output
+	// mat_write_kernel: the segments [g0, g0 + gridDim.x) and the window [w0, w1) of the text they meet; bounds[0 .. 1]: where the chunk
+	// really begins and ends (the row that lies across a window's border goes with the window it starts in); text: chunk + 64 bytes
+	int64_t g0, w0, w1;
+	long long *bounds;
+	char *text;
+	kmahip_vcf_rec *recs;                // vcf_kernel<true>
+};
+
+// exclusive scan of one value per thread over the workgroup (as consensus_kernel does it); *tot: the sum
+__device__ __forceinline__ unsigned block_scan_excl(unsigned v, unsigned *s_scan, unsigned *tot) {
+	const int tid = threadIdx.x;
+	s_scan[tid] = v;
+	__syncthreads();
+	for(int o = 1; o < CONS_THREADS; o <<= 1) {
+		const unsigned x = tid >= o ? s_scan[tid - o] : 0u;
+		__syncthreads();
+		s_scan[tid] += x;
+		__syncthreads();
+	}
+	const unsigned incl = s_scan[tid];
+	*tot = s_scan[CONS_THREADS - 1];
+	__syncthreads();
+	return incl - v;
+}
+
+// `<ref>\t%hu\t%hu\t%hu\t%hu\t%hu\t%hu\n`: 14 to 38 bytes
+__device__ __forceinline__ unsigned mat_digits(unsigned v) { return 1u + (v >= 10u) + (v >= 100u) + (v >= 1000u) + (v >= 10000u); }
+__device__ __forceinline__ unsigned mat_row_len(const uint32_t *c) {
+	unsigned n = 8;
+	for(int j = 0; j < 6; ++j) n += mat_digits(min(c[j], 65535u));
+	return n;
+}
+
+// pass 1: the bytes of every segment's rows
+__global__ __launch_bounds__(CONS_THREADS) void mat_measure_kernel(const ColArgs A) {
+	__shared__ unsigned long long s_sum;
+	const int tid = threadIdx.x, lane = tid & 63;
+	for(int64_t g = blockIdx.x; g < A.n_cs; g += gridDim.x) {
+		const int t = A.cs_t[g];
+		if(!A.mask[t] || A.seg_start[t] >= A.n_kept) continue;           // uniform per workgroup
+		const int t_len = A.db.tlen[t];
+		const int lo = A.cs_lo[g], hi = min(lo + CONS_SEG, t_len);
+		const int64_t base = A.db.cat_off[t];
+		if(tid == 0) s_sum = 0;
+		__syncthreads();
+		unsigned long long n = 0;
+		for(int p = lo + tid; p < hi; p += CONS_THREADS) {
+			n += mat_row_len(A.counts + (size_t) (base + p) * 6);
+			const int np = (p + 1 == t_len) ? 0 : p + 1;
+			for(int h = A.chain_head[base + np]; h; h = A.nodes[h - 1].next) n += mat_row_len(A.nodes[h - 1].c);
+		}
+		n = wave_sum(n);
+		if(lane == 0 && n) atomicAdd(&s_sum, n);
+		__syncthreads();
+		if(tid == 0) A.seg_size[g] = s_sum;
+		__syncthreads();
+	}
+}
+
+constexpr int MAT_TILE = 16384;          // bytes of text staged in LDS at a time (256 rows are 9 728 bytes at the most, insertion columns apart)
+
+// one row into the LDS image of the chunk's bytes [T, T + MAT_TILE): the bytes of the row that lie in [lo_b, hi_b) (chunk coordinates);
+// r: where the row begins
+__device__ __forceinline__ void mat_put_row(unsigned char ref, const uint32_t *c, int64_t r, int64_t lo_b, int64_t hi_b, int64_t T, unsigned char *s_text) {
+	auto put = [&](unsigned char ch) { if(r >= lo_b && r < hi_b) s_text[r - T] = ch; ++r; };
+	put(ref);
+	for(int j = 0; j < 6; ++j) {
+		put((unsigned char) '\t');
+		const unsigned v = min(c[j], 65535u);
+		if(v >= 10000u) put((unsigned char) ('0' + v / 10000u));
+		if(v >= 1000u) put((unsigned char) ('0' + (v / 1000u) % 10u));
+		if(v >= 100u) put((unsigned char) ('0' + (v / 100u) % 10u));
+		if(v >= 10u) put((unsigned char) ('0' + (v / 10u) % 10u));
+		put((unsigned char) ('0' + v % 10u));
+	}
+	put((unsigned char) '\n');
+}
+
+// pass 2: the rows of one window of the text. A workgroup takes a segment, 256 template positions at a time: the rows' lengths, their
+// offsets by a scan, the rows byte by byte into LDS (256 lanes storing bytes into 256 different lines of HBM is what this avoids), the
+// LDS image out in 16-byte vectors, aligned on the chunk buffer. A row goes with the window its first byte lies in, whole.
+__global__ __launch_bounds__(CONS_THREADS) void mat_write_kernel(const ColArgs A) {
+	__shared__ unsigned s_scan[CONS_THREADS];
+	__shared__ __attribute__((aligned(16))) unsigned char s_text[MAT_TILE];
+	__shared__ long long s_e[2];
+	const int tid = threadIdx.x;
+	const int64_t g = A.g0 + blockIdx.x;
+	if(g >= A.n_cs) return;
+	const int t = A.cs_t[g];
+	if(!A.mask[t] || A.seg_start[t] >= A.n_kept) return;           // uniform per workgroup
+	const int t_len = A.db.tlen[t];
+	const int lo = A.cs_lo[g], hi = min(lo + CONS_SEG, t_len);
+	const int64_t base = A.db.cat_off[t];
+	const uint64_t *ts = A.db.tseq + A.db.tseq_off[t];
+	int64_t S = A.seg_off[g];
+	for(int b = lo; b < hi && S < A.w1; b += CONS_THREADS) {
+		const int p = b + tid;
+		const bool valid = p < hi;
+		const int np = (p + 1 == t_len) ? 0 : p + 1;
+		const uint32_t *c0 = A.counts + (size_t) (base + (valid ? p : lo)) * 6;
+		unsigned bytes = 0;
+		if(valid) {
+			bytes = mat_row_len(c0);
+			for(int h = A.chain_head[base + np]; h; h = A.nodes[h - 1].next) bytes += mat_row_len(A.nodes[h - 1].c);
+		}
+		unsigned tot;
+		const unsigned excl = block_scan_excl(bytes, s_scan, &tot);
+		if(S + (int64_t) tot > A.w0) {           // uniform: these rows meet the window
+			// the row across either border of the window, if there is one, is among these rows
+			if(tid == 0) { s_e[0] = A.w0; s_e[1] = A.w1; }
+			__syncthreads();
+			if(valid) {
+				int64_t r = S + excl;
+				unsigned L = mat_row_len(c0);
+				if(r < A.w0 && A.w0 < r + L) s_e[0] = r + L;
+				if(r < A.w1 && A.w1 < r + L) s_e[1] = r + L;
+				r += L;
+				for(int h = A.chain_head[base + np]; h; h = A.nodes[h - 1].next) {
+					L = mat_row_len(A.nodes[h - 1].c);
+					if(r < A.w0 && A.w0 < r + L) s_e[0] = r + L;
+					if(r < A.w1 && A.w1 < r + L) s_e[1] = r + L;
+					r += L;
+				}
+			}
+			__syncthreads();
+			const int64_t e0 = s_e[0], e1 = s_e[1];
+			if(tid == 0) {
+				if(e0 != A.w0) A.bounds[0] = e0;
+				if(e1 != A.w1) A.bounds[1] = e1;
+			}
+			// these rows' bytes of the chunk, in chunk coordinates (B1 <= chunk + 37)
+			const int64_t B0 = max(S, e0) - A.w0, B1 = min(S + (int64_t) tot, e1) - A.w0;
+			const unsigned char ref = (unsigned char) "ACGT"[(int) ((ts[(valid ? p : lo) >> 5] >> (62 - (((valid ? p : lo) & 31) << 1))) & 3ull)];
+			for(int64_t T = B0 & ~15ll; T < B1; T += MAT_TILE) {
+				const int64_t lo_b = max(T, B0), hi_b = min(T + MAT_TILE, B1);
+				if(valid) {
+					int64_t r = S + excl - A.w0;
+					unsigned L = mat_row_len(c0);
+					if(r + L > lo_b && r < hi_b) mat_put_row(ref, c0, r, lo_b, hi_b, T, s_text);
+					r += L;
+					for(int h = A.chain_head[base + np]; h && r < hi_b; h = A.nodes[h - 1].next) {
+						L = mat_row_len(A.nodes[h - 1].c);
+						if(r + L > lo_b) mat_put_row((unsigned char) '-', A.nodes[h - 1].c, r, lo_b, hi_b, T, s_text);
+						r += L;
+					}
+				}
+				__syncthreads();
+				const int nvec = (int) ((hi_b - T + 15) >> 4);
+				for(int v = tid; v < nvec; v += CONS_THREADS) {
+					const int64_t a = T + 16 * (int64_t) v;
+					if(a >= lo_b && a + 16 <= hi_b) *(uint4 *) (A.text + a) = *(const uint4 *) (s_text + 16 * v);
+					else for(int k = 0; k < 16; ++k) if(a + k >= lo_b && a + k < hi_b) A.text[a + k] = (char) s_text[16 * v + k];
+				}
+				__syncthreads();
+			}
+		}
+		S += tot;
+	}
+}
+
+// one column as updateVcf sees it (vcf.c:141-195, 261): is its row printed, and the record the host formats. look: the lookahead term
+// `t_len <= nextPos && *template_seq == '-'` (vcf.c:195), which the caller works out from the chain behind the column.
+__device__ __forceinline__ bool vcf_column(const ColArgs &A, const uint32_t *c32, int tnuc, int t, int pos, bool look, kmahip_vcf_rec *rec) {
+	int cnt[6];
+	for(int j = 0; j < 6; ++j) cnt[j] = (int) min(c32[j], 65535u);
+	int bestScore = cnt[tnuc], DP = 0;
+	for(int j = 0; j < 6; ++j) { bestScore = max(bestScore, cnt[j]); DP += cnt[j]; }
+	const unsigned char ref = (unsigned char) "ACGTN-"[tnuc];
+	rec->tmpl = t; rec->pos = pos; rec->ref = ref; rec->reserved = 0;
+	if(!DP) {          // (bestScore is 0 exactly when nothing was piled on the column)
+		if(tnuc == 5) return false;
+		rec->call = (unsigned char) '.'; rec->best_score = 0;
+		for(int j = 0; j < 6; ++j) rec->counts[j] = 0;
+		return true;
+	}
+	if((bestScore << 1) < DP) bestScore = DP - cnt[5];
+	long long dep = 0;
+	const unsigned char call = call_column_dev(c32, tnuc, A.bcd, A.qstar, A.caller, A.sig90, A.support, &dep);
+	const unsigned char up = (call >= 'a' && call <= 'z') ? (unsigned char) (call - 32) : call;
+	const int num = up == 'A' ? 0 : up == 'C' ? 1 : up == 'G' ? 2 : up == 'T' ? 3 : up == 'N' ? 4 : 5;
+	const int AD = cnt[num];
+	const long long d = (long long) DP - 2ll * bestScore;
+	const double Q = (double) (d * d) / (double) DP;
+	rec->call = call; rec->best_score = bestScore;
+	for(int j = 0; j < 6; ++j) rec->counts[j] = (uint32_t) cnt[j];
+	return ref != call || look || DP < A.bcd || Q < A.qstar || (double) AD < A.support * (double) DP;
+}
+
+// the records of the printed rows: counted per segment (WRITE false), then written at their offsets (WRITE true). The lookahead: the
+// insertion columns the consensus calls '-' are trimmed from the alignment updateVcf walks (assembly.c:2094-2119), so of a chain of
+// insertion columns with m columns called otherwise the FIRST m take a '-' of that alignment each: the term holds where the next column
+// is an insertion column whose index in its chain is below m.
+template <bool WRITE>
+__global__ __launch_bounds__(CONS_THREADS) void vcf_kernel(const ColArgs A) {
+	__shared__ unsigned s_scan[CONS_THREADS];
+	const int tid = threadIdx.x;
+	for(int64_t g = blockIdx.x; g < A.n_cs; g += gridDim.x) {
+		const int t = A.cs_t[g];
+		if(!A.mask[t] || A.seg_start[t] >= A.n_kept) continue;           // uniform per workgroup
+		const int t_len = A.db.tlen[t];
+		const int lo = A.cs_lo[g], hi = min(lo + CONS_SEG, t_len);
+		const int64_t base = A.db.cat_off[t];
+		const uint64_t *ts = A.db.tseq + A.db.tseq_off[t];
+		int64_t S = WRITE ? A.seg_off[g] : 0;
+		for(int b = lo; b < hi; b += CONS_THREADS) {
+			const int p = b + tid;
+			const bool valid = p < hi;
+			const int np = (p + 1 == t_len) ? 0 : p + 1;
+			unsigned n = 0;
+			int m = 0, tnuc = 0;
+			kmahip_vcf_rec rec;
+			if(valid) {
+				tnuc = (int) ((ts[p >> 5] >> (62 - ((p & 31) << 1))) & 3ull);
+				long long dep = 0;
+				for(int h = A.chain_head[base + np]; h; h = A.nodes[h - 1].next)
+					if(call_column_dev(A.nodes[h - 1].c, 5, A.bcd, A.qstar, A.caller, A.sig90, A.support, &dep) != '-') ++m;
+				n += vcf_column(A, A.counts + (size_t) (base + p) * 6, tnuc, t, p + 1, m > 0, &rec) ? 1u : 0u;
+				int i = 0;
+				for(int h = A.chain_head[base + np]; h; h = A.nodes[h - 1].next, ++i) n += vcf_column(A, A.nodes[h - 1].c, 5, t, 0, i + 1 < m, &rec) ? 1u : 0u;
+			}
+			unsigned tot;
+			const unsigned excl = block_scan_excl(n, s_scan, &tot);
+			if(WRITE && valid && n) {
+				int64_t o = S + excl;
+				if(vcf_column(A, A.counts + (size_t) (base + p) * 6, tnuc, t, p + 1, m > 0, &rec)) A.recs[o++] = rec;
+				int i = 0;
+				for(int h = A.chain_head[base + np]; h; h = A.nodes[h - 1].next, ++i) if(vcf_column(A, A.nodes[h - 1].c, 5, t, 0, i + 1 < m, &rec)) A.recs[o++] = rec;
+			}
+			S += tot;
+		}
+		if(!WRITE && tid == 0) A.seg_size[g] = (unsigned long long) S;
+	}
+}
+
+// what both calls begin with: the state of the pile-up, the segment list and the mask on the device, the common arguments
+struct ColSetup {
+	DevGuard G;
+	ColArgs A;
+	std::vector<int32_t> cs_t;           // per segment: its template
+	int64_t n_cs = 0;
+	unsigned blocks = 1;
+	unsigned long long *d_size = nullptr;
+	int64_t *d_off = nullptr;
+};
+
+int col_setup(kmahip_db *db, kmahip_ws *ws, const uint8_t *mask, const char *what, ColSetup *C, bool *nothing) {
+	*nothing = false;
+	if(!ws->ef_state) { kmahip_set_error("%s: the pile-up is not there (call kmahip_assemble2 / kmahip_assemble2_dev on this workspace first)", what); return KMAHIP_EINVAL; }
+	if(ws->ef_state == 3) { kmahip_set_error("%s: the pile-up was called on the host (KMAHIP_HOST_CONSENSUS, or a libm whose p_chisqr is not monotone); its threshold is not on the device", what); return KMAHIP_EINVAL; }
+	if(ws->ef_state == 2 || !ws->p_kept) { *nothing = true; return KMAHIP_OK; }
+	const int64_t D = db->info.DB_size;
+	std::vector<int32_t> cs;
+	for(int64_t t = 1; t < D; ++t) for(int lo = 0; lo < db->h_tlen[(size_t) t]; lo += CONS_SEG) cs.push_back((int32_t) t);
+	const int64_t n_cs = (int64_t) cs.size();
+	C->cs_t = cs;
+	for(int64_t t = 1; t < D; ++t) for(int lo = 0; lo < db->h_tlen[(size_t) t]; lo += CONS_SEG) cs.push_back(lo);
+	if(!n_cs) { *nothing = true; return KMAHIP_OK; }
+	int32_t *d_cs = nullptr;
+	uint8_t *d_mask = nullptr;
+	HIP_TRY(hipMalloc((void **) &d_cs, (size_t) (2 * n_cs + 2) * 4)); C->G.v.push_back(d_cs);
+	HIP_TRY(hipMalloc((void **) &d_mask, (size_t) D + 16)); C->G.v.push_back(d_mask);
+	HIP_TRY(hipMalloc((void **) &C->d_size, (size_t) (n_cs + 1) * 8)); C->G.v.push_back(C->d_size);
+	HIP_TRY(hipMalloc((void **) &C->d_off, (size_t) (n_cs + 1) * 8)); C->G.v.push_back(C->d_off);
+	HIP_TRY(hipMemcpy(d_cs, cs.data(), (size_t) 2 * n_cs * 4, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(d_mask, mask, (size_t) D, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemset(C->d_size, 0, (size_t) (n_cs + 1) * 8));
+	ColArgs &A = C->A;
+	memset((void *) &A, 0, sizeof A);
+	A.db = db->dev; A.counts = ws->p_counts; A.chain_head = ws->p_chain; A.nodes = (const InsNode *) ws->p_nodes; A.seg_start = ws->p_seg; A.n_kept = ws->p_kept;
+	A.bcd = ws->ef_bcd; A.caller = ws->ef_caller; A.sig90 = ws->ef_sig90; A.support = ws->ef_support; A.qstar = ws->ef_qstar;
+	A.cs_t = d_cs; A.cs_lo = d_cs + n_cs; A.n_cs = n_cs; A.mask = d_mask; A.seg_size = C->d_size; A.seg_off = C->d_off;
+	C->n_cs = n_cs;
+	C->blocks = (unsigned) std::min<int64_t>(n_cs, 256 * 16);
+	return KMAHIP_OK;
+}
+
+// pass 1's sizes -> the offsets of the segments (host scan, as the consensus does it) and the sums per template
+int col_offsets(ColSetup *C, std::vector<int64_t> *off, int64_t *per_tmpl) {
+	const int64_t n_cs = C->n_cs;
+	std::vector<unsigned long long> size((size_t) n_cs);
+	HIP_TRY(hipMemcpy(size.data(), C->d_size, (size_t) n_cs * 8, hipMemcpyDeviceToHost));
+	off->assign((size_t) n_cs + 1, 0);
+	for(int64_t g = 0; g < n_cs; ++g) {
+		(*off)[(size_t) g + 1] = (*off)[(size_t) g] + (int64_t) size[(size_t) g];
+		per_tmpl[C->cs_t[(size_t) g]] += (int64_t) size[(size_t) g];
+	}
+	HIP_TRY(hipMemcpy(C->d_off, off->data(), (size_t) (n_cs + 1) * 8, hipMemcpyHostToDevice));
+	return KMAHIP_OK;
+}
+
+}  // namespace
+
+extern "C" int kmahip_assemble_matrix_dev(kmahip_db *db, kmahip_ws *ws, const uint8_t *mask, int64_t chunk_bytes, int64_t *tmpl_bytes, kmahip_text_sink sink, void *user) {
+	if(!db || !ws || !mask || !tmpl_bytes) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	const int64_t D = db->info.DB_size;
+	for(int64_t t = 0; t < D; ++t) tmpl_bytes[t] = 0;
+	ColSetup C;
+	bool nothing = false;
+	int rc = col_setup(db, ws, mask, "count matrix", &C, &nothing);
+	if(rc || nothing) return rc;
+	hipStream_t s = 0;
+	const bool timing = getenv("KMAHIP_DEBUG_TIMING") != nullptr;
+	const auto t0 = std::chrono::steady_clock::now();
+	hipLaunchKernelGGL(mat_measure_kernel, dim3(C.blocks), dim3(CONS_THREADS), 0, s, C.A);
+	HIP_TRY(hipGetLastError());
+	std::vector<int64_t> off;
+	if((rc = col_offsets(&C, &off, tmpl_bytes))) return rc;
+	const double ms_measure = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	const int64_t total = off.back();
+	if(!total || !sink) return KMAHIP_OK;
+	int64_t chunk = chunk_bytes;
+	if(chunk <= 0) { const char *e = getenv("KMAHIP_MAT_CHUNK"); chunk = e ? atoll(e) : 0; }
+	if(chunk <= 0) chunk = 64ll << 20;
+	chunk = std::max<int64_t>(chunk, 256);          // (a row lies across one border of a window at the most)
+	const int64_t room = std::min(chunk, total) + 64;
+	char *d_text = nullptr, *h_text = nullptr;
+	long long *d_bounds = nullptr;
+	HIP_TRY(hipMalloc((void **) &d_text, (size_t) room)); C.G.v.push_back(d_text);
+	HIP_TRY(hipMalloc((void **) &d_bounds, 16)); C.G.v.push_back(d_bounds);
+	if(hipHostMalloc((void **) &h_text, (size_t) room, hipHostMallocDefault) != hipSuccess) { kmahip_set_error("hipHostMalloc failed"); return KMAHIP_ENOMEM; }
+	struct Pinned { char *p; ~Pinned() { (void) hipHostFree(p); } } pinned{h_text};
+	C.A.text = d_text; C.A.bounds = d_bounds;
+	int64_t done = 0, chunks = 0;
+	float ms_write = 0;
+	hipEvent_t ev[2] = {nullptr, nullptr};
+	struct Ev { hipEvent_t *e; ~Ev() { for(int x = 0; x < 2; ++x) if(e[x]) (void) hipEventDestroy(e[x]); } } ev_guard{ev};
+	if(timing) for(int x = 0; x < 2; ++x) HIP_TRY(hipEventCreate(&ev[x]));
+	for(int64_t w0 = 0; w0 < total; w0 += chunk, ++chunks) {
+		const int64_t w1 = std::min(w0 + chunk, total);
+		// the segments that meet [w0, w1): off[g + 1] > w0 and off[g] < w1
+		const int64_t g0 = (int64_t) (std::upper_bound(off.begin(), off.end(), w0) - off.begin()) - 1;
+		const int64_t g1 = (int64_t) (std::lower_bound(off.begin(), off.end(), w1) - off.begin());
+		long long hb[2] = {(long long) w0, (long long) w1};
+		HIP_TRY(hipMemcpyAsync(d_bounds, hb, 16, hipMemcpyHostToDevice, s));
+		C.A.g0 = g0; C.A.w0 = w0; C.A.w1 = w1;
+		if(timing) HIP_TRY(hipEventRecord(ev[0], s));
+		if(g1 > g0) hipLaunchKernelGGL(mat_write_kernel, dim3((unsigned) (g1 - g0)), dim3(CONS_THREADS), 0, s, C.A);
+		if(timing) HIP_TRY(hipEventRecord(ev[1], s));
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(hb, d_bounds, 16, hipMemcpyDeviceToHost, s));
+		HIP_TRY(hipStreamSynchronize(s));
+		if(timing) { float x = 0; (void) hipEventElapsedTime(&x, ev[0], ev[1]); ms_write += x; }
+		const int64_t e0 = hb[0], e1 = hb[1];
+		if(e0 != done || e1 < e0 || e1 > total || e0 - w0 > 37 || e1 - w1 > 37) { kmahip_set_error("count matrix: chunk %lld of the text begins at %lld and ends at %lld, %lld bytes are done", (long long) chunks, (long long) e0, (long long) e1, (long long) done); return KMAHIP_EDEVICE; }
+		if(e1 > e0) {
+			HIP_TRY(hipMemcpy(h_text, d_text + (e0 - w0), (size_t) (e1 - e0), hipMemcpyDeviceToHost));
+			if(sink(user, h_text, e1 - e0)) { kmahip_set_error("count matrix: the sink of the text failed"); return KMAHIP_EIO; }
+		}
+		done = e1;
+	}
+	if(done != total) { kmahip_set_error("count matrix: %lld of %lld bytes written", (long long) done, (long long) total); return KMAHIP_EDEVICE; }
+	if(timing) fprintf(stderr, "[kmahip] count matrix: %lld segments, %lld bytes in %lld chunks; mat_measure_kernel with its copies %.3f ms (host clock), mat_write_kernel %.3f ms (HIP events)\n",
+	                   (long long) C.n_cs, (long long) total, (long long) chunks, ms_measure, ms_write);
+	return KMAHIP_OK;
+}
+
+extern "C" int kmahip_assemble_vcf_dev(kmahip_db *db, kmahip_ws *ws, const uint8_t *mask, int64_t *tmpl_rows, kmahip_vcf_rec *recs, int64_t cap, int64_t *n_recs) {
+	if(!db || !ws || !mask || !tmpl_rows || !n_recs) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	const int64_t D = db->info.DB_size;
+	for(int64_t t = 0; t < D; ++t) tmpl_rows[t] = 0;
+	*n_recs = 0;
+	ColSetup C;
+	bool nothing = false;
+	int rc = col_setup(db, ws, mask, "VCF records", &C, &nothing);
+	if(rc || nothing) return rc;
+	hipStream_t s = 0;
+	const bool timing = getenv("KMAHIP_DEBUG_TIMING") != nullptr;
+	hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+	struct Ev { hipEvent_t *e; ~Ev() { for(int x = 0; x < 3; ++x) if(e[x]) (void) hipEventDestroy(e[x]); } } ev_guard{ev};
+	if(timing) { for(int x = 0; x < 3; ++x) HIP_TRY(hipEventCreate(&ev[x])); HIP_TRY(hipEventRecord(ev[0], s)); }
+	hipLaunchKernelGGL((vcf_kernel<false>), dim3(C.blocks), dim3(CONS_THREADS), 0, s, C.A);
+	if(timing) HIP_TRY(hipEventRecord(ev[1], s));
+	HIP_TRY(hipGetLastError());
+	std::vector<int64_t> off;
+	if((rc = col_offsets(&C, &off, tmpl_rows))) return rc;
+	const int64_t total = off.back();
+	*n_recs = total;
+	if(!recs || !total) return KMAHIP_OK;
+	if(cap < total) { kmahip_set_error("VCF records: room for %lld, %lld needed", (long long) cap, (long long) total); return KMAHIP_EOVERFLOW; }
+	kmahip_vcf_rec *d_recs = nullptr;
+	HIP_TRY(hipMalloc((void **) &d_recs, (size_t) total * sizeof(kmahip_vcf_rec))); C.G.v.push_back(d_recs);
+	C.A.recs = d_recs;
+	if(timing) HIP_TRY(hipEventRecord(ev[1], s));
+	hipLaunchKernelGGL((vcf_kernel<true>), dim3(C.blocks), dim3(CONS_THREADS), 0, s, C.A);
+	if(timing) HIP_TRY(hipEventRecord(ev[2], s));
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpy(recs, d_recs, (size_t) total * sizeof(kmahip_vcf_rec), hipMemcpyDeviceToHost));
+	if(timing) {
+		float b = 0;
+		(void) hipEventElapsedTime(&b, ev[1], ev[2]);
+		fprintf(stderr, "[kmahip] VCF records: %lld segments, %lld records; vcf_kernel<true> %.3f ms (HIP events)\n", (long long) C.n_cs, (long long) total, b);
+	}
+	return KMAHIP_OK;
+}
+
+// `<out>.vcf.gz`, the header lines (initialiseVcf, vcf.c:46-95). Returns the characters written, 0 if cap is too small.
+extern "C" int64_t kmahip_vcf_header(const char *t_db, char *text, int64_t cap) {
+	if(!t_db || !text || cap <= 0) return 0;
+	// noFolder (vcf.c:31-44)
+	int pos = (int) strlen(t_db) - 1;
+	while(pos > 0 && t_db[pos] != '/') --pos;
+	if(pos > 0) ++pos; else pos = 0;
+	const int w = snprintf(text, (size_t) cap, "##fileformat=VCFv4.2\n##kmaVersion=%s\n##FILTER=<ID=LowQual,Description=\"Low quality\">\n"
+	                       "##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Total Depth\">\n##INFO=<ID=AD,Number=1,Type=Integer,Description=\"Allele Depth\">\n"
+	                       "##INFO=<ID=AF,Number=1,Type=Float,Description=\"Allele Fraction\">\n##INFO=<ID=RAF,Number=1,Type=Float,Description=\"Revised Allele Fraction\">\n"
+	                       "##INFO=<ID=DEL,Number=1,Type=Float,Description=\"Fraction of Reads Containing Spanning Deletions\">\n"
+	                       "##INFO=<ID=AD6,Number=6,Type=Integer,Description=\"Count of all alternative alleles: A,C,G,T,N,-\">\n"
+	                       "##FORMAT=<ID=Q,Number=1,Type=Float,Description=\"McNemar quantile\">\n##FORMAT=<ID=P,Number=1,Type=Float,Description=\"McNemar p-value\">\n"
+	                       "##FORMAT=<ID=FT,Number=1,Type=String,Description=\"Filter\">\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t%s\n",
+	                       KMAHIP_MAPSTAT_VERSION, t_db + pos);
+	return (w > 0 && w < cap) ? w : 0;
+}
+
+// power and binP, stdstat.c:149-202
+static double vcf_power(double x, unsigned n) {
+	if(n) { const double y = vcf_power(x, n >> 1); return (n & 1) ? y * y * x : y * y; }
+	return 1.0;
+}
+static double vcf_binP(int n, int k, double p) {
+	const double q = 1 - p;
+	double P;
+	if(k == 0) { P = vcf_power(q, (unsigned) n); return P != 0.0 ? P : 1.0e-308; }
+	else if(n == k) { P = vcf_power(p, (unsigned) n); return P != 0.0 ? P : 1.0e-308; }
+	else if(p == 0 || q == 0) return 0.0;
+	P = 1.0;
+	const int nk = n - k;
+	const double pq = p * q;
+	int i = n + 1, j = k < nk ? k + 1 : nk + 1;
+	while(--j) P *= (--i * pq / j);
+	if(nk < k) P *= vcf_power(p, (unsigned) (k - nk));
+	else if(k < nk) P *= vcf_power(q, (unsigned) (nk - k));
+	return P != 0.0 ? P : 1.0e-308;
+}
+
+// one row of `<out>.vcf.gz` from a record of kmahip_assemble_vcf_dev (vcf.c:180-275), in this host's libm like the reference's
+extern "C" int kmahip_vcf_line(const char *template_name, const kmahip_vcf_rec *r, double evalue, double support, int bcd, int filter, char *line, int64_t cap) {
+	if(!template_name || !r || !line || cap <= 0) return 0;
+	const char *FILTER = "FAIL";
+	int DP = 0;
+	for(int j = 0; j < 6; ++j) DP += (int) r->counts[j];
+	int w;
+	if(!DP) {          // vcf.c:261-275
+		w = snprintf(line, (size_t) cap, "%s\t%d\t.\t%c\t%c\t%d\t%s\tDP=%d;AD=%d;AF=%.2f;RAF=%.2f;DEL=%d;AD6=%d,%d,%d,%d,%d,%d\tQ:P:FT\t%.2f:%4.1e:%s\n", template_name, r->pos,
+		             (char) r->ref, '.', 0, filter == 2 ? FILTER : ".", 0, 0, 0.0, 0.0, 0, 0, 0, 0, 0, 0, 0, 0.0, 1.0, FILTER);
+		return (w > 0 && w < cap) ? w : 0;
+	}
+	const unsigned char up = (r->call >= 'a' && r->call <= 'z') ? (unsigned char) (r->call - 32) : r->call;
+	const int num = up == 'A' ? 0 : up == 'C' ? 1 : up == 'G' ? 2 : up == 'T' ? 3 : up == 'N' ? 4 : 5;
+	const int bestScore = r->best_score;
+	const int AD = (int) r->counts[num];
+	const double AF = (double) AD / DP, RAF = (double) bestScore / DP;
+	const int DEL = (int) r->counts[5];
+	const double Q = pow(DP - (bestScore << 1), 2) / DP;
+	const double P = asm_p_chisqr(Q);
+	const double lnConst = -10 / log(10);
+	int QUAL = (int) (lnConst * log(vcf_binP(DP, AD, 0.25)));
+	QUAL = (QUAL < 0 || 3079 < QUAL) ? 3079 : QUAL;
+	if(bcd <= DP && P <= evalue && support * DP <= AD) FILTER = "PASS";
+	else if(bcd <= DP || P <= evalue || support * DP <= AD) FILTER = "LowQual";
+	char ref[4] = {(char) r->ref, 0, 0, 0}, alt[4] = {(char) r->call, 0, 0, 0};
+	if(r->ref == '-') memcpy(ref, "<->", 4);
+	if(r->call == '-') memcpy(alt, "<->", 4);
+	w = snprintf(line, (size_t) cap, "%s\t%d\t.\t%s\t%s\t%d\t%s\tDP=%d;AD=%d;AF=%.2f;RAF=%.2f;DEL=%d;AD6=%d,%d,%d,%d,%d,%d\tQ:P:FT\t%.2f:%4.1e:%s\n", template_name, r->pos, ref, alt, QUAL,
+	             filter == 2 ? FILTER : ".", DP, AD, AF, RAF, DEL, (int) r->counts[0], (int) r->counts[1], (int) r->counts[2], (int) r->counts[3], (int) r->counts[4], (int) r->counts[5], Q, P, FILTER);
+	return (w > 0 && w < cap) ? w : 0;
+}

@@ -234,6 +234,7 @@ struct KmaPeDev {
 	int64_t *frag_rows;       // out: rows written to the fragment file (may be NULL)
 	int sam_level, sam_fd;    // SAM records of the filed fragments: the value of -sam (0: none) and the descriptor they go to
 	struct KmaEfReq *ef;      // the extended features of the run (or NULL): filled behind the pile-up
+	struct KmaMatVcf *mv;     // the count matrix and the VCF records of the run (or NULL): gathered behind the pile-up
 };
 // what a run gathers for the `.mapstat` file: HOST vectors of DB_size entries, ConClave's two counts and kmahip_assemble_ef_dev's figures
 struct KmaEfReq {
@@ -247,5 +248,20 @@ struct KmaMapstat {
 	const uint32_t *read_counts, *frag_counts;
 	const kmahip_assembly_ef *ef;
 };
+// the count matrix and the VCF file (-matrix, -vcf [n]): what a run gathers behind the pile-up for the templates whose `.res` row passes
+// its gate (kmahip_matvcf_gather, pipeline.hip: kmahip_assemble_matrix_dev / kmahip_assemble_vcf_dev), and what the writer of `.res`
+// needs to write <out>.mat.gz and <out>.vcf.gz from its own loop (kmahip_write_res_fsa)
+struct KmaMatVcf {
+	bool matrix = false;
+	int vcf = 0;                 // the value of -vcf (0: no file, 2: the FILTER column is filled)
+	std::string mat_path, vcf_path, t_db;
+	double evalue = 0, support = 0, ID_t = 1.0, Depth_t = 0;
+	int bcd = 1;
+	std::vector<char> mat_text;          // the rows of template t: mat_text[mat_off[t] .. mat_off[t + 1])
+	std::vector<int64_t> mat_off;
+	std::vector<kmahip_vcf_rec> recs;    // the records of template t: recs[rec_off[t] .. rec_off[t + 1])
+	std::vector<int64_t> rec_off;
+};
+int kmahip_matvcf_gather(kmahip_db *db, kmahip_ws *ws, const kmahip_res_row *rows, int64_t n_rows, const kmahip_assembly *a, KmaMatVcf *mv);
 int kmahip_run_pe_resident(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *batch, const KmaPeDev *pd, const kmahip_params *p, double evalue, int bcd,
                            int64_t max_frag, const char *frag_path, kmahip_run *out);

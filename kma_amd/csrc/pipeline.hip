@@ -2,7 +2,15 @@
 // out), built from the same launchers as the stage-wise entry points; what runKMA does between its input stream and the
 // `.res` / consensus output (runkma.c:104-900), minus the files.
 #include "pipeline_util.h"
+#include <atomic>
+#include <deque>
 #include <mutex>
+#include <string>
+
+struct kmahip_gzstream;
+kmahip_gzstream *kmahip_gzstream_open(const char *path);                                                        // fragout.hip
+void kmahip_gzstream_submit(kmahip_gzstream *g, const char *text, size_t bytes, std::atomic<int> *done);
+int kmahip_gzstream_close(kmahip_gzstream *g);
 
 // ---- the large device blocks kept between runs (pipeline_util.h) -------------------------------------------------------------------
 namespace {
@@ -928,6 +936,7 @@ static int run_pe_impl(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *ba
 		if((rc = kmahip_assemble2_dev(db, ws, &dF, f_rc, f_t, &tr, &ao, &out->assembly))) return rc;
 		// (the extended features behind the pile-up, before anything else uses the workspace; a fragment carries its record's flag)
 		if(ef && (rc = kmahip_assemble_ef_dev(db, ws, nf, f_t, &tr, f_flag, p, &out->assembly, ef->out))) return rc;
+		if(pd && pd->mv && (rc = kmahip_matvcf_gather(db, ws, out->rows, out->n_rows, &out->assembly, pd->mv))) return rc;
 	} else for(size_t i = 0; i < D; ++i) { out->assembly.cover[i] = 0; out->assembly.aln_len[i] = 0; out->assembly.depth[i] = 0; out->assembly.asm_len[i] = 0; }
 	out->ms[4] = since(t);
 
@@ -1431,15 +1440,79 @@ extern "C" int64_t kmahip_aln_entry(kmahip_db *db, int32_t tmpl, const char *nam
 	return (int64_t) text.size();
 }
 
+// The count matrix and the VCF records of a run (-matrix, -vcf), gathered directly behind its pile-up: the mask is the gate of the `.res`
+// loop below (the same call of kmahip_res_line), so what is gathered here is what that loop writes.
+int kmahip_matvcf_gather(kmahip_db *db, kmahip_ws *ws, const kmahip_res_row *rows, int64_t n_rows, const kmahip_assembly *a, KmaMatVcf *mv) {
+	int rc = kmahip_db_load_names(db);
+	if(rc) return rc;
+	const size_t D = (size_t) db->info.DB_size;
+	std::vector<uint8_t> mask(D + 1, 0);
+	std::vector<char> line((1 << 16) + 512);
+	for(int64_t r = 0; r < n_rows; ++r) {
+		const kmahip_res_row &row = rows[r];
+		const size_t tt = (size_t) row.template_id;
+		if(!row.significant || tt - 1 >= db->h_names.size() || tt >= D) continue;
+		if(kmahip_res_line(db->h_names[tt - 1].c_str(), &row, a->cover[tt], a->aln_len[tt], a->depth[tt], mv->ID_t, mv->Depth_t, line.data(), (int64_t) line.size())) mask[tt] = 1;
+	}
+	std::vector<int64_t> per(D + 1, 0);
+	mv->mat_text.clear(); mv->recs.clear();
+	mv->mat_off.assign(D + 1, 0); mv->rec_off.assign(D + 1, 0);
+	if(mv->matrix) {
+		auto sink = [](void *user, const char *text, int64_t bytes) -> int { std::vector<char> *v = (std::vector<char> *) user; v->insert(v->end(), text, text + bytes); return 0; };
+		if((rc = kmahip_assemble_matrix_dev(db, ws, mask.data(), 0, per.data(), sink, &mv->mat_text))) return rc;
+		int64_t total = 0;
+		for(size_t t = 0; t < D; ++t) { mv->mat_off[t] = total; total += per[t]; }
+		mv->mat_off[D] = total;
+		if((int64_t) mv->mat_text.size() != total) { kmahip_set_error("count matrix: %zu bytes of text, %lld measured", mv->mat_text.size(), (long long) total); return KMAHIP_EDEVICE; }
+	}
+	if(mv->vcf) {
+		int64_t n = 0;
+		if((rc = kmahip_assemble_vcf_dev(db, ws, mask.data(), per.data(), nullptr, 0, &n))) return rc;
+		mv->recs.resize((size_t) n);
+		if(n && (rc = kmahip_assemble_vcf_dev(db, ws, mask.data(), per.data(), mv->recs.data(), n, &n))) return rc;
+		int64_t total = 0;
+		for(size_t t = 0; t < D; ++t) { mv->rec_off[t] = total; total += per[t]; }
+		mv->rec_off[D] = total;
+	}
+	return KMAHIP_OK;
+}
+
 // The rows of `.res` (runkma.c:792-809), the entries of the consensus FASTA (printConsensus, printconsensus.c:38-60: the
 // consensus line without its '-' columns, 60 per line) and, with aln_path, the blocks of the `.aln` file (:26-37; the consensus
 // strings were then made with caller + 32) for the significant templates -- all of them, or those `owner` gives to
 // `rank`. fsa_path NULL: no consensus file (-nc); aln_path NULL: no alignment file (-na).
 int kmahip_write_res_fsa(kmahip_db *db, const char *res_path, const char *fsa_path, bool header, const kmahip_res_row *rows, int64_t n_rows,
                          const int32_t *owner, int rank, const int64_t *cover, const int64_t *aln_len, const int64_t *depth, const char *cons,
-                         const int64_t *cons_off, double ID_t, double Depth_t, int ref_fsa, const char *aln_path, const KmaMapstat *mapstat = nullptr) {
+                         const int64_t *cons_off, double ID_t, double Depth_t, int ref_fsa, const char *aln_path, const KmaMapstat *mapstat = nullptr,
+                         const KmaMatVcf *mv = nullptr) {
 	int rc = kmahip_db_load_names(db);
 	if(rc) return rc;
+	// the count matrix and the VCF file (-matrix, -vcf): their entries come from this loop too. Text gathers in blocks of a few megabytes,
+	// a gzip member each, which the IO threads compress while the loop goes on (the blocks live until the file is closed)
+	struct GzText {
+		kmahip_gzstream *gz = nullptr;
+		std::deque<std::string> blocks;
+		~GzText() { if(gz) (void) kmahip_gzstream_close(gz); }
+		void put(const char *text, size_t n) {
+			if(blocks.empty()) blocks.emplace_back();
+			blocks.back().append(text, n);
+			if(blocks.back().size() >= (4u << 20)) flush();
+		}
+		void flush() {
+			if(blocks.empty() || blocks.back().empty()) return;
+			kmahip_gzstream_submit(gz, blocks.back().data(), blocks.back().size(), nullptr);
+			blocks.emplace_back();
+		}
+		int close() { flush(); kmahip_gzstream *g = gz; gz = nullptr; return g ? kmahip_gzstream_close(g) : KMAHIP_OK; }
+	} mat, vcf;
+	if(mv && mv->matrix && !(mat.gz = kmahip_gzstream_open(mv->mat_path.c_str()))) return KMAHIP_EIO;
+	if(mv && mv->vcf) {
+		if(!(vcf.gz = kmahip_gzstream_open(mv->vcf_path.c_str()))) return KMAHIP_EIO;
+		std::vector<char> head(4096 + mv->t_db.size());
+		const int64_t hl = kmahip_vcf_header(mv->t_db.c_str(), head.data(), (int64_t) head.size());
+		if(!hl) { kmahip_set_error("cannot create %s", mv->vcf_path.c_str()); return KMAHIP_EIO; }
+		vcf.put(head.data(), (size_t) hl);
+	}
 	FILE *res = fopen(res_path, "w"), *fsa = fsa_path ? fopen(fsa_path, "w") : nullptr, *aln = aln_path ? fopen(aln_path, "w") : nullptr;
 	if(!res || (fsa_path && !fsa) || (aln_path && !aln)) { if(res) fclose(res); if(fsa) fclose(fsa); if(aln) fclose(aln); kmahip_set_error("cannot create %s", !res ? res_path : (fsa_path && !fsa) ? fsa_path : aln_path); return KMAHIP_EIO; }
 	// the extended-features file (-ef): its rows come from this loop, so that a template is in both files or in neither
@@ -1465,6 +1538,19 @@ int kmahip_write_res_fsa(kmahip_db *db, const char *res_path, const char *fsa_pa
 			const kmahip_mapstat_row m = {mapstat->read_counts[tt], mapstat->frag_counts[tt], e.score_sum[tt], e.var[tt], e.nuc_high_var[tt], e.max_depth[tt], e.snp_sum[tt], e.insert_sum[tt],
 			                              e.deletion_sum[tt], e.read_count_aln[tt], e.fragment_count_aln[tt]};
 			if(kmahip_mapstat_line(name.c_str(), &row, cover[tt], aln_len[tt], depth[tt], ID_t, Depth_t, &m, line.data(), (int64_t) line.size())) fputs(line.data(), mst);
+		}
+		if(mat.gz) {          // updateMatrix (assembly.c:85-140): `#name`, the rows the device formatted, an empty line
+			mat.put("#", 1); mat.put(name.data(), name.size()); mat.put("\n", 1);
+			mat.put(mv->mat_text.data() + mv->mat_off[tt], (size_t) (mv->mat_off[tt + 1] - mv->mat_off[tt]));
+			mat.put("\n", 1);
+		}
+		if(vcf.gz) {          // updateVcf (vcf.c:97-282): the records the device chose, formatted here
+			for(int64_t x = mv->rec_off[tt]; x < mv->rec_off[tt + 1]; ++x) {
+				const int w = kmahip_vcf_line(name.c_str(), &mv->recs[(size_t) x], mv->evalue, mv->support, mv->bcd, mv->vcf, line.data(), (int64_t) line.size());
+				if(!w) { kmahip_set_error("a row of %s does not fit its buffer", mv->vcf_path.c_str()); rc = KMAHIP_EINVAL; break; }
+				vcf.put(line.data(), (size_t) w);
+			}
+			if(rc) break;
 		}
 		const char *q0 = cons_off[tt] >= 0 ? cons + cons_off[tt] : "";
 		if(aln) {
@@ -1495,7 +1581,9 @@ int kmahip_write_res_fsa(kmahip_db *db, const char *res_path, const char *fsa_pa
 	const bool bad2 = fsa && fclose(fsa) != 0, bad3 = aln && fclose(aln) != 0;
 	bool bad4 = false;
 	if(mst) { bad4 = fclose(mst) != 0; mst = nullptr; }
+	const int rc_mat = mat.close(), rc_vcf = vcf.close();
 	if(rc) return rc;
+	if(rc_mat || rc_vcf) { kmahip_set_error("write to %s failed", rc_mat ? mv->mat_path.c_str() : mv->vcf_path.c_str()); return KMAHIP_EIO; }
 	if(bad4) { kmahip_set_error("write to %s failed", mapstat->path); return KMAHIP_EIO; }
 	if(bad || bad2 || bad3) { kmahip_set_error("write to %s failed", res_path); return KMAHIP_EIO; }
 	return KMAHIP_OK;

@@ -22,7 +22,8 @@ void kmahip_gzstream_submit(kmahip_gzstream *g, const char *text, size_t bytes, 
 int kmahip_gzstream_close(kmahip_gzstream *g);
 int kmahip_write_res_fsa(kmahip_db *db, const char *res_path, const char *fsa_path, bool header, const kmahip_res_row *rows, int64_t n_rows,
                          const int32_t *owner, int rank, const int64_t *cover, const int64_t *aln_len, const int64_t *depth, const char *cons,
-                         const int64_t *cons_off, double ID_t, double Depth_t, int ref_fsa, const char *aln_path, const KmaMapstat *mapstat = nullptr);       // pipeline.hip
+                         const int64_t *cons_off, double ID_t, double Depth_t, int ref_fsa, const char *aln_path, const KmaMapstat *mapstat = nullptr,
+                         const KmaMatVcf *mv = nullptr);       // pipeline.hip
 
 namespace {
 
@@ -248,6 +249,10 @@ struct kmahip_session {
 	bool ef = false;
 	std::string ef_cmdline, ef_tdb;
 	int64_t ef_frags = 0;
+	// the count matrix and the VCF file (kmahip_session_set_matrix, kmahip_session_set_vcf): -vcf's value and the header's last column
+	bool matrix = false;
+	int vcf = 0;
+	std::string vcf_tdb;
 	~kmahip_session() {
 		for(Batch &b : batches) b.release();
 		for(Batch &b : uploaded) b.release();
@@ -337,6 +342,20 @@ extern "C" int kmahip_session_set_ef(kmahip_session *S, const char *cmdline, con
 extern "C" int kmahip_session_set_ef_fragments(kmahip_session *S, int64_t records) {
 	if(!S || records < 0) { kmahip_set_error("kmahip_session_set_ef_fragments: a session and a count that is not negative"); return KMAHIP_EINVAL; }
 	S->ef_frags = records;
+	return KMAHIP_OK;
+}
+
+extern "C" int kmahip_session_set_matrix(kmahip_session *S) {
+	if(!S) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(S->n || S->n_reads || !S->uploaded.empty()) { kmahip_set_error("the mode of a session is chosen before its first batch"); return KMAHIP_EINVAL; }
+	S->matrix = true;
+	return KMAHIP_OK;
+}
+
+extern "C" int kmahip_session_set_vcf(kmahip_session *S, int level, const char *t_db) {
+	if(!S || level == 0) { kmahip_set_error("kmahip_session_set_vcf: a session and a level that is not 0"); return KMAHIP_EINVAL; }
+	if(S->n || S->n_reads || !S->uploaded.empty()) { kmahip_set_error("the mode of a session is chosen before its first batch"); return KMAHIP_EINVAL; }
+	S->vcf = level; S->vcf_tdb = t_db ? t_db : S->db->prefix;
 	return KMAHIP_OK;
 }
 
@@ -913,6 +932,15 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 		mapstat.read_counts = ef_req.read_counts; mapstat.frag_counts = ef_req.frag_counts; mapstat.ef = &efo;
 	}
 	const KmaMapstat *mapstat_p = ef_on ? &mapstat : nullptr;
+	// the count matrix and the VCF file (-matrix, -vcf): gathered behind the pile-up, written by the writer of `.res`
+	KmaMatVcf mv;
+	KmaMatVcf *mv_p = (S->matrix || S->vcf) ? &mv : nullptr;
+	if(mv_p) {
+		mv.matrix = S->matrix; mv.vcf = S->vcf; mv.t_db = S->vcf_tdb;
+		mv.mat_path = std::string(out_prefix) + ".mat.gz"; mv.vcf_path = std::string(out_prefix) + ".vcf.gz";
+		mv.evalue = S->opts.evalue; mv.support = S->opts.support; mv.bcd = S->opts.bcd; mv.ID_t = S->opts.ID_t > 0 ? S->opts.ID_t : 1.0; mv.Depth_t = S->opts.Depth_t;
+		mv.mat_off.assign(D + 1, 0); mv.rec_off.assign(D + 1, 0);
+	}
 
 	if(S->pe) {
 		// paired input: the whole run on what the batches left in HBM (kmahip_run_pe's stages; pipeline.hip), then the text files
@@ -921,7 +949,7 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 		kmahip_read_batch hb;
 		session_pe_view(S, 0, n, &hb);
 		int64_t n_frag_rows = 0;
-		KmaPeDev pd{S->names.as<char>(), S->name_off.as<int64_t>(), S->h_text, S->text_chunk, &n_frag_rows, 0, -1, ef_on ? &ef_req : nullptr};
+		KmaPeDev pd{S->names.as<char>(), S->name_off.as<int64_t>(), S->h_text, S->text_chunk, &n_frag_rows, 0, -1, ef_on ? &ef_req : nullptr, mv_p};
 		struct SamFd { int fd = -1; ~SamFd() { (void) kmahip_sam_close(fd); } } sam_fd;
 		if(S->sam_level) {
 			if(ws->pe_chain_on) { kmahip_set_error("SAM records are not built for paired input in the default mode (without -1t1)"); return KMAHIP_EINVAL; }
@@ -944,7 +972,7 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 		(void) since(t);
 		ms[1] += run.ms[0] + run.ms[1]; ms[2] = run.ms[2]; ms[3] = run.ms[3]; ms[4] = run.ms[4]; ms[6] = run.ms[5];
 		if((rc = kmahip_write_res_fsa(db, (prefix + ".res").c_str(), write_fsa ? (prefix + ".fsa").c_str() : nullptr, true, rows.data(), run.n_rows, nullptr, 0, a_cover.data(), a_len.data(),
-		                              a_depth.data(), cons.data(), c_off.data(), S->opts.ID_t > 0 ? S->opts.ID_t : 1.0, S->opts.Depth_t, S->opts.ref_fsa, S->opts.write_aln ? (prefix + ".aln").c_str() : nullptr, mapstat_p))) return rc;
+		                              a_depth.data(), cons.data(), c_off.data(), S->opts.ID_t > 0 ? S->opts.ID_t : 1.0, S->opts.Depth_t, S->opts.ref_fsa, S->opts.write_aln ? (prefix + ".aln").c_str() : nullptr, mapstat_p, mv_p))) return rc;
 		ms[5] = since(t);
 		if(n_rows_out) *n_rows_out = n_frag_rows;
 		return KMAHIP_OK;
@@ -977,11 +1005,13 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 		if(n && score) {
 			kmahip_assemble_opts ao = {mf, S->opts.evalue, S->opts.bcd, 1, S->opts.caller | (S->opts.ref_fsa == 2 ? 8 : 0) | (S->opts.write_aln ? 32 : 0), S->opts.sig90, nullptr, S->opts.support};
 			if((rc = kmahip_assemble2_dev(db, ws, &W, S->t_rc.as<int32_t>(), d_tmpl, &tr, &ao, &asmb))) return rc;
+			// (runKMA_Mt1 writes the matrix and the VCF file too, mt1.c:445-450)
+			if(mv_p && (rc = kmahip_matvcf_gather(db, ws, &row, 1, &asmb, mv_p))) return rc;
 		}
 		ms[4] = since(t);
 		const std::string prefix(out_prefix);
 		if((rc = kmahip_write_res_fsa(db, (prefix + ".res").c_str(), write_fsa ? (prefix + ".fsa").c_str() : nullptr, true, &row, 1, nullptr, 0, a_cover.data(), a_len.data(),
-		                              a_depth.data(), cons.data(), c_off.data(), S->opts.ID_t > 0 ? S->opts.ID_t : 1.0, S->opts.Depth_t, S->opts.ref_fsa, S->opts.write_aln ? (prefix + ".aln").c_str() : nullptr))) return rc;
+		                              a_depth.data(), cons.data(), c_off.data(), S->opts.ID_t > 0 ? S->opts.ID_t : 1.0, S->opts.Depth_t, S->opts.ref_fsa, S->opts.write_aln ? (prefix + ".aln").c_str() : nullptr, nullptr, mv_p))) return rc;
 		ms[5] = since(t);
 		if(S->sink) {          // (written batch by batch: what is left is the end of the file)
 			if((rc = mt1_frag_join(S))) return rc;
@@ -1084,6 +1114,7 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 		if((rc = kmahip_assemble2_dev(db, ws, &W, rc_all, cc.tmpl, &tr, &ao, &asmb))) return rc;
 		// (the extended features behind the pile-up, before anything else uses the workspace; single-end records are fragments all)
 		if(ef_on && (rc = kmahip_assemble_ef_dev(db, ws, n, cc.tmpl, &tr, nullptr, p, &asmb, &efo))) return rc;
+		if(mv_p && (rc = kmahip_matvcf_gather(db, ws, rows.data(), n_rows, &asmb, mv_p))) return rc;
 	}
 	ms[4] = since(t);
 	const std::string prefix(out_prefix);
@@ -1094,7 +1125,7 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 	std::thread text([&]() {
 		auto tt = std::chrono::steady_clock::now();
 		rc_text = kmahip_write_res_fsa(db, (prefix + ".res").c_str(), write_fsa ? (prefix + ".fsa").c_str() : nullptr, true, rows.data(), n_rows, nullptr, 0, a_cover.data(), a_len.data(),
-		                               a_depth.data(), cons.data(), c_off.data(), S->opts.ID_t > 0 ? S->opts.ID_t : 1.0, S->opts.Depth_t, S->opts.ref_fsa, S->opts.write_aln ? (prefix + ".aln").c_str() : nullptr, mapstat_p);
+		                               a_depth.data(), cons.data(), c_off.data(), S->opts.ID_t > 0 ? S->opts.ID_t : 1.0, S->opts.Depth_t, S->opts.ref_fsa, S->opts.write_aln ? (prefix + ".aln").c_str() : nullptr, mapstat_p, mv_p);
 		if(rc_text) err_text = kmahip_last_error();          // (the message is the thread's)
 		ms_text = since(tt);
 	});
