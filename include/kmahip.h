@@ -969,6 +969,11 @@ int kmahip_scan_get_stats(kmahip_ws *ws, kmahip_scan_stats *st, void *stream);
  * records (reads without N's of at most 192 bases, outside the exhaustive mode), out[1] as bare list entries (everything else,
  * and every item with KMAHIP_SCAN_REC=0 in the environment). Read it before another stage is launched on the workspace. */
 int kmahip_ws_scan_routes(kmahip_ws *ws, void *stream, unsigned long long out[2]);
+/* Records of the last scan launch whose template diagonal the prefilter replaced: it counts the bases of the read that differ
+ * from the template store along the diagonal of its first hit and, at two or more, looks up the read's k-mer that ends at the first
+ * of them and files that hit's diagonal when fewer bases differ along it (KMAHIP_SCAN_REFINE=0 in the environment: never). Counted
+ * only while kmahip_scan_set_stats is on; read it before another stage is launched on the workspace. */
+int kmahip_ws_scan_diag_replaced(kmahip_ws *ws, void *stream, unsigned long long *out);
 
 /* work figures of the last long-read trace call on this workspace (kmahip_align_trace_mt1*, kmahip_run_mt1, or the trace stage
  * on reads over 1 kb): DP problems solved, their cells (rows x columns; rows x (band + 1) for banded ones), MEMs of the chained

@@ -197,6 +197,8 @@ def lib():
         L.kmahip_scan_get_stats.argtypes = [C.c_void_p, C.POINTER(ScanStats), C.c_void_p]
         if hasattr(L, "kmahip_ws_scan_routes"):          # (KMAHIP_LIB may name an older library, for side-by-side timing)
             L.kmahip_ws_scan_routes.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]
+        if hasattr(L, "kmahip_ws_scan_diag_replaced"):
+            L.kmahip_ws_scan_diag_replaced.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]
         L.kmahip_ws_set_timing.argtypes = [C.c_void_p, C.c_int]
         L.kmahip_ws_get_timing.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         L.kmahip_align_se_dev.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Reads), C.POINTER(Cands), C.POINTER(Params),
@@ -674,6 +676,12 @@ class KmaHipDB:
         out = (C.c_ulonglong * 2)()
         _check(lib().kmahip_ws_scan_routes(self.ws, C.c_void_p(stream or 0), out))
         return int(out[0]), int(out[1])
+
+    def get_scan_diag_replaced(self, stream=None) -> int:
+        """records of the last scan launch whose diagonal the prefilter replaced (counted with set_stats(True))"""
+        out = C.c_ulonglong(0)
+        _check(lib().kmahip_ws_scan_diag_replaced(self.ws, C.c_void_p(stream or 0), C.byref(out)))
+        return int(out.value)
 
     def get_align_stats(self, stream=None) -> AlignStats:
         st = AlignStats()

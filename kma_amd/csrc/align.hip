@@ -3117,7 +3117,11 @@ static int launch_align(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 	R.uniq_alignment_scores = (unsigned long long *) out->uniq_alignment_scores;
 	R.rec_mate = rec_mate; R.rec_rc = rec_rc; R.out_rc = out->rc; R.pe_mode = rec_mate != nullptr; R.PE = p->rw.PE; R.apm = ((p->apm >> 4) & 3) ? ((p->apm >> 4) & 3) - 1 : (p->apm & 3); R.pe_kind = pe_kind;
 	R.priv = nullptr; R.priv_copies = 0; R.DB_size = db->info.DB_size; R.tasks_cap = tasks_cap;
-	if(out->alignment_scores || out->uniq_alignment_scores) {
+	const unsigned rl_grid = 512;
+	const bool lds_reduce = !R.pe_mode && R.DB_size <= RL_MAX_DB && (out->alignment_scores || out->uniq_alignment_scores) &&
+	                        (n / rl_grid + RL_THREADS) * (int64_t) max_len < (1ll << 31);       // a workgroup's u32 sums cannot overflow
+	// (the private copies belong to reduce_reads_kernel: the LDS reduction never reads them, so it pays for no clear of them)
+	if(!lds_reduce && (out->alignment_scores || out->uniq_alignment_scores)) {
 		const int64_t D = db->info.DB_size;
 		int copies = (int) std::min<int64_t>(64, std::max<int64_t>(1, (256ll << 20) / (16 * D)));
 		if(copies > 1) {
@@ -3132,9 +3136,6 @@ static int launch_align(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 		}
 	}
 	R.t_score_w = A.t_score; R.t_alen_w = A.t_alen; R.t_start_w = A.t_start; R.t_end_w = A.t_end; R.t_tmpl_w = A.t_tmpl;
-	const unsigned rl_grid = 512;
-	const bool lds_reduce = !R.pe_mode && R.DB_size <= RL_MAX_DB && (out->alignment_scores || out->uniq_alignment_scores) &&
-	                        (n / rl_grid + RL_THREADS) * (int64_t) max_len < (1ll << 31);       // a workgroup's u32 sums cannot overflow
 	if(lds_reduce) {
 		ReduceArgs RL = R;
 		RL.priv = nullptr; RL.priv_copies = 0;

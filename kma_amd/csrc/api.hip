@@ -115,6 +115,16 @@ extern "C" int kmahip_ws_scan_routes(kmahip_ws *ws, void *stream, unsigned long 
 	return KMAHIP_OK;
 }
 
+// records whose diagonal the prefilter of the last scan launch replaced (KMAHIP_C_NREPL; counted only with the statistics on)
+extern "C" int kmahip_ws_scan_diag_replaced(kmahip_ws *ws, void *stream, unsigned long long *out) {
+	if(!ws || !out || !ws->counters) return KMAHIP_EINVAL;
+	unsigned long long c = 0;
+	HIP_TRY(hipMemcpyAsync(&c, ws->counters + KMAHIP_C_NREPL, sizeof c, hipMemcpyDeviceToHost, (hipStream_t) stream));
+	HIP_TRY(hipStreamSynchronize((hipStream_t) stream));
+	*out = c;
+	return KMAHIP_OK;
+}
+
 extern "C" int kmahip_align_get_stats(kmahip_ws *ws, kmahip_align_stats *st, void *stream) {
 	if(!ws || !st || !ws->counters) return KMAHIP_EINVAL;
 	unsigned long long c[8];

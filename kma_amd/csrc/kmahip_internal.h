@@ -13,6 +13,7 @@
 // slots of kmahip_ws::counters that scan.hip and api.hip both name: live strand items on the bare list, and as records
 #define KMAHIP_C_NACT 8
 #define KMAHIP_C_NREC 21
+#define KMAHIP_C_NREPL 22      // records whose diagonal the prefilter replaced by a better one (counted with the statistics on)
 #define KMAHIP_KBITS_MUL 0x85EBCA6Bu      // device counter words per workspace
 
 // Probe table in HBM: open hashing over 32-byte buckets of 4 (key, position)
@@ -86,7 +87,7 @@ struct kmahip_ws {
 	int mem_scale;            // MEM slots per (read, template) = the usual 64 (reads up to 1 kb) x this; raised by the runs when a read
 	                          // full of repeats carries more (status 3), 0 = 1
 	// counters (KMAHIP_N_COUNTERS): [0] pool top, [1] status, [2] n_overflow, [3] probes, [4] value elems, [5] active strands,
-	// [6] hash probes, [7] pair pool top, [8] live strand items on the bare list, [9] prefilter probes, [21] records
+	// [6] hash probes, [7] pair pool top, [8] live strand items on the bare list, [9] prefilter probes, [21] records, [22] replaced diagonals
 	unsigned long long *counters;
 	int64_t *overflow_items;
 	int64_t *active_items;    // strand items that passed the prefilter (device-wide compaction)

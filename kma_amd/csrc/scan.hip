@@ -43,6 +43,12 @@ constexpr int THREADS = 256;
 #ifndef KMAHIP_SCAN_WAVES
 #define KMAHIP_SCAN_WAVES 8
 #endif
+// 1 (default): a lane of a RECORD with a usable diagonal settles its whole segment from ONE issue of loads along the diagonal and
+// queues every start that is not on it; 2: the lanes of bare items too (their diagonals are the first hit's, unrepaired: measured
+// slower); 0: a lane probes for its anchor when the diagonal fails there, and walks again (round 6)
+#ifndef KMAHIP_SCAN_SETTLE
+#define KMAHIP_SCAN_SETTLE 1
+#endif
 constexpr int STHREADS = KMAHIP_STHREADS;   // threads of one scan workgroup: SG items x 16 lanes
 constexpr int SG = STHREADS / 16;           // strand items a scan workgroup scores together (16 at 256 threads; 4 = a workgroup of ONE wavefront, whose barriers cost nothing)
 constexpr int CHUNK = 136;            // k-mer start positions per pass
@@ -96,6 +102,7 @@ struct ScanArgs {
 	                     // scan's lanes try that diagonal before they probe
 	uint64_t *recs;      // the prefilter's records of the plain live items (counters[C_NREC] of them, at most rec_cap); NULL: every
 	int64_t rec_cap;     // live item goes to active_items
+	int refine;          // the prefilter checks a record's diagonal against `cat` and tries ONE other when it finds two mismatches or more
 };
 
 constexpr int64_t ITEM_MASK = (1ll << 33) - 1;          // a strand item: (read << 1) | strand, reads < 2^31
@@ -107,7 +114,7 @@ constexpr int64_t DIAG_BIAS = 1ll << 20, DIAG_NONE = 0x7FFFFFFFll;      // (read
 constexpr int REC_WORDS = 8;
 static_assert(REC_WORDS - 2 == SW - 1, "a record carries the staged row but its last, always zero, word");
 
-enum { C_POOL = 0, C_STATUS = 1, C_NOVER = 2, C_PROBES = 3, C_VALS = 4, C_ACTIVE = 5, C_HASH = 6, C_PPOOL = 7, C_NACT = KMAHIP_C_NACT, C_PREF = 9, C_NOVER2 = 10, C_NREC = KMAHIP_C_NREC, N_COUNTERS = KMAHIP_N_COUNTERS };
+enum { C_POOL = 0, C_STATUS = 1, C_NOVER = 2, C_PROBES = 3, C_VALS = 4, C_ACTIVE = 5, C_HASH = 6, C_PPOOL = 7, C_NACT = KMAHIP_C_NACT, C_PREF = 9, C_NOVER2 = 10, C_NREC = KMAHIP_C_NREC, C_NREPL = KMAHIP_C_NREPL, N_COUNTERS = KMAHIP_N_COUNTERS };
 
 // two probes whose home buckets travel together (used after a miss: the k-mer starts behind a mismatch miss in a row)
 __device__ __forceinline__ void probe2(const DevDB &db, uint32_t key1, uint32_t key2, uint32_t &r1, uint32_t &r2) {
@@ -285,14 +292,14 @@ constexpr int PF_ITEMS = PF_BLOCK * PF_ROUNDS;             // items per workgrou
 template <bool STATS>
 __global__ __launch_bounds__(THREADS) void scan_prefilter_kernel(const ScanArgs A) {
 	__shared__ int64_t s_list[PF_ITEMS];      // the bare entries from the front, the entries that become records from the back
-	__shared__ uint32_t s_n, s_nr, s_np, s_nt;
+	__shared__ uint32_t s_n, s_nr, s_np, s_nt, s_nx, s_nrepl;
 	__shared__ unsigned long long s_base, s_rbase;
 	__shared__ uint32_t s_room;
 	const DevDB &db = A.db;
 	const int tid = threadIdx.x;
 	const int k = (int) db.kmersize;
 	const int plane = tid & (PF_PLANES - 1);
-	if(tid == 0) { s_n = 0; s_nr = 0; s_np = 0; s_nt = 0; }
+	if(tid == 0) { s_n = 0; s_nr = 0; s_np = 0; s_nt = 0; s_nx = 0; s_nrepl = 0; }
 	__syncthreads();
 	uint32_t nprobe = 0, ntable = 0;      // k-mers resolved / of them by a gather into the probe table
 	for(int rd = 0; rd < PF_ROUNDS; ++rd) {
@@ -438,9 +445,60 @@ __global__ __launch_bounds__(THREADS) void scan_prefilter_kernel(const ScanArgs 
 			if(x < nw) v = (it & 1) ? strand_win(rs, L, 1, x << 5) : rs[x];
 			w[2 + x] = v;
 		}
+		// The diagonal is the first stride hit's, and a slot of the probe table points at the FIRST occurrence of its k-mer in `cat`: a
+		// read of a family's third variant is filed along the first one's diagonal, where the scan's lanes then fail. So the lane that
+		// holds the read's words counts the bases that differ from `cat` along the diagonal and, at two or more, looks up the read's
+		// k-mer that ENDS at the first of them (it holds what this diagonal has wrong); the diagonal of that hit is filed when fewer
+		// bases differ along it. One try. The diagonal stays a hint either way: the scan verifies every position it takes from it.
+		const int64_t dgf = ent >> 33;
+		if(A.refine && dgf != DIAG_NONE) {
+			// bases of the read that differ from `cat` along the diagonal that puts strand base 0 at `a0` (-1: the read's span leaves
+			// the store there), and the first of them
+			auto mismatches = [&](int64_t a0, int &first_b) -> int {
+				first_b = -1;
+				if(a0 < 0 || ((a0 + ((int64_t) (nw - 1) << 5)) >> 5) > (A.cat_bases >> 5)) return -1;
+				uint64_t tw[SW - 1];
+#pragma unroll
+				for(int x = 0; x < SW - 1; ++x) tw[x] = x < nw ? win2(db.cat, a0 + (x << 5)) : 0ull;
+				int m = 0;
+#pragma unroll
+				for(int x = 0; x < SW - 1; ++x) {
+					const int nb = min(32, L - (x << 5));          // bases of the read in this word
+					if(nb <= 0) continue;
+					uint64_t d = w[2 + x] ^ tw[x];
+					d = (d | (d >> 1)) & 0x5555555555555555ull & (~0ull << (64 - 2 * nb));
+					if(d && first_b < 0) first_b = (x << 5) + (__clzll((long long) d) >> 1);
+					m += __popcll(d);
+				}
+				return m;
+			};
+			int b = -1, b2 = -1;
+			const int m = mismatches(dgf - DIAG_BIAS, b);
+			if(m >= 2) {
+				const int st = min(max(0, b - k + 1), L - k);
+				uint64_t lo = 0, hi = 0;
+#pragma unroll
+				for(int x = 0; x < SW - 1; ++x) if(x == (st >> 5)) { lo = w[2 + x]; hi = x + 1 < SW - 1 ? w[3 + x] : 0ull; }
+				const uint32_t gp = probe(db, (uint32_t) kmer_from(lo, hi, st, k));
+				if(STATS) atomicAdd(&s_nx, 1u);
+				if(gp != MISS) {
+					const int64_t a1 = (int64_t) gp - st;
+					const int m1 = mismatches(a1, b2);
+					if(m1 >= 0 && m1 < m) {
+						w[0] = (uint64_t) (it | ((a1 + DIAG_BIAS) << 33));
+						if(STATS) atomicAdd(&s_nrepl, 1u);
+					}
+				}
+			}
+		}
 		ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(A.recs + (s_rbase + i) * REC_WORDS);
 #pragma unroll
 		for(int x = 0; x < REC_WORDS / 2; ++x) dst[x] = make_ulonglong2(w[2 * x], w[2 * x + 1]);
+	}
+	if(STATS && A.refine) {
+		// the repair probes are table gathers (C_HASH); they examine no stride k-mer and resolve no start (C_PREF, C_PROBES)
+		__syncthreads();
+		if(tid == 0 && s_nx) { atomicAdd(&A.counters[C_HASH], (unsigned long long) s_nx); atomicAdd(&A.counters[C_NREPL], (unsigned long long) s_nrepl); }
 	}
 }
 
@@ -652,18 +710,97 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 #endif
 				if(!s_over[g]) add_run(g, vi, jj, jj + 1);
 			};
-			int own_lo = 0, own_n = 0;          // k-mer starts this lane could not queue
+			constexpr bool SETTLE = KMAHIP_SCAN_SETTLE == 2 || (KMAHIP_SCAN_SETTLE == 1 && REC);
+			constexpr int LPI = STHREADS / SG;                 // lanes per item
+			constexpr int SEG = (CHUNK + LPI - 1) / LPI;         // positions per lane
+			uint32_t own = 0;          // k-mer starts this lane could not queue: bit i = position j0 + i of its segment
 			{
-				constexpr int LPI = STHREADS / SG;                 // lanes per item
-				constexpr int SEG = (CHUNK + LPI - 1) / LPI;         // positions per lane
 				const int g = tid & (SG - 1), sl = tid / SG;
 				const int j0 = sl * SEG, j1 = min(CHUNK, j0 + SEG);
+				constexpr int WALK = SEG - 1;
+				static_assert(WALK + 16 <= 32, "one 32-base window holds the k-mer (k <= 16) and the walk behind it");
+				// starts of the lane's segment (bit i = position j0 + i) into the queue; when the queue is full (every read of the group
+				// riddled with mismatches) the lane keeps them and resolves them itself behind the queue's rounds
+				auto enqueue = [&](uint32_t m) {
+					const int n = __popc(m);
+					if(!n) return;
+					const uint32_t at = atomicAdd(&s_qn, (uint32_t) n);
+					if(at + (uint32_t) n <= (uint32_t) QCAP) {
+						for(uint32_t e = at; m; m &= m - 1, ++e) s_q[e] = (uint16_t) ((g << 8) | (j0 + __ffs((int) m) - 1));
+					} else {
+						for(int i = 0; i < n; ++i) if(at + i < (uint32_t) QCAP) s_q[at + i] = 0xFFFFu;
+						own = m;
+					}
+				};
 				// ONE anchor probe and walk per lane, straight-line. What a lane has left afterwards -- the k-mer starts behind a
 				// miss or behind a walk that a mismatch cut short -- goes into a workgroup-wide queue and is resolved below by all
 				// threads side by side, one probe each: a lane that resolved them itself, two per round trip, kept its workgroup
 				// waiting for five dependent gathers (profiles/r3_scan_phase_counters.md: phase 1 was 28 % of the instructions
 				// and 47 % of the time).
-				if(g < ng && c0 + j0 < s_len[g] - k + 1) {
+				// An item with a diagonal and no N's: everything a lane needs of its segment lies along the diagonal -- the list of every
+				// start (vs_id) and the 32 template bases under the segment -- and is fetched in ONE issue of loads. A start is settled
+				// when its k bases are the template's and a k-mer of the index starts there; every maximal run of such starts is entered,
+				// the ones behind a mismatch too. Every other start, the anchor included, goes to the queue: the lane itself issues no
+				// probe and no second set of loads while its workgroup waits at the barrier.
+				bool settled = false;
+				if(SETTLE && g < ng && c0 + j0 < s_len[g] - k + 1 && s_diag[g] != (int) DIAG_NONE && (REC || !s_nN[g])) {
+					const int npos = s_len[g] - k + 1, p = c0 + j0;
+					const int64_t at = (int64_t) s_diag[g] - DIAG_BIAS + p;
+					if(at >= 0 && at < A.cat_bases) {
+						settled = true;
+						const uint64_t *wsrc = &w_lds[g * SW];
+						const int wb = staged_once ? 0 : (c0 >> 5);
+						const uint64_t qw = win2(wsrc, p - (wb << 5));
+						uint32_t vv[WALK + 1];
+						const uint32_t *vp = db.vs_id + at;          // one address, immediate offsets: the loads merge
+#pragma unroll
+						for(int i = 0; i <= WALK; ++i) vv[i] = vp[i];
+						const uint64_t tw = win2(db.cat, at);
+						// one bit per base, base b at bit 2b: set where read and template differ; then OR over the k bases from b on
+						// (window widths 1, 2, 4, .. doubled up to k: shifts by whole bases, uniform in the workgroup), so that bit 2i
+						// says whether start i has a base off the diagonal. Start 8 needs bases 8 .. 8 + k - 1 <= 23: inside the window.
+						uint64_t d = __brevll(qw ^ tw);
+						d = (d | (d >> 1)) & 0x5555555555555555ull;
+#pragma unroll
+						for(int wdt = 1; wdt < 16; wdt <<= 1) {
+							const int sh = min(wdt, max(0, k - wdt));      // (0 once the window is k wide)
+							d |= d >> (2 * sh);
+						}
+						// the even bits 0 .. 16 side by side
+						uint32_t dirty = (uint32_t) d & 0x15555u;
+						dirty = (dirty | (dirty >> 1)) & 0x33333u;
+						dirty = (dirty | (dirty >> 2)) & 0x0F0F0Fu;
+						dirty = (dirty | (dirty >> 4)) & 0xFF00FFu;
+						dirty = (dirty | (dirty >> 8)) & 0x1FFu;
+						const uint32_t all = (1u << min(j1 - j0, npos - p)) - 1u;      // the starts of the segment inside the read
+						uint32_t on = all & ~dirty;
+#pragma unroll
+						for(int i = 0; i <= WALK; ++i) if(vv[i] == KMAHIP_EMPTY_VI) on &= ~(1u << i);
+						// bit i of bm: a run of equal lists starts at i
+						uint32_t bm = on & ~(on << 1);
+#pragma unroll
+						for(int i = 1; i <= WALK; ++i) if(vv[i] != vv[i - 1]) bm |= on & (1u << i);
+						const int non = __popc(on);
+						nres += non;
+						if(MODE && non) atomicAdd(&s_hits[g], non);
+#ifdef KMAHIP_DIAG
+						if(A.ablate & 1) bm = 0;
+#endif
+						if(s_over[g]) bm = 0;                // the item goes to the overflow kernel anyway
+						while(bm) {
+							const int i0 = __ffs((int) bm) - 1;
+							bm &= bm - 1;
+							// the run ends before the next start of one, and where the starts leave the diagonal
+							const int i1 = min(bm ? __ffs((int) bm) - 1 : 32, __ffs((int) ~(on | ((1u << i0) - 1u))) - 1);
+							uint32_t vi = vv[0];
+#pragma unroll
+							for(int i = 1; i <= WALK; ++i) if(i0 == i) vi = vv[i];
+							add_run(g, vi, j0 + i0, j0 + i1);            // positions [rs, re) of the pass
+						}
+						enqueue(all & ~on);
+					}
+				}
+				if(!settled && g < ng && c0 + j0 < s_len[g] - k + 1) {
 					const int L = s_len[g], npos = L - k + 1, strand = (int) (s_item[g] & 1), nN = REC ? 0 : s_nN[g];
 					const int32_t *Nl = A.N + s_noff[g];
 					const uint64_t *wsrc = &w_lds[g * SW];
@@ -680,7 +817,7 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 						// by its hash probe. A position is right when the k bases there are the k-mer and a k-mer of the index starts there.
 						uint32_t gp = MISS;
 						int attempt = 1;
-						const int dg = s_diag[g];
+						const int dg = SETTLE ? (int) DIAG_NONE : s_diag[g];          // (SETTLE: those lanes are settled above)
 						if(dg != (int) DIAG_NONE) {
 							const int64_t at = (int64_t) dg - DIAG_BIAS + p;
 							if(at >= 0 && at < A.cat_bases) { gp = (uint32_t) at; attempt = 0; }
@@ -695,8 +832,6 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 								if(gp == MISS) break;
 							}
 							// everything the walk needs depends only on gp: issue it all at once (one latency, not one per step)
-							constexpr int WALK = SEG - 1;
-							static_assert(WALK + 16 <= 32, "one 32-base window holds the k-mer (k <= 16) and the walk behind it");
 							uint32_t vv[WALK + 1];
 							const uint32_t *vp = db.vs_id + gp;          // one address, immediate offsets: the loads merge
 #pragma unroll
@@ -749,17 +884,9 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 						++nres;
 					}
 					++jj;
-					// what is left of the segment: into the queue; when the queue is full (every read of the group riddled with
-					// mismatches) the lane keeps it and resolves it itself behind the queue round
+					// what is left of the segment: into the queue
 					const int left = min(j1, npos - c0) - jj;
-					if(left > 0) {
-						const uint32_t at = atomicAdd(&s_qn, (uint32_t) left);
-						if(at + (uint32_t) left <= (uint32_t) QCAP) for(int i = 0; i < left; ++i) s_q[at + i] = (uint16_t) ((g << 8) | (jj + i));
-						else {
-							for(int i = 0; i < left; ++i) if(at + i < (uint32_t) QCAP) s_q[at + i] = 0xFFFFu;
-							own_lo = jj; own_n = left;
-						}
-					}
+					if(left > 0) enqueue(((1u << left) - 1u) << (jj - j0));
 					if(MODE && hc) atomicAdd(&s_hits[g], hc);
 				}
 			}
@@ -769,10 +896,10 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 				const uint32_t qn = min(s_qn, (uint32_t) QCAP);
 				const int q_iters = (int) ((qn + STHREADS - 1) / STHREADS);
 				// (a lane that kept its k-mer starts takes them one by one behind the queue's rounds)
-				for(int it = 0; it < q_iters + own_n; ++it) {
+				for(int it = 0; it < q_iters || own; ++it) {
 					uint32_t v = 0xFFFFu;
 					if(it < q_iters) { const uint32_t e = (uint32_t) it * STHREADS + tid; if(e < qn) v = s_q[e]; }
-					else v = (uint32_t) (((tid & (SG - 1)) << 8) | (own_lo + it - q_iters));
+					else { v = (uint32_t) (((tid & (SG - 1)) << 8) | ((tid / SG) * SEG + __ffs((int) own) - 1)); own &= own - 1; }
 					if(v != 0xFFFFu) resolve((int) (v >> 8), (int) (v & 255u));
 				}
 			}
@@ -1147,23 +1274,28 @@ __global__ __launch_bounds__(CB) void combine_count_kernel(const ScanArgs A, int
 }
 
 __global__ __launch_bounds__(1024) void scan_blocks_kernel(int64_t *blk_sums, int64_t nblk) {
-	// single workgroup exclusive scan over the per-block totals
-	__shared__ int64_t part[1024];
-	const int t = threadIdx.x;
-	const int64_t per = (nblk + 1023) / 1024;
-	const int64_t b0 = t * per, b1 = min(nblk, b0 + per);
-	int64_t s = 0;
-	for(int64_t i = b0; i < b1; ++i) s += blk_sums[i];
-	part[t] = s;
-	__syncthreads();
-	for(int d = 1; d < 1024; d <<= 1) {
-		int64_t v = (t >= d) ? part[t - d] : 0;
+	// single workgroup exclusive scan over the per-block totals, in tiles of 1024 that are read and written coalesced: a wavefront
+	// scans its 64 values by shuffles, the 16 wave totals go through LDS (two buffers in turn, so one barrier per tile) and every
+	// thread carries the sum of the tiles before
+	__shared__ int64_t wtot[2][1024 / 64];
+	const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+	int64_t carry = 0;
+	int64_t nxt = t < nblk ? blk_sums[t] : 0;
+	int buf = 0;
+	for(int64_t base = 0; base < nblk; base += 1024, buf ^= 1) {
+		const int64_t i = base + t, v = nxt;
+		nxt = i + 1024 < nblk ? blk_sums[i + 1024] : 0;          // (the next tile travels while this one is scanned)
+		int64_t inc = v;
+#pragma unroll
+		for(int d = 1; d < 64; d <<= 1) { const int64_t a = __shfl_up(inc, d, 64); if(lane >= d) inc += a; }
+		if(lane == 63) wtot[buf][wave] = inc;
 		__syncthreads();
-		part[t] += v;
-		__syncthreads();
+		int64_t before = 0, total = 0;
+#pragma unroll
+		for(int w = 0; w < 1024 / 64; ++w) { const int64_t c = wtot[buf][w]; if(w < wave) before += c; total += c; }
+		if(i < nblk) blk_sums[i] = carry + before + inc - v;
+		carry += total;
 	}
-	int64_t run = part[t] - s;
-	for(int64_t i = b0; i < b1; ++i) { const int64_t v = blk_sums[i]; blk_sums[i] = run; run += v; }
 }
 
 __global__ __launch_bounds__(CB) void combine_write_kernel(const ScanArgs A, const int32_t *rc_flag, const int32_t *flag,
@@ -1800,6 +1932,12 @@ static int64_t diag_cat_bases(const kmahip_db *db) {
 	return total > 0 && total < (1ll << 30) ? total : 0;
 }
 
+// the prefilter checks and repairs the diagonal of a record (KMAHIP_SCAN_REFINE=0: it files the first hit's, as found)
+static int scan_refine_on(int64_t cat_bases) {
+	if(const char *e = getenv("KMAHIP_SCAN_REFINE")) if(!atoi(e)) return 0;
+	return cat_bases > 0;
+}
+
 // Does the prefilter write records for this batch? KMAHIP_SCAN_REC=0 (read per launch): never. Nor in the exhaustive mode, nor for
 // a batch whose caller declares a read beyond the record's 192 bases (kmahip_reads::max_len; 0 = not told): the bare list's
 // looping launch is for a short list -- with 35 spilled dwords it takes 3.8 ms more per 10 M reads than the straight-line kernel
@@ -1893,6 +2031,7 @@ int kmahip_launch_scan_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	A.dense = ws->dense; A.dense_slots = ws->dense_slots; A.active_items = ws->active_items;
 	A.mode = 0; A.pool_sc = nullptr; A.pool_tail0 = 2 * n * INL; A.cat_bases = diag_cat_bases(db);
 	A.recs = scan_records_on(ws, reads, p) ? ws->recs : nullptr; A.rec_cap = ws->rec_cap;
+	A.refine = scan_refine_on(A.cat_bases);
 	A.ablate = 0;
 #ifdef KMAHIP_DIAG
 	if(const char *e = getenv("KMAHIP_ABLATE_SCAN")) A.ablate = atoi(e);
@@ -1955,7 +2094,7 @@ int kmahip_launch_chain_anchors(kmahip_db *db, kmahip_ws *ws, const kmahip_reads
 	S.pool = ws->pool; S.pool_cap = ws->pool_cap; S.counters = ws->counters; S.overflow_items = ws->overflow_items;
 	S.dense = ws->dense; S.dense_slots = ws->dense_slots; S.active_items = ws->active_items;
 	S.mode = 0; S.pool_sc = nullptr; S.pool_tail0 = 2 * n * INL; S.ablate = 0; S.cat_bases = 0;
-	S.recs = nullptr; S.rec_cap = 0;          // (the anchor kernel takes every live item from the bare list)
+	S.recs = nullptr; S.rec_cap = 0; S.refine = 0;          // (the anchor kernel takes every live item from the bare list)
 	S.in_items = ws->active_items; S.in_count = C_NACT; S.out_over = ws->overflow_items; S.out_count = C_NOVER;
 	A.pool = pool; A.pool_cap = pool_cap; A.a_off = a_off; A.a_n = a_n; A.slow = slow; A.cnt = cnt;
 	HIP_TRY(hipMemsetAsync(ws->counters, 0, sizeof(unsigned long long), stream));
@@ -1995,6 +2134,7 @@ int kmahip_launch_scan_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	A.dense = ws->dense; A.dense_slots = ws->dense_slots; A.active_items = ws->active_items;
 	A.ablate = 0; A.mode = 1; A.pool_sc = ws->pool_sc; A.pool_tail0 = 0; A.cat_bases = diag_cat_bases(db);
 	A.recs = scan_records_on(ws, reads, p) ? ws->recs : nullptr; A.rec_cap = ws->rec_cap;
+	A.refine = scan_refine_on(A.cat_bases);
 #ifdef KMAHIP_DIAG
 	if(const char *e = getenv("KMAHIP_ABLATE_SCAN")) A.ablate = atoi(e);
 #endif
