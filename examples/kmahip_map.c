@@ -215,10 +215,12 @@ static void *xcalloc(size_t n, size_t sz) { void *p = calloc(n ? n : 1, sz); if(
 static void usage(void) {
 	fprintf(stderr, "usage: kmahip_map (-i reads.fq[.gz] | -ipe r1.fq[.gz] r2.fq[.gz] [-apm p|u] | -int interleaved.fq[.gz] [-apm p|u]) -t_db <index prefix> -o <output prefix> [-1t1] [-Mt1 <template>] [-bcNano] [-bc90] [-bc <support>] [-bcg] [-ref_fsa [n]] [-dense]\n"
 	                "       [-t threads] [-nc] [-na] [-nf] [-mf fragments] [-ml len] [-xl len] [-mp phred] [-mi phred] [-eq q] [-mq q] [-ts bases] [-mrs f] [-mrc f] [-mct f]\n"
-	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev] [-sam n] [-ef [n]] [-matrix] [-vcf [n]]\n"
+	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev] [-sam n] [-ef [n]] [-matrix] [-vcf [n]] [-proxi f] [-ill]\n"
 	                "       [-reward n] [-gapopen n] [-gapextend n] [-localopen n] [-Npenalty n] [-per n] [-transition n] [-transversion n] [-penalty n] [-cge]\n"
 	                "       (-s1dev, like -gpus not an option of kma: stage 1 of plain FASTQ input on the device; one rank, -1t1 only; its batches close at a quarter\n"
 	                "        of a gigabase of their own accord, KMAHIP_MAP_BATCH_BASES does not apply to them)\n"
+	                "       (-proxi f, -1 <= f <= 1, and the preset -ill = -1t1 -mrc 0.1 -lc -proxi -0.98 -bc 0.9 -bcd 10: proximity matching on single-end input\n"
+	                "        with -1t1; not with -ipe / -int, -Mt1, -mem_mode, -gpus N, -s1dev or -sam n)\n"
 	                "(the options of kma 1.5.1 this path implements; -apm takes p or u; everything else is refused)\n");
 }
 
@@ -302,6 +304,7 @@ int main(int argc, char **argv) {
 	int sam = 0, sam_bare = 0, status_opt = 0;   /* -sam [n] (kma.c:1005-1017); -status, which the reference refuses beside it (kma.c:1254) */
 	int ef = 0;                                  /* -ef [n] (kma.c:938-948): the extended-features file <out>.mapstat */
 	int matrix = 0, vcf = 0;                     /* -matrix (kma.c:667): <out>.mat.gz; -vcf [n] (kma.c:949-961): <out>.vcf.gz, n = 2 fills its FILTER column */
+	int proxi_opt = 0;                           /* -proxi / -ill given (for the refusals' wording; what counts is par.minFrac) */
 	int base_call = 0, sig_mode = 0, ref_fsa = 0, dense = 0;      /* as kmahip_assemble_opts.caller (0-2 here) / .sig90; printconsensus.c's ref_fsa */
 	double support = 0;
 	long long max_frag = 0;
@@ -414,6 +417,22 @@ int main(int argc, char **argv) {
 		else if(!strcmp(o, "-tmp") || !strcmp(o, "-verbose")) { if(a + 1 < argc && argv[a + 1][0] != '-') ++a; }
 		else if(!strcmp(o, "-mem_mode")) mem_mode = 1;                                           /* kma.c:547 */
 		else if(!strcmp(o, "-lc")) lc = 1;                                                      /* kma.c:694-701 */
+		else if(!strcmp(o, "-proxi")) {                                                         /* kma.c:702-721: 1 and -1 leave everything as it is */
+			char *end = NULL;
+			if(a + 1 >= argc) { fprintf(stderr, "Need argument at: \"-proxi\".\n"); return 1; }
+			par.minFrac = strtod(argv[++a], &end);
+			if(*end != 0 || par.minFrac < -1 || 1 < par.minFrac) { fprintf(stderr, "Invalid argument at \"-proxi\".\n"); return 1; }
+			proxi_opt = 1;
+		}
+		else if(!strcmp(o, "-ill")) {                                                           /* kma.c:1159-1202: a preset, applied where it stands */
+			one2one = 1;                      /* -1t1 */
+			par.mrc = 0.1;                    /* -mrc 0.1 */
+			lc = 1;                           /* -lc */
+			par.minFrac = -0.98;              /* -proxi -0.98 */
+			support = 0.9; sig_mode = 2;      /* -bc 0.9 */
+			bcd = 10;                         /* -bcd 10 */
+			proxi_opt = 1;                    /* (its -cge and -apm p lines are commented out there) */
+		}
 		else if(!strcmp(o, "-and")) cmp_mode = 1;                                               /* kma.c:915-920 */
 		else if(!strcmp(o, "-oa")) { cmp_mode = 2; ID_t = 1e-300; Depth_t = 0.0; }               /* (ID_t = 0 there; a row needs 0 < id anyway, and 0 means "the default" to kmahip_shard_opts) */
 		else if(!strcmp(o, "-5p") || !strcmp(o, "-3p")) (void) need_int(argc, argv, &a, o);     /* parsed and handed to run_input*, where nothing reads them (runinput.c:127-368: phredStat never touches fiveClip / threeClip) */
@@ -476,6 +495,19 @@ int main(int argc, char **argv) {
 	const int rc_mates = mt1 && input2;
 	if(mt1) input2 = NULL;
 	/* stage 1 on the device feeds the -1t1 sessions of one rank; everything else needs the batches' host arrays */
+	if(par.minFrac != 1.0 && par.minFrac != -1.0) {
+		/* proximity matching is built for stages 2 and 3a of the single-end -1t1 run of one rank (getProxiMatch, update_Scores) */
+		const char *why = NULL;
+		if(input2) why = input2[0] ? "paired input (-ipe: getSecondProxiPen, getF_Proxi / getR_Proxi and the proximity branches of alnFragsUnionPE / alnFragsPenaltyPE)" : "interleaved input (-int)";
+		else if(mt1) why = "-Mt1";
+		else if(chain) why = "the default mode without -1t1 (getProxiChainTemplates)";
+		else if(mem_mode) why = "-mem_mode (the soft-proximity vector of the S2 stream)";
+		else if(gpus > 1 || getenv("KMAHIP_RANK") || getenv("RANK")) why = "-gpus N (several ranks)";
+		else if(getenv("KMAHIP_COMM_FORCE_RCCL") && getenv("KMAHIP_COMM_FORCE_RCCL")[0] == '1') why = "KMAHIP_COMM_FORCE_RCCL";
+		else if(s1dev) why = "-s1dev";
+		else if(sam) why = "-sam n";
+		if(why) { fprintf(stderr, "kmahip_map: %s is not built for %s: proximity matching serves the single-end -1t1 run of one rank\n", proxi_opt ? "-proxi / -ill" : "minFrac", why); return 2; }
+	}
 	if(s1dev && (gpus > 1 || getenv("KMAHIP_RANK") || getenv("RANK") || chain || pe_chain || mt1 || getenv("KMAHIP_MAP_ONE_BATCH") ||
 	             (getenv("KMAHIP_COMM_FORCE_RCCL") && getenv("KMAHIP_COMM_FORCE_RCCL")[0] == '1'))) {
 		fprintf(stderr, "kmahip_map: -s1dev serves a single-rank -1t1 run (not -gpus N, the default mode without -1t1, or -Mt1)\n");

@@ -67,7 +67,12 @@ typedef struct kmahip_params {
 	int32_t mq;           /* -mq, default 0 */
 	double scoreT;        /* -mrs, default 0.5 */
 	double mrc;           /* -mrc, default 0.0 */
-	double minFrac;       /* 1.0 */
+	double minFrac;       /* -proxi, default 1.0 (1 and -1: off); -1 <= minFrac <= 1. Proximity matching in the single-end -1t1 run: stage 2 hands on every
+	                       * template of a strand whose k-mer score reaches (int) (|minFrac| * best) (getProxiMatch savekmers.c:296-340), stage 3a keeps a hit
+	                       * when aln_len * (|minFrac| * best normalised score) <= score or |minFrac| * best read score <= score and adds the best read
+	                       * score (minFrac > 0) or the hit's own (minFrac < 0) to alignment_scores (update_Scores updatescores.c:235-272). Every other entry
+	                       * point -- paired reads, kmahip_scan_chain and the chain runs, -Mt1, the sharded runs, anything under kmahip_set_mem_mode(1) --
+	                       * returns KMAHIP_EINVAL for it */
 	int32_t ts;           /* -ts, default 0: the traceback aligner trims this many bases off the front of every seed of the best chain but
 	                       * the first one when that starts the read (trimSeeds chain.c:493-528, called by KMA() align.c:413; KMA_score
 	                       * has no such step); at least one base of a seed remains */
@@ -78,7 +83,8 @@ typedef struct kmahip_params {
 	                       * above, bits 4-5 = stage 3a + 1 (0: the same as stage 2, 1: p, 2: u). Stage 2 also takes 2 = forced pairing
 	                       * (-apm f / -pm f: save_kmers_forcePair savekmers.c:3779 with getFirstForce / getSecondBestForce -- a couple on the
 	                       * templates both mates hit on opposite strands at the best summed score, or no record at all) -- for kmahip_scan_pe
-	                       * only: stage 3a of forced pairing (alnFragsForcePE) is not built */
+	                       * only: stage 3a of forced pairing (alnFragsForcePE) is not built, and the paired stage-3a, run and session entry points return
+	                       * KMAHIP_EINVAL for it (2 in bits 0-1, or 3 in bits 4-5) */
 } kmahip_params;
 
 typedef struct kmahip_db_info {

@@ -592,7 +592,9 @@ class KmaHipDB:
             pass
 
     # -- host buffers in / out ------------------------------------------------
-    def scan_se(self, batch, exhaustive=0, t_cap=None):
+    def scan_se(self, batch, exhaustive=0, t_cap=None, min_frac=1.0):
+        """Stage 2 of the -1t1 run -> (rc_flag, flag, T_off, T). min_frac: proximity matching (-proxi): every template within that
+        fraction of a strand's best k-mer score is handed on, not only the ties (stage 2 takes its absolute value)"""
         n = batch.n
         seq = np.ascontiguousarray(batch.seq, np.uint64)
         Nn = np.ascontiguousarray(batch.N if len(batch.N) else np.zeros(1, np.int32), np.int32)
@@ -604,7 +606,9 @@ class KmaHipDB:
         cap = t_cap or max(1024, 8 * n)
         p = Params.from_buffer_copy(self.params)
         p.exhaustive = exhaustive
-        for _ in range(4):
+        if min_frac != 1.0:
+            p.minFrac = float(min_frac)
+        for _ in range(8):
             T = np.zeros(cap, np.int32)
             out = Cands(_p(rc_flag), _p(flag), _p(T_off), _p(T), cap)
             rc = lib().kmahip_scan_se(self.h, self.ws, C.byref(r), C.byref(p), C.byref(out))
@@ -650,14 +654,16 @@ class KmaHipDB:
             return o
         raise KmaHipError("scan_chain: output capacity kept overflowing")
 
-    def scan_se_dev(self, seq, seq_off, length, N, N_off, rc_flag, flag, T_off, T, exhaustive=0, stream=None):
-        """All arguments are CUDA(HIP) torch tensors; asynchronous on `stream`."""
+    def scan_se_dev(self, seq, seq_off, length, N, N_off, rc_flag, flag, T_off, T, exhaustive=0, stream=None, min_frac=1.0):
+        """All arguments are CUDA(HIP) torch tensors; asynchronous on `stream`. min_frac: as scan_se."""
         n = length.numel()
         r = Reads(n, seq.data_ptr(), seq_off.data_ptr(), length.data_ptr(), N.data_ptr(), N_off.data_ptr(),
                   seq.numel(), N.numel(), 0)
         out = Cands(rc_flag.data_ptr(), flag.data_ptr(), T_off.data_ptr(), T.data_ptr(), T.numel())
         p = Params.from_buffer_copy(self.params)
         p.exhaustive = exhaustive
+        if min_frac != 1.0:
+            p.minFrac = float(min_frac)
         _check(lib().kmahip_scan_se_dev(self.h, self.ws, C.byref(r), C.byref(p), C.byref(out), C.c_void_p(stream or 0)))
 
     def status(self, stream=None):
@@ -703,9 +709,10 @@ class KmaHipDB:
         return ms.value, n.value
 
     # -- stages 2 + 3a, host buffers ------------------------------------------
-    def map_se(self, batch, exhaustive=0, t_cap=None):
+    def map_se(self, batch, exhaustive=0, t_cap=None, min_frac=1.0):
         """-> (rc_flag, flag, T_off, T), hits dict (n_hits, best_score, flag, tmpl, score, start, end,
-        alignment_scores, uniq_alignment_scores)"""
+        alignment_scores, uniq_alignment_scores). min_frac: proximity matching (-proxi f) in stages 2 and 3a; its sign chooses what a
+        kept hit adds to alignment_scores (positive: the read's best score, negative: the hit's own)"""
         n = batch.n
         seq = np.ascontiguousarray(batch.seq, np.uint64)
         Nn = np.ascontiguousarray(batch.N if len(batch.N) else np.zeros(1, np.int32), np.int32)
@@ -717,8 +724,10 @@ class KmaHipDB:
         cap = t_cap or max(1024, 8 * n)
         p = Params.from_buffer_copy(self.params)
         p.exhaustive = exhaustive
+        if min_frac != 1.0:
+            p.minFrac = float(min_frac)
         D = int(self.info.DB_size)
-        for _ in range(4):
+        for _ in range(8):
             T = np.zeros(cap, np.int32)
             h = dict(n_hits=np.zeros(max(n, 1), np.int32), best_score=np.zeros(max(n, 1), np.int32),
                      flag=np.zeros(max(n, 1), np.int32), tmpl=np.zeros(cap, np.int32), score=np.zeros(cap, np.int32),
@@ -732,6 +741,8 @@ class KmaHipDB:
             if rc == -6 and int(T_off[n]) > cap:
                 cap = max(cap * 2, int(T_off[n]) + 16)
                 continue
+            if rc == -6 and b"candidate pool" in lib().kmahip_last_error():          # (the library has grown its pool: once more)
+                continue
             _check(rc)
             for key in ("n_hits", "best_score", "flag", "rc"):
                 h[key] = h[key][:n]
@@ -739,8 +750,8 @@ class KmaHipDB:
         raise KmaHipError("map_se: output capacity kept overflowing")
 
     def align_se_dev(self, seq, seq_off, length, N, N_off, max_len, rc_flag, flag, T_off, T,
-                     n_hits, best_score, out_flag, h_tmpl, h_score, h_start, h_end, aln_scores, uniq_scores, stream=None):
-        """Stage 3a on device tensors (outputs of scan_se_dev); asynchronous on `stream`."""
+                     n_hits, best_score, out_flag, h_tmpl, h_score, h_start, h_end, aln_scores, uniq_scores, stream=None, min_frac=1.0):
+        """Stage 3a on device tensors (outputs of scan_se_dev); asynchronous on `stream`. min_frac: as map_se."""
         n = length.numel()
         r = Reads(n, seq.data_ptr(), seq_off.data_ptr(), length.data_ptr(), N.data_ptr(), N_off.data_ptr(),
                   seq.numel(), N.numel(), int(max_len))
@@ -748,6 +759,8 @@ class KmaHipDB:
         h = Hits(n_hits.data_ptr(), best_score.data_ptr(), out_flag.data_ptr(), h_tmpl.data_ptr(), h_score.data_ptr(),
                  h_start.data_ptr(), h_end.data_ptr(), aln_scores.data_ptr(), uniq_scores.data_ptr(), None)
         p = Params.from_buffer_copy(self.params)
+        if min_frac != 1.0:
+            p.minFrac = float(min_frac)
         _check(lib().kmahip_align_se_dev(self.h, self.ws, C.byref(r), C.byref(c), C.byref(p), C.byref(h),
                                          C.c_void_p(stream or 0)))
 
@@ -937,9 +950,9 @@ class KmaHipDB:
             o["consensus"] = {t: raw[coff[t]:raw.index(b"\0", coff[t])].decode() for t in range(D) if coff[t] >= 0}
         return o
 
-    def run_se(self, batch, evalue=0.05, bcd=1, max_frag=0, consensus=True, per_read=True, bc_nano=False):
+    def run_se(self, batch, evalue=0.05, bcd=1, max_frag=0, consensus=True, per_read=True, bc_nano=False, min_frac=1.0):
         """The whole single-end run in one call (kmahip_run_se) -> dict(rows [ResRow], cover, aln_len, depth, asm_len, consensus,
-        tmpl, n_hits, rc, trace_stats, ms)"""
+        tmpl, n_hits, rc, trace_stats, ms). min_frac: proximity matching (-proxi f), as map_se."""
         n = batch.n
         seq = np.ascontiguousarray(batch.seq, np.uint64)
         Nn = np.ascontiguousarray(batch.N if len(batch.N) else np.zeros(1, np.int32), np.int32)
@@ -961,6 +974,8 @@ class KmaHipDB:
                   *[(_p(pr[k]) if per_read else None) for k in ("tmpl", "n_hits", "rc", "trace_stats")])
         run.caller = run.sig90 = 1 if bc_nano else 0
         p = Params.from_buffer_copy(self.params)
+        if min_frac != 1.0:
+            p.minFrac = float(min_frac)
         _check(lib().kmahip_run_se(self.h, self.ws, C.byref(r), C.byref(p), float(evalue), int(bcd), int(max_frag), C.byref(run)))
         o["rows"] = [rows[i] for i in range(run.n_rows)]
         if consensus:

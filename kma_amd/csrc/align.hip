@@ -2028,6 +2028,7 @@ struct ReduceArgs {
 	const double *t_norm;
 	int k;
 	double scoreT;
+	double minFrac;       // single records: 1.0, or the signed value of -proxi (update_Scores' two other branches, updatescores.c:235-272)
 	int32_t *n_hits, *best_score, *out_flag, *h_tmpl, *h_score, *h_start, *h_end;
 	unsigned long long *alignment_scores, *uniq_alignment_scores;
 	// private copies of the two vectors (copy c at priv + c * 2 * DB_size): every read adds into one of them, chosen by its
@@ -2179,8 +2180,10 @@ __global__ __launch_bounds__(256) void fold_scores_kernel(const unsigned long lo
 	else if(uniq_alignment_scores) uniq_alignment_scores[i - D] += sum;
 }
 
-// one single-end record (alnFragsSE's tail + update_Scores with minFrac == 1, updatescores.c:203-298): keep the hits with the
-// best normalised score or the best read score, add their scores to the ConClave vectors through add_as / add_us
+// one single-end record (alnFragsSE's tail + update_Scores, updatescores.c:203-298): keep the hits with the best normalised score
+// or the best read score, add their scores to the ConClave vectors through add_as / add_us. Proximity matching (minFrac != 1,
+// :235-272): keep a hit when  aln_len * (|minFrac| * bestScore) <= score  or  |minFrac| * bestReadScore <= score, in the reference's
+// double arithmetic; a kept hit adds the best read score (minFrac > 0) or its own (minFrac < 0)
 template <class FA, class FU>
 __device__ __forceinline__ void reduce_single(const ReduceArgs &R, int64_t r, int64_t o, int64_t e, int fl, FA add_as, FU add_us) {
 	int nh = 0, bestRead = 0;
@@ -2195,15 +2198,20 @@ __device__ __forceinline__ void reduce_single(const ReduceArgs &R, int64_t r, in
 			}
 		}
 		if(bestRead > R.k) {
+			const bool proxi = R.minFrac != 1.0;          // (uniform across the launch)
+			const double mf = R.minFrac < 0 ? -R.minFrac : R.minFrac;
+			const double minScore = mf * bestScore, minRead = mf * (double) bestRead;
 			for(int64_t t = o; t < e; ++t) {
 				const int rs = R.t_score[t];
 				if(!(R.k < rs && R.scoreT <= R.t_norm[t])) continue;
-				const double ms = (double) (rs / R.t_alen[t]);
-				if(ms == bestScore || rs == bestRead) {
+				bool keep;
+				if(proxi) keep = (double) R.t_alen[t] * minScore <= (double) rs || minRead <= (double) rs;
+				else { const double ms = (double) (rs / R.t_alen[t]); keep = ms == bestScore || rs == bestRead; }
+				if(keep) {
 					const int64_t w = o + nh;
 					const int tm = R.t_tmpl[t];
 					R.h_tmpl[w] = tm; R.h_score[w] = rs; R.h_start[w] = R.t_start[t]; R.h_end[w] = R.t_end[t];
-					add_as(abs(tm), rs);
+					add_as(abs(tm), proxi && R.minFrac > 0 ? bestRead : rs);
 					++nh;
 				}
 			}
@@ -2915,7 +2923,12 @@ static int launch_align(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 	const int64_t n = reads->n_reads;
 	if(n < 0 || !cands || !out || !p) { kmahip_set_error("bad arguments"); return KMAHIP_EINVAL; }
 	if(!db->dev.tpos_slots) { kmahip_set_error("index has no .length.b/.seq.b: stage 3a unavailable"); return KMAHIP_EINVAL; }
-	if(p->minFrac != 1.0) { kmahip_set_error("minFrac != 1.0 not supported"); return KMAHIP_EINVAL; }
+	if(!(std::fabs(p->minFrac) <= 1.0)) { kmahip_set_error("minFrac %g outside [-1, 1]", p->minFrac); return KMAHIP_EINVAL; }
+	if(rec_mate) {
+		int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_PE);
+		if(!rcp) rcp = kmahip_refuse_forced_pairing(p);
+		if(rcp) return rcp;
+	}
 	if(n == 0) return KMAHIP_OK;
 	int max_len = reads->max_len;
 	if(max_len <= 0) { kmahip_set_error("kmahip_reads.max_len must be set for the align stage"); return KMAHIP_EINVAL; }
@@ -3111,6 +3124,7 @@ static int launch_align(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 	R.n_reads = n; R.rc_flag = cands->rc_flag; R.flag = cands->flag; R.T_off = cands->T_off; R.T = cands->T;
 	R.t_score = A.t_score; R.t_alen = A.t_alen; R.t_start = A.t_start; R.t_end = A.t_end; R.t_norm = A.t_norm; R.t_tmpl = A.t_tmpl;
 	R.k = (int) db->dev.kmersize; R.scoreT = p->scoreT;
+	R.minFrac = (!rec_mate && kmahip_proxi_on(p)) ? p->minFrac : 1.0;
 	R.n_hits = out->n_hits; R.best_score = out->best_score; R.out_flag = out->flag;
 	R.h_tmpl = out->tmpl; R.h_score = out->score; R.h_start = out->start; R.h_end = out->end;
 	R.alignment_scores = (unsigned long long *) out->alignment_scores;
@@ -3120,6 +3134,9 @@ static int launch_align(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 	const unsigned rl_grid = 512;
 	const bool lds_reduce = !R.pe_mode && R.DB_size <= RL_MAX_DB && (out->alignment_scores || out->uniq_alignment_scores) &&
 	                        (n / rl_grid + RL_THREADS) * (int64_t) max_len < (1ll << 31);       // a workgroup's u32 sums cannot overflow
+	// (proximity matching too: a read's longer hit list adds to MORE entries of the vector, but to the entry of a template as often
+	// as before -- once per strand it is listed on -- and never more than its best read score: the bound per entry, reads x longest
+	// read with the factor two that u32 leaves above 2^31, is the same)
 	// (the private copies belong to reduce_reads_kernel: the LDS reduction never reads them, so it pays for no clear of them)
 	if(!lds_reduce && (out->alignment_scores || out->uniq_alignment_scores)) {
 		const int64_t D = db->info.DB_size;

@@ -1280,6 +1280,7 @@ int kmahip_chain_device(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *d, con
                         int64_t *rec_T, int32_t *T, int64_t rec_cap, int64_t T_cap, int64_t *n_recs, int64_t *n_T) {
 	const int64_t n = d->n_reads;
 	*n_recs = 0; *n_T = 0;
+	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_CHAIN)) return rcp;
 	if(n <= 0) return KMAHIP_OK;
 	if(!db->dev.tlen) { kmahip_set_error("index has no .length.b: the default template finder needs the template lengths"); return KMAHIP_EINVAL; }
 	const int max_len = d->max_len;
@@ -1563,6 +1564,7 @@ extern "C" int kmahip_scan_chain(kmahip_db *db, kmahip_ws *ws, const kmahip_read
 	if(!db || !ws || !reads || !p || !out) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	const int64_t n = reads->n_reads;
 	out->n_recs = 0; out->n_T = 0;
+	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_CHAIN)) return rcp;
 	if(n <= 0) return KMAHIP_OK;
 	if(reads->max_len <= 0) { kmahip_set_error("kmahip_reads.max_len must be set"); return KMAHIP_EINVAL; }
 	const bool dbg = getenv("KMAHIP_DEBUG_TIMING") != nullptr;

@@ -162,6 +162,28 @@ int kmahip_cmp(bool t, bool q);          // conclave.hip: the reference's `cmp` 
 #define HIP_TRY(expr) do { hipError_t e__ = (expr); if(e__ != hipSuccess) { \
 	kmahip_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); return KMAHIP_EDEVICE; } } while(0)
 
+// Proximity matching (-proxi: kmahip_params.minFrac other than 1 and -1, kma.c:708) is built for the single-end -1t1 run, stages 2
+// and 3a (getProxiMatch, update_Scores). Every other entry point refuses it by name: KMAHIP_EINVAL, `what` = what is not built.
+int kmahip_mem_mode();          // pipeline.hip
+static inline bool kmahip_proxi_on(const kmahip_params *p) { return p->minFrac != 1.0 && p->minFrac != -1.0; }
+static inline int kmahip_refuse_proxi(const kmahip_params *p, const char *what) {
+	if(!p || !kmahip_proxi_on(p)) return KMAHIP_OK;
+	kmahip_set_error("proximity matching (minFrac %g) serves the single-end -1t1 run, not %s", p->minFrac, what);
+	return KMAHIP_EINVAL;
+}
+// Forced pairing (kmahip_params.apm: 2 in bits 0-1, or 3 in bits 4-5) has its stage 2 only (kmahip_scan_pe): stage 3a would run
+// penalty pairing on its couples, not alnFragsForcePE
+static inline int kmahip_refuse_forced_pairing(const kmahip_params *p) {
+	if(!p || ((p->apm & 3) != 2 && ((p->apm >> 4) & 3) != 3)) return KMAHIP_OK;
+	kmahip_set_error("forced pairing (apm %d) is built for kmahip_scan_pe only: stage 3a (alnFragsForcePE) is not", (int) p->apm);
+	return KMAHIP_EINVAL;
+}
+#define KMAHIP_PROXI_PE "paired reads (getSecondProxiPen, getF_Proxi / getR_Proxi and the minFrac branches of alnFragsUnionPE / alnFragsPenaltyPE are not built)"
+#define KMAHIP_PROXI_CHAIN "the default mode's chain finder (getProxiChainTemplates is not built)"
+#define KMAHIP_PROXI_MT1 "the -Mt1 run"
+#define KMAHIP_PROXI_MEM "-mem_mode (the soft-proximity vector of the S2 stream is not built)"
+#define KMAHIP_PROXI_SHARD "the sharded runs"
+
 int kmahip_launch_scan_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
                           const kmahip_params *p, kmahip_cands *out, hipStream_t stream);
 int kmahip_launch_align_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads, const kmahip_cands *cands,

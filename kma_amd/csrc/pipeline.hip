@@ -151,6 +151,11 @@ __global__ __launch_bounds__(256) void mem_hits_pe_kernel(int64_t np, int k, con
 
 int kmahip_stage3a_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads, const kmahip_pe_recs *recs, const kmahip_params *p, kmahip_hits *out, int32_t *pe_kind, hipStream_t stream) {
 	if(!g_mem_mode) return kmahip_launch_align_pe(db, ws, reads, recs, p, out, pe_kind, stream);
+	{
+		int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_MEM);
+		if(!rcp) rcp = kmahip_refuse_forced_pairing(p);
+		if(rcp) return rcp;
+	}
 	if(!db->dev.tlen) { kmahip_set_error("index has no .length.b"); return KMAHIP_EINVAL; }
 	const int64_t np = reads->n_reads / 2;
 	if(np) hipLaunchKernelGGL(mem_hits_pe_kernel, dim3((unsigned) ((np + 255) / 256)), dim3(256), 0, stream, np, (int) db->info.kmersize, reads->len, *recs, db->dev.tlen, *out, pe_kind,
@@ -161,6 +166,7 @@ int kmahip_stage3a_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads, c
 
 int kmahip_stage3a_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads, const kmahip_cands *cands, const kmahip_params *p, kmahip_hits *out, hipStream_t stream) {
 	if(!g_mem_mode) return kmahip_launch_align_se(db, ws, reads, cands, p, out, stream);
+	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_MEM)) return rcp;
 	if(!db->dev.tlen) { kmahip_set_error("index has no .length.b"); return KMAHIP_EINVAL; }
 	const int64_t n = reads->n_reads;
 	// (a record with a negative score whose list ends on a forward template would be filed with a negative count and take anker_rc in
@@ -597,6 +603,11 @@ static int run_pe_impl(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *ba
 	if(!db || !ws || !batch || !p || !out || !out->rows || !out->assembly.cover || !out->assembly.aln_len || !out->assembly.depth || !out->assembly.asm_len ||
 	   (!batch->pair && batch->reads.n_reads > 0)) {
 		kmahip_set_error("null argument"); return KMAHIP_EINVAL;
+	}
+	{
+		int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_PE);
+		if(!rcp) rcp = kmahip_refuse_forced_pairing(p);
+		if(rcp) return rcp;
 	}
 	const kmahip_reads &R = batch->reads;
 	const int64_t n = R.n_reads;
@@ -1142,6 +1153,7 @@ extern "C" int kmahip_run_chain(kmahip_db *db, kmahip_ws *ws, const kmahip_reads
                                 const kmahip_params *p, const kmahip_chain_params *cp, double evalue, int bcd, int64_t max_frag,
                                 const char *frag_path, kmahip_run *out) {
 	if(!db || !ws || !reads || !p || !out || !out->rows || !out->assembly.cover || !out->assembly.aln_len || !out->assembly.depth || !out->assembly.asm_len) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_CHAIN)) return rcp;
 	if(frag_path && reads && reads->n_reads > 0 && (!names || !name_off)) { kmahip_set_error("the fragment file needs the read headers"); return KMAHIP_EINVAL; }
 	const int64_t n = reads->n_reads;
 	if(n < 0 || reads->seq_words < 0 || reads->N_total < 0) { kmahip_set_error("negative size"); return KMAHIP_EINVAL; }
@@ -1213,6 +1225,7 @@ extern "C" int kmahip_run_mt1(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *
 	if(!db || !ws || !reads || !p || !aopts || !out || !out->rows || out->rows_cap < 1 || !out->assembly.cover || !out->assembly.aln_len || !out->assembly.depth || !out->assembly.asm_len) {
 		kmahip_set_error("null argument"); return KMAHIP_EINVAL;
 	}
+	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_MT1)) return rcp;
 	const int64_t n = reads->n_reads;
 	if(n < 0 || reads->seq_words < 0 || reads->N_total < 0) { kmahip_set_error("negative size"); return KMAHIP_EINVAL; }
 	const size_t D = db->info.DB_size;
@@ -1893,6 +1906,7 @@ static int sharded_after_stage2(kmahip_db *db, kmahip_ws *ws, kmahip_comm *comm,
 extern "C" int kmahip_run_se_sharded(kmahip_db *db, kmahip_ws *ws, kmahip_comm *comm, const kmahip_read_batch *batch, const kmahip_params *p,
                                      const kmahip_shard_opts *opts, const char *out_prefix, double ms[8]) {
 	if(!db || !ws || !batch || !p || !opts || !out_prefix || !ms) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_SHARD)) return rcp;
 	const kmahip_reads &R = batch->reads;
 	const int64_t n = R.n_reads;
 	if(n < 0 || R.seq_words < 0 || R.N_total < 0) { kmahip_set_error("negative size"); return KMAHIP_EINVAL; }
@@ -1942,6 +1956,7 @@ extern "C" int kmahip_run_se_sharded(kmahip_db *db, kmahip_ws *ws, kmahip_comm *
 extern "C" int kmahip_run_chain_sharded(kmahip_db *db, kmahip_ws *ws, kmahip_comm *comm, const kmahip_read_batch *batch, const kmahip_params *p,
                                         const kmahip_chain_params *cp, const kmahip_shard_opts *opts, const char *out_prefix, double ms[8]) {
 	if(!db || !ws || !comm || !batch || !p || !opts || !out_prefix || !ms) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_SHARD)) return rcp;
 	const kmahip_reads &R = batch->reads;
 	const int64_t n = R.n_reads;
 	if(n < 0 || R.seq_words < 0 || R.N_total < 0) { kmahip_set_error("negative size"); return KMAHIP_EINVAL; }
@@ -1997,6 +2012,7 @@ __global__ __launch_bounds__(256) void mt1_kept_kernel(int64_t n, const int32_t 
 extern "C" int kmahip_run_mt1_sharded(kmahip_db *db, kmahip_ws *ws, kmahip_comm *comm, const kmahip_read_batch *batch, int32_t tmpl, int one2one,
                                       const kmahip_params *p, const kmahip_shard_opts *opts, const char *out_prefix, double ms[8]) {
 	if(!db || !ws || !comm || !batch || !p || !opts || !out_prefix || !ms) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_SHARD)) return rcp;
 	const int W = kmahip_comm_world(comm), rank = kmahip_comm_rank(comm);
 	const kmahip_reads &R = batch->reads;
 	const int64_t n = R.n_reads;
@@ -2121,6 +2137,8 @@ static int shard_pe_tail(ShardCtx *sc, kmahip_db *db, kmahip_ws *ws, DevBlock &B
 extern "C" int kmahip_run_pe_sharded(kmahip_db *db, kmahip_ws *ws, kmahip_comm *comm, const kmahip_read_batch *batch, const kmahip_params *p,
                                      const kmahip_shard_opts *opts, const char *out_prefix, double ms[8]) {
 	if(!db || !ws || !batch || !p || !opts || !out_prefix || !ms) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_SHARD)) return rcp;
+	if(int rcf = kmahip_refuse_forced_pairing(p)) return rcf;
 	int rc = kmahip_db_load_names(db);
 	if(rc) return rc;
 	const size_t D = db->info.DB_size;

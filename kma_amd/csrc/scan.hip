@@ -103,6 +103,7 @@ struct ScanArgs {
 	uint64_t *recs;      // the prefilter's records of the plain live items (counters[C_NREC] of them, at most rec_cap); NULL: every
 	int64_t rec_cap;     // live item goes to active_items
 	int refine;          // the prefilter checks a record's diagonal against `cat` and tries ONE other when it finds two mismatches or more
+	double min_frac;     // proximity matching (-proxi, getProxiMatch savekmers.c:296-340): |minFrac|, read by the PROXI finishes only
 };
 
 constexpr int64_t ITEM_MASK = (1ll << 33) - 1;          // a strand item: (read << 1) | strand, reads < 2^31
@@ -522,9 +523,13 @@ __device__ __forceinline__ int compact_threads(bool flag, int tid, int32_t *wcnt
 // REC: the items are the prefilter's records (A.recs), not list entries: only the front of the kernel differs -- no read has an
 // N and every read is staged once, both known to the compiler. LOOP: a fixed grid that loops over the groups (the second tier,
 // and the first tier's launch over the bare list, which is short whenever records are written).
-template <bool STATS, int MODE, int TSLOTS, bool REC = false, bool LOOP = (TSLOTS != TS1)>
+// PROXI: proximity matching -- the finish keeps every template whose score reaches (int) (min_frac * best), not only the ties.
+// Everything before the finish is the same: the tables hold the exact score of EVERY template that shares a k-mer with the item
+// (the all-candidates mode of the paired scan hands all of them on), whichever way a k-mer start was resolved.
+template <bool STATS, int MODE, int TSLOTS, bool REC = false, bool LOOP = (TSLOTS != TS1), bool PROXI = false>
 __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHREADS == 256 ? 2 : 3)) void scan_se_kernel(const ScanArgs A) {
 	static_assert(!REC || TSLOTS == TS1, "records feed the first tier only");
+	static_assert(!PROXI || !MODE, "the all-candidates mode keeps every template as it is");
 	__shared__ uint32_t v_id[VSLOTS * SG];              // value-list offset per slot (MISS = free)
 	__shared__ uint32_t v_mask[MW * VSLOTS * SG];       // positions of the pass whose k-mer carries that value list
 	// forward words: if every read of the group fits in SW-1 words they are staged ONCE and serve all passes;
@@ -1026,9 +1031,17 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 			}
 		}
 		__syncthreads();
+		// is the template of slot j handed on? The ties of the best score; PROXI: every score from proxiScore = (int) (min_frac * best)
+		// on (a double product, truncated) -- the unclamped score, as getProxiMatch compares it (a negative one is never kept)
+		auto kept = [&](int j, int best) -> bool {
+			if(PROXI) return t_score[j] >= (int) (A.min_frac * (double) best);
+			return max(0, t_score[j]) == best;
+		};
 		if(!MODE) {
 			for(int part = 0; part < TSLOTS * SG; part += STHREADS) {
 				const int idx = part + tid, g = idx & (SG - 1);
+				if(PROXI) { if(g < ng && !s_over[g] && t_id[idx] != T_EMPTY && s_best[g] > 0 && kept(idx, s_best[g])) atomicAdd(&s_nb[g], 1); }
+				else
 				if(g < ng && !s_over[g] && t_id[idx] != T_EMPTY) { const int sc = max(0, t_score[idx]); if(sc > 0 && sc == s_best[g]) atomicAdd(&s_nb[g], 1); }
 			}
 			__syncthreads();
@@ -1093,7 +1106,7 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 			const int idx = part + tid, g = idx & (SG - 1);
 			if(g >= ng || s_off[g] < 0 || t_id[idx] == T_EMPTY) continue;
 			const int sc = max(0, t_score[idx]), best = s_best[g];
-			if(!MODE && sc != best) continue;
+			if(!MODE && (PROXI ? !kept(idx, best) : sc != best)) continue;
 			int rank = 0;
 			if(s_nb[g] > 1) {
 				const long long key = ((long long) t_first[idx] << 32) | t_id[idx];
@@ -1101,7 +1114,7 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 				for(int x = 0; x < TSLOTS; ++x) {
 					const int j = x * SG + g;
 					const uint32_t id = t_id[j];
-					if(id == T_EMPTY || (!MODE && max(0, t_score[j]) != best)) continue;
+					if(id == T_EMPTY || (!MODE && !kept(j, best))) continue;
 					rank += ((((long long) t_first[j] << 32) | id) < key);
 				}
 			}
@@ -1221,7 +1234,11 @@ __global__ __launch_bounds__(64) void scan_dense_kernel(const ScanArgs A) {
 			for(int e = lane; e < nlist; e += 64) best = max(best, max(0, (int) score[list[e]]));
 			for(int d = 32; d; d >>= 1) best = max(best, __shfl_xor(best, d));
 			if(best > 0) {
-				for(int e = lane; e < nlist; e += 64) nb += max(0, (int) score[list[e]]) == best;
+				// proximity matching (uniform across the launch): every template from proxiScore on, in the list's first-seen order
+				const bool px = A.min_frac != 1.0;
+				const int thr = px ? (int) (A.min_frac * (double) best) : best;
+				auto kept = [&](int e) -> bool { const int sc = (int) score[list[e]]; return px ? sc >= thr : max(0, sc) == best; };
+				for(int e = lane; e < nlist; e += 64) nb += kept(e);
 				for(int d = 32; d; d >>= 1) nb += __shfl_xor(nb, d);
 				if(lane == 0) off = A.pool_tail0 + (int64_t) atomicAdd(&A.counters[C_POOL], (unsigned long long) nb);
 				off = __shfl(off, 0);
@@ -1229,7 +1246,7 @@ __global__ __launch_bounds__(64) void scan_dense_kernel(const ScanArgs A) {
 					int w = 0;
 					for(int e0 = 0; e0 < nlist; e0 += 64) {
 						const int e = e0 + lane;
-						const bool is = e < nlist && max(0, (int) score[list[e]]) == best;
+						const bool is = e < nlist && kept(e);
 						const unsigned long long m = __ballot(is);
 						if(is) A.pool[off + w + __popcll(m & below)] = list[e];
 						w += __popcll(m);
@@ -1960,21 +1977,21 @@ static unsigned bare_grid() {
 
 // first tier: the records (one group per workgroup), then the bare list on the looping grid; without records the bare list holds
 // every live item and gets one group per workgroup (an upper bound: the workgroups past the live count exit)
-template <int MODE>
+template <int MODE, bool PROXI = false>
 static void launch_first_tier(const ScanArgs &A, bool stats, hipStream_t stream) {
 	if(!A.recs) {
 		const unsigned grid = (unsigned) ((2 * A.n_reads + SG - 1) / SG);
-		if(stats) hipLaunchKernelGGL((scan_se_kernel<true, MODE, TS1>), dim3(grid), dim3(STHREADS), 0, stream, A);
-		else hipLaunchKernelGGL((scan_se_kernel<false, MODE, TS1>), dim3(grid), dim3(STHREADS), 0, stream, A);
+		if(stats) hipLaunchKernelGGL((scan_se_kernel<true, MODE, TS1, false, false, PROXI>), dim3(grid), dim3(STHREADS), 0, stream, A);
+		else hipLaunchKernelGGL((scan_se_kernel<false, MODE, TS1, false, false, PROXI>), dim3(grid), dim3(STHREADS), 0, stream, A);
 		return;
 	}
 	{
 		const unsigned rgrid = (unsigned) ((std::min(A.rec_cap, 2 * A.n_reads) + SG - 1) / SG);
-		if(stats) hipLaunchKernelGGL((scan_se_kernel<true, MODE, TS1, true>), dim3(rgrid), dim3(STHREADS), 0, stream, A);
-		else hipLaunchKernelGGL((scan_se_kernel<false, MODE, TS1, true>), dim3(rgrid), dim3(STHREADS), 0, stream, A);
+		if(stats) hipLaunchKernelGGL((scan_se_kernel<true, MODE, TS1, true, false, PROXI>), dim3(rgrid), dim3(STHREADS), 0, stream, A);
+		else hipLaunchKernelGGL((scan_se_kernel<false, MODE, TS1, true, false, PROXI>), dim3(rgrid), dim3(STHREADS), 0, stream, A);
 	}
-	if(stats) hipLaunchKernelGGL((scan_se_kernel<true, MODE, TS1, false, true>), dim3(bare_grid()), dim3(STHREADS), 0, stream, A);
-	else hipLaunchKernelGGL((scan_se_kernel<false, MODE, TS1, false, true>), dim3(bare_grid()), dim3(STHREADS), 0, stream, A);
+	if(stats) hipLaunchKernelGGL((scan_se_kernel<true, MODE, TS1, false, true, PROXI>), dim3(bare_grid()), dim3(STHREADS), 0, stream, A);
+	else hipLaunchKernelGGL((scan_se_kernel<false, MODE, TS1, false, true, PROXI>), dim3(bare_grid()), dim3(STHREADS), 0, stream, A);
 }
 
 static int ws_reserve(kmahip_ws *ws, int64_t n_reads) {
@@ -2030,6 +2047,11 @@ int kmahip_launch_scan_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	A.pool = ws->pool; A.pool_cap = ws->pool_cap; A.counters = ws->counters; A.overflow_items = ws->overflow_items;
 	A.dense = ws->dense; A.dense_slots = ws->dense_slots; A.active_items = ws->active_items;
 	A.mode = 0; A.pool_sc = nullptr; A.pool_tail0 = 2 * n * INL; A.cat_bases = diag_cat_bases(db);
+	// proximity matching: stage 2 takes |minFrac| (kma.c:1605; the sign is stage 3a's), and -1 is 1 (kma.c:708)
+	A.min_frac = std::fabs(p->minFrac);
+	const bool proxi = A.min_frac != 1.0;
+	if(!(A.min_frac <= 1.0)) { kmahip_set_error("minFrac %g outside [-1, 1]", p->minFrac); return KMAHIP_EINVAL; }
+	if(kmahip_mem_mode() && (rc = kmahip_refuse_proxi(p, KMAHIP_PROXI_MEM))) return rc;
 	A.recs = scan_records_on(ws, reads, p) ? ws->recs : nullptr; A.rec_cap = ws->rec_cap;
 	A.refine = scan_refine_on(A.cat_bases);
 	A.ablate = 0;
@@ -2055,7 +2077,8 @@ int kmahip_launch_scan_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	if(ws->timing_on) { HIP_TRY(hipEventRecord(evq, stream)); HIP_TRY(hipEventRecord(ev0, stream)); }
 	int64_t *over1 = ws->overflow_items, *over2 = ws->overflow_items + 2 * ws->cap_reads;
 	A.in_items = ws->active_items; A.in_count = C_NACT; A.out_over = over1; A.out_count = C_NOVER;
-	launch_first_tier<0>(A, ws->stats_on != 0, stream);
+	if(proxi) launch_first_tier<0, true>(A, ws->stats_on != 0, stream);
+	else launch_first_tier<0>(A, ws->stats_on != 0, stream);
 	if(ws->timing_on) {
 		HIP_TRY(hipEventRecord(ev1, stream));
 		if(!ws->events) ws->events = new std::vector<std::pair<hipEvent_t, hipEvent_t>>();
@@ -2066,7 +2089,11 @@ int kmahip_launch_scan_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	{
 		// second tier (64-slot tables, a fixed grid looping over the groups), then whatever is left one wavefront per item
 		A.in_items = over1; A.in_count = C_NOVER; A.out_over = over2; A.out_count = C_NOVER2;
-		if(ws->stats_on) hipLaunchKernelGGL((scan_se_kernel<true, 0, TS2>), dim3(TIER2_GRID), dim3(STHREADS), 0, stream, A);
+		if(proxi) {
+			if(ws->stats_on) hipLaunchKernelGGL((scan_se_kernel<true, 0, TS2, false, true, true>), dim3(TIER2_GRID), dim3(STHREADS), 0, stream, A);
+			else hipLaunchKernelGGL((scan_se_kernel<false, 0, TS2, false, true, true>), dim3(TIER2_GRID), dim3(STHREADS), 0, stream, A);
+		}
+		else if(ws->stats_on) hipLaunchKernelGGL((scan_se_kernel<true, 0, TS2>), dim3(TIER2_GRID), dim3(STHREADS), 0, stream, A);
 		else hipLaunchKernelGGL((scan_se_kernel<false, 0, TS2>), dim3(TIER2_GRID), dim3(STHREADS), 0, stream, A);
 		A.in_items = over2; A.in_count = C_NOVER2;
 		hipLaunchKernelGGL(scan_dense_kernel, dim3((unsigned) ws->dense_slots), dim3(64), 0, stream, A);
@@ -2083,7 +2110,9 @@ int kmahip_launch_chain_anchors(kmahip_db *db, kmahip_ws *ws, const kmahip_reads
                                 int64_t *a_off, int32_t *a_n, uint8_t *slow, unsigned long long *cnt, hipStream_t stream) {
 	const int64_t n = reads->n_reads;
 	if(n <= 0 || !p) { kmahip_set_error("bad arguments"); return KMAHIP_EINVAL; }
-	int rc = ws_reserve(ws, n);
+	int rc = kmahip_refuse_proxi(p, KMAHIP_PROXI_CHAIN);
+	if(rc) return rc;
+	rc = ws_reserve(ws, n);
 	if(rc) return rc;
 	AnchorArgs A;
 	ScanArgs &S = A.S;
@@ -2095,6 +2124,7 @@ int kmahip_launch_chain_anchors(kmahip_db *db, kmahip_ws *ws, const kmahip_reads
 	S.dense = ws->dense; S.dense_slots = ws->dense_slots; S.active_items = ws->active_items;
 	S.mode = 0; S.pool_sc = nullptr; S.pool_tail0 = 2 * n * INL; S.ablate = 0; S.cat_bases = 0;
 	S.recs = nullptr; S.rec_cap = 0; S.refine = 0;          // (the anchor kernel takes every live item from the bare list)
+	S.min_frac = 1.0;
 	S.in_items = ws->active_items; S.in_count = C_NACT; S.out_over = ws->overflow_items; S.out_count = C_NOVER;
 	A.pool = pool; A.pool_cap = pool_cap; A.a_off = a_off; A.a_n = a_n; A.slow = slow; A.cnt = cnt;
 	HIP_TRY(hipMemsetAsync(ws->counters, 0, sizeof(unsigned long long), stream));
@@ -2115,7 +2145,9 @@ int kmahip_launch_scan_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	const int64_t n = reads->n_reads;
 	if(n < 0 || (n & 1) || !out || !p) { kmahip_set_error("paired scan needs an even number of reads (mates interleaved)"); return KMAHIP_EINVAL; }
 	const int64_t np = n / 2;
-	int rc = ws_reserve(ws, n > 0 ? n : 1);
+	int rc = kmahip_refuse_proxi(p, KMAHIP_PROXI_PE);
+	if(rc) return rc;
+	rc = ws_reserve(ws, n > 0 ? n : 1);
 	if(rc) return rc;
 	if(ws->pe_cap < ws->pool_cap) {
 		(void) hipFree(ws->pool_sc); (void) hipFree(ws->ppool); (void) hipFree(ws->pe_rec);
@@ -2135,6 +2167,7 @@ int kmahip_launch_scan_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	A.ablate = 0; A.mode = 1; A.pool_sc = ws->pool_sc; A.pool_tail0 = 0; A.cat_bases = diag_cat_bases(db);
 	A.recs = scan_records_on(ws, reads, p) ? ws->recs : nullptr; A.rec_cap = ws->rec_cap;
 	A.refine = scan_refine_on(A.cat_bases);
+	A.min_frac = 1.0;
 #ifdef KMAHIP_DIAG
 	if(const char *e = getenv("KMAHIP_ABLATE_SCAN")) A.ablate = atoi(e);
 #endif

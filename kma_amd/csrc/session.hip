@@ -293,6 +293,7 @@ extern "C" int kmahip_session_set_mt1(kmahip_session *S, int32_t tmpl, int one2o
 	if(S->n || S->n_reads || !S->uploaded.empty() || S->chain || S->mt1 || S->pe) { kmahip_set_error("the mode of a session is chosen before its first batch"); return KMAHIP_EINVAL; }
 	if(S->sam_level) { kmahip_set_error("SAM records (kmahip_session_set_sam) are not built for a -Mt1 session"); return KMAHIP_EINVAL; }
 	if(tmpl < 1 || (size_t) tmpl >= S->db->info.DB_size) { kmahip_set_error("template %d out of range", tmpl); return KMAHIP_EINVAL; }
+	if(int rcp = kmahip_refuse_proxi(&S->par, KMAHIP_PROXI_MT1)) return rcp;
 	if(hipMalloc((void **) &S->mt1_sum, 8) != hipSuccess || hipMemset(S->mt1_sum, 0, 8) != hipSuccess) { kmahip_set_error("hipMalloc failed"); return KMAHIP_ENOMEM; }
 	if(frag_path) {
 		int rc = kmahip_db_load_names(S->db);
@@ -308,6 +309,11 @@ extern "C" int kmahip_session_set_pe(kmahip_session *S) {
 	if(!S) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	if(S->n || S->n_reads || !S->uploaded.empty() || S->chain || S->mt1) { kmahip_set_error("the mode of a session is chosen before its first batch"); return KMAHIP_EINVAL; }
 	if(S->sam_level == 1) { kmahip_set_error("SAM records at level 1 are not built for a session with paired input: the unmapped-mate flags of stages 2 and 3a"); return KMAHIP_EINVAL; }
+	{
+		int rcp = kmahip_refuse_proxi(&S->par, KMAHIP_PROXI_PE);
+		if(!rcp) rcp = kmahip_refuse_forced_pairing(&S->par);
+		if(rcp) return rcp;
+	}
 	S->pe = true;
 	return KMAHIP_OK;
 }
@@ -316,6 +322,7 @@ extern "C" int kmahip_session_set_chain(kmahip_session *S, const kmahip_chain_pa
 	if(!S) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	if(S->n || S->n_reads || !S->uploaded.empty() || S->mt1 || S->pe) { kmahip_set_error("the mode of a session is chosen before its first batch"); return KMAHIP_EINVAL; }
 	if(S->sam_level) { kmahip_set_error("SAM records (kmahip_session_set_sam) are not built for a session in the default mode (without -1t1)"); return KMAHIP_EINVAL; }
+	if(int rcp = kmahip_refuse_proxi(&S->par, KMAHIP_PROXI_CHAIN)) return rcp;
 	S->chain = true;
 	if(cp) S->cp = *cp; else { S->cp.minlen = 16; S->cp.pad_ = 0; S->cp.coverT = 0.1; S->cp.mrs = 0.5; }
 	return KMAHIP_OK;
