@@ -215,12 +215,15 @@ static void *xcalloc(size_t n, size_t sz) { void *p = calloc(n ? n : 1, sz); if(
 static void usage(void) {
 	fprintf(stderr, "usage: kmahip_map (-i reads.fq[.gz] | -ipe r1.fq[.gz] r2.fq[.gz] [-apm p|u] | -int interleaved.fq[.gz] [-apm p|u]) -t_db <index prefix> -o <output prefix> [-1t1] [-Mt1 <template>] [-bcNano] [-bc90] [-bc <support>] [-bcg] [-ref_fsa [n]] [-dense]\n"
 	                "       [-t threads] [-nc] [-na] [-nf] [-mf fragments] [-ml len] [-xl len] [-mp phred] [-mi phred] [-eq q] [-mq q] [-ts bases] [-mrs f] [-mrc f] [-mct f]\n"
-	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev] [-sam n] [-ef [n]] [-matrix] [-vcf [n]] [-proxi f] [-ill]\n"
+	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev] [-sam n] [-ef [n]] [-matrix] [-vcf [n]] [-proxi f] [-ill] [-ca] [-mint2] [-mint3]\n"
 	                "       [-reward n] [-gapopen n] [-gapextend n] [-localopen n] [-Npenalty n] [-per n] [-transition n] [-transversion n] [-penalty n] [-cge]\n"
 	                "       (-s1dev, like -gpus not an option of kma: stage 1 of plain FASTQ input on the device; one rank, -1t1 only; its batches close at a quarter\n"
 	                "        of a gigabase of their own accord, KMAHIP_MAP_BATCH_BASES does not apply to them)\n"
 	                "       (-proxi f, -1 <= f <= 1, and the preset -ill = -1t1 -mrc 0.1 -lc -proxi -0.98 -bc 0.9 -bcd 10: proximity matching on single-end input\n"
 	                "        with -1t1; not with -ipe / -int, -Mt1, -mem_mode, -gpus N, -s1dev or -sam n)\n"
+	                "       (-ca: circular alignments, the seeds of every aligner chained across the template's origin (chainSeeds_circular), in every mode served;\n"
+	                "        the presets -mint2 = -1t1 -mem_mode -ca -cge -mrs 0.75 -mq 1 -ref_fsa 2 -dense -bcg -bcd 10 -bc 0.9 -vcf -ef and\n"
+	                "        -mint3 = -1t1 -mem_mode -ca -mq 1 -ref_fsa 2 -dense -bcNano -bcd 10 -bc 0.7 -vcf -ef, applied where they stand)\n"
 	                "(the options of kma 1.5.1 this path implements; -apm takes p or u; everything else is refused)\n");
 }
 
@@ -306,7 +309,8 @@ int main(int argc, char **argv) {
 	int matrix = 0, vcf = 0;                     /* -matrix (kma.c:667): <out>.mat.gz; -vcf [n] (kma.c:949-961): <out>.vcf.gz, n = 2 fills its FILTER column */
 	int proxi_opt = 0;                           /* -proxi / -ill given (for the refusals' wording; what counts is par.minFrac) */
 	int base_call = 0, sig_mode = 0, ref_fsa = 0, dense = 0;      /* as kmahip_assemble_opts.caller (0-2 here) / .sig90; printconsensus.c's ref_fsa */
-	double support = 0;
+	double support = 0;                          /* -bc x: the variable the reference hands updateVcf (kma.c:747, vcf.c:195) ... */
+	double call_support = 0;                     /* ... and the threshold of significantAndSupport, a static that keeps the FIRST non-zero value it is given (assembly.c:153-157): -bc x, -ill and the presets -mint2 / -mint3 all give it one, and the two presets leave `support` alone (kma.c:1092, 1112) */
 	long long max_frag = 0;
 	double evalue = 0.05, ID_t = 1.0, Depth_t = 0.0;
 	kmahip_params par;
@@ -327,6 +331,7 @@ int main(int argc, char **argv) {
 				support = need_num(argc, argv, &a, o);
 				if(support < 0 || 1 < support) { fprintf(stderr, "kmahip_map: invalid argument at \"-bc\"\n"); return 1; }
 				sig_mode = 2;
+				if(call_support == 0) call_support = support;
 			} else sig_mode = 0;
 		}
 		else if(!strcmp(o, "-ref_fsa")) {                                                       /* kma.c:671-684 */
@@ -430,8 +435,24 @@ int main(int argc, char **argv) {
 			lc = 1;                           /* -lc */
 			par.minFrac = -0.98;              /* -proxi -0.98 */
 			support = 0.9; sig_mode = 2;      /* -bc 0.9 */
+			if(call_support == 0) call_support = 0.9;
 			bcd = 10;                         /* -bcd 10 */
 			proxi_opt = 1;                    /* (its -cge and -apm p lines are commented out there) */
+		}
+		else if(!strcmp(o, "-ca")) par.ca = 1;                                                  /* kma.c:722-723: chainSeedsPtr = &chainSeeds_circular */
+		else if(!strcmp(o, "-mint2")) {                                                         /* kma.c:1069-1094: a preset, applied where it stands */
+			one2one = 1; mem_mode = 1; par.ca = 1;                                              /* -1t1 -mem_mode -ca */
+			par.scoreT = 0.75; cp.mrs = 0.75;                                                   /* (not the 0.5 of -cge) */
+			par.rw.M = 1; par.rw.W1 = -5; par.rw.U = -1; par.rw.PE = 17;                        /* -cge (its MM = -3 does not survive kma.c:1308) */
+			par.mq = 1; ref_fsa = 2; dense = 1;                                                 /* -mq 1 -ref_fsa 2 -dense */
+			base_call = 2; bcd = 10; sig_mode = 2; if(call_support == 0) call_support = 0.9;    /* -bcg -bcd 10 -bc 0.9 (the callers' threshold, not the VCF file's) */
+			vcf = 1; ef = 1;                                                                    /* -vcf -ef */
+		}
+		else if(!strcmp(o, "-mint3")) {                                                         /* kma.c:1095-1114 */
+			one2one = 1; mem_mode = 1; par.ca = 1;                                              /* -1t1 -mem_mode -ca */
+			par.mq = 1; ref_fsa = 2; dense = 1;                                                 /* -mq 1 -ref_fsa 2 -dense */
+			base_call = 1; bcd = 10; sig_mode = 2; if(call_support == 0) call_support = 0.7;    /* -bcNano -bcd 10 -bc 0.7 (likewise) */
+			vcf = 1; ef = 1;                                                                    /* -vcf -ef */
 		}
 		else if(!strcmp(o, "-and")) cmp_mode = 1;                                               /* kma.c:915-920 */
 		else if(!strcmp(o, "-oa")) { cmp_mode = 2; ID_t = 1e-300; Depth_t = 0.0; }               /* (ID_t = 0 there; a row needs 0 < id anyway, and 0 means "the default" to kmahip_shard_opts) */
@@ -616,7 +637,7 @@ int main(int argc, char **argv) {
 		const double t_open = now_s();
 		kmahip_shard_opts so;
 		memset(&so, 0, sizeof so);
-		so.evalue = evalue; so.bcd = bcd; so.caller = base_call | (dense ? 16 : 0); so.sig90 = sig_mode; so.support = support; so.ref_fsa = ref_fsa; so.write_aln = !no_aln; so.max_frag = max_frag; so.ID_t = ID_t; so.Depth_t = Depth_t;
+		so.evalue = evalue; so.bcd = bcd; so.caller = base_call | (dense ? 16 : 0); so.sig90 = sig_mode; so.support = call_support; so.vcf_support_own = call_support != support; so.pad_ = 0; so.vcf_support = support; so.ref_fsa = ref_fsa; so.write_aln = !no_aln; so.max_frag = max_frag; so.ID_t = ID_t; so.Depth_t = Depth_t;
 		int64_t hint = 0;
 		{	/* (a guess at the number of reads from the size of the input: it only sizes the first allocation) */
 			struct stat sb;
@@ -748,7 +769,7 @@ int main(int argc, char **argv) {
 		}
 		kmahip_shard_opts so;
 		memset(&so, 0, sizeof so);
-		so.evalue = evalue; so.bcd = bcd; so.caller = base_call | (dense ? 16 : 0); so.sig90 = sig_mode; so.support = support; so.ref_fsa = ref_fsa; so.write_aln = !no_aln; so.max_frag = max_frag; so.ID_t = ID_t; so.Depth_t = Depth_t;
+		so.evalue = evalue; so.bcd = bcd; so.caller = base_call | (dense ? 16 : 0); so.sig90 = sig_mode; so.support = call_support; so.vcf_support_own = call_support != support; so.pad_ = 0; so.vcf_support = support; so.ref_fsa = ref_fsa; so.write_aln = !no_aln; so.max_frag = max_frag; so.ID_t = ID_t; so.Depth_t = Depth_t;
 		double ms[8];
 		if(mt1 ? kmahip_run_mt1_sharded(db, ws, comm, &b, mt1, one2one, &par, &so, out, ms)
 		       : chain ? kmahip_run_chain_sharded(db, ws, comm, &b, &par, &cp, &so, out, ms)
@@ -793,7 +814,7 @@ int main(int argc, char **argv) {
 	for(int64_t t = 0; t < D; ++t) run.assembly.consensus_off[t] = -1;
 	run.tmpl = xcalloc((size_t) n + 1, 4); run.n_hits = xcalloc((size_t) n + 1, 4); run.rc = xcalloc((size_t) n + 1, 4);
 	run.trace_stats = xcalloc((size_t) n * 10 + 10, 4);
-	run.caller = base_call | (ref_fsa == 2 ? 8 : 0) | (dense ? 16 : 0) | (no_aln ? 0 : 32); run.sig90 = sig_mode; run.support = support;      /* -bcNano, -bc90, -bc, -bcg, -ref_fsa (bit 3: mark the trimmed insertion columns) */
+	run.caller = base_call | (ref_fsa == 2 ? 8 : 0) | (dense ? 16 : 0) | (no_aln ? 0 : 32); run.sig90 = sig_mode; run.support = call_support;      /* -bcNano, -bc90, -bc, -bcg, -ref_fsa (bit 3: mark the trimmed insertion columns) */
 	touch_job tj = { { (char *) run.tmpl, (char *) run.n_hits, (char *) run.rc, (char *) run.trace_stats },
 	                 { ((size_t) n + 1) * 4, ((size_t) n + 1) * 4, ((size_t) n + 1) * 4, ((size_t) n * 10 + 10) * 4 } };
 	pthread_t touch_thread;
@@ -804,7 +825,7 @@ int main(int argc, char **argv) {
 	if(mt1) {
 		kmahip_assemble_opts ao;
 		memset(&ao, 0, sizeof ao);
-		ao.evalue = evalue; ao.bcd = bcd; ao.order = 1; ao.caller = base_call | (ref_fsa == 2 ? 8 : 0) | (dense ? 16 : 0) | (no_aln ? 0 : 32); ao.sig90 = sig_mode; ao.support = support;
+		ao.evalue = evalue; ao.bcd = bcd; ao.order = 1; ao.caller = base_call | (ref_fsa == 2 ? 8 : 0) | (dense ? 16 : 0) | (no_aln ? 0 : 32); ao.sig90 = sig_mode; ao.support = call_support;
 		if(kmahip_run_mt1(db, ws, &b.reads, mt1, one2one, &par, &ao, &run)) die("kmahip_run_mt1");
 	} else if(chain) {
 		if(kmahip_run_chain(db, ws, &b.reads, b.names, b.name_off, &par, &cp, evalue, bcd, max_frag, dev_frag, &run)) die("kmahip_run_chain");

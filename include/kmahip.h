@@ -85,6 +85,10 @@ typedef struct kmahip_params {
 	                       * templates both mates hit on opposite strands at the best summed score, or no record at all) -- for kmahip_scan_pe
 	                       * only: stage 3a of forced pairing (alnFragsForcePE) is not built, and the paired stage-3a, run and session entry points return
 	                       * KMAHIP_EINVAL for it (2 in bits 0-1, or 3 in bits 4-5) */
+	int32_t ca;           /* -ca, default 0: circular alignments. 0 = the seeds of stage 3a and of every traceback are chained by chainSeeds
+	                       * (chain.c:79), non-zero = by chainSeeds_circular (chain.c:262, chosen at kma.c:722): a chain may go on across the
+	                       * template's origin, the alignment then ends before it starts (end < start in the fragment row). Stage 2 does not
+	                       * read it */
 } kmahip_params;
 
 typedef struct kmahip_db_info {
@@ -837,6 +841,12 @@ typedef struct kmahip_shard_opts {
 	double support;       /* -bc x with sig90 == 2 */
 	int32_t ref_fsa;      /* the consensus file: 0 gap columns left out, 1 gaps as n (-ref_fsa), 2 as they are (-ref_fsa 0; printconsensus.c:38-60) */
 	int32_t write_aln;    /* != 0: <prefix>.aln as well (printConsensus printconsensus.c:26-37; the reference writes it unless -na) */
+	int32_t vcf_support_own; /* sessions with kmahip_session_set_vcf. 0: the `.vcf.gz` rows and their FILTER column test AD against support * DP
+	                       * (vcf.c:195-204), as `-bc x` has it. != 0: against vcf_support * DP. The reference keeps the callers' threshold
+	                       * (significantAndSupport's static, assembly.c:153) and the variable it hands updateVcf apart, and its presets -mint2 /
+	                       * -mint3 set the first alone (kma.c:1092, 1112): vcf_support = 0 there unless a `-bc x` stands beside them */
+	int32_t pad_;
+	double vcf_support;
 } kmahip_shard_opts;
 /* One template's block of the `.aln` file: "# name", then per 60 alignment columns the lines "template:", the match line ('|' where
  * the call equals the template's base, '_' elsewhere) and "query:", of the alignment as assemble_KMA trims it (assembly.c:2094-2119:

@@ -20,7 +20,8 @@ class Rewards(C.Structure):
 
 class Params(C.Structure):
     _fields_ = [("rw", Rewards), ("exhaustive", C.c_int32), ("minlen", C.c_int32), ("mq", C.c_int32),
-                ("scoreT", C.c_double), ("mrc", C.c_double), ("minFrac", C.c_double), ("ts", C.c_int32), ("apm", C.c_int32)]
+                ("scoreT", C.c_double), ("mrc", C.c_double), ("minFrac", C.c_double), ("ts", C.c_int32), ("apm", C.c_int32),
+                ("ca", C.c_int32)]
 
 
 class DBInfo(C.Structure):
@@ -140,7 +141,8 @@ class TraceDrops(C.Structure):
 
 class ShardOpts(C.Structure):
     _fields_ = [("evalue", C.c_double), ("bcd", C.c_int32), ("caller", C.c_int32), ("sig90", C.c_int32), ("max_frag", C.c_int64),
-                ("ID_t", C.c_double), ("Depth_t", C.c_double), ("support", C.c_double), ("ref_fsa", C.c_int32), ("write_aln", C.c_int32)]
+                ("ID_t", C.c_double), ("Depth_t", C.c_double), ("support", C.c_double), ("ref_fsa", C.c_int32), ("write_aln", C.c_int32),
+                ("vcf_support_own", C.c_int32), ("pad_", C.c_int32), ("vcf_support", C.c_double)]
 
 
 class KmaHipError(RuntimeError):
@@ -709,7 +711,7 @@ class KmaHipDB:
         return ms.value, n.value
 
     # -- stages 2 + 3a, host buffers ------------------------------------------
-    def map_se(self, batch, exhaustive=0, t_cap=None, min_frac=1.0):
+    def map_se(self, batch, exhaustive=0, t_cap=None, min_frac=1.0, circular=False):
         """-> (rc_flag, flag, T_off, T), hits dict (n_hits, best_score, flag, tmpl, score, start, end,
         alignment_scores, uniq_alignment_scores). min_frac: proximity matching (-proxi f) in stages 2 and 3a; its sign chooses what a
         kept hit adds to alignment_scores (positive: the read's best score, negative: the hit's own)"""
@@ -723,6 +725,8 @@ class KmaHipDB:
         T_off = np.zeros(n + 1, np.int64)
         cap = t_cap or max(1024, 8 * n)
         p = Params.from_buffer_copy(self.params)
+        if circular:
+            p.ca = 1          # -ca: chainSeeds_circular (chain.c:262, kma.c:722)
         p.exhaustive = exhaustive
         if min_frac != 1.0:
             p.minFrac = float(min_frac)
@@ -750,7 +754,7 @@ class KmaHipDB:
         raise KmaHipError("map_se: output capacity kept overflowing")
 
     def align_se_dev(self, seq, seq_off, length, N, N_off, max_len, rc_flag, flag, T_off, T,
-                     n_hits, best_score, out_flag, h_tmpl, h_score, h_start, h_end, aln_scores, uniq_scores, stream=None, min_frac=1.0):
+                     n_hits, best_score, out_flag, h_tmpl, h_score, h_start, h_end, aln_scores, uniq_scores, stream=None, min_frac=1.0, circular=False):
         """Stage 3a on device tensors (outputs of scan_se_dev); asynchronous on `stream`. min_frac: as map_se."""
         n = length.numel()
         r = Reads(n, seq.data_ptr(), seq_off.data_ptr(), length.data_ptr(), N.data_ptr(), N_off.data_ptr(),
@@ -759,6 +763,8 @@ class KmaHipDB:
         h = Hits(n_hits.data_ptr(), best_score.data_ptr(), out_flag.data_ptr(), h_tmpl.data_ptr(), h_score.data_ptr(),
                  h_start.data_ptr(), h_end.data_ptr(), aln_scores.data_ptr(), uniq_scores.data_ptr(), None)
         p = Params.from_buffer_copy(self.params)
+        if circular:
+            p.ca = 1          # -ca: chainSeeds_circular (chain.c:262, kma.c:722)
         if min_frac != 1.0:
             p.minFrac = float(min_frac)
         _check(lib().kmahip_align_se_dev(self.h, self.ws, C.byref(r), C.byref(c), C.byref(p), C.byref(h),
@@ -775,7 +781,7 @@ class KmaHipDB:
         _check(lib().kmahip_scan_pe_dev(self.h, self.ws, C.byref(r), C.byref(p), C.byref(out), C.c_void_p(stream or 0)))
 
     def align_pe_dev(self, seq, seq_off, length, N, N_off, max_len, mate, rc, rc_flag, flag, R_off, T,
-                     n_hits, best_score, out_flag, h_tmpl, h_score, h_start, h_end, aln_scores, uniq_scores, out_rc, kind, stream=None):
+                     n_hits, best_score, out_flag, h_tmpl, h_score, h_start, h_end, aln_scores, uniq_scores, out_rc, kind, stream=None, circular=False):
         """Stage 3a for the records of scan_pe_dev on device tensors; asynchronous on `stream`. kind: i32[pairs]."""
         n = length.numel()
         r = Reads(n, seq.data_ptr(), seq_off.data_ptr(), length.data_ptr(), N.data_ptr(), N_off.data_ptr(), seq.numel(), N.numel(), int(max_len))
@@ -783,6 +789,8 @@ class KmaHipDB:
         h = Hits(n_hits.data_ptr(), best_score.data_ptr(), out_flag.data_ptr(), h_tmpl.data_ptr(), h_score.data_ptr(),
                  h_start.data_ptr(), h_end.data_ptr(), aln_scores.data_ptr(), uniq_scores.data_ptr(), out_rc.data_ptr())
         p = Params.from_buffer_copy(self.params)
+        if circular:
+            p.ca = 1          # -ca: chainSeeds_circular (chain.c:262, kma.c:722)
         _check(lib().kmahip_align_pe_dev(self.h, self.ws, C.byref(r), C.byref(recs), C.byref(p), C.byref(h), C.c_void_p(kind.data_ptr()),
                                          C.c_void_p(stream or 0)))
 
@@ -860,7 +868,7 @@ class KmaHipDB:
                      dp(read_counts), dp(depth))
         _check(lib().kmahip_conclave_se_dev(self.h, self.ws, C.byref(r), C.byref(c), C.byref(h), C.byref(o), C.c_void_p(stream or 0)))
 
-    def align_trace(self, batch, rc, tmpl, tmpl_ok=None):
+    def align_trace(self, batch, rc, tmpl, tmpl_ok=None, circular=False):
         """Stage 3c per read (host arrays): traceback alignment of every read against the template ConClave chose.
         -> stats [n, 10] (score, start, end, aln_len, clip_start, clip_end, match, tGaps, qGaps, mapQ; zeros = dropped),
         ops_off [n], n_ops [n], ops (runs (len << 2) | class, classes = X I D)"""
@@ -877,6 +885,8 @@ class KmaHipDB:
         nops = np.zeros(max(n, 1), np.int32)
         cap = max(1024, 8 * n)
         p = Params.from_buffer_copy(self.params)
+        if circular:
+            p.ca = 1          # -ca: chainSeeds_circular (chain.c:262, kma.c:722)
         need = C.c_int64()
         for _ in range(3):
             ops = np.zeros(cap, np.uint32)
@@ -890,7 +900,7 @@ class KmaHipDB:
             return stats[:n], off[:n], nops[:n], ops[:need.value]
         raise KmaHipError("align_trace: output capacity kept overflowing")
 
-    def align_trace_mt1(self, batch, tmpl, one2one=0):
+    def align_trace_mt1(self, batch, tmpl, one2one=0, circular=False):
         """`-Mt1 tmpl`: every raw read against one template, strand by anker_rc -> (stats, ops_off, n_ops, ops) as align_trace, rc [n]"""
         n = batch.n
         seq = np.ascontiguousarray(batch.seq, np.uint64)
@@ -903,6 +913,8 @@ class KmaHipDB:
         rc_out = np.zeros(max(n, 1), np.int32)
         cap = max(1024, int(batch.length.sum()) // 4)
         p = Params.from_buffer_copy(self.params)
+        if circular:
+            p.ca = 1          # -ca: chainSeeds_circular (chain.c:262, kma.c:722)
         need = C.c_int64()
         for _ in range(3):
             ops = np.zeros(cap, np.uint32)
@@ -950,7 +962,7 @@ class KmaHipDB:
             o["consensus"] = {t: raw[coff[t]:raw.index(b"\0", coff[t])].decode() for t in range(D) if coff[t] >= 0}
         return o
 
-    def run_se(self, batch, evalue=0.05, bcd=1, max_frag=0, consensus=True, per_read=True, bc_nano=False, min_frac=1.0):
+    def run_se(self, batch, evalue=0.05, bcd=1, max_frag=0, consensus=True, per_read=True, bc_nano=False, min_frac=1.0, circular=False):
         """The whole single-end run in one call (kmahip_run_se) -> dict(rows [ResRow], cover, aln_len, depth, asm_len, consensus,
         tmpl, n_hits, rc, trace_stats, ms). min_frac: proximity matching (-proxi f), as map_se."""
         n = batch.n
@@ -974,6 +986,8 @@ class KmaHipDB:
                   *[(_p(pr[k]) if per_read else None) for k in ("tmpl", "n_hits", "rc", "trace_stats")])
         run.caller = run.sig90 = 1 if bc_nano else 0
         p = Params.from_buffer_copy(self.params)
+        if circular:
+            p.ca = 1          # -ca: chainSeeds_circular (chain.c:262, kma.c:722)
         if min_frac != 1.0:
             p.minFrac = float(min_frac)
         _check(lib().kmahip_run_se(self.h, self.ws, C.byref(r), C.byref(p), float(evalue), int(bcd), int(max_frag), C.byref(run)))
@@ -986,7 +1000,7 @@ class KmaHipDB:
         o["ms"] = list(run.ms)
         return o
 
-    def run_mt1(self, batch, tmpl, one2one=0, bc_nano=True, evalue=0.05, bcd=1, consensus=True):
+    def run_mt1(self, batch, tmpl, one2one=0, bc_nano=True, evalue=0.05, bcd=1, consensus=True, circular=False):
         """The `-Mt1 tmpl [-bcNano]` run in one call (kmahip_run_mt1) -> dict(row, cover, aln_len, depth, asm_len, consensus, tmpl, n_hits,
         rc, trace_stats, ms)"""
         n = batch.n
@@ -1009,6 +1023,8 @@ class KmaHipDB:
                            None if coff is None else _p(coff), cap, 0),
                   *[_p(pr[k]) for k in ("tmpl", "n_hits", "rc", "trace_stats")])
         p = Params.from_buffer_copy(self.params)
+        if circular:
+            p.ca = 1          # -ca: chainSeeds_circular (chain.c:262, kma.c:722)
         ao = AssembleOpts(0, float(evalue), int(bcd), 1, 1 if bc_nano else 0, 1 if bc_nano else 0)
         _check(lib().kmahip_run_mt1(self.h, self.ws, C.byref(r), int(tmpl), int(one2one), C.byref(p), C.byref(ao), C.byref(run)))
         o["row"] = rows[0]
@@ -1090,7 +1106,7 @@ class KmaHipDB:
         finder (kmahip_ws_set_pe_chain); on=False: back to -1t1."""
         _check(lib().kmahip_ws_set_pe_chain(self.ws, C.byref(ChainParams(int(minlen), 0, float(coverT), float(mrs))) if on else None))
 
-    def run_pe(self, batch, names, pair, evalue=0.05, bcd=1, max_frag=0, frag_path=None):
+    def run_pe(self, batch, names, pair, evalue=0.05, bcd=1, max_frag=0, frag_path=None, circular=False):
         """The paired run in one call (kmahip_run_pe) on what Ingest.next returned for two mate files -> dict(rows, cover, aln_len,
         depth, asm_len, consensus, ms)"""
         n = batch.n
@@ -1113,6 +1129,8 @@ class KmaHipDB:
         run = Run(C.cast(rows, C.c_void_p), D, 0, Assembly(_p(o["cover"]), _p(o["aln_len"]), _p(o["depth"]), _p(o["asm_len"]), _p(cbuf), _p(coff), cap, 0),
                   None, None, None, None)
         p = Params.from_buffer_copy(self.params)
+        if circular:
+            p.ca = 1          # -ca: chainSeeds_circular (chain.c:262, kma.c:722)
         _check(lib().kmahip_run_pe(self.h, self.ws, C.byref(rb), C.byref(p), float(evalue), int(bcd), int(max_frag),
                                    os.fsencode(frag_path) if frag_path else None, C.byref(run)))
         o["rows"] = [rows[i] for i in range(run.n_rows)]
@@ -1268,7 +1286,7 @@ class KmaHipDB:
             return mate[:n], rc[:n], rc_flag[:n], flag[:n], R_off, T[:R_off[n]]
         raise KmaHipError("scan_pe: output capacity kept overflowing")
 
-    def map_pe(self, batch, exhaustive=0, t_cap=None):
+    def map_pe(self, batch, exhaustive=0, t_cap=None, circular=False):
         """Stages 2 + 3a for interleaved mates -> (mate, rc, rc_flag, flag, R_off, T), hits dict (+ "kind" per pair)"""
         n = batch.n
         assert n % 2 == 0
@@ -1280,6 +1298,8 @@ class KmaHipDB:
         R_off = np.zeros(n + 1, np.int64)
         cap = t_cap or max(1024, 16 * n)
         p = Params.from_buffer_copy(self.params)
+        if circular:
+            p.ca = 1          # -ca: chainSeeds_circular (chain.c:262, kma.c:722)
         p.exhaustive = exhaustive
         D = int(self.info.DB_size)
         for _ in range(6):

@@ -774,7 +774,10 @@ __device__ void nw_coop_x(const Lane &L, const DevDB &db, const AlignArgs &A, in
 	}
 }
 
-// chainSeeds, chain.c:79-260; returns best start, *bestScore its score
+// chainSeeds, chain.c:79-260; returns best start, *bestScore its score.
+// CIRC (-ca, kma.c:722): chainSeeds_circular, chain.c:262-494 -- two more joins, both across the template's origin and both accepted
+// strictly, and `<=` for the query-overlap join whose cut start lies behind tEnd (chain.c:412)
+template <bool CIRC>
 __device__ int chain_seeds(const Lane &L, int n, int q_len, int t_len, int k, unsigned *mapQ) {
 	const int W1 = L.W1, U = L.U, M = L.M, MM = L.MM;
 	int best = 0, second = 0, bestPos = n - 1;
@@ -803,14 +806,30 @@ __device__ int chain_seeds(const Lane &L, int n, int q_len, int t_len, int k, un
 					if(g) g = (g - 1) * U + W1;
 					g += weight + MEMA(L, 5, j) - (tSj - tEnd) * M;
 					if(score < g) { score = g; nxt = j; }
+				} else if(CIRC && MEMA(L, 1, j) < MEMA(L, 0, i)) {
+					// circular join, chain.c:366-394
+					const int tGap = t_len - tEnd + tSj, qGap = qSj - qEnd;
+					int g = abs(tGap - qGap);
+					if(g) g = (g - 1) * U + W1;
+					g += weight + MEMA(L, 5, j) + mism_score(min(tGap, qGap), k, M, MM);
+					if(score < g) { score = g; nxt = j; }
 				}
 			} else if(k <= MEMA(L, 3, j) - qEnd) {
-				const int tStart = tSj + qEnd - qSj;
+				int tStart = tSj + qEnd - qSj;
 				if(tEnd < tStart) {
 					int g = tStart - tEnd;
 					if(g) g = (g - 1) * U + W1;
 					g += weight + MEMA(L, 5, j) - (tStart - tEnd) * M;
-					if(score < g) { score = g; nxt = j; }
+					if(CIRC ? score <= g : score < g) { score = g; nxt = j; }
+				} else if(CIRC) {
+					// chain.c:416-437
+					if(t_len < tStart) tStart -= t_len;
+					if(tStart != tEnd && MEMA(L, 1, j) < tStart) {
+						int g = t_len - tEnd + tStart;
+						if(g) g = (g - 1) * U + W1;
+						g += weight + MEMA(L, 5, j) - (tEnd - tStart) * M;
+						if(score < g) { score = g; nxt = j; }
+					}
 				}
 			}
 		}
@@ -979,6 +998,7 @@ __device__ int anker_rc_comp(const Lane &L, const DevDB &db, int t, const uint64
 }
 
 // KMA_score, align.c:509-748. status: 0 ok, 1 = MEM capacity exceeded
+template <bool CIRC>
 __device__ Aln kma_score(const Lane &L, const DevDB &db, int t, const uint64_t *ts, int t_len, const QView &q, int mq, int preseeded, int *status) {
 	const Aln FAIL = {0, 1, 0, 0, 0, 0};
 	const int k = (int) db.kmersize, q_len = q.L, bw = 64, cap = L.cap1 - 1;
@@ -1030,7 +1050,7 @@ __device__ Aln kma_score(const Lane &L, const DevDB &db, int t, const uint64_t *
 #ifdef KMAHIP_DIAG
 	if(L.ablate & 4) return FAIL;
 #endif
-	int start = chain_seeds(L, nm, q_len, t_len, k, &mapQ);
+	int start = chain_seeds<CIRC>(L, nm, q_len, t_len, k, &mapQ);
 	if(mapQ < (unsigned) mq || MEMA(L, 5, start) < k) return FAIL;
 
 	// leading tail (leadTailAln, align.c:53-131)
@@ -1368,7 +1388,7 @@ __device__ __forceinline__ void task_finish(const AlignArgs &A, int64_t task, in
 }
 
 // PEM: paired records (couples, mate / orientation tables); the single-end instantiation carries none of that code
-template <bool STATS, bool PEM>
+template <bool STATS, bool PEM, bool CIRC>
 __global__ __launch_bounds__(ATHREADS, 4) void align_tasks_kernel(const AlignArgs A) {
 	__shared__ int s_d[25];
 	__shared__ uint32_t s_wide[(ATHREADS / 64) * WSLOTS * 4 * WCOLS];
@@ -1470,8 +1490,8 @@ __global__ __launch_bounds__(ATHREADS, 4) void align_tasks_kernel(const AlignArg
 								const int qS = (int) (e.y & 0xFFFFu), ln = (int) (e.y >> 16);
 								MEMA(L, 0, x) = (int) e.x; MEMA(L, 1, x) = (int) e.x + ln; MEMA(L, 2, x) = qS; MEMA(L, 3, x) = qS + ln; MEMA(L, 4, x) = ln;
 							}
-							st = kma_score(L, A.db, at, ts, t_len, q, A.mq, pre, &status);
-						} else if(pre < 0) st = kma_score(L, A.db, at, ts, t_len, q, A.mq, 0, &status);
+							st = kma_score<CIRC>(L, A.db, at, ts, t_len, q, A.mq, pre, &status);
+						} else if(pre < 0) st = kma_score<CIRC>(L, A.db, at, ts, t_len, q, A.mq, 0, &status);
 					}
 					if(m == 0) { S0 = st; qlen0 = q.L; } else { S1 = st; qlen1 = q.L; }
 				}
@@ -1493,14 +1513,14 @@ __global__ __launch_bounds__(ATHREADS, 4) void align_tasks_kernel(const AlignArg
 							const int qS = (int) (e.y & 0xFFFFu), ln = (int) (e.y >> 16);
 							MEMA(L, 0, m) = (int) e.x; MEMA(L, 1, m) = (int) e.x + ln; MEMA(L, 2, m) = qS; MEMA(L, 3, m) = qS + ln; MEMA(L, 4, m) = ln;
 						}
-						S0 = kma_score(L, A.db, at, ts, t_len, q, A.mq, pre, &status);
+						S0 = kma_score<CIRC>(L, A.db, at, ts, t_len, q, A.mq, pre, &status);
 					} else if(pre == 0) S0 = Aln{0, 1, 0, 0, 0, 0};
-					else S0 = kma_score(L, A.db, at, ts, t_len, q, A.mq, 0, &status);
+					else S0 = kma_score<CIRC>(L, A.db, at, ts, t_len, q, A.mq, 0, &status);
 				} else {
 					// strand tie: per template strand decision (alnfrags.c:1101-1124)
 					const int side = anker_rc_comp(L, A.db, at, ts, t_len, q, &status);
-					if(side < 0) { q.rc ^= 1; tmpl_out = -at; S0 = kma_score(L, A.db, at, ts, t_len, q, A.mq, -side, &status); }
-					else if(side > 0) { tmpl_out = at; S0 = kma_score(L, A.db, at, ts, t_len, q, A.mq, side, &status); }
+					if(side < 0) { q.rc ^= 1; tmpl_out = -at; S0 = kma_score<CIRC>(L, A.db, at, ts, t_len, q, A.mq, -side, &status); }
+					else if(side > 0) { tmpl_out = at; S0 = kma_score<CIRC>(L, A.db, at, ts, t_len, q, A.mq, side, &status); }
 				}
 			}
 			if(status) atomicMax(&A.counters[1], 3ull);
@@ -1635,6 +1655,7 @@ __device__ __forceinline__ Aln nw_auto_fast(FastCtx &C, const Lane &L, const uin
 
 // KMA_score on n <= SEEDS preseeded MEMs (1-based template start, query start, length), everything in registers.
 // *punt: the task needs the general kernel.
+template <bool CIRC>
 __device__ __forceinline__ Aln kma_score_fast(FastCtx &C, const Lane &L, const uint64_t *ts, int t_len, const QView &q, int mq, int k,
                                               int n, const uint2 (&mem)[SEEDS], bool *punt) {
 	const Aln FAIL = {0, 1, 0, 0, 0, 0};
@@ -1676,14 +1697,30 @@ __device__ __forceinline__ Aln kma_score_fast(FastCtx &C, const Lane &L, const u
 							if(g) g = (g - 1) * U + W1;
 							g += weight + sc[j] - (tSj - tEnd) * M;
 							if(score < g) { score = g; nxt = j; }
+						} else if(CIRC && tE[j] < tS[i]) {
+							// circular join, chain.c:366-394
+							const int tGap = t_len - tEnd + tSj, qGap = qSj - qEnd;
+							int g = abs(tGap - qGap);
+							if(g) g = (g - 1) * U + W1;
+							g += weight + sc[j] + mism_score(min(tGap, qGap), k, M, MM);
+							if(score < g) { score = g; nxt = j; }
 						}
 					} else if(k <= qE[j] - qEnd) {
-						const int tStart = tSj + qEnd - qSj;
+						int tStart = tSj + qEnd - qSj;
 						if(tEnd < tStart) {
 							int g = tStart - tEnd;
 							if(g) g = (g - 1) * U + W1;
 							g += weight + sc[j] - (tStart - tEnd) * M;
-							if(score < g) { score = g; nxt = j; }
+							if(CIRC ? score <= g : score < g) { score = g; nxt = j; }
+						} else if(CIRC) {
+							// chain.c:416-437
+							if(t_len < tStart) tStart -= t_len;
+							if(tStart != tEnd && tE[j] < tStart) {
+								int g = t_len - tEnd + tStart;
+								if(g) g = (g - 1) * U + W1;
+								g += weight + sc[j] - (tEnd - tStart) * M;
+								if(score < g) { score = g; nxt = j; }
+							}
 						}
 					}
 				}
@@ -1832,7 +1869,7 @@ __device__ void fast_flush(const AlignArgs &A, int *st_cnt, const int *st_dq, co
 	__builtin_amdgcn_wave_barrier();
 }
 
-template <bool PEM>
+template <bool PEM, bool CIRC>
 __global__ __launch_bounds__(FTHREADS, KMAHIP_FAST_WAVES) void align_fast_kernel(const AlignArgs A) {
 	__shared__ int s_d[25];
 	__shared__ int s_cnt[(FTHREADS / 64) * 4];
@@ -1910,7 +1947,7 @@ __global__ __launch_bounds__(FTHREADS, KMAHIP_FAST_WAVES) void align_fast_kernel
 								const uint4 m01 = mp[0], m23 = mp[1];
 								const uint2 mem[SEEDS] = {make_uint2(m01.x, m01.y), make_uint2(m01.z, m01.w), make_uint2(m23.x, m23.y), make_uint2(m23.z, m23.w)};
 								C.mate = m; C.rc = q.rc; C.rd = rdm;
-								st = kma_score_fast(C, L, ts, t_len, q, A.mq, k, pre, mem, &punt);
+								st = kma_score_fast<CIRC>(C, L, ts, t_len, q, A.mq, k, pre, mem, &punt);
 								queued += C.n_queued;
 							}
 						}
@@ -1933,7 +1970,7 @@ __global__ __launch_bounds__(FTHREADS, KMAHIP_FAST_WAVES) void align_fast_kernel
 							const uint4 m01 = mp[0], m23 = mp[1];
 							const uint2 mem[SEEDS] = {make_uint2(m01.x, m01.y), make_uint2(m01.z, m01.w), make_uint2(m23.x, m23.y), make_uint2(m23.z, m23.w)};
 							C.mate = 0; C.rc = q.rc; C.rd = rd;
-							S0 = kma_score_fast(C, L, ts, t_len, q, A.mq, k, pre, mem, &punt);
+							S0 = kma_score_fast<CIRC>(C, L, ts, t_len, q, A.mq, k, pre, mem, &punt);
 							queued = C.n_queued;
 						}
 					}
@@ -2586,7 +2623,7 @@ __device__ bool nw_trace(TLane &T, const uint64_t *ts, int tlen_total, const QVi
 // KMA(), align.c:214-507. Returns the alignment statistics (len == 1, score == 0: no alignment); columns go to T.em.
 // FAST (the first pass): problems are either settled on the diagonal or the read is put off -- no move matrix in this instantiation,
 // which is what lets it run at more waves per SIMD than the full one
-template <bool FAST>
+template <bool FAST, bool CIRC>
 __device__ Aln kma_trace(TLane &T, const DevDB &db, int t, const uint64_t *ts, int t_len, const QView &q, int mq,
                          int &clip_start, int &clip_end, unsigned &mapQ) {
 	const Aln FAIL = {0, 1, 0, 0, 0, 0};
@@ -2631,7 +2668,7 @@ __device__ Aln kma_trace(TLane &T, const DevDB &db, int t, const uint64_t *ts, i
 		}
 	}
 	if(!nm) return FAIL;
-	int start = chain_seeds(L, nm, q_len, t_len, k, &mapQ);
+	int start = chain_seeds<CIRC>(L, nm, q_len, t_len, k, &mapQ);
 	if(mapQ < (unsigned) mq || MEMA(L, 5, start) < k) return FAIL;
 	if(T.ts) {
 		// trimSeeds (chain.c:493-528; align.c:413): the front of every seed of the chain -- but not of a first seed that starts the read --
@@ -2740,7 +2777,7 @@ __device__ Aln kma_trace(TLane &T, const DevDB &db, int t, const uint64_t *ts, i
 	return S;
 }
 
-template <bool FAST>
+template <bool FAST, bool CIRC>
 __global__ __launch_bounds__(256) void trace_kernel(const TraceArgs A) {      // (64 threads in the LDS pass)
 	__shared__ int s_d[25];
 	if(threadIdx.x < 25) s_d[threadIdx.x] = A.d[threadIdx.x];
@@ -2787,7 +2824,7 @@ __global__ __launch_bounds__(256) void trace_kernel(const TraceArgs A) {      //
 				t_len = A.db.tlen[t];
 				const uint64_t *ts = A.db.tseq + A.db.tseq_off[t];
 				T.em.n = 0; T.em.over = false; T.status = 0;
-				S = kma_trace<FAST>(T, A.db, t, ts, t_len, q, A.mq, cs, ce, mapQ);
+				S = kma_trace<FAST, CIRC>(T, A.db, t, ts, t_len, q, A.mq, cs, ce, mapQ);
 				if(T.status == 32 || (T.status == 1 && A.lds_bytes)) A.q_out[atomicAdd(&A.counters[A.q_out_cnt], 1ull)] = (int32_t) r;
 				else if(T.status || T.em.over) atomicMax(&A.counters[1], (unsigned long long) (T.em.over ? 4 : (T.status == 1 ? 8 : 16)));
 				else {
@@ -2966,6 +3003,9 @@ static int launch_align(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 	A.M = p->rw.M; A.MM = p->rw.MM; A.U = p->rw.U; A.W1 = p->rw.W1;
 	for(int i = 0; i < 5; ++i) for(int j = 0; j < 5; ++j) A.d[i * 5 + j] = p->rw.d[i][j];
 	A.minlen = p->minlen; A.mq = p->mq; A.scoreT = p->scoreT; A.mrc = p->mrc;
+	// kmahip_params::ca: the launches below take the chainSeeds_circular instantiations (chain.c:262, kma.c:722). The kernels read no
+	// flag -- the argument struct, and with it the plain instantiations, are what they were
+	const bool circ = p->ca != 0;
 	// per task: the MEMs of two seed slots first (32 bytes each: read as two 16-byte loads), the norm, the hand-on list, eight int columns
 	uint2 *seed_mem = (uint2 *) ws->a_task;
 	double *norm = (double *) (seed_mem + (size_t) 2 * SEEDS * tasks_cap);
@@ -3043,14 +3083,20 @@ static int launch_align(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 	bool fast = A.seed_n && !A.stats && A.d[0] == A.d[6] && A.d[0] == A.d[12] && A.d[0] == A.d[18] && tasks_cap < (1ll << 31);
 	if(const char *e = getenv("KMAHIP_ALIGN_FAST")) if(!atoi(e)) fast = false;
 	if(A.stats) {
-		if(A.pe_mode) hipLaunchKernelGGL((align_tasks_kernel<true, true>), agrid, dim3(ATHREADS), 0, stream, A);
-		else hipLaunchKernelGGL((align_tasks_kernel<true, false>), agrid, dim3(ATHREADS), 0, stream, A);
+		if(circ) {
+			if(A.pe_mode) hipLaunchKernelGGL((align_tasks_kernel<true, true, true>), agrid, dim3(ATHREADS), 0, stream, A);
+			else hipLaunchKernelGGL((align_tasks_kernel<true, false, true>), agrid, dim3(ATHREADS), 0, stream, A);
+		} else if(A.pe_mode) hipLaunchKernelGGL((align_tasks_kernel<true, true, false>), agrid, dim3(ATHREADS), 0, stream, A);
+		else hipLaunchKernelGGL((align_tasks_kernel<true, false, false>), agrid, dim3(ATHREADS), 0, stream, A);
 	} else {
 		hipStream_t gstream = stream;
 		if(fast) {
 			const dim3 fgrid(256 * 8);
-			if(A.pe_mode) hipLaunchKernelGGL((align_fast_kernel<true>), fgrid, dim3(FTHREADS), 0, stream, A);
-			else hipLaunchKernelGGL((align_fast_kernel<false>), fgrid, dim3(FTHREADS), 0, stream, A);
+			if(circ) {
+				if(A.pe_mode) hipLaunchKernelGGL((align_fast_kernel<true, true>), fgrid, dim3(FTHREADS), 0, stream, A);
+				else hipLaunchKernelGGL((align_fast_kernel<false, true>), fgrid, dim3(FTHREADS), 0, stream, A);
+			} else if(A.pe_mode) hipLaunchKernelGGL((align_fast_kernel<true, false>), fgrid, dim3(FTHREADS), 0, stream, A);
+			else hipLaunchKernelGGL((align_fast_kernel<false, false>), fgrid, dim3(FTHREADS), 0, stream, A);
 			// the general kernel over the handed-on tasks (a few wavefronts, each a chain of dependent round trips) beside the class
 			// queues: neither reads what the other writes (a task is pending or handed on, never both: see fast_flush)
 			if(!ws->a_side && !getenv("KMAHIP_ALIGN_SERIAL")) {
@@ -3066,8 +3112,11 @@ static int launch_align(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 			// problems) and what does not fit is walked by single lanes: fewer tasks per round, all 64 lanes on their problems
 			A.use_list = 1; A.per_round = getenv("KMAHIP_ALIGN_ROUND") ? std::min(64, std::max(1, atoi(getenv("KMAHIP_ALIGN_ROUND")))) : 16;
 		}
-		if(A.pe_mode) hipLaunchKernelGGL((align_tasks_kernel<false, true>), agrid, dim3(ATHREADS), 0, gstream, A);
-		else hipLaunchKernelGGL((align_tasks_kernel<false, false>), agrid, dim3(ATHREADS), 0, gstream, A);
+		if(circ) {
+			if(A.pe_mode) hipLaunchKernelGGL((align_tasks_kernel<false, true, true>), agrid, dim3(ATHREADS), 0, gstream, A);
+			else hipLaunchKernelGGL((align_tasks_kernel<false, false, true>), agrid, dim3(ATHREADS), 0, gstream, A);
+		} else if(A.pe_mode) hipLaunchKernelGGL((align_tasks_kernel<false, true, false>), agrid, dim3(ATHREADS), 0, gstream, A);
+		else hipLaunchKernelGGL((align_tasks_kernel<false, false, false>), agrid, dim3(ATHREADS), 0, gstream, A);
 		if(fast) {
 			const dim3 qgrid(1024);
 			hipLaunchKernelGGL((dp_queue_kernel<8>), qgrid, dim3(256), 0, stream, A, 2);
@@ -3114,7 +3163,8 @@ static int launch_align(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 			// seed_tasks_kernel left out by itself, and reports its own lack of room as status 3: the caller raises mem_scale)
 			A.long_min = 0;
 			HIP_TRY(hipMemsetAsync(ws->counters + 7, 0, sizeof(unsigned long long), stream));
-			hipLaunchKernelGGL((align_tasks_kernel<false, false>), agrid, dim3(ATHREADS), 0, stream, A);
+			if(circ) hipLaunchKernelGGL((align_tasks_kernel<false, false, true>), agrid, dim3(ATHREADS), 0, stream, A);
+			else hipLaunchKernelGGL((align_tasks_kernel<false, false, false>), agrid, dim3(ATHREADS), 0, stream, A);
 			HIP_TRY(hipGetLastError());
 			rcl = KMAHIP_OK;
 		}
@@ -3295,6 +3345,7 @@ int kmahip_launch_trace(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 	A.M = p->rw.M; A.MM = p->rw.MM; A.U = p->rw.U; A.W1 = p->rw.W1; A.Wl = p->rw.Wl;
 	for(int i = 0; i < 25; ++i) A.d[i] = p->rw.d[i / 5][i % 5];
 	A.minlen = p->minlen; A.mq = p->mq; A.scoreT = p->scoreT; A.mrc = p->mrc; A.ts = p->ts;
+	const bool circ = p->ca != 0;      // chainSeeds_circular (chain.c:262, kma.c:722)
 	A.s32 = ws->t_s32; A.rows = ws->t_s32 + (size_t) lanes * 7 * (mem_cap + 1);
 	A.ops_s = (uint32_t *) (A.rows + (size_t) lanes * 4 * ncols);
 	A.E = ws->t_E; A.lanes = lanes; A.e_cap = e_cap; A.mem_cap = mem_cap; A.ncols = ncols; A.ops_cap = ops_cap;
@@ -3322,8 +3373,10 @@ int kmahip_launch_trace(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 		lanes_fast = std::min<int64_t>(lanes_fast, ((n + 255) / 256) * 256);
 		F.lanes = lanes_fast;
 		F.ops_s = (uint32_t *) (ws->t_s32 + (size_t) lanes_fast * 7 * (mem_cap + 1));
-		hipLaunchKernelGGL(trace_kernel<true>, dim3((unsigned) (lanes_fast / 256)), dim3(256), 0, stream, F);
-	} else hipLaunchKernelGGL(trace_kernel<false>, dim3((unsigned) (lanes / 256)), dim3(256), 0, stream, A);
+		if(circ) hipLaunchKernelGGL((trace_kernel<true, true>), dim3((unsigned) (lanes_fast / 256)), dim3(256), 0, stream, F);
+		else hipLaunchKernelGGL((trace_kernel<true, false>), dim3((unsigned) (lanes_fast / 256)), dim3(256), 0, stream, F);
+	} else if(circ) hipLaunchKernelGGL((trace_kernel<false, true>), dim3((unsigned) (lanes / 256)), dim3(256), 0, stream, A);
+	else hipLaunchKernelGGL((trace_kernel<false, false>), dim3((unsigned) (lanes / 256)), dim3(256), 0, stream, A);
 	HIP_TRY(hipGetLastError());
 	if(plain) {
 		// pass 2: the reads put off, with their move matrices in HBM. (KMAHIP_TRACE_LDS=1 puts a pass with the matrices of small
@@ -3335,12 +3388,14 @@ int kmahip_launch_trace(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 		if(lds_pass) {
 			A.lds_bytes = 1008; A.lds_ncols = 24;
 			const unsigned g2 = (unsigned) std::min<int64_t>(lanes / 64, 256 * 2 * 8);
-			hipLaunchKernelGGL(trace_kernel<false>, dim3(g2), dim3(64), 64 * 1008, stream, A);
+			if(circ) hipLaunchKernelGGL((trace_kernel<false, true>), dim3(g2), dim3(64), 64 * 1008, stream, A);
+			else hipLaunchKernelGGL((trace_kernel<false, false>), dim3(g2), dim3(64), 64 * 1008, stream, A);
 			HIP_TRY(hipGetLastError());
 			A.q_in = ws->t_queue + n; A.q_in_cnt = 4;
 		}
 		A.q_out = nullptr; A.lds_bytes = 0; A.lds_ncols = 0;
-		hipLaunchKernelGGL(trace_kernel<false>, dim3((unsigned) (lanes / 256)), dim3(256), 0, stream, A);
+		if(circ) hipLaunchKernelGGL((trace_kernel<false, true>), dim3((unsigned) (lanes / 256)), dim3(256), 0, stream, A);
+		else hipLaunchKernelGGL((trace_kernel<false, false>), dim3((unsigned) (lanes / 256)), dim3(256), 0, stream, A);
 		HIP_TRY(hipGetLastError());
 		if(getenv("KMAHIP_DEBUG_TIMING")) {
 			unsigned long long put_off[2] = {0, 0};

@@ -535,8 +535,9 @@ __device__ void pile_cols(const PileArgs &A, const Walk<LDS> &W, int64_t r, int 
 		if(cls == 2) { qpos += len; after_ins = true; continue; }
 		for(int c = max(i, lo); c < min(i + len, hi); ++c) {
 			if(after_ins && c == i) continue;                       // pile_ins
+			// (a circular alignment may go round the template more than once: chainSeeds_circular only keeps a link off the MEM in front of it)
 			int p = R.start + c;
-			if(p >= W.t_len) p -= W.t_len;
+			while(p >= W.t_len) p -= W.t_len;
 			W.add_col(p, cls == 3 ? 5 : q_base(R.q, qpos + (c - i)));
 			if(c > 0) for(int h = W.head(p); h; h = W.next(h)) W.add_node(h, 5);
 		}
@@ -556,7 +557,7 @@ __device__ void pile_ins(const PileArgs &A, const Walk<LDS> &W, int64_t r) {
 		int left = (int) (run >> 2);
 		if(cls != 2) { if(cls != 3) qpos += left; i += left; continue; }
 		int gaps = R.start + i;                                     // the template column behind the insertion
-		if(gaps >= W.t_len) gaps -= W.t_len;
+		while(gaps >= W.t_len) gaps -= W.t_len;                     // (more than once for an alignment that goes round the template and on)
 		int last = 0;                                               // last column of the chain walked so far (0: none)
 		int h = W.head(gaps);
 		// insertion columns that already exist
@@ -1900,6 +1901,7 @@ struct ColArgs {
 	int64_t n_kept;
 	int bcd, caller, sig90;
 	double support, qstar;
+	double vcf_support;                  // vcf.c:195: AD < support * DP with the run's own variable, which need not be the callers' threshold
 	const int32_t *cs_t, *cs_lo;
 	int64_t n_cs;
 	const uint8_t *mask;                 // per template: 1 = its columns are written
@@ -2090,7 +2092,7 @@ __device__ __forceinline__ bool vcf_column(const ColArgs &A, const uint32_t *c32
 	const double Q = (double) (d * d) / (double) DP;
 	rec->call = call; rec->best_score = bestScore;
 	for(int j = 0; j < 6; ++j) rec->counts[j] = (uint32_t) cnt[j];
-	return ref != call || look || DP < A.bcd || Q < A.qstar || (double) AD < A.support * (double) DP;
+	return ref != call || look || DP < A.bcd || Q < A.qstar || (double) AD < A.vcf_support * (double) DP;
 }
 
 // the records of the printed rows: counted per segment (WRITE false), then written at their offsets (WRITE true). The lookahead: the
@@ -2175,6 +2177,7 @@ int col_setup(kmahip_db *db, kmahip_ws *ws, const uint8_t *mask, const char *wha
 	memset((void *) &A, 0, sizeof A);
 	A.db = db->dev; A.counts = ws->p_counts; A.chain_head = ws->p_chain; A.nodes = (const InsNode *) ws->p_nodes; A.seg_start = ws->p_seg; A.n_kept = ws->p_kept;
 	A.bcd = ws->ef_bcd; A.caller = ws->ef_caller; A.sig90 = ws->ef_sig90; A.support = ws->ef_support; A.qstar = ws->ef_qstar;
+	A.vcf_support = ws->ef_vcf_own ? ws->ef_vcf_support : ws->ef_support;
 	A.cs_t = d_cs; A.cs_lo = d_cs + n_cs; A.n_cs = n_cs; A.mask = d_mask; A.seg_size = C->d_size; A.seg_off = C->d_off;
 	C->n_cs = n_cs;
 	C->blocks = (unsigned) std::min<int64_t>(n_cs, 256 * 16);

@@ -38,7 +38,7 @@ extern "C" void kmahip_default_params(kmahip_params *p) {
 	for(int j = 0; j < 5; ++j) p->rw.d[4][j] = p->rw.Mn;
 	p->rw.d[4][4] = 0;
 	p->exhaustive = 0; p->minlen = 16; p->mq = 0;
-	p->scoreT = 0.5; p->mrc = 0.0; p->minFrac = 1.0; p->ts = 0; p->apm = 0;
+	p->scoreT = 0.5; p->mrc = 0.0; p->minFrac = 1.0; p->ts = 0; p->apm = 0; p->ca = 0;
 }
 
 static std::atomic<int> g_device{0};          // (kmahip_init may be called by several threads, each for its own current device)

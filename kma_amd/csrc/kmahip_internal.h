@@ -138,6 +138,10 @@ struct kmahip_ws {
 	// what the last kmahip_assemble2_dev left for kmahip_assemble_ef_dev (assemble.hip): 0 = no pile-up, else how its columns were called
 	int ef_state, ef_bcd, ef_caller, ef_sig90;
 	double ef_support, ef_qstar;
+	// kmahip_matvcf_gather, around its kmahip_assemble_vcf_dev calls: the VCF rows test AD against this support instead of ef_support
+	// (the reference's presets leave the two apart: kmahip_shard_opts.vcf_support)
+	int ef_vcf_own;
+	double ef_vcf_support;
 	// long-read trace pipeline (longtrace.hip): per-wavefront MEM arrays, per-pass pools, queues, scratch, counters
 	void *lt_buf[20];
 	size_t lt_bytes[20];

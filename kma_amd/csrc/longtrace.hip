@@ -400,6 +400,10 @@ __device__ bool lt_seed_strand(const LtArgs &A, SeedLds &S, const MemArr &Mm, co
 // two per lane out of an LDS ring, the reference's left-to-right acceptance rule (`<=` for a free join, `<` for the
 // overlapping ones) resolved from the wave maximum: the later of the free joins that reach it, else the first join that does.
 // Returns the best start (relative to base); links in S.next (n <= LT_NEXT_CAP) or Mm.nx.
+// CIRC (-ca, kma.c:722): chainSeeds_circular (chain.c:262-494). The join of two MEMs that overlap on the read and leave a template gap
+// is accepted with `<=` there (chain.c:412), so it joins the free class of the rule above; the two joins across the origin
+// (chain.c:366-394, :416-437) are accepted strictly and belong to the other class.
+template <bool CIRC>
 __device__ int lt_chain(const LtArgs &A, SeedLds &S, const MemArr &Mm, int base, int n, int q_len, int t_len, int k, unsigned *mapQ, int *bestScore) {
 	const int lane = threadIdx.x & 63;
 	const int W1 = A.W1, U = A.U, M = A.M, MM = A.MM;
@@ -447,14 +451,29 @@ __device__ int lt_chain(const LtArgs &A, SeedLds &S, const MemArr &Mm, int base,
 						if(x) x = (x - 1) * U + W1;
 						g[h] = x + weight + scj - (tSj - tEnd) * M;
 						ok[h] = true;
+					} else if(CIRC && tEj < tSi) {
+						const int tGap = t_len - tEnd + tSj, qGap = qSj - qEnd;
+						int x = abs(tGap - qGap);
+						if(x) x = (x - 1) * U + W1;
+						g[h] = x + weight + scj + mism_score(min(tGap, qGap), k, M, MM);
+						ok[h] = true;
 					}
 				} else if(k <= qEj - qEnd) {
-					const int tStart = tSj + qEnd - qSj;
+					int tStart = tSj + qEnd - qSj;
 					if(tEnd < tStart) {
 						int x = tStart - tEnd;
 						if(x) x = (x - 1) * U + W1;
 						g[h] = x + weight + scj - (tStart - tEnd) * M;
 						ok[h] = true;
+						if(CIRC) free_join[h] = true;
+					} else if(CIRC) {
+						if(t_len < tStart) tStart -= t_len;
+						if(tStart != tEnd && tEj < tStart) {
+							int x = t_len - tEnd + tStart;
+							if(x) x = (x - 1) * U + W1;
+							g[h] = x + weight + scj - (tEnd - tStart) * M;
+							ok[h] = true;
+						}
 					}
 				}
 			}
@@ -632,6 +651,7 @@ __device__ __forceinline__ int lt_lane_class(int q_l, int t_l, int band, int k, 
 
 // (five wavefronts per SIMD: 94 registers, three spilled dwords; with the tile and the chain's window sharing one piece of LDS twenty
 // wavefronts fit a CU and leave the sweeps that run beside them room -- the stage at 200 k reads 174 -> 161 ms with the LDS alone, 155 with both)
+template <bool CIRC>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void lt_seed_kernel(const LtArgs A) {
 	__shared__ SeedLds S;
 	const int lane = threadIdx.x;
@@ -704,7 +724,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5))) void
 		int start = 0, nc = 0;
 		if(go) {
 			int best = 0;
-			start = lt_chain(A, S, Mm, base, n, q_len, t_len, k, &mapQ, &best);
+			start = lt_chain<CIRC>(A, S, Mm, base, n, q_len, t_len, k, &mapQ, &best);
 			if(mapQ < (unsigned) A.mq || best < k || A.stop == 2) go = false;
 		}
 		if(go) {
@@ -2371,6 +2391,7 @@ int kmahip_launch_longtrace(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *re
 	A.M = p->rw.M; A.MM = p->rw.MM; A.U = p->rw.U; A.W1 = p->rw.W1; A.Wl = p->rw.Wl;
 	for(int i = 0; i < 25; ++i) A.d[i] = p->rw.d[i / 5][i % 5];
 	A.minlen = p->minlen; A.mq = p->mq; A.scoreT = p->scoreT; A.mrc = p->mrc; A.ts = score_mode ? 0 : p->ts;
+	const bool circ = p->ca != 0;      // kmahip_params::ca: lt_seed_kernel<true> chains by chainSeeds_circular (chain.c:262, kma.c:722)
 	A.mem = (int32_t *) ws->lt_buf[0]; A.mcap = mcap;
 	A.tmp = (uint32_t *) ws->lt_buf[5]; A.tmp_cap = tmp_cap;
 	A.xE = (uint8_t *) ws->lt_buf[6]; A.xe_cap = xe_cap; A.xrow = xrow;
@@ -2449,7 +2470,8 @@ int kmahip_launch_longtrace(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *re
 	auto launch_seed = [&](int x, hipStream_t s) -> int {
 		HIP_TRY(hipMemsetAsync(A.counters, 0, LCI(LC_OUT) * 8, s));
 		if(dbg0) { fprintf(stderr, "[kmahip] longtrace pass %lld+%lld: seeding (prob_cap %lld, runs_cap %lld)\n", (long long) A.r0, (long long) A.n_reads, (long long) prob_cap, (long long) runs_cap); fflush(stderr); }
-		hipLaunchKernelGGL(lt_seed_kernel, dim3((unsigned) std::min<int64_t>(seed_wgs, A.n_reads)), dim3(64), 0, s, A);
+		if(circ) hipLaunchKernelGGL(lt_seed_kernel<true>, dim3((unsigned) std::min<int64_t>(seed_wgs, A.n_reads)), dim3(64), 0, s, A);
+		else hipLaunchKernelGGL(lt_seed_kernel<false>, dim3((unsigned) std::min<int64_t>(seed_wgs, A.n_reads)), dim3(64), 0, s, A);
 		HIP_TRY(hipMemcpyAsync(hc + (size_t) x * LCI(LC_N), A.counters, (size_t) LCI(LC_N) * 8, hipMemcpyDeviceToHost, s));
 		HIP_TRY(hipEventRecord(ev.seed[x], s));
 		Ap[x] = A;

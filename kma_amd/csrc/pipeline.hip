@@ -1480,9 +1480,15 @@ int kmahip_matvcf_gather(kmahip_db *db, kmahip_ws *ws, const kmahip_res_row *row
 	}
 	if(mv->vcf) {
 		int64_t n = 0;
-		if((rc = kmahip_assemble_vcf_dev(db, ws, mask.data(), per.data(), nullptr, 0, &n))) return rc;
-		mv->recs.resize((size_t) n);
-		if(n && (rc = kmahip_assemble_vcf_dev(db, ws, mask.data(), per.data(), mv->recs.data(), n, &n))) return rc;
+		// (the rows are chosen with the support the file's FILTER column is written with: kmahip_shard_opts.vcf_support)
+		ws->ef_vcf_own = 1; ws->ef_vcf_support = mv->support;
+		rc = kmahip_assemble_vcf_dev(db, ws, mask.data(), per.data(), nullptr, 0, &n);
+		if(!rc) {
+			mv->recs.resize((size_t) n);
+			if(n) rc = kmahip_assemble_vcf_dev(db, ws, mask.data(), per.data(), mv->recs.data(), n, &n);
+		}
+		ws->ef_vcf_own = 0;
+		if(rc) return rc;
 		int64_t total = 0;
 		for(size_t t = 0; t < D; ++t) { mv->rec_off[t] = total; total += per[t]; }
 		mv->rec_off[D] = total;

@@ -945,7 +945,7 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 	if(mv_p) {
 		mv.matrix = S->matrix; mv.vcf = S->vcf; mv.t_db = S->vcf_tdb;
 		mv.mat_path = std::string(out_prefix) + ".mat.gz"; mv.vcf_path = std::string(out_prefix) + ".vcf.gz";
-		mv.evalue = S->opts.evalue; mv.support = S->opts.support; mv.bcd = S->opts.bcd; mv.ID_t = S->opts.ID_t > 0 ? S->opts.ID_t : 1.0; mv.Depth_t = S->opts.Depth_t;
+		mv.evalue = S->opts.evalue; mv.support = S->opts.vcf_support_own ? S->opts.vcf_support : S->opts.support; mv.bcd = S->opts.bcd; mv.ID_t = S->opts.ID_t > 0 ? S->opts.ID_t : 1.0; mv.Depth_t = S->opts.Depth_t;
 		mv.mat_off.assign(D + 1, 0); mv.rec_off.assign(D + 1, 0);
 	}
 
