@@ -23,6 +23,7 @@
 // walk's quirk that a gap run ends on the first cell with EITHER may-open bit.
 #include "kmahip_internal.h"
 #include "dna_dev.h"
+#include "chain_dev.h"
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
@@ -774,9 +775,8 @@ __device__ void nw_coop_x(const Lane &L, const DevDB &db, const AlignArgs &A, in
 	}
 }
 
-// chainSeeds, chain.c:79-260; returns best start, *bestScore its score.
-// CIRC (-ca, kma.c:722): chainSeeds_circular, chain.c:262-494 -- two more joins, both across the template's origin and both accepted
-// strictly, and `<=` for the query-overlap join whose cut start lies behind tEnd (chain.c:412)
+// chainSeeds / chainSeeds_circular (CIRC) over the lane's MEM arrays: the rule is chain_dev.h's; returns the best start, its score in
+// field 5 of it
 template <bool CIRC>
 __device__ int chain_seeds(const Lane &L, int n, int q_len, int t_len, int k, unsigned *mapQ) {
 	const int W1 = L.W1, U = L.U, M = L.M, MM = L.MM;
@@ -786,135 +786,33 @@ __device__ int chain_seeds(const Lane &L, int n, int q_len, int t_len, int k, un
 		const int wi = MEMA(L, 4, i);
 		const int weight = wi * M, tEnd = MEMA(L, 1, i), qEnd = MEMA(L, 3, i);
 		int nxt = 0;
-		int span = min(t_len - tEnd, q_len - qEnd);
-		int gap = span - 1;
-		gap = gap ? gap * U + W1 : W1;
-		int sub = mism_score(span, k, M, MM);
-		int score = weight + (sub < gap ? gap : sub);
+		int score = chain_tail_score(weight, tEnd, qEnd, t_len, q_len, k, M, MM, U, W1);
 		const int lim = min(n, i + 128);
 		for(int j = i + 1; j < lim; ++j) {
-			const int qSj = MEMA(L, 2, j), tSj = MEMA(L, 0, j);
-			if(qEnd < qSj) {
-				if(tEnd < tSj) {
-					const int tGap = tSj - tEnd, qGap = qSj - qEnd;
-					int g = abs(tGap - qGap);
-					if(g) g = (g - 1) * U + W1;
-					g += weight + MEMA(L, 5, j) + mism_score(min(tGap, qGap), k, M, MM);
-					if(score <= g) { score = g; nxt = j; }
-				} else if(k <= MEMA(L, 1, j) - tEnd) {
-					int g = qSj - qEnd;
-					if(g) g = (g - 1) * U + W1;
-					g += weight + MEMA(L, 5, j) - (tSj - tEnd) * M;
-					if(score < g) { score = g; nxt = j; }
-				} else if(CIRC && MEMA(L, 1, j) < MEMA(L, 0, i)) {
-					// circular join, chain.c:366-394
-					const int tGap = t_len - tEnd + tSj, qGap = qSj - qEnd;
-					int g = abs(tGap - qGap);
-					if(g) g = (g - 1) * U + W1;
-					g += weight + MEMA(L, 5, j) + mism_score(min(tGap, qGap), k, M, MM);
-					if(score < g) { score = g; nxt = j; }
-				}
-			} else if(k <= MEMA(L, 3, j) - qEnd) {
-				int tStart = tSj + qEnd - qSj;
-				if(tEnd < tStart) {
-					int g = tStart - tEnd;
-					if(g) g = (g - 1) * U + W1;
-					g += weight + MEMA(L, 5, j) - (tStart - tEnd) * M;
-					if(CIRC ? score <= g : score < g) { score = g; nxt = j; }
-				} else if(CIRC) {
-					// chain.c:416-437
-					if(t_len < tStart) tStart -= t_len;
-					if(tStart != tEnd && MEMA(L, 1, j) < tStart) {
-						int g = t_len - tEnd + tStart;
-						if(g) g = (g - 1) * U + W1;
-						g += weight + MEMA(L, 5, j) - (tEnd - tStart) * M;
-						if(score < g) { score = g; nxt = j; }
-					}
-				}
-			}
+			// (MEM i's start is read where it is used, not held across the loop: trace_kernel<false, *> spills an SGPR less otherwise)
+			const ChainJoin c = chain_join<CIRC>(MEMA(L, 0, i), tEnd, qEnd, weight, MEMA(L, 0, j), MEMA(L, 1, j), MEMA(L, 2, j), MEMA(L, 3, j),
+			                                     MEMA(L, 5, j), t_len, k, M, MM, U, W1);
+			if(chain_accepts(score, c)) { score = c.g; nxt = j; }
 		}
 		MEMA(L, 6, i) = nxt;
 		MEMA(L, 4, i) = nxt ? (wi + MEMA(L, 4, nxt) - k + 1) : (wi - (k - 1));
 		MEMA(L, 5, i) = score;
-		span = min(MEMA(L, 0, i), MEMA(L, 2, i));
-		gap = span - 1;
-		if(0 < gap) gap = gap * U + W1; else if(gap == 0) gap = W1; else gap = 0;
-		sub = mism_score(span, k, M, MM);
-		score += sub < gap ? gap : sub;
-		if(best <= score) {
-			if(nxt != bestPos) second = best;
-			best = score; bestPos = i;
-		} else if(second <= score && nxt != bestPos) {
-			second = best;
-		}
+		score += chain_head_bonus(MEMA(L, 0, i), MEMA(L, 2, i), k, M, MM, U, W1);
+		chain_rank(best, second, bestPos, score, i, nxt);
 	}
 	*mapQ = 0 < best ? kma_mapq(best, second, MEMA(L, 4, bestPos)) : 0;
 	MEMA(L, 5, bestPos) = best;
 	return bestPos;
 }
 
-// one maximal exact match through k-mer hit (q pos j, template 1-based pos1); returns its query end.
-// Same result as the reference's base-by-base loops (align.c:548-575), done 32 bases per step on the
-// 2-bit words: lowq = first query position after the previous N (an N never matches, so the backward
-// walk cannot cross it), segstop = end of the N-free segment.
-__device__ __forceinline__ void mem_extend(const uint64_t *ts, int t_len, const QView &q, int j, int pos1, int k, int lowq, int segstop,
-                                           int &tS, int &tE, int &qS, int &qE) {
-	int kk = j - 1, prev = pos1 - 2;
-	for(;;) {
-		const int room = min(kk - lowq + 1, prev + 1);
-		if(room <= 0) break;
-		const int step = min(32, room);
-		const uint64_t xq = qwin(q, kk - step + 1) >> (64 - 2 * step);
-		const uint64_t xt = win2(ts, prev - step + 1) >> (64 - 2 * step);
-		const uint64_t x = xq ^ xt;
-		const int same = x ? (__ffsll((long long) x) - 1) >> 1 : step;
-		kk -= same; prev -= same;
-		if(same < step) break;
-	}
-	qS = kk + 1; tS = prev + 2;
-	int value = pos1 + k - 1, l = j + k;
-	for(;;) {
-		const int room = min(segstop - l, t_len - value);
-		if(room <= 0) break;
-		const int step = min(32, room);
-		const uint64_t x = (qwin(q, l) ^ win2(ts, value)) >> (64 - 2 * step);
-		const int same = x ? (__clzll((long long) x) - (64 - 2 * step)) >> 1 : step;
-		l += same; value += same;
-		if(same < step) break;
-	}
-	qE = l; tE = value + 1;
-}
-
+// one MEM (mem_extend) into slot m of the lane's arrays; returns its query end
 __device__ int add_mem(const Lane &L, int m, const uint64_t *ts, int t_len, const QView &q, int j, int pos1, int k, int lowq, int segstop) {
-	// backward
-	int kk = j - 1, prev = pos1 - 2;
-	for(;;) {
-		const int room = min(kk - lowq + 1, prev + 1);
-		if(room <= 0) break;
-		const int step = min(32, room);
-		const uint64_t xq = qwin(q, kk - step + 1) >> (64 - 2 * step);
-		const uint64_t xt = win2(ts, prev - step + 1) >> (64 - 2 * step);
-		const uint64_t x = xq ^ xt;
-		const int same = x ? (__ffsll((long long) x) - 1) >> 1 : step;
-		kk -= same; prev -= same;
-		if(same < step) break;
-	}
-	MEMA(L, 2, m) = kk + 1; MEMA(L, 0, m) = prev + 2;
-	// forward
-	int value = pos1 + k - 1, l = j + k;
-	for(;;) {
-		const int room = min(segstop - l, t_len - value);
-		if(room <= 0) break;
-		const int step = min(32, room);
-		const uint64_t x = (qwin(q, l) ^ win2(ts, value)) >> (64 - 2 * step);
-		const int same = x ? (__clzll((long long) x) - (64 - 2 * step)) >> 1 : step;
-		l += same; value += same;
-		if(same < step) break;
-	}
-	MEMA(L, 3, m) = l; MEMA(L, 1, m) = value + 1;
-	MEMA(L, 4, m) = l - (kk + 1);
-	if(L.cnt) atomicAdd(&L.cnt[4], (unsigned long long) (l - (kk + 1)));
-	return l;
+	const Mem e = mem_extend(ts, t_len, q, j, pos1, k, lowq, segstop);
+	MEMA(L, 2, m) = e.qS; MEMA(L, 0, m) = e.tS;
+	MEMA(L, 3, m) = e.qE; MEMA(L, 1, m) = e.tE;
+	MEMA(L, 4, m) = e.qE - e.qS;
+	if(L.cnt) atomicAdd(&L.cnt[4], (unsigned long long) (e.qE - e.qS));
+	return e.qE;
 }
 
 // anker_rc_comp, align.c:993-1176: a read whose two strands tied in stage 2 is seeded on both strands of
@@ -1053,6 +951,7 @@ __device__ Aln kma_score(const Lane &L, const DevDB &db, int t, const uint64_t *
 	int start = chain_seeds<CIRC>(L, nm, q_len, t_len, k, &mapQ);
 	if(mapQ < (unsigned) mq || MEMA(L, 5, start) < k) return FAIL;
 
+	// (the three windows written out, not chain_dev.h's: through them align_tasks_kernel<false, true, *> goes from 128 to 105 spilled VGPRs)
 	// leading tail (leadTailAln, align.c:53-131)
 	Aln S = {0, 0, 0, 0, 0, 0};
 	{
@@ -1148,12 +1047,11 @@ __device__ __forceinline__ int seed_view(const AlignArgs &A, int t, const QView 
 				++j; v = v2;
 			}
 			if(v < 0 || nm >= SEEDS) return -1;      // duplicated k-mer (several MEMs per lookup) or too many MEMs
-			int tS, tE, qS, qE;
-			mem_extend(ts, t_len, q, j, v, k, lowq, segstop, tS, tE, qS, qE);
+			const Mem e = mem_extend(ts, t_len, q, j, v, k, lowq, segstop);
 #pragma unroll
-			for(int x = 0; x < SEEDS; ++x) if(x == nm) mem[x] = make_uint2((uint32_t) tS, (uint32_t) qS | ((uint32_t) (qE - qS) << 16));
+			for(int x = 0; x < SEEDS; ++x) if(x == nm) mem[x] = make_uint2((uint32_t) e.tS, (uint32_t) e.qS | ((uint32_t) (e.qE - e.qS) << 16));
 			++nm;
-			j = qE;
+			j = e.qE;
 		}
 		j = Ni + 1;
 		lowq = Ni + 1;
@@ -1606,7 +1504,8 @@ __global__ __launch_bounds__(ATHREADS, 4) void align_tasks_kernel(const AlignArg
 //   align_tasks_kernel   the general kernel, over the list of tasks the first handed on: no MEMs from the seeding kernel (N-rich
 //                        or repeat-rich reads, > SEEDS MEMs), a strand tie, a problem of 64 and more columns or a banded one, a
 //                        chain that fails after queueing. It runs last and overwrites whatever the others left for such a task.
-// Same arithmetic, statement for statement, as kma_score / chain_seeds above (KMA_score align.c:509-748, chainSeeds chain.c:79-260);
+// The join rule and the end bonuses are the functions of chain_dev.h that chain_seeds above calls too; the three windows are written
+// out here as in kma_score (their kernels' spill counts move through the header's functions, DESIGN.md "One chaining rule");
 // tests/test_align_gpu.py runs both routes against the oracle (KMAHIP_ALIGN_FAST=0: the general kernel for every task).
 constexpr int AC_DQ = 16, AC_PEND = 20, DQ_CLASSES = 4;      // counters: entries of the class queues (wide 33..63 columns, narrow 9..16, tiny 2..8, mid 17..32), pending tasks
 constexpr int DQ_STAGE = 96, PEND_STAGE = 96, PUNT_STAGE = 64;      // per wavefront, in LDS
@@ -1632,7 +1531,7 @@ __device__ __forceinline__ Aln nw_auto_fast(FastCtx &C, const Lane &L, const uin
 	const int ql = q_e - q_s;
 	Aln r = {0, 0, 0, 0, 0, 0};
 	ok = true;
-	if(!(ql <= band || tspan <= band)) { ok = false; return r; }             // NW_band_score
+	if(!dp_full(tspan, ql, band)) { ok = false; return r; }                  // NW_band_score
 	if(ql == 0 || tspan == 0) return nw_degenerate(tspan, ql, C.U, C.W1);
 	if(nw_diagonal(L, ts, q, k, t_s, t_e, q_s, q_e, tspan, r)) return r;
 	if(ql == 1 && tspan < 998) return nw_col1(L, ts, t_len, q, k, t_s, t_e, q_s);
@@ -1676,69 +1575,19 @@ __device__ __forceinline__ Aln kma_score_fast(FastCtx &C, const Lane &L, const u
 			const int wi = wt[i];
 			const int weight = wi * M, tEnd = tE[i], qEnd = qE[i];
 			int nxt = 0;
-			int span = min(t_len - tEnd, q_len - qEnd);
-			int gap = span - 1;
-			gap = gap ? gap * U + W1 : W1;
-			int sub = mism_score(span, k, M, MM);
-			int score = weight + (sub < gap ? gap : sub);
+			int score = chain_tail_score(weight, tEnd, qEnd, t_len, q_len, k, M, MM, U, W1);
 #pragma unroll
 			for(int j = i + 1; j < SEEDS; ++j) {
 				if(j < n) {
-					const int qSj = qS[j], tSj = tS[j];
-					if(qEnd < qSj) {
-						if(tEnd < tSj) {
-							const int tGap = tSj - tEnd, qGap = qSj - qEnd;
-							int g = abs(tGap - qGap);
-							if(g) g = (g - 1) * U + W1;
-							g += weight + sc[j] + mism_score(min(tGap, qGap), k, M, MM);
-							if(score <= g) { score = g; nxt = j; }
-						} else if(k <= tE[j] - tEnd) {
-							int g = qSj - qEnd;
-							if(g) g = (g - 1) * U + W1;
-							g += weight + sc[j] - (tSj - tEnd) * M;
-							if(score < g) { score = g; nxt = j; }
-						} else if(CIRC && tE[j] < tS[i]) {
-							// circular join, chain.c:366-394
-							const int tGap = t_len - tEnd + tSj, qGap = qSj - qEnd;
-							int g = abs(tGap - qGap);
-							if(g) g = (g - 1) * U + W1;
-							g += weight + sc[j] + mism_score(min(tGap, qGap), k, M, MM);
-							if(score < g) { score = g; nxt = j; }
-						}
-					} else if(k <= qE[j] - qEnd) {
-						int tStart = tSj + qEnd - qSj;
-						if(tEnd < tStart) {
-							int g = tStart - tEnd;
-							if(g) g = (g - 1) * U + W1;
-							g += weight + sc[j] - (tStart - tEnd) * M;
-							if(CIRC ? score <= g : score < g) { score = g; nxt = j; }
-						} else if(CIRC) {
-							// chain.c:416-437
-							if(t_len < tStart) tStart -= t_len;
-							if(tStart != tEnd && tE[j] < tStart) {
-								int g = t_len - tEnd + tStart;
-								if(g) g = (g - 1) * U + W1;
-								g += weight + sc[j] - (tEnd - tStart) * M;
-								if(score < g) { score = g; nxt = j; }
-							}
-						}
-					}
+					const ChainJoin c = chain_join<CIRC>(tS[i], tEnd, qEnd, weight, tS[j], tE[j], qS[j], qE[j], sc[j], t_len, k, M, MM, U, W1);
+					if(chain_accepts(score, c)) { score = c.g; nxt = j; }
 				}
 			}
 			nx[i] = nxt;
 			wt[i] = nxt ? (wi + sel4(wt, nxt) - k + 1) : (wi - (k - 1));
 			sc[i] = score;
-			span = min(tS[i], qS[i]);
-			gap = span - 1;
-			if(0 < gap) gap = gap * U + W1; else if(gap == 0) gap = W1; else gap = 0;
-			sub = mism_score(span, k, M, MM);
-			score += sub < gap ? gap : sub;
-			if(best <= score) {
-				if(nxt != bestPos) second = best;
-				best = score; bestPos = i;
-			} else if(second <= score && nxt != bestPos) {
-				second = best;
-			}
+			score += chain_head_bonus(tS[i], qS[i], k, M, MM, U, W1);
+			chain_rank(best, second, bestPos, score, i, nxt);
 		}
 	}
 	unsigned mapQ = 0;
@@ -1748,6 +1597,7 @@ __device__ __forceinline__ Aln kma_score_fast(FastCtx &C, const Lane &L, const u
 	// the chain from its best start: the MEM in hand in scalars (the reference's write-backs of a clipped start, align.c:694-711, are
 	// only ever read for the MEM in hand). One loop for the leading tail (leadTailAln, align.c:53-131), every MEM with the link behind
 	// it (:640-735) and the trailing tail (trailTailAln, :140-212), so that the DP dispatch exists once.
+	// (the three windows written out, not chain_dev.h's: through them align_fast_kernel<false, false> goes from 58 to 61 spilled SGPRs)
 	int start = bestPos;
 	int ctS = sel4(tS, start), ctE = sel4(tE, start), cqS = sel4(qS, start), cqE = sel4(qE, start);
 	Aln S = {0, 0, 0, 0, 0, 0};
@@ -2681,6 +2531,7 @@ __device__ Aln kma_trace(TLane &T, const DevDB &db, int t, const uint64_t *ts, i
 	}
 
 	Aln S = {0, 0, 0, 0, 0, 0};
+	// (the three windows written out, not chain_dev.h's: through them trace_kernel<true, false> goes from 115 to 105 spilled SGPRs)
 	{	// leading tail (leadTailAln with Frag_align, align.c:53-131)
 		const int t_e = MEMA(L, 0, start) - 1, q_e = MEMA(L, 2, start);
 		S.pos = t_e;

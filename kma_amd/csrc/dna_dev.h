@@ -89,6 +89,37 @@ __device__ __forceinline__ uint64_t qwin(const QView &q, int i) {
 	return revcomp64(q.w[0] >> ((-s) << 1));
 }
 
+// one maximal exact match through k-mer hit (q pos j, template 1-based pos1): its ends, template 1-based, ends exclusive.
+// Same result as the reference's base-by-base loops (align.c:548-575), done 32 bases per step on the
+// 2-bit words: lowq = first query position after the previous N (an N never matches, so the backward
+// walk cannot cross it), segstop = end of the N-free segment.
+struct Mem { int tS, tE, qS, qE; };
+__device__ __forceinline__ Mem mem_extend(const uint64_t *ts, int t_len, const QView &q, int j, int pos1, int k, int lowq, int segstop) {
+	int kk = j - 1, prev = pos1 - 2;
+	for(;;) {
+		const int room = min(kk - lowq + 1, prev + 1);
+		if(room <= 0) break;
+		const int step = min(32, room);
+		const uint64_t xq = qwin(q, kk - step + 1) >> (64 - 2 * step);
+		const uint64_t xt = win2(ts, prev - step + 1) >> (64 - 2 * step);
+		const uint64_t x = xq ^ xt;
+		const int same = x ? (__ffsll((long long) x) - 1) >> 1 : step;
+		kk -= same; prev -= same;
+		if(same < step) break;
+	}
+	int value = pos1 + k - 1, l = j + k;
+	for(;;) {
+		const int room = min(segstop - l, t_len - value);
+		if(room <= 0) break;
+		const int step = min(32, room);
+		const uint64_t x = (qwin(q, l) ^ win2(ts, value)) >> (64 - 2 * step);
+		const int same = x ? (__clzll((long long) x) - (64 - 2 * step)) >> 1 : step;
+		l += same; value += same;
+		if(same < step) break;
+	}
+	return {prev + 2, value + 1, kk + 1, l};
+}
+
 // the k-mers at oriented positions j and j + 1 from ONE 32-base window (k <= 16 here, so both fit): one 16-byte access
 // instead of up to four word loads and two reverse complements
 __device__ __forceinline__ void q_kmer2(const QView &q, int j, int k, uint32_t &km1, uint32_t &km2) {

@@ -20,6 +20,7 @@
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 #include "dna_dev.h"
+#include "chain_dev.h"
 #include <algorithm>
 #include <vector>
 #include <climits>
@@ -187,30 +188,8 @@ __device__ __forceinline__ int lt_lookup(const uint2 *tab, uint32_t sh, uint32_t
 // exact match lengths around the k-mer hit (query position s, template position pos1, 1-based): fwd = matching bases from s on
 // (>= k; bounded by the N-free stretch [lowq, segE) and the template end), bwd = matching bases in front of s
 __device__ __forceinline__ void lt_extend(const uint64_t *ts, int t_len, const QView &q, int s, int pos1, int k, int lowq, int segE, int &fwd, int &bwd) {
-	int kk = s - 1, prev = pos1 - 2;
-	for(;;) {
-		const int room = min(kk - lowq + 1, prev + 1);
-		if(room <= 0) break;
-		const int step = min(32, room);
-		const uint64_t xq = qwin(q, kk - step + 1) >> (64 - 2 * step);
-		const uint64_t xt = win2(ts, prev - step + 1) >> (64 - 2 * step);
-		const uint64_t x = xq ^ xt;
-		const int same = x ? (__ffsll((long long) x) - 1) >> 1 : step;
-		kk -= same; prev -= same;
-		if(same < step) break;
-	}
-	bwd = s - 1 - kk;
-	int value = pos1 + k - 1, l = s + k;
-	for(;;) {
-		const int room = min(segE - l, t_len - value);
-		if(room <= 0) break;
-		const int step = min(32, room);
-		const uint64_t x = (qwin(q, l) ^ win2(ts, value)) >> (64 - 2 * step);
-		const int same = x ? (__clzll((long long) x) - (64 - 2 * step)) >> 1 : step;
-		l += same; value += same;
-		if(same < step) break;
-	}
-	fwd = l - s;
+	const Mem e = mem_extend(ts, t_len, q, s, pos1, k, lowq, segE);
+	bwd = s - e.qS; fwd = e.qE - s;
 }
 
 struct SeedLds {
@@ -400,9 +379,8 @@ __device__ bool lt_seed_strand(const LtArgs &A, SeedLds &S, const MemArr &Mm, co
 // two per lane out of an LDS ring, the reference's left-to-right acceptance rule (`<=` for a free join, `<` for the
 // overlapping ones) resolved from the wave maximum: the later of the free joins that reach it, else the first join that does.
 // Returns the best start (relative to base); links in S.next (n <= LT_NEXT_CAP) or Mm.nx.
-// CIRC (-ca, kma.c:722): chainSeeds_circular (chain.c:262-494). The join of two MEMs that overlap on the read and leave a template gap
-// is accepted with `<=` there (chain.c:412), so it joins the free class of the rule above; the two joins across the origin
-// (chain.c:366-394, :416-437) are accepted strictly and belong to the other class.
+// The join itself and its class are chain_dev.h's chain_join: CJ_EQ is the free class here, CJ_STRICT the other -- so under CIRC
+// (-ca, chainSeeds_circular) the read-overlap join of chain.c:412 is free and the two joins across the origin are not.
 template <bool CIRC>
 __device__ int lt_chain(const LtArgs &A, SeedLds &S, const MemArr &Mm, int base, int n, int q_len, int t_len, int k, unsigned *mapQ, int *bestScore) {
 	const int lane = threadIdx.x & 63;
@@ -423,11 +401,7 @@ __device__ int lt_chain(const LtArgs &A, SeedLds &S, const MemArr &Mm, int base,
 		const int si = i & 63;
 		const int tSi = S.stage[0][si], tEnd = S.stage[1][si], qSi = S.stage[2][si], qEnd = S.stage[3][si], wi = S.stage[4][si];
 		const int weight = wi * M;
-		int span = min(t_len - tEnd, q_len - qEnd);
-		int gap = span - 1;
-		gap = gap ? gap * U + W1 : W1;
-		int sub = mism_score(span, k, M, MM);
-		const int score0 = weight + (sub < gap ? gap : sub);
+		const int score0 = chain_tail_score(weight, tEnd, qEnd, t_len, q_len, k, M, MM, U, W1);
 		// candidates
 		const int lim = min(n, i + 128);
 		int g[2];
@@ -438,44 +412,9 @@ __device__ int lt_chain(const LtArgs &A, SeedLds &S, const MemArr &Mm, int base,
 			ok[h] = false; free_join[h] = false; g[h] = INT_MIN;
 			if(j < lim) {
 				const int sl = j & 127;
-				const int tSj = S.ring[0][sl], tEj = S.ring[1][sl], qSj = S.ring[2][sl], qEj = S.ring[3][sl], scj = S.ring[4][sl];
-				if(qEnd < qSj) {
-					if(tEnd < tSj) {
-						const int tGap = tSj - tEnd, qGap = qSj - qEnd;
-						int x = abs(tGap - qGap);
-						if(x) x = (x - 1) * U + W1;
-						g[h] = x + weight + scj + mism_score(min(tGap, qGap), k, M, MM);
-						ok[h] = true; free_join[h] = true;
-					} else if(k <= tEj - tEnd) {
-						int x = qSj - qEnd;
-						if(x) x = (x - 1) * U + W1;
-						g[h] = x + weight + scj - (tSj - tEnd) * M;
-						ok[h] = true;
-					} else if(CIRC && tEj < tSi) {
-						const int tGap = t_len - tEnd + tSj, qGap = qSj - qEnd;
-						int x = abs(tGap - qGap);
-						if(x) x = (x - 1) * U + W1;
-						g[h] = x + weight + scj + mism_score(min(tGap, qGap), k, M, MM);
-						ok[h] = true;
-					}
-				} else if(k <= qEj - qEnd) {
-					int tStart = tSj + qEnd - qSj;
-					if(tEnd < tStart) {
-						int x = tStart - tEnd;
-						if(x) x = (x - 1) * U + W1;
-						g[h] = x + weight + scj - (tStart - tEnd) * M;
-						ok[h] = true;
-						if(CIRC) free_join[h] = true;
-					} else if(CIRC) {
-						if(t_len < tStart) tStart -= t_len;
-						if(tStart != tEnd && tEj < tStart) {
-							int x = t_len - tEnd + tStart;
-							if(x) x = (x - 1) * U + W1;
-							g[h] = x + weight + scj - (tEnd - tStart) * M;
-							ok[h] = true;
-						}
-					}
-				}
+				const ChainJoin c = chain_join<CIRC>(tSi, tEnd, qEnd, weight, S.ring[0][sl], S.ring[1][sl], S.ring[2][sl], S.ring[3][sl], S.ring[4][sl],
+				                                     t_len, k, M, MM, U, W1);
+				if(c.cls != CJ_NONE) { g[h] = c.g; ok[h] = true; free_join[h] = c.cls == CJ_EQ; }
 			}
 		}
 		const int G = wave_max(max(g[0], g[1]));
@@ -500,17 +439,8 @@ __device__ int lt_chain(const LtArgs &A, SeedLds &S, const MemArr &Mm, int base,
 			if(lds_next) S.next[i] = (uint16_t) nxt; else Mm.nx[base + i] = nxt;
 		}
 		wave_sync();
-		span = min(tSi, qSi);
-		gap = span - 1;
-		if(0 < gap) gap = gap * U + W1; else if(gap == 0) gap = W1; else gap = 0;
-		sub = mism_score(span, k, M, MM);
-		score += sub < gap ? gap : sub;
-		if(best <= score) {
-			if(nxt != bestPos) second = best;
-			best = score; bestPos = i; bestW = wnew;
-		} else if(second <= score && nxt != bestPos) {
-			second = best;
-		}
+		score += chain_head_bonus(tSi, qSi, k, M, MM, U, W1);
+		if(chain_rank(best, second, bestPos, score, i, nxt)) bestW = wnew;
 	}
 	*mapQ = 0 < best ? kma_mapq(best, second, bestW) : 0;
 	*bestScore = best;
@@ -522,64 +452,30 @@ __device__ int lt_chain(const LtArgs &A, SeedLds &S, const MemArr &Mm, int base,
 // (trailTailAln, align.c:140-212).
 struct Join { int t_s, t_l, q_s, q_l, k, band, flags, body, bq, fail, clip0, qe; };
 __device__ Join lt_join(const LtArgs &A, const MemArr &Mm, int ia, int ib, int l, int nc, int q_len, int t_len) {
-	const int bw = 64;
 	Join J;
 	J.t_s = 0; J.t_l = 0; J.q_s = 0; J.q_l = 0; J.k = 0; J.band = 0; J.flags = PF_NONE; J.body = 0; J.bq = 0; J.fail = 0; J.clip0 = 0; J.qe = 0;
+	// the window is chain_dev.h's; J.band == 0: full matrix
+	ChainWin w;
 	if(l == 0) {
-		const int t_e = Mm.tS[ib] - 1, q_e = Mm.qS[ib];
-		J.body = Mm.qE[ib] - Mm.qS[ib]; J.bq = q_e;
-		if(q_e) {
-			int t_s = 0, q_s = 0;
-			if((q_e << 1) < t_e || (q_e + bw) < t_e) t_s = t_e - (q_e + (q_e < bw ? q_e : bw));
-			else if((t_e << 1) < q_e || (t_e + bw) < q_e) q_s = q_e - (t_e + (t_e < bw ? t_e : bw));
-			J.clip0 = q_s;
-			if(t_e - t_s > 0 && q_e - q_s > 0) {
-				const int band = abs(t_e - t_s - q_e + q_s) + bw;
-				J.t_s = t_s; J.t_l = t_e - t_s; J.q_s = q_s; J.q_l = q_e - q_s; J.k = -1 - (t_s == 0);
-				J.band = (q_e - q_s <= band || t_e - t_s <= band) ? 0 : band;
-				J.flags = (t_s == 0 && !A.score_mode) ? PF_LEAD_TRIM : 0;          // (KMA_score keeps the gap columns at the template's ends: no Frag_align, align.c:95, 174)
-			}
-		}
-		return J;
+		w = lead_window(Mm.tS[ib], Mm.qS[ib]);
+		J.body = Mm.qE[ib] - w.q_e; J.bq = w.q_e;
+		J.clip0 = w.q_s;
+		if(w.dp) J.flags = (w.t_s == 0 && !A.score_mode) ? PF_LEAD_TRIM : 0;          // (KMA_score keeps the gap columns at the template's ends: no Frag_align, align.c:95, 174)
+	} else if(l == nc) {
+		w = trail_window(Mm.tE[ia], Mm.qE[ia], t_len, q_len);
+		J.qe = w.q_e;
+		if(w.dp) J.flags = (w.t_e == t_len && !A.score_mode) ? PF_TRAIL_TRIM : 0;
+	} else {
+		const ChainLink lk = link_window(Mm.tE[ia], Mm.qE[ia], Mm.tS[ib], Mm.tE[ib], Mm.qS[ib], t_len, q_len, A.U, A.M);
+		w = lk.w;
+		J.body = Mm.qE[ib] - lk.qSn; J.bq = lk.qSn;
+		if(lk.reject) { J.fail = 1; return J; }
+		if(w.dp) J.flags = w.t_l == 0 ? PF_DEGEN_I : w.q_e == w.q_s ? PF_DEGEN_D : 0;
 	}
-	if(l == nc) {
-		const int t_s = Mm.tE[ia] - 1, q_s = Mm.qE[ia];
-		int q_e = q_len, t_e = t_len;
-		if(((q_len - q_s) << 1) < (t_len - t_s) || (q_len - q_s + bw) < (t_len - t_s)) {
-			t_e = q_len - q_s; t_e = t_s + (t_e + (t_e < bw ? t_e : bw));
-		} else if(((t_len - t_s) << 1) < (q_len - q_s) || (t_len - t_s + bw) < (q_len - q_s)) {
-			q_e = t_len - t_s; q_e = q_s + (q_e + (q_e < bw ? q_e : bw));
-		}
-		J.qe = q_e;
-		if(t_e - t_s > 0 && q_e - q_s > 0) {
-			const int band = abs(t_e - t_s - q_e + q_s) + bw;
-			J.t_s = t_s; J.t_l = t_e - t_s; J.q_s = q_s; J.q_l = q_e - q_s; J.k = 1 + (t_e == t_len);
-			J.band = (q_e - q_s <= band || t_e - t_s <= band) ? 0 : band;
-			J.flags = (t_e == t_len && !A.score_mode) ? PF_TRAIL_TRIM : 0;
-		}
-		return J;
-	}
-	const int q_s = Mm.qE[ia], t_s = Mm.tE[ia] - 1;
-	int qSn = Mm.qS[ib], tSn = Mm.tS[ib];
-	const int tEb = Mm.tE[ib], qEb = Mm.qE[ib];
-	if(qSn < q_s) { tSn += q_s - qSn; qSn = q_s; }
-	int t_e = tSn - 1, t_l;
-	if(t_e < t_s) {
-		if(t_s <= tEb) { qSn += t_s - t_e; t_e = t_s; t_l = 0; }
-		else t_l = t_len - t_s + t_e;
-	} else t_l = t_e - t_s;
-	const int q_e = qSn;
-	J.body = qEb - qSn; J.bq = qSn;
-	if(abs(t_l - q_e + q_s) * A.U > q_len * A.M || t_l > q_len || q_e - q_s > (q_len >> 1)) { J.fail = 1; return J; }
-	if(t_l > 0 || q_e - q_s > 0) {
-		J.t_s = t_s; J.t_l = t_l; J.q_s = q_s; J.q_l = q_e - q_s; J.k = 0;
-		if(t_l == 0) J.flags = PF_DEGEN_I;
-		else if(q_e - q_s == 0) J.flags = PF_DEGEN_D;
-		else {
-			const int band = abs(t_l - q_e + q_s) + bw;
-			J.band = (q_e - q_s <= band || t_l <= band) ? 0 : band;
-			J.flags = 0;
-		}
+	if(w.dp) {
+		J.t_s = w.t_s; J.t_l = w.t_l; J.q_s = w.q_s; J.q_l = w.q_e - w.q_s; J.k = w.k;
+		const int band = dp_band(w);
+		if(!dp_full(J.t_l, J.q_l, band)) J.band = band;
 	}
 	return J;
 }

@@ -89,6 +89,13 @@ def test_l_long_reads(inputs, extra):
     _same(s, "l" + "".join(extra), extra)
 
 
+def test_l_long_reads_lane_chain(inputs):
+    """the same reads with the long route off (KMAHIP_ALIGN_LONG=0): chain_seeds<true> of align_tasks_kernel on reads of many MEMs, its
+    i + 128 window with the joins across the origin"""
+    extra = ["-1t1", "-ca", "-bcNano"]
+    _same(inputs("L"), "l1t1lane", extra, {"KMAHIP_ALIGN_LONG": "0"})
+
+
 # ---- 5: reads as long as the template -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("extra", [["-1t1", "-ca"], ["-Mt1", "2", "-ca"]], ids=["1t1", "mt1"])
 def test_o_whole_turns(inputs, extra):
