@@ -215,7 +215,7 @@ static void *xcalloc(size_t n, size_t sz) { void *p = calloc(n ? n : 1, sz); if(
 static void usage(void) {
 	fprintf(stderr, "usage: kmahip_map (-i reads.fq[.gz] | -ipe r1.fq[.gz] r2.fq[.gz] [-apm p|u] | -int interleaved.fq[.gz] [-apm p|u]) -t_db <index prefix> -o <output prefix> [-1t1] [-Mt1 <template>] [-bcNano] [-bc90] [-bc <support>] [-bcg] [-ref_fsa [n]] [-dense]\n"
 	                "       [-t threads] [-nc] [-na] [-nf] [-mf fragments] [-ml len] [-xl len] [-mp phred] [-mi phred] [-eq q] [-mq q] [-ts bases] [-mrs f] [-mrc f] [-mct f]\n"
-	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev] [-sam n] [-ef [n]] [-matrix] [-vcf [n]] [-proxi f] [-ill] [-ca] [-mint2] [-mint3]\n"
+	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev] [-sam n] [-ef [n]] [-matrix] [-vcf [n]] [-proxi f] [-ill] [-ca] [-mint2] [-mint3] [-ConClave n]\n"
 	                "       [-reward n] [-gapopen n] [-gapextend n] [-localopen n] [-Npenalty n] [-per n] [-transition n] [-transversion n] [-penalty n] [-cge]\n"
 	                "       (-s1dev, like -gpus not an option of kma: stage 1 of plain FASTQ input on the device; one rank, -1t1 only; its batches close at a quarter\n"
 	                "        of a gigabase of their own accord, KMAHIP_MAP_BATCH_BASES does not apply to them)\n"
@@ -224,6 +224,9 @@ static void usage(void) {
 	                "       (-ca: circular alignments, the seeds of every aligner chained across the template's origin (chainSeeds_circular), in every mode served;\n"
 	                "        the presets -mint2 = -1t1 -mem_mode -ca -cge -mrs 0.75 -mq 1 -ref_fsa 2 -dense -bcg -bcd 10 -bc 0.9 -vcf -ef and\n"
 	                "        -mint3 = -1t1 -mem_mode -ca -mq 1 -ref_fsa 2 -dense -bcNano -bcd 10 -bc 0.7 -vcf -ef, applied where they stand)\n"
+	                "       (-ConClave n: 1, the default, gives every read to the best template of its list (runConClave); 2 drops the templates that are not\n"
+	                "        significant, credits the reads unique among the rest and draws a template for every other read in proportion to those unique scores\n"
+	                "        (runConClave2); in every run of one rank, not with -gpus N; -Mt1 runs no ConClave and ignores it)\n"
 	                "(the options of kma 1.5.1 this path implements; -apm takes p or u; everything else is refused)\n");
 }
 
@@ -301,6 +304,7 @@ int main(int argc, char **argv) {
 	const char *prefix = NULL, *input = NULL, *input2 = NULL, *out = NULL;
 	int Ts = -2, Tv = -2;          /* -transition / -transversion (kma.c:335-336) */
 	int cmp_mode = 0, lc = 0, mem_mode = 0;      /* -and / -oa, -lc, -mem_mode */
+	int conclave = 1;                            /* -ConClave n (kma.c:493-501) */
 	int pm = 0, fpm = 0;           /* -pm / -fpm (1 p, 2 u; 0: not given) */
 	char *list1[256], *list2[256]; int n_files = 0;          /* the input files (mate files side by side) */
 	int mt1 = 0, one2one = 0, chain = 0, apm = 0, no_cons = 0, no_frag = 0, no_aln = 0, gpus = 0, threads = 0, bcd = 1, s1dev = 0;
@@ -422,6 +426,13 @@ int main(int argc, char **argv) {
 		else if(!strcmp(o, "-tmp") || !strcmp(o, "-verbose")) { if(a + 1 < argc && argv[a + 1][0] != '-') ++a; }
 		else if(!strcmp(o, "-mem_mode")) mem_mode = 1;                                           /* kma.c:547 */
 		else if(!strcmp(o, "-lc")) lc = 1;                                                      /* kma.c:694-701 */
+		else if(!strcmp(o, "-ConClave")) {                                                      /* kma.c:493-501: the next argument, whatever it is; none leaves version 1 */
+			if(a + 1 < argc) {
+				char *end = NULL;
+				conclave = (int) strtoul(argv[++a], &end, 10);
+				if(*end != 0 || conclave < 0 || 2 < conclave) { fprintf(stderr, " Invalid ConClave version specified.\n"); return 1; }
+			}
+		}
 		else if(!strcmp(o, "-proxi")) {                                                         /* kma.c:702-721: 1 and -1 leave everything as it is */
 			char *end = NULL;
 			if(a + 1 >= argc) { fprintf(stderr, "Need argument at: \"-proxi\".\n"); return 1; }
@@ -504,6 +515,19 @@ int main(int argc, char **argv) {
 	const int pe_chain = chain && input2;
 	if(lc && chain) { fprintf(stderr, "kmahip_map: -lc needs -1t1 (the chain finder's length-corrected anchors are not built)\n"); return 2; }
 	if(kmahip_set_conclave_lc(lc)) return 1;
+	if(conclave == 0) {
+		/* the reference then runs no ConClave at all (runkma.c:588-594) and reads a file count it never set */
+		fprintf(stderr, "kmahip_map: -ConClave 0 is not built: the reference runs no ConClave there and reads a count it never set; give -ConClave 1 or -ConClave 2\n");
+		return 2;
+	}
+	if(conclave == 2 && !mt1) {          /* (runKMA_Mt1 runs no ConClave, kma.c:1598: the option is taken there and does nothing) */
+		/* the passes of runConClave2 are global over the stream: built for the runs of one rank */
+		const char *why = NULL;
+		if(gpus > 1 || getenv("KMAHIP_RANK") || getenv("RANK")) why = "-gpus N (several ranks)";
+		else if(getenv("KMAHIP_COMM_FORCE_RCCL") && getenv("KMAHIP_COMM_FORCE_RCCL")[0] == '1') why = "KMAHIP_COMM_FORCE_RCCL";
+		if(why) { fprintf(stderr, "kmahip_map: -ConClave 2 is not built for %s: it serves the runs of one rank (the vectors of its first and third pass are not summed over ranks)\n", why); return 2; }
+		if(kmahip_set_conclave_version(2)) { fprintf(stderr, "kmahip_map: %s\n", kmahip_last_error()); return 1; }
+	}
 	if(mem_mode && !mt1) {          /* (runKMA_Mt1 comes before runKMA_MEM, kma.c:1598-1623: -Mt1 leaves -mem_mode without effect) */
 		if(kmahip_set_mem_mode(1)) return 1;
 	}

@@ -298,6 +298,29 @@ int kmahip_set_conclave_lc(int on);
  * is one record with both scores added up (update_Scores_pe_MEM :69-107, runkma.c:1090-1134). One setting per process, read by the
  * whole-run entry points (kmahip_run_se / _pe / _chain, the sessions, the sharded runs). */
 int kmahip_set_mem_mode(int on);
+/* `-ConClave n` (kma.c:493-501, runkma.c:588-594): 1 = runConClave (the default), 2 = runConClave2 / runConClave2_lc
+ * (conclave.c:386-1110); anything else returns KMAHIP_EINVAL. One setting per process, read by the whole-run entry points of one rank
+ * (kmahip_run_se / _pe / _chain, the sessions); the sharded runs return KMAHIP_EINVAL under version 2 (the vectors of its first and
+ * third pass would have to be summed over the ranks). `-Mt1` runs no ConClave and ignores it. The stage entry points say which
+ * scheme they are by their names: kmahip_conclave_* is version 1, kmahip_conclave2_* version 2, whatever is set here. */
+int kmahip_set_conclave_version(int v);
+/* Stage 3b, ConClave version 2 (runConClave2, conclave.c:386-747; with kmahip_set_conclave_lc, runConClave2_lc :749-1110), the general
+ * record form of kmahip_conclave_records: the same records, and per record q_seed[r], the value of `rand` behind the seven-step loop
+ * over the first and last seven bases of the record's first sequence (conclave.c:566-571; read only where q_len[r] >= 16). Four
+ * passes: every record's best-of-list template collects its score (:404-466); templates that fail the test of `.res` on those sums
+ * are dropped (:469-491, host arithmetic with evalue, scoreT and kmahip_set_cmp: one vector goes to the host and comes back); a record
+ * with several templates of which one survived adds its score to that template's unique score (:493-532); a record with several
+ * templates draws one in proportion to the unique scores, or takes the best of its list where they are all 0, the sequence is
+ * shorter than 16 or nothing was drawn (:534-743). Outputs as kmahip_conclave_records, except that out->w_scores is SET, not
+ * added to (:535); hits->uniq_alignment_scores is not changed (the third pass adds into a copy). A sum of unique scores that wraps
+ * a 32-bit int negative is undefined in the reference (:580): nothing is claimed for it. */
+int kmahip_conclave2_records(kmahip_db *db, kmahip_ws *ws, int64_t n_records, const int32_t *q_len, const int32_t *q_len2,
+                             const int64_t *off, const int32_t *q_seed, const kmahip_hits *hits, double evalue, double scoreT,
+                             kmahip_conclave *out);
+/* ... with DEVICE pointers on `stream`; returns when the four passes are done (the host step in the middle waits for the first) */
+int kmahip_conclave2_records_dev(kmahip_db *db, kmahip_ws *ws, int64_t n_records, const int32_t *q_len, const int32_t *q_len2,
+                                 const int64_t *off, const int32_t *q_seed, const kmahip_hits *hits, double evalue, double scoreT,
+                                 kmahip_conclave *out, void *stream);
 int kmahip_res_rows(const kmahip_db *db, const uint64_t *w_scores, double evalue, double scoreT,
                     kmahip_res_row *rows, int64_t cap, int64_t *n_rows);
 

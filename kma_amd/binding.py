@@ -4,6 +4,7 @@ built (python -c 'import __graft_entry__ as g; g.build()') import fails loudly.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -219,6 +220,9 @@ def lib():
                                          C.POINTER(Conclave)]
         L.kmahip_conclave_se_dev.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Reads), C.POINTER(Cands), C.POINTER(Hits),
                                              C.POINTER(Conclave), C.c_void_p]
+        L.kmahip_conclave2_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Hits),
+                                               C.c_double, C.c_double, C.POINTER(Conclave)]
+        L.kmahip_set_conclave_version.argtypes = [C.c_int]
         L.kmahip_conclave_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Hits),
                                               C.POINTER(Conclave)]
         L.kmahip_align_trace.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Reads), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Params),
@@ -515,9 +519,11 @@ class Session:
     """A kmahip_session on a database, as far as choosing its mode goes: set_sam (kmahip_session_set_sam) beside set_chain / set_mt1 /
     set_pe, each before the first batch. Feeding batches and finishing the run is the host program's (examples/kmahip_map.c)."""
 
-    def __init__(self, db, evalue=0.05, bcd=1, max_frag=0, reads_hint=0):
+    def __init__(self, db, evalue=0.05, bcd=1, max_frag=0, reads_hint=0, conclave=1):
         self._db = db
         self._h = C.c_void_p()
+        self._conclave_was = _conclave_now          # (-ConClave: one setting per process, read when the session finishes; close() puts it back)
+        set_conclave_version(conclave)
         so = ShardOpts(evalue, bcd, 0, 0, int(max_frag), 1.0, 0.0, 0.0, 0, 1)
         p = Params.from_buffer_copy(db.params)
         _check(lib().kmahip_session_open(db.h, db.ws, C.byref(p), C.byref(so), int(reads_hint), C.byref(self._h)))
@@ -550,12 +556,34 @@ class Session:
         if self._h:
             lib().kmahip_session_close(self._h)
             self._h = C.c_void_p()
+            set_conclave_version(self._conclave_was)
 
     def __enter__(self):
         return self
 
     def __exit__(self, *a):
         self.close()
+
+
+_conclave_now = 1
+
+
+def set_conclave_version(v):
+    """`-ConClave v` for the whole-run entry points of this process (kmahip_set_conclave_version): 1 runConClave, 2 runConClave2"""
+    global _conclave_now
+    _check(lib().kmahip_set_conclave_version(int(v)))
+    _conclave_now = int(v)
+
+
+@contextlib.contextmanager
+def conclave_version(v):
+    """set_conclave_version(v) for a block, the earlier value after it"""
+    was = _conclave_now
+    set_conclave_version(v)
+    try:
+        yield
+    finally:
+        set_conclave_version(was)
 
 
 def default_params() -> Params:
@@ -856,6 +884,24 @@ class KmaHipDB:
             o[key] = o[key][:n]
         return o
 
+    def conclave2_records(self, n_hits, score, q_len, q_len2, off, q_seed, tmpl, start, end, alignment_scores, uniq_alignment_scores,
+                          evalue=0.05, scoreT=0.5):
+        """Stage 3b, version 2 (runConClave2, kmahip_conclave2_records) over explicit frag_raw records in stream order; q_seed: per record
+        the seed of its draw (conclave.c:566-571). The `-lc` order with kmahip_set_conclave_lc."""
+        n = len(n_hits)
+        ql = np.ascontiguousarray(q_len if n else np.zeros(1, np.int32), np.int32)
+        ql2 = np.ascontiguousarray(q_len2 if n else np.zeros(1, np.int32), np.int32)
+        sd = np.ascontiguousarray(q_seed if n else np.zeros(1, np.int32), np.int32)
+        of = np.ascontiguousarray(off, np.int64)
+        assert len(of) == n + 1 and len(sd) >= n
+        keep, hs = self._hits_struct(dict(n_hits=n_hits, best_score=score, tmpl=tmpl, start=start, end=end,
+                                          alignment_scores=alignment_scores, uniq_alignment_scores=uniq_alignment_scores))
+        o, oc = self._conclave_out(n)
+        _check(lib().kmahip_conclave2_records(self.h, self.ws, n, _p(ql), _p(ql2), _p(of), _p(sd), C.byref(hs), float(evalue), float(scoreT), C.byref(oc)))
+        for key in ("tmpl", "start", "end"):
+            o[key] = o[key][:n]
+        return o
+
     def conclave_se_dev(self, length, T_off, n_hits, best_score, h_tmpl, h_start, h_end, aln_scores, uniq_scores,
                         o_tmpl, o_start, o_end, w_scores, fragment_counts=None, read_counts=None, depth=None, stream=None):
         """Stage 3b on device tensors (outputs of align_se_dev); asynchronous on `stream`."""
@@ -962,9 +1008,9 @@ class KmaHipDB:
             o["consensus"] = {t: raw[coff[t]:raw.index(b"\0", coff[t])].decode() for t in range(D) if coff[t] >= 0}
         return o
 
-    def run_se(self, batch, evalue=0.05, bcd=1, max_frag=0, consensus=True, per_read=True, bc_nano=False, min_frac=1.0, circular=False):
+    def run_se(self, batch, evalue=0.05, bcd=1, max_frag=0, consensus=True, per_read=True, bc_nano=False, min_frac=1.0, circular=False, conclave=1):
         """The whole single-end run in one call (kmahip_run_se) -> dict(rows [ResRow], cover, aln_len, depth, asm_len, consensus,
-        tmpl, n_hits, rc, trace_stats, ms). min_frac: proximity matching (-proxi f), as map_se."""
+        tmpl, n_hits, rc, trace_stats, ms). min_frac: proximity matching (-proxi f), as map_se. conclave: `-ConClave n`, for this call."""
         n = batch.n
         seq = np.ascontiguousarray(batch.seq, np.uint64)
         Nn = np.ascontiguousarray(batch.N if len(batch.N) else np.zeros(1, np.int32), np.int32)
@@ -990,7 +1036,8 @@ class KmaHipDB:
             p.ca = 1          # -ca: chainSeeds_circular (chain.c:262, kma.c:722)
         if min_frac != 1.0:
             p.minFrac = float(min_frac)
-        _check(lib().kmahip_run_se(self.h, self.ws, C.byref(r), C.byref(p), float(evalue), int(bcd), int(max_frag), C.byref(run)))
+        with conclave_version(conclave):
+            _check(lib().kmahip_run_se(self.h, self.ws, C.byref(r), C.byref(p), float(evalue), int(bcd), int(max_frag), C.byref(run)))
         o["rows"] = [rows[i] for i in range(run.n_rows)]
         if consensus:
             raw = cbuf.tobytes()
@@ -1097,18 +1144,18 @@ class KmaHipDB:
                                       None if fr is None else _p(fr), blob, _p(noff), int(level), C.byref(rows), per))
         return rows.value, list(per)
 
-    def session(self, evalue=0.05, bcd=1, max_frag=0, reads_hint=0):
-        """a kmahip_session on this database and workspace, for choosing its mode (Session)"""
-        return Session(self, evalue, bcd, max_frag, reads_hint)
+    def session(self, evalue=0.05, bcd=1, max_frag=0, reads_hint=0, conclave=1):
+        """a kmahip_session on this database and workspace, for choosing its mode (Session); conclave: `-ConClave n` until it is closed"""
+        return Session(self, evalue, bcd, max_frag, reads_hint, conclave)
 
     def set_pe_chain(self, on=True, minlen=16, coverT=0.1, mrs=0.5):
         """Paired runs on this workspace in the reference's default mode (no -1t1): records that lost their mate go to the chain
         finder (kmahip_ws_set_pe_chain); on=False: back to -1t1."""
         _check(lib().kmahip_ws_set_pe_chain(self.ws, C.byref(ChainParams(int(minlen), 0, float(coverT), float(mrs))) if on else None))
 
-    def run_pe(self, batch, names, pair, evalue=0.05, bcd=1, max_frag=0, frag_path=None, circular=False):
+    def run_pe(self, batch, names, pair, evalue=0.05, bcd=1, max_frag=0, frag_path=None, circular=False, conclave=1):
         """The paired run in one call (kmahip_run_pe) on what Ingest.next returned for two mate files -> dict(rows, cover, aln_len,
-        depth, asm_len, consensus, ms)"""
+        depth, asm_len, consensus, ms). conclave: `-ConClave n`, for this call."""
         n = batch.n
         seq = np.ascontiguousarray(batch.seq, np.uint64)
         Nn = np.ascontiguousarray(batch.N if len(batch.N) else np.zeros(1, np.int32), np.int32)
@@ -1131,8 +1178,9 @@ class KmaHipDB:
         p = Params.from_buffer_copy(self.params)
         if circular:
             p.ca = 1          # -ca: chainSeeds_circular (chain.c:262, kma.c:722)
-        _check(lib().kmahip_run_pe(self.h, self.ws, C.byref(rb), C.byref(p), float(evalue), int(bcd), int(max_frag),
-                                   os.fsencode(frag_path) if frag_path else None, C.byref(run)))
+        with conclave_version(conclave):
+            _check(lib().kmahip_run_pe(self.h, self.ws, C.byref(rb), C.byref(p), float(evalue), int(bcd), int(max_frag),
+                                       os.fsencode(frag_path) if frag_path else None, C.byref(run)))
         o["rows"] = [rows[i] for i in range(run.n_rows)]
         raw = cbuf.tobytes()
         o["consensus"] = {t: raw[coff[t]:raw.index(b"\0", coff[t])].decode() for t in range(D) if coff[t] >= 0}

@@ -3,7 +3,8 @@
 // rows start from. Behaviour restated from runConClave (conclave.c:43-215, the default `-ConClave 1`) and
 // runKMA's row statistics (runkma.c:608-613, 765-783; p_chisqr / fastp, stdstat.c:36-147).
 // The reference streams frag_raw records through one thread; here every record is one lane: the choice reads only
-// the two read-only vectors, and the per-template sums are order-free u64 atomics.
+// the two read-only vectors, and the per-template sums are order-free u64 atomics. `-ConClave 2` (runConClave2, conclave.c:386-1110):
+// the same records through four passes, at the end of this file.
 #include "kmahip_internal.h"
 #include <cmath>
 
@@ -360,5 +361,305 @@ extern "C" int kmahip_res_rows(const kmahip_db *db, const uint64_t *w_scores, do
 	}
 	*n_rows = n;
 	if(n > cap) { kmahip_set_error("row capacity %lld < %lld", (long long) cap, (long long) n); return KMAHIP_EOVERFLOW; }
+	return KMAHIP_OK;
+}
+
+// ---- `-ConClave 2` (runConClave2 / runConClave2_lc, conclave.c:386-1110): four passes over the same records ---------------------
+// 1. every record's best-of-list template collects the record's score in a scratch vector w1 (conclave.c:404-466);
+// 2. the host drops the templates of w1 that are not significant (:469-491);
+// 3. a record with one surviving template among several listed adds its score to that template's unique score (:493-532);
+// 4. a record with several templates draws one in proportion to those unique scores, seeded from its own bases, or falls back to the
+//    best-of-list rule (:534-743).
+// The passes are global over the stream: every part (batch) goes through pass 1 before any goes through pass 3, and so on.
+#include "dna_dev.h"
+#include <climits>
+
+static int g_conclave_version = 1;
+extern "C" int kmahip_set_conclave_version(int v) {
+	if(v != 1 && v != 2) { kmahip_set_error("ConClave version %d (1 = runConClave, 2 = runConClave2)", v); return KMAHIP_EINVAL; }
+	g_conclave_version = v;
+	return KMAHIP_OK;
+}
+int kmahip_conclave_version() { return g_conclave_version; }
+int kmahip_refuse_conclave2(const char *what) {
+	if(g_conclave_version != 2) return KMAHIP_OK;
+	kmahip_set_error("-ConClave 2 is not built for %s: it serves the runs of one rank (its pass-1 and pass-3 vectors are not summed over ranks)", what);
+	return KMAHIP_EINVAL;
+}
+
+namespace {
+
+struct CC2Args {
+	CCArgs A;                        // the records, stage 3a's two vectors (read only), the outputs of pass 4
+	unsigned long long *w1;          // pass 1 adds; pass 2 zeroes the discarded entries; pass 3 reads
+	unsigned long long *uniq2;       // working copy of uniq_alignment_scores: pass 3 adds, pass 4 reads
+	const int32_t *seed;             // per slot: `rand` of conclave.c:566-571 (before the minimal-standard step)
+};
+
+// The best-of-list rule as runConClave2 declares it (conclave.c:388-394): best_read_score is an `int` (a vector entry is truncated into
+// it and sign-extended for the comparison), bestNum a `long unsigned` (no truncation, unlike runConClave's), bestTemplate starts at
+// best_tmpl: -1 in pass 1 (:418), 0 in pass 4 (:604). -> index into the record's list, -1: nothing taken.
+__device__ int cc2_best(const CCArgs &A, const Rec &r, const uint64_t *us, int best_tmpl) {
+	int best_read_score = 0, pick = -1;
+	uint64_t best_num = 0;
+	double best_score = 0;
+	for(int i = 0; i < r.n; ++i) {
+		const int x = A.h_tmpl[r.o + i], t = abs(x);
+		const uint64_t a = A.as[t], u = us[t], b = (uint64_t) (int64_t) best_read_score;
+		const double sc = 1.0 * (double) a / (double) A.tlen[t];
+		// (-lc, runConClave2_lc conclave.c:781-819, 967-1016: the score per template base decides before the score itself)
+		const bool first_gt = A.lc ? sc > best_score : a > b, first_eq = A.lc ? sc == best_score : a == b;
+		const bool second_gt = A.lc ? a > b : sc > best_score, second_eq = A.lc ? a == b : sc == best_score;
+		bool take = false;
+		if(first_gt) take = true;
+		else if(first_eq) {
+			if(second_gt) take = true;
+			else if(second_eq) take = u > best_num || (u == best_num && t < abs(best_tmpl));
+		}
+		if(take) { pick = i; best_tmpl = x; best_read_score = (int) a; best_score = sc; best_num = u; }
+	}
+	return pick;
+}
+
+// pass 1 (conclave.c:404-466)
+__global__ __launch_bounds__(256) void cc2_first_kernel(const CC2Args C) {
+	const CCArgs &A = C.A;
+	const int64_t s = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if(s >= A.n_slots) return;
+	Rec r;
+	if(!record_at(A, s, r)) return;
+	int tt;
+	if(r.n > 1) {
+		const int pick = cc2_best(A, r, A.us, -1);
+		tt = pick >= 0 ? A.h_tmpl[r.o + pick] : -1;
+	} else if(r.n == 1) tt = A.h_tmpl[r.o];
+	else {
+		// empty list (a proper pair's record): zero entries are read into a buffer that still holds the list of the last record
+		// that had one (conclave.c:414, 458)
+		Rec q;
+		tt = A.carry_t;
+		for(int64_t s2 = s - 1; s2 >= 0; --s2) if(record_at(A, s2, q) && q.n >= 1) { tt = A.h_tmpl[q.o]; break; }
+	}
+	atomicAdd(&C.w1[abs(tt)], (unsigned long long) abs(r.score));
+}
+
+// pass 3 (conclave.c:493-532)
+__global__ __launch_bounds__(256) void cc2_uniq_kernel(const CC2Args C) {
+	const CCArgs &A = C.A;
+	const int64_t s = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if(s >= A.n_slots) return;
+	Rec r;
+	if(!record_at(A, s, r) || r.n == 1) return;
+	int best = 0;
+	for(int i = r.n - 1; i >= 0; --i) {
+		const int t = abs(A.h_tmpl[r.o + i]);
+		if(C.w1[t]) {
+			if(best) { best = 0; break; }
+			best = t;
+		}
+	}
+	if(best) atomicAdd(&C.uniq2[best], (unsigned long long) abs(r.score));
+}
+
+// pass 4 (conclave.c:534-743)
+__global__ __launch_bounds__(256) void cc2_choose_kernel(const CC2Args C) {
+	const CCArgs &A = C.A;
+	const int64_t s = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if(s >= A.n_slots) return;
+	Rec r;
+	int tt = 0, st = 0, en = 0;
+	const bool written = record_at(A, s, r);
+	if(written) {
+		if(r.n != 1) {
+			int tot = 0;          // (an `int` that the `long unsigned` entries are added into: it wraps like the reference's)
+			for(int i = 0; i < r.n; ++i) tot = (int) ((uint32_t) tot + (uint32_t) C.uniq2[abs(A.h_tmpl[r.o + i])]);
+			if(tot && 16 <= r.q_len) {
+				int rnd = C.seed[s];
+				rnd = 16807 * (rnd % 127773) - 2836 * (rnd / 127773);          // minimal standard (:573-576)
+				if(rnd <= 0) rnd += 0x7fffffff;
+				double tmp = rnd;
+				tmp /= INT_MAX;
+				const unsigned rand_score = (unsigned) (tmp * tot);
+				uint64_t score = 0;
+				for(int i = 0; i < r.n; ++i) {
+					score += C.uniq2[abs(A.h_tmpl[r.o + i])];
+					if(rand_score < score) { tt = A.h_tmpl[r.o + i]; st = A.h_start[r.o + i]; en = A.h_end[r.o + i]; break; }
+				}
+				if(tt == 0) tot = 0;
+			} else tot = 0;
+			if(tot == 0) {
+				const int pick = cc2_best(A, r, (const uint64_t *) C.uniq2, 0);
+				if(pick >= 0) { tt = A.h_tmpl[r.o + pick]; st = A.h_start[r.o + pick]; en = A.h_end[r.o + pick]; }
+			}
+		} else { tt = A.h_tmpl[r.o]; st = A.h_start[r.o]; en = A.h_end[r.o]; }
+	}
+	A.o_tmpl[s] = tt; A.o_start[s] = st; A.o_end[s] = en;
+	const int t = abs(tt);
+	if(!written || t == 0) return;          // (template 0: not filed, and neither is the mate, :677, 726)
+	atomicAdd(&A.w_scores[t], (unsigned long long) abs(r.score));
+	if(A.frag_counts) atomicAdd(&A.frag_counts[t], 1u);
+	if(A.read_counts) atomicAdd(&A.read_counts[t], r.score < 0 ? 2u : 1u);
+	if(A.depth) atomicAdd(&A.depth[t], (unsigned long long) (r.q_len + (r.score < 0 ? r.q_len2 : 0)));
+}
+
+// The seed of a record's draw (conclave.c:566-571) from the packed reads: slot s holds read src[s * src_stride] (NULL: read s; < 0: no
+// record) of batch a (index < n0) or b (index - n0), in the orientation stage 3a left it (rc[s * rc_stride] & 1: reverse complemented),
+// codes 0..3 and 4 for N. A sequence of fewer than 16 bases draws nothing (:564): its seed is 0.
+struct SeedArgs {
+	int64_t n_slots, n0;
+	const uint64_t *seq[2];
+	const int64_t *seq_off[2], *N_off[2];
+	const int32_t *len[2], *N[2];
+	const int32_t *src, *rc;
+	int src_stride, rc_stride;
+	int32_t *seed;
+};
+__global__ __launch_bounds__(256) void cc2_seed_kernel(const SeedArgs G) {
+	const int64_t s = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if(s >= G.n_slots) return;
+	int64_t rd = G.src ? (int64_t) G.src[s * G.src_stride] : s;
+	int32_t out = 0;
+	if(rd >= 0) {
+		const int w = rd >= G.n0;
+		if(w) rd -= G.n0;
+		QView q;
+		q.L = G.len[w][rd];
+		if(q.L >= 16) {
+			q.w = G.seq[w] + G.seq_off[w][rd];
+			q.N = G.N[w] + G.N_off[w][rd];
+			q.nN = (int) (G.N_off[w][rd + 1] - G.N_off[w][rd]);
+			q.rc = G.rc ? (G.rc[s * G.rc_stride] & 1) : 0;
+			uint32_t rnd = (uint32_t) qn(q, 0);
+			int j = q.L;
+			for(int i = 0; i < 7; ++i) rnd = (((rnd << 2) | (uint32_t) qn(q, i)) << 2) | (uint32_t) qn(q, --j);
+			out = (int32_t) rnd;
+		}
+	}
+	G.seed[s] = out;
+}
+
+} // namespace
+
+int kmahip_cc2_seeds(const kmahip_reads *a, const kmahip_reads *b, int64_t n0, int64_t n_slots, const int32_t *src, int src_stride, const int32_t *rc, int rc_stride,
+                     int32_t *seed, hipStream_t stream) {
+	if(!a || !seed || n_slots < 0) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(!b) { b = a; n0 = INT64_MAX; }
+	SeedArgs G{};
+	G.n_slots = n_slots; G.n0 = n0; G.src = src; G.rc = rc; G.src_stride = src_stride; G.rc_stride = rc_stride; G.seed = seed;
+	const kmahip_reads *R[2] = {a, b};
+	for(int x = 0; x < 2; ++x) { G.seq[x] = R[x]->seq; G.seq_off[x] = R[x]->seq_off; G.N_off[x] = R[x]->N_off; G.len[x] = R[x]->len; G.N[x] = R[x]->N; }
+	if(n_slots) hipLaunchKernelGGL(cc2_seed_kernel, dim3((unsigned) ((n_slots + 255) / 256)), dim3(256), 0, stream, G);
+	HIP_TRY(hipGetLastError());
+	return KMAHIP_OK;
+}
+
+// pass 2 (conclave.c:469-491), host arithmetic in long double with the host's erf / tgamma: w1 with the discarded entries zeroed.
+// Not the guards of kmahip_res_rows: read_score is an `int` here, Nhits is used as it is, and there is no branch on `0 < expected`.
+static void cc2_significance(const kmahip_db *db, uint64_t *w1, double evalue, double scoreT) {
+	const int D = (int) db->info.DB_size;
+	long unsigned Nhits = 0, template_tot_ulen = 0;
+	for(int i = D - 1; i > 0; --i) { template_tot_ulen += (long unsigned) db->h_tlen[i]; Nhits += w1[i]; }      // (runkma.c:581-585)
+	for(int t = D - 1; t > 0; --t) {
+		const int read_score = (int) w1[t];
+		if(!read_score) continue;
+		const int t_len = db->h_tlen[t];
+		long double expected = t_len, q_value;
+		const long unsigned rest = template_tot_ulen - t_len;
+		expected /= (1 < rest ? rest : 1);
+		expected *= (Nhits - read_score);
+		q_value = read_score - expected;
+		q_value /= (expected + read_score);
+		q_value *= read_score - expected;
+		const double p_value = p_chisqr(q_value);
+		if(kmahip_cmp(p_value <= evalue && read_score > expected, read_score >= scoreT * t_len) == 0) w1[t] = 0;
+	}
+}
+
+static int cc2_part_args(kmahip_db *db, const KmaCC2Part &P, const uint64_t *as, const uint64_t *us, const kmahip_conclave *tot, CC2Args *C) {
+	const kmahip_hits *h = P.hits;
+	if(!h || !h->n_hits || !h->best_score || !h->tmpl || !h->start || !h->end || !P.len || !P.off || !P.o_tmpl || !P.o_start || !P.o_end || !P.seed ||
+	   (P.pe == 1 && (!P.mate || !P.pe_kind || (P.n & 1))) || P.n < 0) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	CCArgs &A = C->A;
+	A = CCArgs{};
+	A.n_slots = P.n; A.pe = P.pe; A.len = P.len; A.len2 = P.len2; A.mate = P.mate; A.pe_kind = P.pe_kind; A.off = P.off;
+	A.n_hits = h->n_hits; A.best_score = h->best_score; A.h_tmpl = h->tmpl; A.h_start = h->start; A.h_end = h->end;
+	A.as = as; A.us = us; A.tlen = db->dev.tlen; A.lc = g_conclave_lc;
+	A.o_tmpl = P.o_tmpl; A.o_start = P.o_start; A.o_end = P.o_end;
+	A.w_scores = (unsigned long long *) tot->w_scores; A.depth = (unsigned long long *) tot->depth;
+	A.frag_counts = tot->fragment_counts; A.read_counts = tot->read_counts;
+	C->seed = P.seed;
+	return KMAHIP_OK;
+}
+
+// The four passes over the parts of one stream, in order. An empty-list record looks for the last record with a list inside its own
+// part: the callers hand over a paired stream as one part, and a single-end record is never written with an empty list.
+int kmahip_conclave2_parts(kmahip_db *db, const KmaCC2Part *parts, int n_parts, const uint64_t *as, const uint64_t *us, const kmahip_conclave *tot,
+                           double evalue, double scoreT, hipStream_t stream) {
+	if(!db || (n_parts > 0 && !parts) || !as || !us || !tot || !tot->w_scores) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(!db->dev.tlen || db->h_tlen.size() < (size_t) db->info.DB_size) { kmahip_set_error("index has no .length.b: stage 3b unavailable"); return KMAHIP_EINVAL; }
+	const size_t D = db->info.DB_size;
+	DevBuf S;
+	unsigned long long *w1 = nullptr, *uniq2 = nullptr;
+	int rc;
+	if((rc = S.up((const unsigned long long *) nullptr, D, &w1)) || (rc = S.up((const unsigned long long *) nullptr, D, &uniq2))) return rc;
+	HIP_TRY(hipMemcpyAsync(uniq2, us, D * 8, hipMemcpyDeviceToDevice, stream));
+	HIP_TRY(hipMemsetAsync(tot->w_scores, 0, D * 8, stream));          // (:535)
+	std::vector<CC2Args> C((size_t) n_parts);
+	for(int x = 0; x < n_parts; ++x) {
+		if((rc = cc2_part_args(db, parts[x], as, us, tot, &C[(size_t) x]))) return rc;
+		C[(size_t) x].w1 = w1; C[(size_t) x].uniq2 = uniq2;
+	}
+	auto pass = [&](void (*k)(const CC2Args)) {
+		for(const CC2Args &c : C) if(c.A.n_slots) hipLaunchKernelGGL(k, dim3((unsigned) ((c.A.n_slots + 255) / 256)), dim3(256), 0, stream, c);
+		return hipGetLastError();
+	};
+	HIP_TRY(pass(cc2_first_kernel));
+	std::vector<uint64_t> h_w1(D);
+	HIP_TRY(hipMemcpyAsync(h_w1.data(), w1, D * 8, hipMemcpyDeviceToHost, stream));
+	HIP_TRY(hipStreamSynchronize(stream));
+	cc2_significance(db, h_w1.data(), evalue, scoreT);
+	HIP_TRY(hipMemcpyAsync(w1, h_w1.data(), D * 8, hipMemcpyHostToDevice, stream));
+	HIP_TRY(pass(cc2_uniq_kernel));
+	HIP_TRY(pass(cc2_choose_kernel));
+	HIP_TRY(hipStreamSynchronize(stream));          // (the scratch vectors go with this call)
+	return KMAHIP_OK;
+}
+
+extern "C" int kmahip_conclave2_records_dev(kmahip_db *db, kmahip_ws *ws, int64_t n_records, const int32_t *q_len, const int32_t *q_len2, const int64_t *off,
+                                            const int32_t *q_seed, const kmahip_hits *hits, double evalue, double scoreT, kmahip_conclave *out, void *stream) {
+	(void) ws;
+	if(!db || !q_len || !off || !q_seed || !hits || !out || n_records < 0 || !hits->alignment_scores || !hits->uniq_alignment_scores) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	KmaCC2Part P{};
+	P.pe = 2; P.n = n_records; P.len = q_len; P.len2 = q_len2; P.off = off; P.hits = hits; P.o_tmpl = out->tmpl; P.o_start = out->start; P.o_end = out->end; P.seed = q_seed;
+	return kmahip_conclave2_parts(db, &P, 1, hits->alignment_scores, hits->uniq_alignment_scores, out, evalue, scoreT, (hipStream_t) stream);
+}
+
+extern "C" int kmahip_conclave2_records(kmahip_db *db, kmahip_ws *ws, int64_t n_records, const int32_t *q_len, const int32_t *q_len2, const int64_t *off,
+                                        const int32_t *q_seed, const kmahip_hits *hits, double evalue, double scoreT, kmahip_conclave *out) {
+	if(!db || !q_len || !off || !q_seed || !hits || !out || n_records < 0) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(!hits->n_hits || !hits->best_score || !hits->tmpl || !hits->start || !hits->end || !hits->alignment_scores ||
+	   !hits->uniq_alignment_scores || !out->tmpl || !out->start || !out->end || !out->w_scores) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	const size_t D = db->info.DB_size, nn = (size_t) n_records, total = nn ? (size_t) off[nn] : 0;
+	DevBuf B;
+	kmahip_hits dh{};
+	kmahip_conclave dc{};
+	int32_t *d_len, *d_len2 = nullptr, *d_seed;
+	int64_t *d_off;
+	int rc;
+	if((rc = B.up(q_len, nn, &d_len)) || (rc = B.up(off, nn + 1, &d_off)) || (rc = B.up(q_seed, nn, &d_seed)) ||
+	   (rc = B.up(hits->n_hits, nn, &dh.n_hits)) || (rc = B.up(hits->best_score, nn, &dh.best_score)) ||
+	   (rc = B.up(hits->tmpl, total, &dh.tmpl)) || (rc = B.up(hits->start, total, &dh.start)) || (rc = B.up(hits->end, total, &dh.end)) ||
+	   (rc = B.up(hits->alignment_scores, D, &dh.alignment_scores)) || (rc = B.up(hits->uniq_alignment_scores, D, &dh.uniq_alignment_scores)) ||
+	   (rc = B.up((const int32_t *) nullptr, nn, &dc.tmpl)) || (rc = B.up((const int32_t *) nullptr, nn, &dc.start)) ||
+	   (rc = B.up((const int32_t *) nullptr, nn, &dc.end)) || (rc = B.up((const uint64_t *) nullptr, D, &dc.w_scores))) return rc;
+	if(q_len2 && (rc = B.up(q_len2, nn, &d_len2))) return rc;
+	if(out->fragment_counts && (rc = B.up(out->fragment_counts, D, &dc.fragment_counts))) return rc;
+	if(out->read_counts && (rc = B.up(out->read_counts, D, &dc.read_counts))) return rc;
+	if(out->depth && (rc = B.up(out->depth, D, &dc.depth))) return rc;
+	if((rc = kmahip_conclave2_records_dev(db, ws, n_records, d_len, d_len2, d_off, d_seed, &dh, evalue, scoreT, &dc, nullptr))) return rc;
+	HIP_TRY(hipDeviceSynchronize());
+	if((rc = down(out->tmpl, dc.tmpl, nn)) || (rc = down(out->start, dc.start, nn)) || (rc = down(out->end, dc.end, nn)) ||
+	   (rc = down(out->w_scores, dc.w_scores, D)) || (rc = down(out->fragment_counts, dc.fragment_counts, D)) ||
+	   (rc = down(out->read_counts, dc.read_counts, D)) || (rc = down(out->depth, dc.depth, D))) return rc;
 	return KMAHIP_OK;
 }

@@ -246,6 +246,27 @@ int kmahip_launch_chain_anchors(kmahip_db *db, kmahip_ws *ws, const kmahip_reads
                                 int64_t *a_off, int32_t *a_n, uint8_t *slow, unsigned long long *cnt, hipStream_t stream);
 int kmahip_db_load_names(kmahip_db *db);       // fragout.hip: fills db->h_names from <prefix>.name
 double kmahip_p_chisqr(long double q);      // stdstat.c:136-147 (conclave.hip)
+
+// `-ConClave 2` (conclave.hip): the runs ask which version is set (kmahip_set_conclave_version) and, for 2, hand the records of their
+// stream over in parts (the batches of a session; anything else is one part). Everything is a DEVICE pointer.
+int kmahip_conclave_version();
+int kmahip_refuse_conclave2(const char *what);          // KMAHIP_EINVAL by name where version 2 is set (the sharded runs), else KMAHIP_OK
+struct KmaCC2Part {
+	int pe;                                  // as CCArgs.pe: 0 single-end reads, 1 record slots of kmahip_align_pe_dev, 2 explicit records
+	int64_t n;                               // slots
+	const int32_t *len, *len2, *mate, *pe_kind;
+	const int64_t *off;
+	const kmahip_hits *hits;                 // n_hits, best_score, tmpl, start, end
+	int32_t *o_tmpl, *o_start, *o_end;       // per slot
+	const int32_t *seed;                     // per slot (kmahip_cc2_seeds)
+};
+// as / us: stage 3a's two vectors (read only); tot: the per-template outputs (w_scores is set, the others are added to)
+int kmahip_conclave2_parts(kmahip_db *db, const KmaCC2Part *parts, int n_parts, const uint64_t *as, const uint64_t *us, const kmahip_conclave *tot,
+                           double evalue, double scoreT, hipStream_t stream);
+// seed[s] for slot s = read src[s * src_stride] (src NULL: read s; < 0: none) of batch a, or of b where the index is >= n0 (b NULL: a
+// alone), reverse complemented where rc[s * rc_stride] & 1 (rc NULL: as stored)
+int kmahip_cc2_seeds(const kmahip_reads *a, const kmahip_reads *b, int64_t n0, int64_t n_slots, const int32_t *src, int src_stride, const int32_t *rc, int rc_stride,
+                     int32_t *seed, hipStream_t stream);
 int kmahip_launch_scan_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads, const kmahip_params *p,
                           kmahip_pe_recs *out, hipStream_t stream);
 int kmahip_launch_align_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads, const kmahip_pe_recs *recs,

@@ -212,7 +212,14 @@ static int run_after_stage2(kmahip_db *db, kmahip_ws *ws, DevBlock &B, const kma
 	   (rc = B.get(D, &cc.w_scores, true))) return rc;
 	cc.fragment_counts = nullptr; cc.read_counts = nullptr; cc.depth = nullptr;
 	if(dbg) { auto t2 = t; fprintf(stderr, "[kmahip] run_se: ConClave buffers after %.2f ms\n", since(t2)); }
-	if(n && (rc = kmahip_conclave_se_dev(db, ws, &d, &c, &h, &cc, s))) return rc;
+	if(kmahip_conclave_version() == 2) {
+		// -ConClave 2: the four passes over the one batch; a record's seed from the read as stage 3a oriented it (h.rc)
+		int32_t *seed = nullptr;
+		if((rc = B.get((size_t) n + 1, &seed)) || (rc = kmahip_cc2_seeds(&d, nullptr, 0, n, nullptr, 0, h.rc, 1, seed, s))) return rc;
+		KmaCC2Part P{};
+		P.pe = 0; P.n = n; P.len = d.len; P.off = c.T_off; P.hits = &h; P.o_tmpl = cc.tmpl; P.o_start = cc.start; P.o_end = cc.end; P.seed = seed;
+		if(n && (rc = kmahip_conclave2_parts(db, &P, 1, h.alignment_scores, h.uniq_alignment_scores, &cc, evalue, p->scoreT, s))) return rc;
+	} else if(n && (rc = kmahip_conclave_se_dev(db, ws, &d, &c, &h, &cc, s))) return rc;
 	std::vector<uint64_t> w(D);
 	HIP_TRY(hipMemcpy(w.data(), cc.w_scores, D * 8, hipMemcpyDeviceToHost));
 	if(dbg) { auto t2 = t; fprintf(stderr, "[kmahip] run_se: ConClave kernel + scores back after %.2f ms\n", since(t2)); }
@@ -818,6 +825,15 @@ static int run_pe_impl(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *ba
 			HIP_TRY(hipMemcpy(last, d_last, sizeof last, hipMemcpyDeviceToHost));
 			if((rc = shard_carry_in(sc, last, carry))) return rc;
 			if(U > 0 && (rc = kmahip_conclave_records_carry(db, n_slots, A.r_ql, A.r_ql2, A.r_off, &h, &cc, carry, s))) return rc;
+		} else if(kmahip_conclave_version() == 2) {
+			// -ConClave 2: the stream is one part; a record's seed from its FIRST fragment (either mate, alnFragsPE's two update_Scores_pe
+			// calls) as stage 3a oriented it -- a read of the uploaded batch, or a record of the chain finder's
+			int32_t *seed = nullptr;
+			if((rc = B.get((size_t) n_slots + 1, &seed)) ||
+			   (rc = kmahip_cc2_seeds(&dR, cp ? &CR.d : nullptr, n, n_slots, A.fr_read, 2, A.fr_rc, 2, seed, s))) return rc;
+			KmaCC2Part P{};
+			P.pe = 2; P.n = n_slots; P.len = A.r_ql; P.len2 = A.r_ql2; P.off = A.r_off; P.hits = &h; P.o_tmpl = cc.tmpl; P.o_start = cc.start; P.o_end = cc.end; P.seed = seed;
+			if(U > 0 && (rc = kmahip_conclave2_parts(db, &P, 1, AS, US, &cc, evalue, p->scoreT, s))) return rc;
 		} else if(U > 0 && (rc = kmahip_conclave_records_dev(db, ws, n_slots, A.r_ql, A.r_ql2, A.r_off, &h, &cc, s))) return rc;
 	}
 	if(sc) {          // exchange 2: ConClave's per-template outputs summed (the fragment counts cut the owners' template ranges)
@@ -1913,6 +1929,7 @@ extern "C" int kmahip_run_se_sharded(kmahip_db *db, kmahip_ws *ws, kmahip_comm *
                                      const kmahip_shard_opts *opts, const char *out_prefix, double ms[8]) {
 	if(!db || !ws || !batch || !p || !opts || !out_prefix || !ms) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_SHARD)) return rcp;
+	if(int rcc = kmahip_refuse_conclave2("the sharded single-end run (kmahip_run_se_sharded)")) return rcc;
 	const kmahip_reads &R = batch->reads;
 	const int64_t n = R.n_reads;
 	if(n < 0 || R.seq_words < 0 || R.N_total < 0) { kmahip_set_error("negative size"); return KMAHIP_EINVAL; }
@@ -1963,6 +1980,7 @@ extern "C" int kmahip_run_chain_sharded(kmahip_db *db, kmahip_ws *ws, kmahip_com
                                         const kmahip_chain_params *cp, const kmahip_shard_opts *opts, const char *out_prefix, double ms[8]) {
 	if(!db || !ws || !comm || !batch || !p || !opts || !out_prefix || !ms) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_SHARD)) return rcp;
+	if(int rcc = kmahip_refuse_conclave2("the sharded run of the default mode (kmahip_run_chain_sharded)")) return rcc;
 	const kmahip_reads &R = batch->reads;
 	const int64_t n = R.n_reads;
 	if(n < 0 || R.seq_words < 0 || R.N_total < 0) { kmahip_set_error("negative size"); return KMAHIP_EINVAL; }
@@ -2144,6 +2162,7 @@ extern "C" int kmahip_run_pe_sharded(kmahip_db *db, kmahip_ws *ws, kmahip_comm *
                                      const kmahip_shard_opts *opts, const char *out_prefix, double ms[8]) {
 	if(!db || !ws || !batch || !p || !opts || !out_prefix || !ms) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_SHARD)) return rcp;
+	if(int rcc = kmahip_refuse_conclave2("the sharded paired run (kmahip_run_pe_sharded)")) return rcc;
 	if(int rcf = kmahip_refuse_forced_pairing(p)) return rcf;
 	int rc = kmahip_db_load_names(db);
 	if(rc) return rc;

@@ -1047,8 +1047,30 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 	if(ef_on && ((rc = B.get(D, &cc.fragment_counts, true)) || (rc = B.get(D, &cc.read_counts, true)))) return rc;
 	if((rc = B.get((size_t) n + 1, &cc.tmpl, true)) || (rc = B.get((size_t) n + 1, &cc.start, true)) || (rc = B.get((size_t) n + 1, &cc.end, true)) || (rc = B.get(D, &cc.w_scores, true)) ||
 	   (rc = B.get((size_t) n + 1, &rc_all, true)) || (rc = B.get((size_t) n + 1, &nh_all, true))) return rc;
+	const bool cc2 = kmahip_conclave_version() == 2;
+	if(cc2) {
+		// -ConClave 2: its three record passes are global over the stream, so the batches are gone through three times, with the host's
+		// significance step between the first and the second (kmahip_conclave2_parts). A record's seed: the item as stage 3a oriented it.
+		int32_t *seed = nullptr;
+		if((rc = B.get((size_t) n + 1, &seed, true))) return rc;
+		std::vector<KmaCC2Part> parts;
+		const uint64_t *as = nullptr, *us = nullptr;
+		for(Batch &b : S->batches) {
+			if(!b.n) continue;
+			HIP_TRY(hipMemcpyAsync(rc_all + b.r0, b.h.rc, (size_t) b.n * 4, hipMemcpyDeviceToDevice, s));
+			HIP_TRY(hipMemcpyAsync(nh_all + b.r0, b.h.n_hits, (size_t) b.n * 4, hipMemcpyDeviceToDevice, s));
+			if(fl_all) HIP_TRY(hipMemcpyAsync(fl_all + b.r0, b.h.flag, (size_t) b.n * 4, hipMemcpyDeviceToDevice, s));
+			KmaCC2Part P{};
+			P.pe = 0; P.n = b.n; P.len = W.len + b.r0; P.off = b.c.T_off; P.hits = &b.h;
+			P.o_tmpl = cc.tmpl + b.r0; P.o_start = cc.start + b.r0; P.o_end = cc.end + b.r0; P.seed = seed + b.r0;
+			parts.push_back(P);
+			as = b.h.alignment_scores; us = b.h.uniq_alignment_scores;          // (the session's two vectors: every batch adds into the same)
+		}
+		if(n && (rc = kmahip_cc2_seeds(&W, nullptr, 0, n, nullptr, 0, rc_all, 1, seed, s))) return rc;
+		if(!parts.empty() && (rc = kmahip_conclave2_parts(db, parts.data(), (int) parts.size(), as, us, &cc, S->opts.evalue, p->scoreT, s))) return rc;
+	}
 	for(Batch &b : S->batches) {
-		if(!b.n) continue;
+		if(!b.n || cc2) continue;
 		kmahip_reads d = W;
 		d.n_reads = b.n; d.seq_off = W.seq_off + b.r0; d.len = W.len + b.r0; d.N_off = W.N_off + b.r0; d.max_len = b.max_len;
 		if(W.q_start) { d.q_start = W.q_start + b.r0; d.q_end = W.q_end + b.r0; }

@@ -216,6 +216,9 @@ def run_se_sharded(db, batch: ReadBatch, names=None, evalue=0.05, bcd=1, max_fra
     statistics of all templates (identical everywhere), owner [DB_size], cover / aln_len / depth / asm_len [DB_size] summed over
     the owners, consensus {template: str} of the templates this rank owns, frag_rows). frag_path: each rank writes the
     `.frag(.gz)` rows of its templates to frag_path % rank; concatenated in rank order they are the reference's file."""
+    from . import binding
+    if binding._conclave_now == 2:          # (this run calls ConClave version 1 stage by stage; version 2's vectors are not summed over ranks)
+        raise binding.KmaHipError("kmahip error -1: -ConClave 2 is not built for the sharded runs: it serves the runs of one rank")
     world = dist.get_world_size(group)
     (rc_flag, flag, T_off, T), h = db.map_se(batch)
     aln = torch.from_numpy(h["alignment_scores"].astype(np.int64))
