@@ -37,7 +37,7 @@ struct VisitDesc {
 	int32_t start;               // first template column of run `first`
 	int32_t L, nN;
 	int32_t flags;               // 1: reverse complement, 2: runs behind the unit need not be looked at
-	int32_t pad;
+	int32_t turn;                // which turn of the read round its template this visit piles up (0 unless the read is longer than the ring)
 };
 
 static_assert(sizeof(VisitDesc) == 64, "a visit record is sixteen words");
@@ -219,16 +219,23 @@ __device__ bool read_has_ins(const PileArgs &A, int64_t r) {
 // the units a kept read visits: [u0, u1] and, for an alignment that wraps around a circular template, [w0, w1] as well. A unit
 // [lo, hi) is visited when the read covers one of the columns lo - 1 .. hi - 1: the column in front of the unit is counted there
 // too (its depth is what a new insertion column in front of column lo starts from, assembly.c:1377-1397).
-struct Visits { int u0, u1, w0, w1; };
+// A read that goes round the ring more than once (a circular alignment chains on past a whole turn) is taken a turn at a time, as the
+// reference's walk takes it: `full` whole turns, each a visit to EVERY unit of the template, then the rest as a read of its own
+// ([u0, u1], [w0, w1]). A turn covers a column at most once, and the turns of a read follow each other in a unit's order, so a
+// later turn finds the insertion columns and the depths the earlier ones left.
+constexpr int PILE_TURN_BITS = 4, PILE_KEY_UNIT = 28 + PILE_TURN_BITS;      // sort key: unit, order (< 2^28), turn
+struct Visits { int u0, u1, w0, w1, full; };
+__device__ __forceinline__ int64_t visit_count(const Visits &V, int nu) { return (int64_t) V.full * nu + (V.u1 - V.u0 + 1) + (V.w1 >= V.w0 ? V.w1 - V.w0 + 1 : 0); }
 __device__ Visits pile_visits(const PileArgs &A, int64_t r) {
-	Visits V = {0, -1, 0, -1};
+	Visits V = {0, -1, 0, -1, 0};
 	const int t = abs(A.tmpl[r]);
 	const int ub = A.unit_base[t], nu = A.unit_base[t + 1] - ub;
 	if(nu == 1) { V.u0 = V.u1 = ub; return V; }
 	const ReadRuns R = read_runs(A, r);
 	const int32_t *st = A.stats + 10 * r;
 	const int t_len = A.db.tlen[t];
-	const int span = st[3] - st[7] - R.lead_d - R.trail_d;       // template columns the piled-up part covers
+	int span = st[3] - st[7] - R.lead_d - R.trail_d;             // template columns the piled-up part covers
+	if(span > t_len) { V.full = (span - 1) / t_len; span -= V.full * t_len; }      // (the last turn: 1 .. t_len columns)
 	const int S = A.seg_cols;
 	int start = R.start;
 	if(start >= t_len) start -= t_len;
@@ -251,8 +258,11 @@ __global__ __launch_bounds__(256) void pile_count_kernel(const PileArgs A) {
 	int64_t c = 0;
 	if(A.stats[10 * r + 3] != 0) {
 		const Visits V = pile_visits(A, r);
-		c = (V.u1 - V.u0 + 1) + (V.w1 >= V.w0 ? V.w1 - V.w0 + 1 : 0);
-		A.seg_start[abs(A.tmpl[r])] = 0;
+		const int t = abs(A.tmpl[r]);
+		c = visit_count(V, A.unit_base[t + 1] - A.unit_base[t]);
+		// (more turns than the sort key has room for: the host ends the call)
+		if(V.full >= (1 << PILE_TURN_BITS)) { atomicMax(&A.counters[1], 128ull); c = 0; }
+		A.seg_start[t] = 0;
 	}
 	A.vis_cnt[r] = c;
 }
@@ -266,9 +276,16 @@ __global__ __launch_bounds__(256) void pile_keys_kernel(const PileArgs A) {
 	const uint64_t chunk = (uint64_t) (rk / A.max_frag), in = (uint64_t) (rk % A.max_frag);
 	const uint64_t ord = A.order ? (uint64_t) rk : chunk * (uint64_t) A.max_frag + ((uint64_t) A.max_frag - 1 - in);
 	const Visits V = pile_visits(A, r);
+	if(V.full >= (1 << PILE_TURN_BITS)) return;
 	int64_t slot = A.vis_off[r];
-	for(int u = V.u0; u <= V.u1; ++u, ++slot) { A.keys[slot] = ((uint64_t) u << 28) | ord; A.vals[slot] = (int32_t) r; }
-	for(int u = V.w0; u <= V.w1; ++u, ++slot) { A.keys[slot] = ((uint64_t) u << 28) | ord; A.vals[slot] = (int32_t) r; }
+	const uint64_t last = (ord << PILE_TURN_BITS) | (uint64_t) V.full;
+	for(int u = V.u0; u <= V.u1; ++u, ++slot) { A.keys[slot] = ((uint64_t) u << PILE_KEY_UNIT) | last; A.vals[slot] = (int32_t) r; }
+	for(int u = V.w0; u <= V.w1; ++u, ++slot) { A.keys[slot] = ((uint64_t) u << PILE_KEY_UNIT) | last; A.vals[slot] = (int32_t) r; }
+	if(V.full) {
+		const int t = abs(A.tmpl[r]);
+		for(int k = 0; k < V.full; ++k)
+			for(int u = A.unit_base[t]; u < A.unit_base[t + 1]; ++u, ++slot) { A.keys[slot] = ((uint64_t) u << PILE_KEY_UNIT) | (ord << PILE_TURN_BITS) | (uint64_t) k; A.vals[slot] = (int32_t) r; }
+	}
 }
 
 // checkpoints of the reads that lie on a template cut into units and do not wrap around its end: one wavefront per read, its runs
@@ -281,15 +298,16 @@ __global__ __launch_bounds__(64) void pile_ckpt_kernel(const PileArgs A) {
 		const int ub = A.unit_base[t], nu = A.unit_base[t + 1] - ub;
 		if(nu <= 1) continue;
 		const Visits V = pile_visits(A, r);
+		if(V.full >= (1 << PILE_TURN_BITS)) continue;          // (no entries: pile_count_kernel)
 		const ReadRuns R = read_runs(A, r);
 		const int t_len = A.db.tlen[t];
 		int start = R.start;
 		if(start >= t_len) start -= t_len;
 		const int nvis = V.u1 - V.u0 + 1;
 		const int64_t slot0 = A.vis_off[r];
-		const int nslots = nvis + (V.w1 >= V.w0 ? V.w1 - V.w0 + 1 : 0);
+		const int nslots = (int) visit_count(V, nu);
 		for(int x = lane; x < nslots; x += 64) { A.ck_j[slot0 + x] = R.first; A.ck_col[slot0 + x] = 0; A.ck_q[slot0 + x] = R.qp; }
-		if(V.w1 >= V.w0 || V.u0 != ub + start / A.seg_cols) continue;          // (wraps, or covers everything: the units scan from the first run)
+		if(V.full || V.w1 >= V.w0 || V.u0 != ub + start / A.seg_cols) continue;          // (wraps, or covers everything: the units scan from the first run)
 		const int S = A.seg_cols, u0l = V.u0 - ub;
 		int col_carry = 0, q_carry = R.qp;
 		for(int j0 = R.first; j0 < R.n; j0 += 64) {
@@ -316,9 +334,9 @@ __global__ __launch_bounds__(64) void pile_ckpt_kernel(const PileArgs A) {
 __global__ __launch_bounds__(256) void pile_segments_kernel(const uint64_t *keys, int64_t n_ent, int64_t *unit_start, int64_t *unit_end) {
 	const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
 	if(i >= n_ent) return;
-	const int64_t u = (int64_t) (keys[i] >> 28);
-	if(i == 0 || (int64_t) (keys[i - 1] >> 28) != u) unit_start[u] = i;
-	if(i + 1 == n_ent || (int64_t) (keys[i + 1] >> 28) != u) unit_end[u] = i + 1;
+	const int64_t u = (int64_t) (keys[i] >> PILE_KEY_UNIT);
+	if(i == 0 || (int64_t) (keys[i - 1] >> PILE_KEY_UNIT) != u) unit_start[u] = i;
+	if(i + 1 == n_ent || (int64_t) (keys[i + 1] >> PILE_KEY_UNIT) != u) unit_end[u] = i + 1;
 }
 
 // one thread per sorted entry: the visit's record (only for units of templates that are cut into units)
@@ -326,7 +344,7 @@ __global__ __launch_bounds__(256) void pile_desc_kernel(const PileArgs A, int64_
 	const int64_t e = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
 	if(e >= n_ent) return;
 	const int64_t r = A.vals[e];
-	const int unit = (int) (A.keys[e] >> 28);
+	const int unit = (int) (A.keys[e] >> PILE_KEY_UNIT);
 	const int t = abs(A.tmpl[r]);
 	const int ub = A.unit_base[t];
 	if(A.unit_base[t + 1] - ub <= 1) return;
@@ -339,7 +357,7 @@ __global__ __launch_bounds__(256) void pile_desc_kernel(const PileArgs A, int64_
 	if(start >= t_len) start -= t_len;
 	D.start = start;
 	D.j_begin = R.first; D.col_carry = 0; D.q_carry = R.qp;
-	D.flags = R.q.rc ? 1 : 0; D.pad = 0;
+	D.flags = R.q.rc ? 1 : 0; D.turn = (int32_t) (A.keys[e] & ((1u << PILE_TURN_BITS) - 1));
 	// where this unit's stretch of the read begins (pile_ckpt_kernel); a read that wraps round the template's end has no checkpoints
 	const int u0 = ub + start / A.seg_cols;
 	const int32_t *st = A.stats + 10 * r;
@@ -423,8 +441,11 @@ __device__ __forceinline__ void pile_seg_read(const PileArgs &A, const SegWalk &
 	int64_t col_carry = V.col_carry, q_carry = V.q_carry;
 	const int j_begin = V.j_begin;
 	const bool ends_early = (V.flags & 2) != 0;
+	// this visit's turn: the read's columns [turn_lo, turn_lo + t_len), counted from its first one
+	const int64_t turn_lo = (int64_t) V.turn * W.t_len, turn_hi = turn_lo + W.t_len;
 	for(int j0 = j_begin; j0 < R.n; j0 += (int) blockDim.x) {
 		if(ends_early && start + col_carry > (int64_t) W.hi) break;          // (every further run lies behind the unit)
+		if(col_carry >= turn_hi) break;                                      // (... or in a later turn)
 		const int j = j0 + tid;
 		const bool valid = j < R.n;
 		const bool pre = j0 == j_begin;                 // the first round's runs were asked for during the visit before
@@ -458,7 +479,7 @@ __device__ __forceinline__ void pile_seg_read(const PileArgs &A, const SegWalk &
 				else continue;
 				int64_t rel = (int64_t) p - start;
 				if(rel < 0) rel += W.t_len;
-				rel -= colA;
+				rel += turn_lo - colA;
 				if(rel < 0 || rel >= span) continue;
 				// last run that begins at or before the column (a run without template columns shares its column with the run behind it)
 				int a = 0, bnd = nr;
@@ -476,7 +497,7 @@ __device__ __forceinline__ void pile_seg_read(const PileArgs &A, const SegWalk &
 		__syncthreads();
 		// ---- phase 2a: insertion runs whose column lies in the unit
 		int site = -1, qafter = 0;
-		if(valid && cls == 2) {
+		if(valid && cls == 2 && col0 >= turn_lo && col0 < turn_hi) {
 			const int p = (int) ((start + col0) % W.t_len);
 			const int ci = W.ci(p);
 			if(ci >= 0) { site = ci; qafter = (int) (q0 + len); }      // (index 0, the column in front of the unit: counted, its chain is not ours)
@@ -492,9 +513,24 @@ __device__ __forceinline__ void pile_seg_read(const PileArgs &A, const SegWalk &
 						myBias = W.depth16_col(cprev);
 						// the column in front of the site is the single column between two insertion runs of this read: its own
 						// base is added in phase 2b of this round -- count it now (16-bit counters: only while below the ceiling)
-						if(j - 2 >= j0 && j - 2 >= R.first && (prun & 3u) != 2u && (prun >> 2) == 1u && (A.ops[R.o + j - 2] & 3u) == 2u) {
+						if(j - 2 >= j0 && j - 2 >= R.first && col0 - 1 >= turn_lo && (prun & 3u) != 2u && (prun >> 2) == 1u && (A.ops[R.o + j - 2] & 3u) == 2u) {
 							const int b = (prun & 3u) == 3u ? 5 : q_base(R.q, (int) q0 - 1);
 							if(pile_lds[6 * cprev + b] < 65535u) ++myBias;
+						}
+					}
+					// the site is the first column of a later turn: the column in front of it closed the turn before, and this turn
+					// passes it again t_len - 1 columns on. If phase 1 of this round has counted that pass, take it out again: the
+					// reference has not walked that far
+					if(!last && col0 == turn_lo && turn_lo > 0 && turn_hi - 1 < col_carry) {
+						const uint32_t *rc0 = pile_lds + W.run_base(), *rq0 = rc0 + blockDim.x, *rrun = rq0 + blockDim.x;
+						const int64_t rel = turn_hi - 1 - (col_carry - (int64_t) (total >> 32));
+						int a = 0, bnd = min((int) blockDim.x, R.n - j0);
+						while(bnd - a > 1) { const int mid = (a + bnd) >> 1; if((int64_t) rc0[mid] <= rel) a = mid; else bnd = mid; }
+						const int rcls = (int) (rrun[a] & 3u), c = (int) (rel - (int64_t) rc0[a]);
+						const bool waits = c == 0 && a > 0 && (rrun[a - 1] & 3u) == 2u;      // (phase 2b has it)
+						if(rcls != 2 && !waits) {
+							const int b = rcls == 3 ? 5 : q_base(R.q, (int) ((int64_t) (int32_t) rq0[a] + c));
+							if(pile_lds[6 * W.ci(p ? p - 1 : W.t_len - 1) + b] <= 65535u) --myBias;
 						}
 					}
 					const int tmp = W.depth16_col(ci);
@@ -550,6 +586,26 @@ __device__ void pile_cols(const PileArgs &A, const Walk<LDS> &W, int64_t r, int 
 template <bool LDS>
 __device__ void pile_ins(const PileArgs &A, const Walk<LDS> &W, int64_t r) {
 	ReadRuns R = read_runs(A, r);
+	const int span = A.stats[10 * r + 3] - A.stats[10 * r + 7] - R.lead_d - R.trail_d;
+	// A read that goes round the template more than once: pile_cols has already counted the LATER turns' passes over a column (and the
+	// gaps they give the chain in front of it), which the reference, walking on from here, has not made yet. `later(c)`: the passes of
+	// the read's columns c + t_len, c + 2 t_len, ... that pile_cols made (not those behind an insertion run, which wait for this loop)
+	auto later = [&](int c) {
+		int n = 0;
+		for(int64_t c2 = (int64_t) c + W.t_len; c2 < span; c2 += W.t_len) {
+			int x = 0;
+			bool ins = false, waits = false;
+			for(int k = R.first; k < R.n && x <= c2; ++k) {
+				const uint32_t rk = A.ops[R.o + k];
+				if((rk & 3u) == 2u) { ins = true; continue; }
+				if(x == c2 && ins) waits = true;
+				x += (int) (rk >> 2);
+				ins = false;
+			}
+			if(!waits) ++n;
+		}
+		return n;
+	};
 	int i = 0, qpos = R.qp;
 	for(int j = R.first; j < R.n; ++j) {
 		const uint32_t run = A.ops[R.o + j];
@@ -569,13 +625,15 @@ __device__ void pile_ins(const PileArgs &A, const Walk<LDS> &W, int64_t r) {
 		}
 		if(left > 0) {
 			// new columns in front of template position `gaps` (assembly.c:1368-1428)
-			int myBias = W.depth16(last, gaps ? gaps - 1 : W.t_len - 1);
-			const int tmp = W.depth16(0, gaps);
+			const int more = i + W.t_len < span ? later(i) : 0;             // later passes over the site: a gap for each new column
+			int myBias = W.depth16(last, gaps ? gaps - 1 : W.t_len - 1) - (last ? more : (i - 1 + W.t_len < span ? later(i - 1) : 0));
+			const int tmp = W.depth16(0, gaps) - more;
 			myBias = (tmp < myBias) ? tmp : (myBias - 1);
 			if(65535 < myBias) myBias = 65535;
 			while(left > 0) {
 				const int id = W.new_node(myBias, q_base(R.q, qpos++), gaps);
 				if(!id) return;
+				for(int x = 0; x < more; ++x) W.add_node(id, 5);
 				wg_fence();
 				if(last) W.set_next(last, id); else W.set_head(gaps, id);
 				last = id;
@@ -1122,7 +1180,12 @@ static int pileup_device(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads
 			ws->p_kept = n_ent;
 		}
 		const int64_t n_ent = ws->p_kept;
-		if(!n_ent) return KMAHIP_OK;
+		if(!n_ent) {
+			// (nothing to pile up -- or pile_count_kernel turned the only reads away)
+			HIP_TRY(hipMemcpy(c, ws->counters, sizeof c, hipMemcpyDeviceToHost));
+			if(c[1]) break;
+			return KMAHIP_OK;
+		}
 		if(ws->p_ent_cap < n_ent) {
 			(void) hipFree(ws->p_keys); (void) hipFree(ws->p_vals);
 			ws->p_keys = nullptr; ws->p_vals = nullptr; ws->p_ent_cap = 0;
@@ -1180,15 +1243,21 @@ static int pileup_device(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads
 		HIP_TRY(hipStreamSynchronize(stream));
 		(void) hipFree(tmp); tmp = nullptr;
 		lap("pileup_kernel");
+		if(dbg) fprintf(stderr, "[kmahip] pile-up: launch of %lld units, %d columns per segment, %s LDS, whole templates %s, %s\n", (long long) n_units, seg_cols,
+		                half ? "half" : "full", lds_cols ? "in LDS" : "on HBM", A.ck_j ? "run checkpoints" : "no run checkpoints");
 		HIP_TRY(hipMemcpy(c, ws->counters, sizeof c, hipMemcpyDeviceToHost));
 		if(c[1] == 64 && half && seg_cols > 256) { seg_cols >>= 1; if(dbg) fprintf(stderr, "[kmahip] pile-up: a segment ran out of its half of the LDS, again with %d columns per segment\n", seg_cols); continue; }
 		if((c[1] == 16 || c[1] == 64) && half) { lds_half = false; if(dbg) fprintf(stderr, "[kmahip] pile-up: half the LDS did not hold a unit's insertion columns, again with all of it\n"); continue; }
 		if(c[1] == 64 && seg_cols > 64) { seg_cols >>= 1; if(dbg) fprintf(stderr, "[kmahip] pile-up: a segment ran out of LDS room, again with %d columns per segment\n", seg_cols); continue; }
-		if(c[1] == 16 && lds_cols) { lds_cols = 0; continue; }      // a template's insertion columns did not fit LDS: those on HBM
+		if(c[1] == 16 && lds_cols) { lds_cols = 0; if(dbg) fprintf(stderr, "[kmahip] pile-up: the LDS did not hold a template's insertion columns, again with whole templates on HBM\n"); continue; }
 		break;
 	}
 	if(c[1]) {
 		HIP_TRY(hipMemset(ws->counters + 1, 0, sizeof(unsigned long long)));
+		if(c[1] >= 128) {
+			kmahip_set_error("pile-up: a read goes round a template cut into units more than %d times", 1 << PILE_TURN_BITS);
+			return KMAHIP_EINVAL;
+		}
 		kmahip_set_error("pile-up: insertion column pool exhausted (%lld columns, status %llu)", (long long) ws->p_node_cap, c[1]);
 		return KMAHIP_EOVERFLOW;
 	}

@@ -164,3 +164,21 @@ void orc_assembly_call2(const orc_assembly *m, const uint64_t *tseq, int bcd, do
 }
 
 int orc_assembly_has_reads(const orc_assembly *m) { return m->score != 0; }
+
+/* The columns read back in ring order: from template position 0 along `next` until the walk is back at 0 (the order callConsensus and
+ * the matrix writer print them in). counts (may be NULL) receives six 16-bit counts per column, is_ins (may be NULL) one byte per column:
+ * 1 = an insertion column, 0 = a template position. At most cap columns are written; -> the number of columns on the ring. */
+int orc_assembly_columns(const orc_assembly *m, uint16_t *counts, uint8_t *is_ins, int cap) {
+	const node *A = m->a;
+	int n = 0, pos = 0;
+	if(!m->t_len) return 0;
+	do {
+		if(n < cap) {
+			if(counts) for(int j = 0; j < 6; ++j) counts[6 * n + j] = A[pos].counts[j];
+			if(is_ins) is_ins[n] = m->t_len <= pos;
+		}
+		++n;
+		pos = A[pos].next;
+	} while(pos != 0 && n <= m->len);
+	return n;
+}

@@ -165,6 +165,8 @@ void orc_assembly_call(const orc_assembly *m, const uint64_t *tseq, int bcd, dou
  * (-bcNano, assembly.c:147-149, kma.c:762-766) */
 void orc_assembly_call2(const orc_assembly *m, const uint64_t *tseq, int bcd, double evalue, int caller, int sig, int64_t *out, char *cons);
 int orc_assembly_has_reads(const orc_assembly *m);
+/* the columns in ring order from template position 0: six counts each, is_ins 1 for an insertion column -> columns on the ring */
+int orc_assembly_columns(const orc_assembly *m, uint16_t *counts, uint8_t *is_ins, int cap);
 const uint64_t *orc_db_template(const orc_db *db, int t);
 
 #ifdef __cplusplus

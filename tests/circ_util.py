@@ -15,9 +15,12 @@ HEADER = os.path.join(ROOT, "include", "kmahip.h")
 TIMEOUT = 120
 
 # seeds of the inputs: (database, reads). A seed that misses a floor of test_circular_gpu.FLOORS is changed here, never the floor.
-SEEDS = {"A": (301, 11), "P": (301, 12), "L": (302, 13), "O": (301, 18)}
+SEEDS = {"A": (301, 11), "P": (301, 12), "L": (302, 13), "O": (301, 18), "M": (302, 21)}
 # wrapped rows (end < start in the inflated .frag.gz) the reference must file with -ca on each input
 FLOORS = {"A": 300, "P": 60, "L": 40, "O": 40}
+# input M: with -ca the deepest column of a template's count matrix must exceed the rows filed under it by at least this much (second
+# turns are counted), and without -ca it must not exceed them at all
+TURNS_FLOOR = 10
 
 
 def db_short():
@@ -105,9 +108,33 @@ def reads_o(seqs, n=400):
     return out
 
 
+def reads_m(seqs, n=60):
+    """reads of 1.15-1.65 turns of a 6 000-base template (7-10 kb on a 6 kb plasmid), the templates in turn, 3 % substitutions, an
+    insertion or a deletion of 1-3 bases every 150-500 bases, both strands: more than one turn of a template that the pile-up cuts
+    into units"""
+    rng = np.random.default_rng(SEEDS["M"][1])
+    out = []
+    for i in range(n):
+        s = seqs[i % len(seqs)]
+        L = int(len(s) * (1.15 + 0.5 * rng.random()))
+        r = _subst(_turn(s, int(rng.integers(0, len(s))), L), 0.03, rng)
+        parts, p = [], 0
+        while p < len(r):
+            q = min(len(r), p + int(rng.integers(150, 500)))
+            parts.append(r[p:q])
+            u = rng.random()
+            if u < 0.4:
+                parts.append(rng.integers(0, 4, int(rng.integers(1, 4)), dtype=np.uint8))
+            elif u < 0.8:
+                q = min(len(r), q + int(rng.integers(1, 4)))
+            p = q
+        out.append(_strand(np.concatenate(parts), rng))
+    return out
+
+
 def make_input(tmp, key):
-    """index files and FASTQ of input `key` (A, P, L, O) in directory tmp -> dict(tmp, prefix, fq, fq2, reads, runs)"""
-    names, seqs = db_long() if key == "L" else db_short()
+    """index files and FASTQ of input `key` (A, P, L, O, M) in directory tmp -> dict(tmp, prefix, fq, fq2, reads, runs)"""
+    names, seqs = db_long() if key in "LM" else db_short()
     prefix = str(tmp / "db")
     formats.write_index(prefix, names, seqs)
     fq, fq2, rd = str(tmp / "reads.fq"), None, None
@@ -117,7 +144,7 @@ def make_input(tmp, key):
         synth.write_fastq(fq, m1, lens=None)
         synth.write_fastq(fq2, m2, lens=None)
     else:
-        rd = {"A": reads_a, "L": reads_l, "O": reads_o}[key](seqs)
+        rd = {"A": reads_a, "L": reads_l, "O": reads_o, "M": reads_m}[key](seqs)
         synth.write_fastq(fq, rd, lens=None)
     return dict(tmp=tmp, key=key, prefix=prefix, fq=fq, fq2=fq2, reads=rd, runs={}, names=names, seqs=seqs)
 
@@ -187,3 +214,19 @@ def mapstat(stem):
 
 def gz(stem, ext):
     return gzip.open(stem + ext, "rb").read()
+
+
+def matrix_blocks(raw):
+    """an inflated .mat.gz -> {template name: its rows as bytes, each ended by a newline}"""
+    out, name, rows = {}, None, []
+    for ln in raw.split(b"\n"):
+        if ln.startswith(b"#"):
+            name, rows = ln[1:], []
+            out[name] = rows
+        elif ln:
+            rows.append(ln)
+    return {k: b"".join(r + b"\n" for r in v) for k, v in out.items()}
+
+
+def deepest_column(block):
+    return max(sum(int(x) for x in ln.split(b"\t")[1:7]) for ln in block.split(b"\n") if ln)

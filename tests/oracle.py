@@ -275,10 +275,35 @@ class Assembly:
         L.orc_assembly_call2(self.h, self.tseq, bcd, evalue, caller, sig, _p(out), cons)
         return dict(cover=int(out[0]), aln_len=int(out[1]), depth=int(out[2]), asm_len=int(out[3]), consensus=cons.value.decode())
 
+    def columns(self):
+        """The pile-up read back column by column, in ring order from template position 0 (orc_assembly_columns)
+        -> (counts [asm_len, 6] uint16: A C G T N -, is_ins [asm_len] bool: an insertion column)"""
+        L = lib()
+        L.orc_assembly_columns.restype = C.c_int
+        L.orc_assembly_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        n = L.orc_assembly_columns(self.h, None, None, 0)
+        counts = np.zeros((n, 6), np.uint16)
+        ins = np.zeros(n, np.uint8)
+        assert L.orc_assembly_columns(self.h, _p(counts), _p(ins), n) == n
+        return counts, ins.astype(bool)
+
+    def matrix_text(self, seq):
+        """The columns as kmahip_assemble_matrix_dev and the reference's `.mat.gz` print them: a row `base A C G T N -` per column,
+        tab separated, '-' as the base of an insertion column. seq = the template's bases (codes 0-3)."""
+        return matrix_text(*self.columns(), seq)
+
     def __del__(self):
         if getattr(self, "h", None):
             lib().orc_assembly_free(self.h)
             self.h = None
+
+
+def matrix_text(counts, is_ins, seq):
+    """rows of a count matrix from Assembly.columns() -> bytes"""
+    assert int((~is_ins).sum()) == len(seq)
+    base = np.full(len(counts), ord("-"), np.uint8)
+    base[~is_ins] = np.frombuffer(b"ACGTN", np.uint8)[np.asarray(seq, np.uint8)]
+    return b"".join(b"%c\t%d\t%d\t%d\t%d\t%d\t%d\n" % ((b,) + tuple(int(x) for x in c)) for b, c in zip(base, counts))
 
 
 def res_identity_columns(call, t_len):

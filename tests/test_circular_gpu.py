@@ -104,6 +104,97 @@ def test_o_whole_turns(inputs, extra):
     _same(s, "o" + "".join(extra), extra)
 
 
+# ---- 5b: more than one turn of a template the pile-up cuts into units ----------------------------------------------------------------------
+M_RUNS = {"mt1": ["-Mt1", "1", "-ca", "-matrix", "-vcf", "-ef"], "1t1": ["-1t1", "-ca", "-bcNano", "-matrix"],
+          "1t1_side": ["-1t1", "-ca", "-bcNano", "-matrix", "-vcf", "-ef"]}          # (the last one for a `.mapstat`: -Mt1 writes none)
+
+
+def _rows_and_depths(stem):
+    """-> {template name: (rows of .frag.gz filed under it, deepest column of its count matrix)}"""
+    rows = {}
+    for r in cu.frag_rows(cu.frag(stem)):
+        rows[r[5]] = rows.get(r[5], 0) + 1
+    blocks = cu.matrix_blocks(cu.gz(stem, ".mat.gz"))
+    assert set(blocks) == set(rows)
+    return {k: (rows[k], cu.deepest_column(blocks[k])) for k in rows}
+
+
+@pytest.mark.parametrize("run", list(M_RUNS))
+def test_m_reference_counts_the_second_turn(inputs, run):
+    """the reference first: with -ca the reads of input M go round their template more than once and it counts every turn -- a column
+    deeper than the template has reads, by TURNS_FLOOR at least; without -ca no column is deeper than the reads are many"""
+    s = inputs("M")
+    extra = M_RUNS[run]
+    got = _rows_and_depths(cu.ref(s, extra))
+    assert sum(n for n, _ in got.values()) == 60 and len(got) == (1 if run == "mt1" else 2)
+    w, _ = cu.wrapped(cu.frag(cu.ref(s, extra)))
+    assert w >= 20
+    for name, (n, deepest) in got.items():
+        print("input M %s %s: %d rows, deepest column %d" % (run, name.decode(), n, deepest))
+        assert deepest >= n + cu.TURNS_FLOOR, (name, n, deepest)
+    plain = _rows_and_depths(cu.ref(s, [x for x in extra if x != "-ca"]))
+    for name, (n, deepest) in plain.items():
+        assert deepest <= n, (name, n, deepest)
+
+
+@pytest.mark.parametrize("env", [{}, {"KMAHIP_PILE_SEG_COLS": "256"}], ids=["default", "seg256"])
+@pytest.mark.parametrize("run", list(M_RUNS))
+def test_m_more_than_one_turn(inputs, run, env):
+    """kmahip_map on input M: the pile-up takes a read that is longer than its cut template a turn at a time"""
+    s = inputs("M")
+    extra = M_RUNS[run]
+    _, got = _same(s, "m" + run + "".join(env.values()), extra, env)
+    want = cu.ref(s, extra)
+    assert cu.gz(got, ".mat.gz") == cu.gz(want, ".mat.gz")
+    if "-vcf" in extra:
+        assert cu.gz(got, ".vcf.gz") == cu.gz(want, ".vcf.gz")
+    if "-ef" in extra and "-Mt1" in extra:
+        # (runKMA_Mt1 writes no extended-features file, mt1.c:313, 378: the option is taken and leaves none, on either side)
+        assert not os.path.exists(got + ".mapstat") and not os.path.exists(want + ".mapstat")
+    elif "-ef" in extra:
+        assert cu.mapstat(got) == cu.mapstat(want)
+
+
+def test_m_library_and_ring_walk(inputs):
+    """the traces of align_trace_mt1(circular=True) on input M, piled up by the plain ring walk (oracle.Assembly) in stream order: the
+    reference's own count matrix of its `-Mt1 1 -ca` run, whole turns and all; and the device's assemble + assemble_matrix on the same
+    traces: the same text"""
+    import oracle
+    from kma_amd import synth
+    s = inputs("M")
+    want = cu.matrix_blocks(cu.gz(cu.ref(s, M_RUNS["mt1"]), ".mat.gz"))[s["names"][0].encode()]
+    batch = formats.pack_ragged(s["reads"])
+    tlen = formats.read_lengths(s["prefix"])
+    db = binding.KmaHipDB(s["prefix"])
+    try:
+        (stats, off, nops, ops), rc = db.align_trace_mt1(batch, 1, circular=True)
+        kept = stats[:, 3] != 0
+        tmpl = kept.astype(np.int32)
+        # stream order (`-Mt1`) through the ranks: the last read first in its chunk
+        rank = np.arange(batch.n, dtype=np.int64)[::-1].copy()
+        asm = db.assemble(batch, rc, tmpl, (stats, off, nops, ops), consensus=True, frag_rank=rank)
+        mask = np.zeros(int(db.info.DB_size), np.uint8)
+        mask[1] = 1
+        text = db.assemble_matrix(mask)[0]
+    finally:
+        db.close()
+    assert int(kept.sum()) == 60
+    spans = stats[kept, 3] - stats[kept, 7]
+    assert int((spans > tlen[1]).sum()) >= 20          # (reads of more than one turn, as traced)
+    odb = oracle.OracleDB(s["prefix"])
+    oa = oracle.Assembly(odb, 1, int(tlen[1]))
+    for i in np.nonzero(kept)[0]:
+        rd = synth.revcomp_codes(s["reads"][i]) if rc[i] & 1 else s["reads"][i]
+        cols = "".join("=XID"[int(x) & 3] * (int(x) >> 2) for x in ops[off[i]:off[i] + nops[i]]).encode()
+        oa.add(dict(cols=cols, start=int(stats[i, 1]), score=int(stats[i, 0]), clip_start=int(stats[i, 4])), rd)
+    ring = oa.matrix_text(s["seqs"][0])
+    assert ring == want
+    assert text == want
+    call = oa.call()
+    assert (call["cover"], call["aln_len"], call["depth"], call["asm_len"]) == (asm["cover"][1], asm["aln_len"][1], asm["depth"][1], asm["asm_len"][1])
+    assert call["consensus"] == asm["consensus"][1]
+
+
 # ---- 6: the side outputs ------------------------------------------------------------------------------------------------------------------
 def test_a_ef_matrix_vcf(inputs):
     s = inputs("A")

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 from kma_amd import binding, formats, synth
+from matvcf_sets import v_reads, v_templates
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -99,33 +100,6 @@ def _make_p(tmp):
             b = b"@p%d/2\n" % k + LUT[y].tobytes() + b"\n+\n" + b"I" * len(y) + b"\n"
             f1.write(a); f2.write(b); fi.write(a + b)
     return dict(tmp=tmp, prefix=prefix, fq=["-ipe", paths[0], paths[1]], fq_int=["-int", paths[2]], plain={})
-
-
-def v_templates():
-    rng = np.random.default_rng(99)
-    return ["hand%d" % i for i in range(3)], [rng.integers(0, 4, 300, dtype=np.uint8) for _ in range(3)]
-
-
-def v_reads(seqs):
-    s = seqs[1]
-    reads = []
-    for i in range(20):
-        r = []
-        for pos in range(20, 172):
-            if pos == 110:
-                continue
-            b = int(s[pos])
-            if pos == 50:
-                b = (b + 1) & 3
-            if pos == 140 and i < 8:
-                b = (b + 2) & 3
-            r.append(b)
-            if pos == 80 and i < 14:
-                r += [(int(s[81]) + 1) & 3, (int(s[81]) + 2) & 3]
-            if pos == 125 and 14 <= i <= 16:
-                r.append((int(s[126]) + 1) & 3)
-        reads.append(np.array(r[:150], np.uint8))
-    return reads
 
 
 def _make_v(tmp):
