@@ -1,8 +1,9 @@
-/* kmahip_index.c -- `kma index -i templates.fsa [more.fsa ...] (or -batch list.txt) -o prefix [-k k]` on an MI355X: plain C99 over kmahip_index_build
- * (the k-mers are sorted and made unique on the device). Writes prefix.comp.b / .length.b / .seq.b / .name, which the reference
- * and libkmahip load alike.
+/* kmahip_index.c -- `kma index -i templates.fsa [more.fsa ...] (or -batch list.txt) -o prefix [-k k] [-deCon host.fsa ...]` on an MI355X:
+ * plain C99 over kmahip_index_build / kmahip_index_build_decon (the k-mers are sorted and made unique on the device). Writes
+ * prefix.comp.b / .length.b / .seq.b / .name, which the reference and libkmahip load alike, and with -deCon prefix.decon.comp.b
+ * beside them (what `kma ... -deCon` and `kmahip_map ... -deCon` map against).
  *
- *     kmahip_index -i genes.fsa -o genes [-k 16]
+ *     kmahip_index -i genes.fsa -o genes [-k 16] [-deCon host.fsa phix.fsa]
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -11,8 +12,8 @@
 #include "kmahip.h"
 
 int main(int argc, char **argv) {
-	const char *inputs[256], *out = NULL;
-	int n_in = 0, k = 16;
+	const char *inputs[256], *decon[256], *out = NULL;
+	int n_in = 0, n_decon = 0, decon_opt = 0, k = 16;
 	for(int a = 1; a < argc; ++a) {
 		if(!strcmp(argv[a], "-i")) { while(a + 1 < argc && argv[a + 1][0] != '-' && n_in < 256) inputs[n_in++] = argv[++a]; }
 		else if(!strcmp(argv[a], "-batch") && a + 1 < argc) {          /* index.c:351-401: a file that lists the inputs, one path a line */
@@ -26,11 +27,21 @@ int main(int argc, char **argv) {
 			}
 			fclose(f);
 		}
+		else if(!strcmp(argv[a], "-deCon")) {          /* index.c:200-220: every argument up to the next option; `--` is standard input there */
+			decon_opt = 1;
+			while(a + 1 < argc && (argv[a + 1][0] != '-' || !strcmp(argv[a + 1], "--")) && n_decon < 256) {
+				if(!strcmp(argv[a + 1], "--")) { fprintf(stderr, "kmahip_index: -deCon -- (contamination from standard input) is not built: give a file\n"); return 2; }
+				decon[n_decon++] = argv[++a];
+			}
+			if(n_decon == 0) { fprintf(stderr, "No deCon file specified.\n"); return 1; }
+		}
 		else if(!strcmp(argv[a], "-o") && a + 1 < argc) out = argv[++a];
 		else if(!strcmp(argv[a], "-k") && a + 1 < argc) k = atoi(argv[++a]);
-		else { fprintf(stderr, "usage: kmahip_index (-i <fasta> [<fasta> ...] | -batch <file of paths>) -o <index prefix> [-k <k-mer length, 4 ... 16>]\n"); return 2; }
+		else { fprintf(stderr, "usage: kmahip_index (-i <fasta> [<fasta> ...] | -batch <file of paths>) -o <index prefix> [-k <k-mer length, 4 ... 16>] [-deCon <fasta> [<fasta> ...]]\n"); return 2; }
 	}
 	if(!n_in || !out) { fprintf(stderr, "kmahip_index: -i and -o are required\n"); return 2; }
-	if(kmahip_init(0) || kmahip_index_build(inputs, n_in, out, k)) { fprintf(stderr, "kmahip_index: %s\n", kmahip_last_error()); return 1; }
+	if(kmahip_init(0) || (decon_opt ? kmahip_index_build_decon(inputs, n_in, decon, n_decon, out, k) : kmahip_index_build(inputs, n_in, out, k))) {
+		fprintf(stderr, "kmahip_index: %s\n", kmahip_last_error()); return 1;
+	}
 	return 0;
 }

@@ -215,7 +215,7 @@ static void *xcalloc(size_t n, size_t sz) { void *p = calloc(n ? n : 1, sz); if(
 static void usage(void) {
 	fprintf(stderr, "usage: kmahip_map (-i reads.fq[.gz] | -ipe r1.fq[.gz] r2.fq[.gz] [-apm p|u] | -int interleaved.fq[.gz] [-apm p|u]) -t_db <index prefix> -o <output prefix> [-1t1] [-Mt1 <template>] [-bcNano] [-bc90] [-bc <support>] [-bcg] [-ref_fsa [n]] [-dense]\n"
 	                "       [-t threads] [-nc] [-na] [-nf] [-mf fragments] [-ml len] [-xl len] [-mp phred] [-mi phred] [-eq q] [-mq q] [-ts bases] [-mrs f] [-mrc f] [-mct f]\n"
-	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev] [-sam n] [-ef [n]] [-matrix] [-vcf [n]] [-proxi f] [-ill] [-ca] [-mint2] [-mint3] [-ConClave n]\n"
+	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev] [-sam n] [-ef [n]] [-matrix] [-vcf [n]] [-proxi f] [-ill] [-ca] [-mint2] [-mint3] [-ConClave n] [-deCon]\n"
 	                "       [-reward n] [-gapopen n] [-gapextend n] [-localopen n] [-Npenalty n] [-per n] [-transition n] [-transversion n] [-penalty n] [-cge]\n"
 	                "       (-s1dev, like -gpus not an option of kma: stage 1 of plain FASTQ input on the device; one rank, -1t1 only; its batches close at a quarter\n"
 	                "        of a gigabase of their own accord, KMAHIP_MAP_BATCH_BASES does not apply to them)\n"
@@ -227,6 +227,8 @@ static void usage(void) {
 	                "       (-ConClave n: 1, the default, gives every read to the best template of its list (runConClave); 2 drops the templates that are not\n"
 	                "        significant, credits the reads unique among the rest and draws a template for every other read in proportion to those unique scores\n"
 	                "        (runConClave2); in every run of one rank, not with -gpus N; -Mt1 runs no ConClave and ignores it)\n"
+	                "       (-deCon: decontamination, against <index prefix>.decon.comp.b (kmahip_index -deCon / kma index -deCon): a read that fits the contamination\n"
+	                "        better than any template has no record; in the -1t1 runs of one rank, not in the default mode, with -mem_mode, -Mt1 or -gpus N)\n"
 	                "(the options of kma 1.5.1 this path implements; -apm takes p or u; everything else is refused)\n");
 }
 
@@ -312,6 +314,7 @@ int main(int argc, char **argv) {
 	int ef = 0;                                  /* -ef [n] (kma.c:938-948): the extended-features file <out>.mapstat */
 	int matrix = 0, vcf = 0;                     /* -matrix (kma.c:667): <out>.mat.gz; -vcf [n] (kma.c:949-961): <out>.vcf.gz, n = 2 fills its FILTER column */
 	int proxi_opt = 0;                           /* -proxi / -ill given (for the refusals' wording; what counts is par.minFrac) */
+	int decon = 0;                               /* -deCon: map against <t_db>.decon.comp.b and drop what fits the contamination best */
 	int base_call = 0, sig_mode = 0, ref_fsa = 0, dense = 0;      /* as kmahip_assemble_opts.caller (0-2 here) / .sig90; printconsensus.c's ref_fsa */
 	double support = 0;                          /* -bc x: the variable the reference hands updateVcf (kma.c:747, vcf.c:195) ... */
 	double call_support = 0;                     /* ... and the threshold of significantAndSupport, a static that keeps the FIRST non-zero value it is given (assembly.c:153-157): -bc x, -ill and the presets -mint2 / -mint3 all give it one, and the two presets leave `support` alone (kma.c:1092, 1112) */
@@ -450,6 +453,7 @@ int main(int argc, char **argv) {
 			bcd = 10;                         /* -bcd 10 */
 			proxi_opt = 1;                    /* (its -cge and -apm p lines are commented out there) */
 		}
+		else if(!strcmp(o, "-deCon")) decon = 1;                                                /* kma.c:511-513: deConPrint / deConPrintPair, <t_db>.decon.comp.b */
 		else if(!strcmp(o, "-ca")) par.ca = 1;                                                  /* kma.c:722-723: chainSeedsPtr = &chainSeeds_circular */
 		else if(!strcmp(o, "-mint2")) {                                                         /* kma.c:1069-1094: a preset, applied where it stands */
 			one2one = 1; mem_mode = 1; par.ca = 1;                                              /* -1t1 -mem_mode -ca */
@@ -552,6 +556,19 @@ int main(int argc, char **argv) {
 		else if(s1dev) why = "-s1dev";
 		else if(sam) why = "-sam n";
 		if(why) { fprintf(stderr, "kmahip_map: %s is not built for %s: proximity matching serves the single-end -1t1 run of one rank\n", proxi_opt ? "-proxi / -ill" : "minFrac", why); return 2; }
+	}
+	if(decon) {
+		/* decontamination is built where its filter sits: stage 2 of the -1t1 runs of one rank. Everything else is refused, so that
+		 * nothing runs without the filter. In the default mode and under -mem_mode the reference itself reads template_lengths[DB_size],
+		 * one element past that array (savekmers.c:5573, kmeranker.c:68, :204): what it prints there depends on unrelated memory */
+		const char *why = NULL;
+		if(mt1) why = "-Mt1 (it scans no k-mers)";
+		else if(chain || pe_chain) why = "the default mode without -1t1 (the reference's chain finder reads template_lengths[DB_size], past the array's end)";
+		else if(mem_mode) why = "-mem_mode (the reference reads template_lengths[DB_size] there, past the array's end)";
+		else if(gpus > 1 || getenv("KMAHIP_RANK") || getenv("RANK")) why = "-gpus N (several ranks)";
+		else if(getenv("KMAHIP_COMM_FORCE_RCCL") && getenv("KMAHIP_COMM_FORCE_RCCL")[0] == '1') why = "KMAHIP_COMM_FORCE_RCCL";
+		else if(getenv("KMAHIP_MAP_ONE_BATCH")) why = "KMAHIP_MAP_ONE_BATCH";
+		if(why) { fprintf(stderr, "kmahip_map: -deCon is not built for %s: decontamination serves the -1t1 runs of one rank (single end, -ipe, -int)\n", why); return 2; }
 	}
 	if(s1dev && (gpus > 1 || getenv("KMAHIP_RANK") || getenv("RANK") || chain || pe_chain || mt1 || getenv("KMAHIP_MAP_ONE_BATCH") ||
 	             (getenv("KMAHIP_COMM_FORCE_RCCL") && getenv("KMAHIP_COMM_FORCE_RCCL")[0] == '1'))) {
@@ -656,7 +673,7 @@ int main(int argc, char **argv) {
 		pthread_t reader;
 		if(pthread_create(&reader, NULL, stream_main, &sj)) fail("cannot start a thread");
 		kmahip_db *db; kmahip_ws *ws;
-		if(kmahip_init(local) || kmahip_db_open(prefix, &db) || kmahip_ws_create(db, &ws)) die("open");
+		if(kmahip_init(local) || (decon ? kmahip_db_open_decon(prefix, &db) : kmahip_db_open(prefix, &db)) || kmahip_ws_create(db, &ws)) die("open");
 		if(pe_chain && kmahip_ws_set_pe_chain(ws, &cp)) die("open");
 		const double t_open = now_s();
 		kmahip_shard_opts so;

@@ -185,6 +185,14 @@ const char *kmahip_last_error(void);
 int kmahip_init(int device);
 
 int kmahip_db_open(const char *prefix, kmahip_db **out);
+/* Decontamination (`kma ... -deCon`, kmers.c:76-80): the same database read from <prefix>.decon.comp.b (KMAHIP_EIO, naming the file,
+ * when it is missing). Its value lists hold the pseudo-template DB_size where a k-mer is also the contamination's. Stage 2 scores it
+ * like any template and then takes it out of every final list (deConPrint / deConPrintPair, ankers.c:74-148): a read whose list
+ * empties has no record, and no list that leaves kmahip_scan_se[_dev] / kmahip_scan_pe[_dev] holds +-DB_size. Served by the one-rank
+ * -1t1 entry points (single end, also with proximity matching; paired at apm p / u / f); the default mode's chain finder, -mem_mode,
+ * the -Mt1 run and the sharded entry points refuse such a database with KMAHIP_EINVAL, by name. */
+int kmahip_db_open_decon(const char *prefix, kmahip_db **out);
+int kmahip_db_is_decon(const kmahip_db *db);          /* 1: opened by kmahip_db_open_decon, 0: not (or NULL) */
 void kmahip_db_close(kmahip_db *db);
 int kmahip_db_get_info(const kmahip_db *db, kmahip_db_info *info);
 
@@ -608,9 +616,16 @@ int kmahip_chain_unpinned_reads(const int32_t *len, const int32_t *N, const int6
  * made unique there (rocPRIM); grouping, list sharing and the bucket directory are one pass on the host. The files hold the
  * same k-mer -> template-list mapping as the reference's (tests compare the two) and the reference maps against them with
  * identical results; bucket count, key order inside a bucket and list order are the builder's own. FASTA input, plain or .gz.
- * Not covered: -Sparse / prefixes, minimizers (-m), homopolymer compression (-hc), -deCon, appending (-t_db); `-batch list` is the
+ * Not covered: -Sparse / prefixes, minimizers (-m), homopolymer compression (-hc), appending (-t_db); `-batch list` is the
  * host program's (examples/kmahip_index: the listed paths become fasta_paths). */
 int kmahip_index_build(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize);
+/* `kma index ... -deCon <fasta ...>` (index.c:676-729, decon.c:77-227): the four files of kmahip_index_build, byte for byte, and
+ * <prefix>.decon.comp.b beside them, the same mapping with the pseudo-template DB_size (one past the last template) appended to the
+ * list of every database k-mer that occurs in a contamination record or in its reverse complement. A record counts when it is
+ * longer than k; N's split it as they split a template. A k-mer that only the contamination holds is not added. decon_paths: FASTA,
+ * plain or .gz; "--" (standard input) is refused with KMAHIP_EINVAL. Appending to an existing index is not covered. */
+int kmahip_index_build_decon(const char *const *fasta_paths, int n_files, const char *const *decon_paths, int n_decon,
+                             const char *out_prefix, int kmersize);
 
 /* ---- stage 1: FASTQ / FASTA ingest into packed read batches -------------------------------------------
  * Host code (zlib for .gz, plain files read as they are): the record parser of FileBuffgetFq / FileBuffgetFsa
@@ -1008,6 +1023,10 @@ int kmahip_scan_get_stats(kmahip_ws *ws, kmahip_scan_stats *st, void *stream);
  * records (reads without N's of at most 192 bases, outside the exhaustive mode), out[1] as bare list entries (everything else,
  * and every item with KMAHIP_SCAN_REC=0 in the environment). Read it before another stage is launched on the workspace. */
 int kmahip_ws_scan_routes(kmahip_ws *ws, void *stream, unsigned long long out[2]);
+/* Strand items of the last scan launch whose candidates did not fit the first tier's table (out[0]: handed to the second tier, 64
+ * slots) and not the second tier's either (out[1]: handed to scan_dense_kernel, a wavefront per item on tables as wide as the
+ * database). Read it before another stage is launched on the workspace. */
+int kmahip_ws_scan_overflow(kmahip_ws *ws, void *stream, unsigned long long out[2]);
 /* Records of the last scan launch whose template diagonal the prefilter replaced: it counts the bases of the read that differ
  * from the template store along the diagonal of its first hit and, at two or more, looks up the read's k-mer that ends at the first
  * of them and files that hit's diagonal when fewer bases differ along it (KMAHIP_SCAN_REFINE=0 in the environment: never). Counted

@@ -187,6 +187,9 @@ def lib():
         L.kmahip_default_params.restype = None
         L.kmahip_init.argtypes = [C.c_int]
         L.kmahip_db_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+        if hasattr(L, "kmahip_db_open_decon"):          # (KMAHIP_LIB may name an older library, for side-by-side timing)
+            L.kmahip_db_open_decon.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+            L.kmahip_db_is_decon.argtypes = [C.c_void_p]
         L.kmahip_db_close.argtypes = [C.c_void_p]
         L.kmahip_db_close.restype = None
         L.kmahip_db_get_info.argtypes = [C.c_void_p, C.POINTER(DBInfo)]
@@ -368,11 +371,19 @@ def test_mapq(best, second, w):
     return out
 
 
-def index_build(fasta_paths, out_prefix, k=16):
-    """kmahip_index_build: the four index files from FASTA file(s) (needs a GPU: the k-mers are sorted on the device)"""
+def index_build(fasta_paths, out_prefix, k=16, decon=None):
+    """kmahip_index_build: the four index files from FASTA file(s) (needs a GPU: the k-mers are sorted on the device).
+    decon: contamination FASTA file(s) (`kma index -deCon`) -> kmahip_index_build_decon, which writes <out_prefix>.decon.comp.b too"""
     paths = [os.fsencode(p) for p in ([fasta_paths] if isinstance(fasta_paths, (str, bytes)) else fasta_paths)]
     arr = (C.c_char_p * len(paths))(*paths)
     L = lib()
+    if decon is not None:
+        dpaths = [os.fsencode(p) for p in ([decon] if isinstance(decon, (str, bytes)) else decon)]
+        darr = (C.c_char_p * max(1, len(dpaths)))(*dpaths)
+        L.kmahip_index_build_decon.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_int]
+        L.kmahip_index_build_decon.restype = C.c_int
+        _check(L.kmahip_index_build_decon(arr, len(paths), darr, len(dpaths), os.fsencode(out_prefix), int(k)))
+        return
     L.kmahip_index_build.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_int]
     L.kmahip_index_build.restype = C.c_int
     _check(L.kmahip_index_build(arr, len(paths), os.fsencode(out_prefix), int(k)))
@@ -595,12 +606,17 @@ def default_params() -> Params:
 class KmaHipDB:
     """An index resident in HBM + one workspace."""
 
-    def __init__(self, prefix: str, device: int = 0):
+    def __init__(self, prefix: str, device: int = 0, decon: bool = False):
+        """decon: open <prefix>.decon.comp.b (kmahip_db_open_decon): stage 2 then drops what fits the contamination best"""
         L = lib()
         _check(L.kmahip_init(device))
         self.prefix = prefix
+        self.decon = bool(decon)
         self.h = C.c_void_p()
-        _check(L.kmahip_db_open(prefix.encode(), C.byref(self.h)))
+        if decon:
+            _check(L.kmahip_db_open_decon(prefix.encode(), C.byref(self.h)))
+        else:
+            _check(L.kmahip_db_open(prefix.encode(), C.byref(self.h)))
         self.ws = C.c_void_p()
         _check(L.kmahip_ws_create(self.h, C.byref(self.ws)))
         self.info = DBInfo()
@@ -706,6 +722,14 @@ class KmaHipDB:
         st = ScanStats()
         _check(lib().kmahip_scan_get_stats(self.ws, C.byref(st), C.c_void_p(stream or 0)))
         return st
+
+    def get_scan_overflow(self, stream=None):
+        """(items handed to the second tier, items handed to scan_dense_kernel) of the last scan launch"""
+        out = (C.c_ulonglong * 2)()
+        L = lib()
+        L.kmahip_ws_scan_overflow.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]
+        _check(L.kmahip_ws_scan_overflow(self.ws, C.c_void_p(stream or 0), out))
+        return int(out[0]), int(out[1])
 
     def get_scan_routes(self, stream=None):
         """(items taken as records, items taken from the bare list) of the last scan launch"""

@@ -17,6 +17,7 @@ extern "C" int kmahip_ws_create(kmahip_db *db, kmahip_ws **out) {
 
 extern "C" int kmahip_ws_set_pe_chain(kmahip_ws *ws, const kmahip_chain_params *cp) {
 	if(!ws) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(cp) if(int rcd = kmahip_refuse_decon(ws->db, KMAHIP_DECON_CHAIN)) return rcd;
 	ws->pe_chain_on = cp != nullptr;
 	if(cp) ws->pe_chain = *cp;
 	return KMAHIP_OK;
@@ -112,6 +113,16 @@ extern "C" int kmahip_ws_scan_routes(kmahip_ws *ws, void *stream, unsigned long 
 	const unsigned long long cap = ws->rec_cap > 0 ? (unsigned long long) ws->rec_cap : 0ull;
 	out[0] = c[KMAHIP_C_NREC] < cap ? c[KMAHIP_C_NREC] : cap;
 	out[1] = c[KMAHIP_C_NACT];
+	return KMAHIP_OK;
+}
+
+// strand items the first tier of the last scan launch handed to the second (counters[2]) and the second to scan_dense_kernel (counters[10])
+extern "C" int kmahip_ws_scan_overflow(kmahip_ws *ws, void *stream, unsigned long long out[2]) {
+	if(!ws || !out || !ws->counters) return KMAHIP_EINVAL;
+	unsigned long long c[KMAHIP_N_COUNTERS];
+	HIP_TRY(hipMemcpyAsync(c, ws->counters, sizeof c, hipMemcpyDeviceToHost, (hipStream_t) stream));
+	HIP_TRY(hipStreamSynchronize((hipStream_t) stream));
+	out[0] = c[2]; out[1] = c[10];
 	return KMAHIP_OK;
 }
 

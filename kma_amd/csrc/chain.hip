@@ -1281,6 +1281,7 @@ int kmahip_chain_device(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *d, con
 	const int64_t n = d->n_reads;
 	*n_recs = 0; *n_T = 0;
 	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_CHAIN)) return rcp;
+	if(int rcd = kmahip_refuse_decon(db, KMAHIP_DECON_CHAIN)) return rcd;
 	if(n <= 0) return KMAHIP_OK;
 	if(!db->dev.tlen) { kmahip_set_error("index has no .length.b: the default template finder needs the template lengths"); return KMAHIP_EINVAL; }
 	const int max_len = d->max_len;
@@ -1565,6 +1566,7 @@ extern "C" int kmahip_scan_chain(kmahip_db *db, kmahip_ws *ws, const kmahip_read
 	const int64_t n = reads->n_reads;
 	out->n_recs = 0; out->n_T = 0;
 	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_CHAIN)) return rcp;
+	if(int rcd = kmahip_refuse_decon(db, KMAHIP_DECON_CHAIN)) return rcd;
 	if(n <= 0) return KMAHIP_OK;
 	if(reads->max_len <= 0) { kmahip_set_error("kmahip_reads.max_len must be set"); return KMAHIP_EINVAL; }
 	const bool dbg = getenv("KMAHIP_DEBUG_TIMING") != nullptr;

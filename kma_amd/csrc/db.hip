@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256) void tpos_insert_kernel(const unsigned long lo
 
 }  // namespace
 
-extern "C" int kmahip_db_open(const char *prefix, kmahip_db **out) {
+static int db_open(const char *prefix, bool decon, kmahip_db **out) {
 	if(!prefix || !out) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	*out = nullptr;
 	std::string base(prefix);
@@ -218,11 +218,13 @@ extern "C" int kmahip_db_open(const char *prefix, kmahip_db **out) {
 		fprintf(stderr, "[kmahip] db_open: %s %.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
 		t_last = now;
 	};
-	FILE *f = fopen((base + ".comp.b").c_str(), "rb");
-	if(!f) { kmahip_set_error("cannot open %s.comp.b", prefix); return KMAHIP_EIO; }
+	// decontamination (kmers.c:76-80): the table with the pseudo-template DB_size in its lists; everything else is the same index
+	const std::string comp = base + (decon ? ".decon.comp.b" : ".comp.b");
+	FILE *f = fopen(comp.c_str(), "rb");
+	if(!f) { kmahip_set_error("cannot open %s", comp.c_str()); return KMAHIP_EIO; }
 	uint32_t h32[3];
 	uint64_t h64[5];
-	if(!read_exact(f, h32, 12) || !read_exact(f, h64, 40)) { fclose(f); kmahip_set_error("short header in %s.comp.b", prefix); return KMAHIP_EIO; }
+	if(!read_exact(f, h32, 12) || !read_exact(f, h64, 40)) { fclose(f); kmahip_set_error("short header in %s", comp.c_str()); return KMAHIP_EIO; }
 	const uint32_t DB_size = h32[0], mlen = h32[1];
 	const uint64_t size = h64[1], n_hdr = h64[2], v_index = h64[3];
 	// `kma index -Sparse`: only the k-mers behind a prefix are stored and the reference maps with save_kmers_sparse, without
@@ -263,7 +265,7 @@ extern "C" int kmahip_db_open(const char *prefix, kmahip_db **out) {
 	}
 	if(ok && read_exact(f, &tail[0], 4)) ok = read_exact(f, &tail[1], 4);
 	fclose(f);
-	if(!ok) { kmahip_set_error("truncated %s.comp.b", prefix); return KMAHIP_EIO; }
+	if(!ok) { kmahip_set_error("truncated %s", comp.c_str()); return KMAHIP_EIO; }
 	stamp("read .comp.b");
 	if(tail[1] != 0) { kmahip_set_error("minimizer / homopolymer-compressed index (flag %u) not supported", tail[1]); return KMAHIP_EFORMAT; }
 	if(tail[0] != mlen) { kmahip_set_error("kmersize %u != mlen %u not supported", tail[0], mlen); return KMAHIP_EFORMAT; }
@@ -296,6 +298,7 @@ extern "C" int kmahip_db_open(const char *prefix, kmahip_db **out) {
 	DevDB &d = db->dev;
 	memset(&d, 0, sizeof d);
 	d.DB_size = DB_size; d.kmersize = tail[0]; d.mlen = mlen; d.nb_log2 = nb_log2; d.values_u16 = u16;
+	d.decon = decon ? 1u : 0u; db->decon = decon;
 	// the probe table and the presence bits, filled on the device from the k-mers and their list offsets
 	uint2 *d_slots = nullptr;
 	{
@@ -470,6 +473,12 @@ extern "C" int kmahip_db_open(const char *prefix, kmahip_db **out) {
 	*out = db;
 	return KMAHIP_OK;
 }
+
+extern "C" int kmahip_db_open(const char *prefix, kmahip_db **out) { return db_open(prefix, false, out); }
+
+extern "C" int kmahip_db_open_decon(const char *prefix, kmahip_db **out) { return db_open(prefix, true, out); }
+
+extern "C" int kmahip_db_is_decon(const kmahip_db *db) { return db && db->decon ? 1 : 0; }
 
 extern "C" void kmahip_db_close(kmahip_db *db) {
 	if(!db) return;

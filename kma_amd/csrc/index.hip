@@ -6,7 +6,11 @@
 // equal template lists, cut into buckets). The files hold the same k-mer -> template-list mapping as the reference's and load into
 // it; bucket count, key order inside a bucket and the order of the shared lists are the builder's own (the reference's follow
 // from the growth history of its in-memory hash table and carry no meaning for a reader).
-// Covered: the default hashed form, k <= 16, no prefix (-Sparse), no minimizers / homopolymer compression, no -batch / -deCon.
+// Covered: the default hashed form, k <= 16, no prefix (-Sparse), no minimizers / homopolymer compression, no -batch.
+// -deCon (kmahip_index_build_decon; index.c:676-729, decon.c:77-227): every k-mer of either strand of the contamination records
+// becomes a key of the pseudo-template DB_size and joins the same sort; the host pass runs twice over the sorted pairs, once
+// without those keys (<prefix>.comp.b, as ever) and once with them (<prefix>.decon.comp.b), where a k-mer that only the
+// contamination holds is dropped: decontamination marks k-mers of the database, it adds none.
 #include "kmahip_internal.h"
 #include <zlib.h>
 #include <cstring>
@@ -53,6 +57,30 @@ __global__ __launch_bounds__(256) void index_kmers_kernel(const uint8_t *codes, 
 	keys[p] = key;
 }
 
+// one thread per base of the concatenated contamination records: the k-mer that starts there and its reverse complement, both as keys
+// of the pseudo-template `id` (deConNode on the record and on its comp_rc, decon.c:199-205); keys[2 p], keys[2 p + 1]
+__global__ __launch_bounds__(256) void index_decon_kmers_kernel(const uint8_t *codes, const int64_t *r_off, int n_r, int64_t total, int k, uint32_t id,
+                                                                  unsigned long long *keys) {
+	const int64_t p = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if(p >= total) return;
+	int lo = 0, hi = n_r;                      // record holding p: last r with r_off[r] <= p
+	while(hi - lo > 1) { const int mid = (lo + hi) >> 1; if(r_off[mid] <= p) lo = mid; else hi = mid; }
+	unsigned long long fw = ~0ull, rc = ~0ull;
+	if(p + k <= r_off[lo + 1]) {
+		unsigned long long km = 0, rk = 0;
+		bool ok = true;
+		for(int i = 0; i < k; ++i) {
+			const uint8_t c = codes[p + i];
+			ok = ok && c < 4;
+			km = (km << 2) | (c & 3);
+			rk |= (unsigned long long) (3 - (c & 3)) << (2 * i);
+		}
+		if(ok) { fw = (km << 32) | id; rc = (rk << 32) | id; }
+	}
+	keys[2 * p] = fw;
+	keys[2 * p + 1] = rc;
+}
+
 struct SameKey { __device__ bool operator()(unsigned long long a, unsigned long long b) const { return a == b; } };
 
 int read_whole(const char *path, std::vector<uint8_t> &buf) {
@@ -71,9 +99,79 @@ int read_whole(const char *path, std::vector<uint8_t> &buf) {
 	return KMAHIP_OK;
 }
 
-}  // namespace
+// host pass over the sorted (k-mer << 32 | template) pairs and the .comp.b image of what it finds: group by k-mer, share equal
+// lists (valuesHash, compress.c:218), lists laid out in the order they are first needed. with_decon = false: the pairs of the
+// pseudo-template DB_size are passed over; true: they stay, but a k-mer that holds nothing else is dropped
+int write_comp_b(const std::vector<unsigned long long> &pairs, uint32_t DB_size, int k, bool with_decon, const std::string &path) {
+	const bool u16 = DB_size < 65535;                               // hashmapkma.c:340-348
+	std::vector<uint32_t> ukm, vi_of_key;
+	std::vector<uint32_t> values;                                   // [cnt, t1 .. tcnt] per list
+	std::unordered_map<uint64_t, std::vector<uint32_t>> by_sig;     // signature -> offsets of lists with it
+	std::vector<uint32_t> list;
+	for(size_t a = 0; a < pairs.size();) {
+		size_t b = a;
+		const uint32_t km = (uint32_t) (pairs[a] >> 32);
+		list.clear();
+		uint64_t sig = 0x9E3779B97F4A7C15ull;
+		for(; b < pairs.size() && (uint32_t) (pairs[b] >> 32) == km; ++b) {
+			const uint32_t t = (uint32_t) pairs[b];
+			if(t == DB_size && (!with_decon || list.empty())) continue;      // (DB_size sorts behind every template of its k-mer)
+			list.push_back(t);
+			sig = (sig ^ t) * 0xBF58476D1CE4E5B9ull; sig ^= sig >> 29;
+		}
+		a = b;
+		if(list.empty()) continue;
+		uint32_t off = 0xFFFFFFFFu;
+		std::vector<uint32_t> &cand = by_sig[sig];
+		for(uint32_t o : cand) {
+			if(values[o] == list.size() && !memcmp(&values[o + 1], list.data(), list.size() * 4)) { off = o; break; }
+		}
+		if(off == 0xFFFFFFFFu) {
+			if(values.size() + list.size() + 1 >= 0xFFFFFFFFull) { kmahip_set_error("value lists exceed 32-bit offsets"); return KMAHIP_EFORMAT; }
+			off = (uint32_t) values.size();
+			values.push_back((uint32_t) list.size());
+			values.insert(values.end(), list.begin(), list.end());
+			cand.push_back(off);
+		}
+		ukm.push_back(km); vi_of_key.push_back(off);
+	}
+	const uint64_t n = ukm.size(), v_index = values.size();
+	if(n == 0) { kmahip_set_error("the templates hold no k-mer"); return KMAHIP_EFORMAT; }
+	// buckets: kpos = key & (size - 1) (hashMap_getGlobal, hashmapkma.c:149-178); never the direct-address form
+	uint64_t size = 1u << 20;
+	while(size < n) size <<= 1;
+	const uint64_t kspace = 1ull << (2 * k);
+	if(size >= kspace) size = kspace >> 1;
+	if(size < 2 || n > 0xFFFFFFFFull) { kmahip_set_error("index shape not supported"); return KMAHIP_EFORMAT; }
+	std::vector<uint32_t> exist(size, (uint32_t) n), fill(size + 1, 0);
+	for(uint64_t i = 0; i < n; ++i) ++fill[(ukm[i] & (size - 1)) + 1];
+	for(uint64_t b = 0; b < size; ++b) { if(fill[b + 1]) exist[b] = fill[b]; fill[b + 1] += fill[b]; }
+	std::vector<uint32_t> key_index(n + 1), value_index(n);
+	{
+		std::vector<uint32_t> at(fill.begin(), fill.end() - 1);
+		for(uint64_t i = 0; i < n; ++i) { const uint32_t s = at[ukm[i] & (size - 1)]++; key_index[s] = ukm[i]; value_index[s] = vi_of_key[i]; }
+	}
+	// the sentinel behind the last key ends the scan of the last bucket: any key of another bucket (compress.c:549-585)
+	key_index[n] = (uint32_t) (((key_index[n - 1] & (size - 1)) + 1) & (size - 1));
 
-extern "C" int kmahip_index_build(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize) {
+	FILE *f = fopen(path.c_str(), "wb");
+	if(!f) { kmahip_set_error("cannot create %s", path.c_str()); return KMAHIP_EIO; }
+	const uint32_t h32[3] = {DB_size, (uint32_t) k, 0};
+	const uint64_t h64[5] = {0, size, n, v_index, n};
+	bool ok = fwrite(h32, 4, 3, f) == 3 && fwrite(h64, 8, 5, f) == 5 && fwrite(exist.data(), 4, size, f) == size;
+	if(u16) {
+		std::vector<uint16_t> v16(values.begin(), values.end());
+		ok = ok && fwrite(v16.data(), 2, v16.size(), f) == v16.size();
+	} else ok = ok && fwrite(values.data(), 4, values.size(), f) == values.size();
+	const uint32_t tail[2] = {(uint32_t) k, 0};
+	ok = ok && fwrite(key_index.data(), 4, n + 1, f) == n + 1 && fwrite(value_index.data(), 4, n, f) == n && fwrite(tail, 4, 2, f) == 2;
+	ok = (fclose(f) == 0) && ok;
+	if(!ok) { kmahip_set_error("writing %s failed", path.c_str()); return KMAHIP_EIO; }
+	return KMAHIP_OK;
+}
+
+// the build itself: n_decon = 0 is `kma index` without -deCon
+int index_build(const char *const *fasta_paths, int n_files, const char *const *decon_paths, int n_decon, const char *out_prefix, int kmersize) {
 	if(!fasta_paths || n_files <= 0 || !out_prefix) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	const int k = kmersize > 0 ? kmersize : 16;
 	if(k < 4 || k > 16) { kmahip_set_error("k-mer length %d: 4 ... 16 supported", k); return KMAHIP_EINVAL; }
@@ -114,6 +212,28 @@ extern "C" int kmahip_index_build(const char *const *fasta_paths, int n_files, c
 	if(n_t == 0) { kmahip_set_error("no template of at least %d bases", k); return KMAHIP_EFORMAT; }
 	const uint32_t DB_size = (uint32_t) n_t + 1;
 	const int64_t total = (int64_t) codes.size();
+	// the contamination records (deConDB, decon.c:161-227): the same parser and letter table; a record counts when it is LONGER than
+	// k (:193), N's and all. Leading and trailing N's need no trimming here: no k-mer holds one
+	std::vector<uint8_t> dcodes;
+	std::vector<int64_t> d_roff(1, 0);
+	for(int fi = 0; fi < n_decon; ++fi) {
+		std::vector<uint8_t> raw;
+		const int rc = read_whole(decon_paths[fi], raw);
+		if(rc) return rc;
+		if(raw.empty() || raw[0] != '>') { kmahip_set_error("%s is not a FASTA file", decon_paths[fi]); return KMAHIP_EFORMAT; }
+		size_t p = 0;
+		while(p < raw.size()) {
+			while(p < raw.size() && raw[p] != '\n') ++p;
+			if(p < raw.size()) ++p;
+			const size_t at = dcodes.size();
+			while(p < raw.size() && raw[p] != '>') { const uint8_t c = T.t[raw[p]]; if(c < 8) dcodes.push_back(c); ++p; }
+			if((int64_t) (dcodes.size() - at) > k) d_roff.push_back((int64_t) dcodes.size());
+			else dcodes.resize(at);
+		}
+	}
+	const int64_t dtotal = (int64_t) dcodes.size();
+	const int n_dr = (int) d_roff.size() - 1;
+	const int64_t n_keys = total + 2 * dtotal;
 
 	// device: keys, sort, unique
 	std::vector<int64_t> t_off((size_t) n_t + 1);
@@ -125,21 +245,36 @@ extern "C" int kmahip_index_build(const char *const *fasta_paths, int n_files, c
 	struct Guard { decltype(release) &r; ~Guard() { r(); } } guard{release};
 	HIP_TRY(hipMalloc((void **) &d_codes, (size_t) total + 32));
 	HIP_TRY(hipMalloc((void **) &d_off, t_off.size() * 8));
-	HIP_TRY(hipMalloc((void **) &d_keys, (size_t) total * 8));
-	HIP_TRY(hipMalloc((void **) &d_sorted, (size_t) total * 8));
-	HIP_TRY(hipMalloc((void **) &d_uniq, (size_t) total * 8));
+	HIP_TRY(hipMalloc((void **) &d_keys, (size_t) n_keys * 8));
+	HIP_TRY(hipMalloc((void **) &d_sorted, (size_t) n_keys * 8));
+	HIP_TRY(hipMalloc((void **) &d_uniq, (size_t) n_keys * 8));
 	HIP_TRY(hipMalloc((void **) &d_count, sizeof(size_t)));
 	HIP_TRY(hipMemcpy(d_codes, codes.data(), (size_t) total, hipMemcpyHostToDevice));
 	HIP_TRY(hipMemcpy(d_off, t_off.data(), t_off.size() * 8, hipMemcpyHostToDevice));
 	hipLaunchKernelGGL(index_kmers_kernel, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, 0, d_codes, d_off, n_t, total, k, d_keys);
 	HIP_TRY(hipGetLastError());
+	if(dtotal > 0) {
+		// the contamination's keys behind the templates': keys[total .. total + 2 * dtotal)
+		uint8_t *d_dcodes = nullptr; int64_t *d_doff = nullptr;
+		hipError_t e = hipMalloc((void **) &d_dcodes, (size_t) dtotal + 32);
+		if(e == hipSuccess) e = hipMalloc((void **) &d_doff, d_roff.size() * 8);
+		if(e == hipSuccess) e = hipMemcpy(d_dcodes, dcodes.data(), (size_t) dtotal, hipMemcpyHostToDevice);
+		if(e == hipSuccess) e = hipMemcpy(d_doff, d_roff.data(), d_roff.size() * 8, hipMemcpyHostToDevice);
+		if(e == hipSuccess) {
+			hipLaunchKernelGGL(index_decon_kmers_kernel, dim3((unsigned) ((dtotal + 255) / 256)), dim3(256), 0, 0, d_dcodes, d_doff, n_dr, dtotal, k, DB_size, d_keys + total);
+			e = hipGetLastError();
+			if(e == hipSuccess) e = hipDeviceSynchronize();
+		}
+		(void) hipFree(d_dcodes); (void) hipFree(d_doff);
+		if(e != hipSuccess) { kmahip_set_error("decontamination keys: %s", hipGetErrorString(e)); return KMAHIP_EDEVICE; }
+	}
 	size_t tmp_bytes = 0, tmp2 = 0;
-	if(rocprim::radix_sort_keys(nullptr, tmp_bytes, d_keys, d_sorted, (size_t) total, 0, 64, 0) != hipSuccess ||
-	   rocprim::unique(nullptr, tmp2, d_sorted, d_uniq, d_count, (size_t) total, SameKey(), 0) != hipSuccess) { kmahip_set_error("rocprim size query failed"); return KMAHIP_EDEVICE; }
+	if(rocprim::radix_sort_keys(nullptr, tmp_bytes, d_keys, d_sorted, (size_t) n_keys, 0, 64, 0) != hipSuccess ||
+	   rocprim::unique(nullptr, tmp2, d_sorted, d_uniq, d_count, (size_t) n_keys, SameKey(), 0) != hipSuccess) { kmahip_set_error("rocprim size query failed"); return KMAHIP_EDEVICE; }
 	tmp_bytes = std::max(tmp_bytes, tmp2);
 	HIP_TRY(hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16));
-	if(rocprim::radix_sort_keys(d_tmp, tmp_bytes, d_keys, d_sorted, (size_t) total, 0, 64, 0) != hipSuccess ||
-	   rocprim::unique(d_tmp, tmp_bytes, d_sorted, d_uniq, d_count, (size_t) total, SameKey(), 0) != hipSuccess) { kmahip_set_error("rocprim sort / unique failed"); return KMAHIP_EDEVICE; }
+	if(rocprim::radix_sort_keys(d_tmp, tmp_bytes, d_keys, d_sorted, (size_t) n_keys, 0, 64, 0) != hipSuccess ||
+	   rocprim::unique(d_tmp, tmp_bytes, d_sorted, d_uniq, d_count, (size_t) n_keys, SameKey(), 0) != hipSuccess) { kmahip_set_error("rocprim sort / unique failed"); return KMAHIP_EDEVICE; }
 	HIP_TRY(hipDeviceSynchronize());
 	size_t n_pairs = 0;
 	HIP_TRY(hipMemcpy(&n_pairs, d_count, sizeof n_pairs, hipMemcpyDeviceToHost));
@@ -148,70 +283,13 @@ extern "C" int kmahip_index_build(const char *const *fasta_paths, int n_files, c
 	if(n_pairs && pairs.back() == ~0ull) pairs.pop_back();         // the starts that hold no k-mer sorted to the end
 	if(pairs.empty()) { kmahip_set_error("the templates hold no k-mer"); return KMAHIP_EFORMAT; }
 
-	// host: group by k-mer, share equal lists (valuesHash, compress.c:218), lists laid out in the order they are first needed
-	const bool u16 = DB_size < 65535;                               // hashmapkma.c:340-348
-	std::vector<uint32_t> ukm, vi_of_key;
-	std::vector<uint32_t> values;                                   // [cnt, t1 .. tcnt] per list
-	std::unordered_map<uint64_t, std::vector<uint32_t>> by_sig;     // signature -> offsets of lists with it
-	std::vector<uint32_t> list;
-	for(size_t a = 0; a < pairs.size();) {
-		size_t b = a;
-		const uint32_t km = (uint32_t) (pairs[a] >> 32);
-		list.clear();
-		uint64_t sig = 0x9E3779B97F4A7C15ull;
-		for(; b < pairs.size() && (uint32_t) (pairs[b] >> 32) == km; ++b) {
-			const uint32_t t = (uint32_t) pairs[b];
-			list.push_back(t);
-			sig = (sig ^ t) * 0xBF58476D1CE4E5B9ull; sig ^= sig >> 29;
-		}
-		uint32_t off = 0xFFFFFFFFu;
-		std::vector<uint32_t> &cand = by_sig[sig];
-		for(uint32_t o : cand) {
-			if(values[o] == list.size() && !memcmp(&values[o + 1], list.data(), list.size() * 4)) { off = o; break; }
-		}
-		if(off == 0xFFFFFFFFu) {
-			if(values.size() + list.size() + 1 >= 0xFFFFFFFFull) { kmahip_set_error("value lists exceed 32-bit offsets"); return KMAHIP_EFORMAT; }
-			off = (uint32_t) values.size();
-			values.push_back((uint32_t) list.size());
-			values.insert(values.end(), list.begin(), list.end());
-			cand.push_back(off);
-		}
-		ukm.push_back(km); vi_of_key.push_back(off);
-		a = b;
-	}
-	const uint64_t n = ukm.size(), v_index = values.size();
-	// buckets: kpos = key & (size - 1) (hashMap_getGlobal, hashmapkma.c:149-178); never the direct-address form
-	uint64_t size = 1u << 20;
-	while(size < n) size <<= 1;
-	const uint64_t kspace = 1ull << (2 * k);
-	if(size >= kspace) size = kspace >> 1;
-	if(size < 2 || n > 0xFFFFFFFFull) { kmahip_set_error("index shape not supported"); return KMAHIP_EFORMAT; }
-	std::vector<uint32_t> exist(size, (uint32_t) n), fill(size + 1, 0);
-	for(uint64_t i = 0; i < n; ++i) ++fill[(ukm[i] & (size - 1)) + 1];
-	for(uint64_t b = 0; b < size; ++b) { if(fill[b + 1]) exist[b] = fill[b]; fill[b + 1] += fill[b]; }
-	std::vector<uint32_t> key_index(n + 1), value_index(n);
-	{
-		std::vector<uint32_t> at(fill.begin(), fill.end() - 1);
-		for(uint64_t i = 0; i < n; ++i) { const uint32_t s = at[ukm[i] & (size - 1)]++; key_index[s] = ukm[i]; value_index[s] = vi_of_key[i]; }
-	}
-	// the sentinel behind the last key ends the scan of the last bucket: any key of another bucket (compress.c:549-585)
-	key_index[n] = (uint32_t) (((key_index[n - 1] & (size - 1)) + 1) & (size - 1));
-
 	const std::string base(out_prefix);
-	FILE *f = fopen((base + ".comp.b").c_str(), "wb");
-	if(!f) { kmahip_set_error("cannot create %s.comp.b", out_prefix); return KMAHIP_EIO; }
-	const uint32_t h32[3] = {DB_size, (uint32_t) k, 0};
-	const uint64_t h64[5] = {0, size, n, v_index, n};
-	bool ok = fwrite(h32, 4, 3, f) == 3 && fwrite(h64, 8, 5, f) == 5 && fwrite(exist.data(), 4, size, f) == size;
-	if(u16) {
-		std::vector<uint16_t> v16(values.begin(), values.end());
-		ok = ok && fwrite(v16.data(), 2, v16.size(), f) == v16.size();
-	} else ok = ok && fwrite(values.data(), 4, values.size(), f) == values.size();
-	const uint32_t tail[2] = {(uint32_t) k, 0};
-	ok = ok && fwrite(key_index.data(), 4, n + 1, f) == n + 1 && fwrite(value_index.data(), 4, n, f) == n && fwrite(tail, 4, 2, f) == 2;
-	ok = (fclose(f) == 0) && ok;
+	int rcw = write_comp_b(pairs, DB_size, k, false, base + ".comp.b");
+	if(!rcw && n_decon > 0) rcw = write_comp_b(pairs, DB_size, k, true, base + ".decon.comp.b");
+	if(rcw) return rcw;
+	bool ok = true;
 	// .length.b: DB_size, then the lengths with slot 0 = the k of the position index (makeindex.c:300-311)
-	f = fopen((base + ".length.b").c_str(), "wb");
+	FILE *f = fopen((base + ".length.b").c_str(), "wb");
 	if(!f) { kmahip_set_error("cannot create %s.length.b", out_prefix); return KMAHIP_EIO; }
 	std::vector<uint32_t> lens(DB_size);
 	lens[0] = (uint32_t) k;
@@ -235,4 +313,18 @@ extern "C" int kmahip_index_build(const char *const *fasta_paths, int n_files, c
 	ok = (fclose(f) == 0) && ok;
 	if(!ok) { kmahip_set_error("writing the index under %s failed", out_prefix); return KMAHIP_EIO; }
 	return KMAHIP_OK;
+}
+
+}  // namespace
+
+extern "C" int kmahip_index_build(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize) {
+	return index_build(fasta_paths, n_files, nullptr, 0, out_prefix, kmersize);
+}
+
+extern "C" int kmahip_index_build_decon(const char *const *fasta_paths, int n_files, const char *const *decon_paths, int n_decon,
+                                        const char *out_prefix, int kmersize) {
+	if(!decon_paths || n_decon <= 0) { kmahip_set_error("decontamination: no contamination file given"); return KMAHIP_EINVAL; }
+	for(int i = 0; i < n_decon; ++i)
+		if(!decon_paths[i] || !strcmp(decon_paths[i], "--")) { kmahip_set_error("decontamination from standard input (--) is not built: give a file"); return KMAHIP_EINVAL; }
+	return index_build(fasta_paths, n_files, decon_paths, n_decon, out_prefix, kmersize);
 }

@@ -56,6 +56,10 @@ struct DevDB {
 	// everything the seeding kernel needs to know about a template in one 32-byte record (two 16-byte gathers instead of four
 	// scattered ones): x = {tseq_off lo, hi, tpos_off lo, hi}, y = {tlen, tpos_shift, 0, 0}
 	const uint4 *tmeta;           // 2 * DB_size
+	// decontamination (kmahip_db_open_decon): 1 = the value lists may hold the pseudo-template DB_size. Nothing above has an entry
+	// for that id (tlen, cat_off, tseq_off, tpos_*, tmeta all end at DB_size - 1): stage 2 scores it by id alone and takes it out of
+	// every list it hands on, and every entry point that would look a listed template up refuses such a database
+	uint32_t decon;
 };
 
 struct kmahip_db {
@@ -70,6 +74,7 @@ struct kmahip_db {
 	std::vector<std::string> h_names;
 	std::vector<uint64_t> h_tseq;     // <prefix>.seq.b, read when the `.aln` writer first asks (pipeline.hip: load_tseq)
 	std::vector<int64_t> h_tseq_off;
+	bool decon = false;               // opened by kmahip_db_open_decon (dev.decon says the same to the kernels)
 };
 
 // per-call scratch, grown on demand
@@ -182,6 +187,18 @@ static inline int kmahip_refuse_forced_pairing(const kmahip_params *p) {
 	kmahip_set_error("forced pairing (apm %d) is built for kmahip_scan_pe only: stage 3a (alnFragsForcePE) is not", (int) p->apm);
 	return KMAHIP_EINVAL;
 }
+// Decontamination (a database opened by kmahip_db_open_decon) is built for stage 2 of the one-rank -1t1 runs, where the filter sits
+// (scan.hip: decon_filter). Every other entry point that reads value lists refuses such a database by name: it would hand the
+// pseudo-template DB_size on, or run without the filter
+static inline int kmahip_refuse_decon(const kmahip_db *db, const char *what) {
+	if(!db || !db->decon) return KMAHIP_OK;
+	kmahip_set_error("decontamination (a database opened with its .decon.comp.b) serves the one-rank -1t1 runs, not %s", what);
+	return KMAHIP_EINVAL;
+}
+#define KMAHIP_DECON_CHAIN "the default mode's chain finder (the reference's reads template_lengths[DB_size] there, past the array's end)"
+#define KMAHIP_DECON_MEM "-mem_mode (the reference's reads template_lengths[DB_size] there, past the array's end)"
+#define KMAHIP_DECON_MT1 "the -Mt1 run (it scans no k-mers)"
+#define KMAHIP_DECON_SHARD "the sharded runs"
 #define KMAHIP_PROXI_PE "paired reads (getSecondProxiPen, getF_Proxi / getR_Proxi and the minFrac branches of alnFragsUnionPE / alnFragsPenaltyPE are not built)"
 #define KMAHIP_PROXI_CHAIN "the default mode's chain finder (getProxiChainTemplates is not built)"
 #define KMAHIP_PROXI_MT1 "the -Mt1 run"

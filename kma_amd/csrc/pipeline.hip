@@ -1170,6 +1170,7 @@ extern "C" int kmahip_run_chain(kmahip_db *db, kmahip_ws *ws, const kmahip_reads
                                 const char *frag_path, kmahip_run *out) {
 	if(!db || !ws || !reads || !p || !out || !out->rows || !out->assembly.cover || !out->assembly.aln_len || !out->assembly.depth || !out->assembly.asm_len) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_CHAIN)) return rcp;
+	if(int rcd = kmahip_refuse_decon(db, KMAHIP_DECON_CHAIN)) return rcd;
 	if(frag_path && reads && reads->n_reads > 0 && (!names || !name_off)) { kmahip_set_error("the fragment file needs the read headers"); return KMAHIP_EINVAL; }
 	const int64_t n = reads->n_reads;
 	if(n < 0 || reads->seq_words < 0 || reads->N_total < 0) { kmahip_set_error("negative size"); return KMAHIP_EINVAL; }
@@ -1242,6 +1243,7 @@ extern "C" int kmahip_run_mt1(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *
 		kmahip_set_error("null argument"); return KMAHIP_EINVAL;
 	}
 	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_MT1)) return rcp;
+	if(int rcd = kmahip_refuse_decon(db, KMAHIP_DECON_MT1)) return rcd;
 	const int64_t n = reads->n_reads;
 	if(n < 0 || reads->seq_words < 0 || reads->N_total < 0) { kmahip_set_error("negative size"); return KMAHIP_EINVAL; }
 	const size_t D = db->info.DB_size;
@@ -1929,6 +1931,7 @@ extern "C" int kmahip_run_se_sharded(kmahip_db *db, kmahip_ws *ws, kmahip_comm *
                                      const kmahip_shard_opts *opts, const char *out_prefix, double ms[8]) {
 	if(!db || !ws || !batch || !p || !opts || !out_prefix || !ms) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_SHARD)) return rcp;
+	if(int rcd = kmahip_refuse_decon(db, KMAHIP_DECON_SHARD)) return rcd;
 	if(int rcc = kmahip_refuse_conclave2("the sharded single-end run (kmahip_run_se_sharded)")) return rcc;
 	const kmahip_reads &R = batch->reads;
 	const int64_t n = R.n_reads;
@@ -1980,6 +1983,7 @@ extern "C" int kmahip_run_chain_sharded(kmahip_db *db, kmahip_ws *ws, kmahip_com
                                         const kmahip_chain_params *cp, const kmahip_shard_opts *opts, const char *out_prefix, double ms[8]) {
 	if(!db || !ws || !comm || !batch || !p || !opts || !out_prefix || !ms) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_SHARD)) return rcp;
+	if(int rcd = kmahip_refuse_decon(db, KMAHIP_DECON_SHARD)) return rcd;
 	if(int rcc = kmahip_refuse_conclave2("the sharded run of the default mode (kmahip_run_chain_sharded)")) return rcc;
 	const kmahip_reads &R = batch->reads;
 	const int64_t n = R.n_reads;
@@ -2037,6 +2041,7 @@ extern "C" int kmahip_run_mt1_sharded(kmahip_db *db, kmahip_ws *ws, kmahip_comm 
                                       const kmahip_params *p, const kmahip_shard_opts *opts, const char *out_prefix, double ms[8]) {
 	if(!db || !ws || !comm || !batch || !p || !opts || !out_prefix || !ms) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_SHARD)) return rcp;
+	if(int rcd = kmahip_refuse_decon(db, KMAHIP_DECON_SHARD)) return rcd;
 	const int W = kmahip_comm_world(comm), rank = kmahip_comm_rank(comm);
 	const kmahip_reads &R = batch->reads;
 	const int64_t n = R.n_reads;
@@ -2162,6 +2167,7 @@ extern "C" int kmahip_run_pe_sharded(kmahip_db *db, kmahip_ws *ws, kmahip_comm *
                                      const kmahip_shard_opts *opts, const char *out_prefix, double ms[8]) {
 	if(!db || !ws || !batch || !p || !opts || !out_prefix || !ms) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_SHARD)) return rcp;
+	if(int rcd = kmahip_refuse_decon(db, KMAHIP_DECON_SHARD)) return rcd;
 	if(int rcc = kmahip_refuse_conclave2("the sharded paired run (kmahip_run_pe_sharded)")) return rcc;
 	if(int rcf = kmahip_refuse_forced_pairing(p)) return rcf;
 	int rc = kmahip_db_load_names(db);

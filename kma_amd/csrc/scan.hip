@@ -23,6 +23,9 @@
 //                per item
 //   combine    = per read strand pick / tie merge (:3037-3062), CSR output; for pairs
 //                pair_penalty_kernel (getFirstPen / getSecondBestPen / getF_Best)
+//   decon      = a database opened with its decon table (kmahip_db_open_decon) lists the pseudo-template DB_size: scored like
+//                any template above, taken out of every final list by decon_filter (deConPrint / deConPrintPair,
+//                ankers.c:74-148) in the combine and in the pairing kernels
 //
 // The words of a read are staged in LDS in STRAND orientation, so no k-mer or walk
 // window is reverse-complemented after staging.
@@ -1150,7 +1153,7 @@ __global__ __launch_bounds__(64) void scan_dense_kernel(const ScanArgs A) {
 	const int64_t n_over = (int64_t) A.counters[A.in_count];
 	const int64_t slot = blockIdx.x;
 	if(slot >= A.dense_slots) return;
-	const int64_t D = db.DB_size;
+	const int64_t D = (int64_t) db.DB_size + db.decon;      // (a decon table lists the pseudo-template DB_size: one entry more, as ws_reserve laid the planes out)
 	volatile int32_t *score = A.dense + slot * 3 * D;
 	volatile int32_t *ext = score + D;
 	volatile int32_t *list = ext + D;   // list[0..nlist): templates in first-seen order; ext[t] == -1 marks "absent"
@@ -1260,9 +1263,78 @@ __global__ __launch_bounds__(64) void scan_dense_kernel(const ScanArgs A) {
 	}
 }
 
+// ---- decontamination: deConPrint / deConPrintPair (ankers.c:106-148) on a FINAL list, strands merged and signs set, elements
+// 1 .. n as the reference counts them. find_contamination (:74-87) looks from the end for +D and find_contamination2 (:89-104)
+// for -D, the second only as far as the first positive element; what is found is overwritten by the last element and the list is
+// one shorter -- which changes its order. Returns the new length (0: the read has no record). D = DB_size, the pseudo-template
+// of a database opened by kmahip_db_open_decon. L: get(i), set(i, v).
+template <class L>
+__device__ __forceinline__ int decon_filter(L &l, int n, int D) {
+	for(int i = n; i >= 1; --i) {
+		if(l.get(i) == D) { l.set(i, l.get(n)); --n; break; }
+	}
+	for(int i = n; i >= 1; --i) {
+		const int v = l.get(i);
+		if(v == -D) { l.set(i, l.get(n)); --n; break; }
+		else if(0 < v) break;
+	}
+	return n;
+}
+
+// a list in memory
+struct DeconArr {
+	int32_t *p;
+	__device__ __forceinline__ int get(int i) const { return p[i - 1]; }
+	__device__ __forceinline__ void set(int i, int v) { p[i - 1] = v; }
+};
+
+// the list the single-end combine is about to write, not yet in memory: item list a, then item list b with the sign sb, under the
+// (at most two) elements the filter has overwritten
+struct DeconMerged {
+	const int32_t *a, *b;
+	int na, sb;
+	int op0 = 0, ov0 = 0, op1 = 0, ov1 = 0;
+	__device__ __forceinline__ int get(int i) const {
+		if(i == op1) return ov1;
+		if(i == op0) return ov0;
+		return i <= na ? a[i - 1] : sb * b[i - 1 - na];
+	}
+	__device__ __forceinline__ void set(int i, int v) {
+		if(op0 == 0 || op0 == i) { op0 = i; ov0 = v; }
+		else { op1 = i; ov1 = v; }
+	}
+};
+
+// the merged list of read r as combine_count_kernel decided it (rf = rc_flag, fl = flag; savekmers.c:3043-3059)
+__device__ __forceinline__ DeconMerged decon_merged(const ScanArgs &A, int64_t r, int rf, int fl) {
+	DeconMerged l;
+	if(rf > 0) { const int64_t it = 2 * r + (fl ? 1 : 0); l.a = A.pool + A.item_off[it]; l.na = A.item_n[it]; l.b = nullptr; l.sb = 1; }
+	else { l.a = A.pool + A.item_off[2 * r]; l.na = A.item_n[2 * r]; l.b = A.pool + A.item_off[2 * r + 1]; l.sb = -1; }
+	return l;
+}
+
+// the records of a pair as one of the pairing kernels has set them (m: mate or -1, fl: flag, nn / of: list in the pair pool): a couple
+// (flag bit 2: the first record's list is empty, the second carries the couple's) goes through deConPrintPair and is filed or dropped
+// as one; every other record through deConPrint, each for itself (savekmers.c:3509-3510, :3697-3704)
+__device__ __forceinline__ void decon_pair_records(int32_t *ppool, int D, int m[2], const int fl[2], int nn[2], const int64_t of[2]) {
+	if(m[0] >= 0 && m[1] >= 0 && (fl[0] & 2)) {
+		DeconArr l{ppool + of[1]};
+		nn[1] = decon_filter(l, nn[1], D);
+		if(nn[1] == 0) m[0] = m[1] = -1;
+		return;
+	}
+	for(int x = 0; x < 2; ++x) {
+		if(m[x] < 0) continue;
+		DeconArr l{ppool + of[x]};
+		nn[x] = decon_filter(l, nn[x], D);
+		if(nn[x] == 0) m[x] = -1;
+	}
+}
+
 // ---- combine: strand decision + CSR ---------------------------------------
 constexpr int CB = 256;
 
+template <bool DECON>
 __global__ __launch_bounds__(CB) void combine_count_kernel(const ScanArgs A, int32_t *rc_flag, int32_t *flag, int64_t *T_off, int64_t *blk_sums) {
 	__shared__ int64_t red[CB];
 	const int64_t r = (int64_t) blockIdx.x * CB + threadIdx.x;
@@ -1276,6 +1348,12 @@ __global__ __launch_bounds__(CB) void combine_count_kernel(const ScanArgs A, int
 			if(bs > br) { nT = A.item_n[2 * r]; rf = bs; }
 			else if(bs < br) { nT = A.item_n[2 * r + 1]; rf = br; fl = 16; }
 			else { nT = A.item_n[2 * r] + A.item_n[2 * r + 1]; rf = -bs; }
+		}
+		if(DECON && nT > 0) {
+			// deConPrint on the merged list: its new length is what the offsets are built from; the write kernel repeats the filter
+			DeconMerged l = decon_merged(A, r, rf, fl);
+			nT = decon_filter(l, (int) nT, (int) A.db.DB_size);
+			if(nT == 0) { rf = 0; fl = 0; }          // nothing left: no record, as for a read without a hit
 		}
 		rc_flag[r] = rf;
 		flag[r] = fl;
@@ -1315,6 +1393,7 @@ __global__ __launch_bounds__(1024) void scan_blocks_kernel(int64_t *blk_sums, in
 	}
 }
 
+template <bool DECON>
 __global__ __launch_bounds__(CB) void combine_write_kernel(const ScanArgs A, const int32_t *rc_flag, const int32_t *flag,
                                                             int64_t *T_off, const int64_t *blk_sums, int32_t *T, int64_t T_cap) {
 	__shared__ int64_t sc[CB];
@@ -1338,6 +1417,13 @@ __global__ __launch_bounds__(CB) void combine_write_kernel(const ScanArgs A, con
 	if(end > T_cap) { atomicMax(&A.counters[C_STATUS], 2ull); return; }
 	const int rf = rc_flag[r], fl = flag[r];
 	int64_t w = beg;
+	if(DECON) {
+		// the same filter on the same list as in combine_count_kernel: nT elements are left, in the order the swaps gave them
+		DeconMerged l = decon_merged(A, r, rf, fl);
+		const int n = decon_filter(l, l.na + (l.b ? A.item_n[2 * r + 1] : 0), (int) A.db.DB_size);
+		for(int i = 1; i <= n && i <= (int) nT; ++i) T[w++] = l.get(i);
+		return;
+	}
 	if(rf > 0 && fl == 0) {
 		const int64_t o = A.item_off[2 * r];
 		for(int i = 0; i < A.item_n[2 * r]; ++i) T[w++] = A.pool[o + i];
@@ -1503,6 +1589,7 @@ __global__ __launch_bounds__(256) void pair_penalty_kernel(const PairArgs P) {
 			m[1] = 1; rcv[1] = o2; sc[1] = s2; fl[1] = flag_r; nn[1] = nreg; of[1] = base;
 		}
 	}
+	if(A.db.decon) decon_pair_records(P.ppool, (int) A.db.DB_size, m, fl, nn, of);      // deConPrint / deConPrintPair in place of print_ankers / printPair
 	for(int x = 0; x < 2; ++x) {
 		const int64_t r = 2 * p + x;
 		P.r_mate[r] = m[x]; P.r_rc[r] = rcv[x]; P.r_score[r] = sc[x]; P.r_flag[r] = fl[x];
@@ -1607,6 +1694,7 @@ __global__ __launch_bounds__(256) void pair_union_kernel(const PairArgs P) {
 		else { flag_r |= 16; for(int i = 0; i < nreg; ++i) regT[i] = -regT[i]; }
 		m[1] = 1; rcv[1] = o2; sc[1] = s2; fl[1] = flag_r; nn[1] = nreg; of[1] = base;
 	}
+	if(A.db.decon) decon_pair_records(P.ppool, (int) A.db.DB_size, m, fl, nn, of);      // deConPrint / deConPrintPair in place of print_ankers / printPair
 	for(int x = 0; x < 2; ++x) {
 		const int64_t r = 2 * p + x;
 		P.r_mate[r] = m[x]; P.r_rc[r] = rcv[x]; P.r_score[r] = sc[x]; P.r_flag[r] = fl[x];
@@ -1668,6 +1756,7 @@ __global__ __launch_bounds__(256) void pair_force_kernel(const PairArgs P) {
 			}
 		}
 	}
+	if(A.db.decon) decon_pair_records(P.ppool, (int) A.db.DB_size, m, fl, nn, of);      // deConPrint / deConPrintPair in place of print_ankers / printPair
 	for(int x = 0; x < 2; ++x) {
 		const int64_t r = 2 * p + x;
 		P.r_mate[r] = m[x]; P.r_rc[r] = rcv[x]; P.r_score[r] = sc[x]; P.r_flag[r] = fl[x];
@@ -2023,11 +2112,13 @@ static int ws_reserve(kmahip_ws *ws, int64_t n_reads) {
 	if(!ws->dense) {
 		// overflow scratch: up to 4096 concurrent items, bounded to 1 GiB
 		int64_t slots = 4096;
-		const int64_t per = (int64_t) db->info.DB_size * 3 * sizeof(int32_t);
+		// (one entry per id a value list can hold: the templates 0 .. DB_size - 1 and, in a decon table, the pseudo-template DB_size)
+		const int64_t ids = (int64_t) db->info.DB_size + (db->decon ? 1 : 0);
+		const int64_t per = ids * 3 * sizeof(int32_t);
 		while(slots > 64 && slots * per > (1ll << 30)) slots >>= 1;
 		ws->dense_slots = slots;
 		HIP_TRY(hipMalloc((void **) &ws->dense, slots * per));
-		hipLaunchKernelGGL(dense_init_kernel, dim3(1024), dim3(256), 0, 0, ws->dense, slots * 3 * (int64_t) db->info.DB_size, (int64_t) db->info.DB_size);
+		hipLaunchKernelGGL(dense_init_kernel, dim3(1024), dim3(256), 0, 0, ws->dense, slots * 3 * ids, ids);
 		HIP_TRY(hipDeviceSynchronize());
 	}
 	return KMAHIP_OK;
@@ -2052,6 +2143,7 @@ int kmahip_launch_scan_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	const bool proxi = A.min_frac != 1.0;
 	if(!(A.min_frac <= 1.0)) { kmahip_set_error("minFrac %g outside [-1, 1]", p->minFrac); return KMAHIP_EINVAL; }
 	if(kmahip_mem_mode() && (rc = kmahip_refuse_proxi(p, KMAHIP_PROXI_MEM))) return rc;
+	if(kmahip_mem_mode() && (rc = kmahip_refuse_decon(db, KMAHIP_DECON_MEM))) return rc;
 	A.recs = scan_records_on(ws, reads, p) ? ws->recs : nullptr; A.rec_cap = ws->rec_cap;
 	A.refine = scan_refine_on(A.cat_bases);
 	A.ablate = 0;
@@ -2099,9 +2191,12 @@ int kmahip_launch_scan_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 		hipLaunchKernelGGL(scan_dense_kernel, dim3((unsigned) ws->dense_slots), dim3(64), 0, stream, A);
 	}
 	const unsigned cgrid = (unsigned) ((n + CB - 1) / CB);
-	hipLaunchKernelGGL(combine_count_kernel, dim3(cgrid), dim3(CB), 0, stream, A, out->rc_flag, out->flag, out->T_off, ws->blk_sums);
+	// a decon table: the combine is where the strands are merged and the lists get their final order, so the filter sits there
+	if(db->decon) hipLaunchKernelGGL(combine_count_kernel<true>, dim3(cgrid), dim3(CB), 0, stream, A, out->rc_flag, out->flag, out->T_off, ws->blk_sums);
+	else hipLaunchKernelGGL(combine_count_kernel<false>, dim3(cgrid), dim3(CB), 0, stream, A, out->rc_flag, out->flag, out->T_off, ws->blk_sums);
 	hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, stream, ws->blk_sums, (int64_t) cgrid);
-	hipLaunchKernelGGL(combine_write_kernel, dim3(cgrid), dim3(CB), 0, stream, A, out->rc_flag, out->flag, out->T_off, ws->blk_sums, out->T, out->T_cap);
+	if(db->decon) hipLaunchKernelGGL(combine_write_kernel<true>, dim3(cgrid), dim3(CB), 0, stream, A, out->rc_flag, out->flag, out->T_off, ws->blk_sums, out->T, out->T_cap);
+	else hipLaunchKernelGGL(combine_write_kernel<false>, dim3(cgrid), dim3(CB), 0, stream, A, out->rc_flag, out->flag, out->T_off, ws->blk_sums, out->T, out->T_cap);
 	HIP_TRY(hipGetLastError());
 	return KMAHIP_OK;
 }
@@ -2112,6 +2207,7 @@ int kmahip_launch_chain_anchors(kmahip_db *db, kmahip_ws *ws, const kmahip_reads
 	if(n <= 0 || !p) { kmahip_set_error("bad arguments"); return KMAHIP_EINVAL; }
 	int rc = kmahip_refuse_proxi(p, KMAHIP_PROXI_CHAIN);
 	if(rc) return rc;
+	if((rc = kmahip_refuse_decon(db, KMAHIP_DECON_CHAIN))) return rc;
 	rc = ws_reserve(ws, n);
 	if(rc) return rc;
 	AnchorArgs A;
@@ -2147,6 +2243,7 @@ int kmahip_launch_scan_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	const int64_t np = n / 2;
 	int rc = kmahip_refuse_proxi(p, KMAHIP_PROXI_PE);
 	if(rc) return rc;
+	if(kmahip_mem_mode() && (rc = kmahip_refuse_decon(db, KMAHIP_DECON_MEM))) return rc;
 	rc = ws_reserve(ws, n > 0 ? n : 1);
 	if(rc) return rc;
 	if(ws->pe_cap < ws->pool_cap) {

@@ -294,6 +294,7 @@ extern "C" int kmahip_session_set_mt1(kmahip_session *S, int32_t tmpl, int one2o
 	if(S->sam_level) { kmahip_set_error("SAM records (kmahip_session_set_sam) are not built for a -Mt1 session"); return KMAHIP_EINVAL; }
 	if(tmpl < 1 || (size_t) tmpl >= S->db->info.DB_size) { kmahip_set_error("template %d out of range", tmpl); return KMAHIP_EINVAL; }
 	if(int rcp = kmahip_refuse_proxi(&S->par, KMAHIP_PROXI_MT1)) return rcp;
+	if(int rcd = kmahip_refuse_decon(S->db, KMAHIP_DECON_MT1)) return rcd;
 	if(hipMalloc((void **) &S->mt1_sum, 8) != hipSuccess || hipMemset(S->mt1_sum, 0, 8) != hipSuccess) { kmahip_set_error("hipMalloc failed"); return KMAHIP_ENOMEM; }
 	if(frag_path) {
 		int rc = kmahip_db_load_names(S->db);
@@ -323,6 +324,7 @@ extern "C" int kmahip_session_set_chain(kmahip_session *S, const kmahip_chain_pa
 	if(S->n || S->n_reads || !S->uploaded.empty() || S->mt1 || S->pe) { kmahip_set_error("the mode of a session is chosen before its first batch"); return KMAHIP_EINVAL; }
 	if(S->sam_level) { kmahip_set_error("SAM records (kmahip_session_set_sam) are not built for a session in the default mode (without -1t1)"); return KMAHIP_EINVAL; }
 	if(int rcp = kmahip_refuse_proxi(&S->par, KMAHIP_PROXI_CHAIN)) return rcp;
+	if(int rcd = kmahip_refuse_decon(S->db, KMAHIP_DECON_CHAIN)) return rcd;
 	S->chain = true;
 	if(cp) S->cp = *cp; else { S->cp.minlen = 16; S->cp.pad_ = 0; S->cp.coverT = 0.1; S->cp.mrs = 0.5; }
 	return KMAHIP_OK;
