@@ -8,6 +8,7 @@
  *     kmahip_map -ipe r1.fq.gz r2.fq.gz -t_db db -o out              (paired input in the default mode: couples by union, single records in pieces)
  *     kmahip_map -i ont.fq.gz -t_db db -o out -Mt1 1 -bcNano        (every read against template 1, runKMA_Mt1 mt1.c:86-500)
  *     kmahip_map -gpus 8 -i reads.fq -t_db db -o out -1t1           (one process per GPU, the reads sharded; see below)
+ *     kmahip_map -i reads.fq.gz -t_db sparse_db -o out -Sparse      (`kma -Sparse` against an index of `kma index -Sparse`: k-mer counts, out.spa only; run_sparse)
  *
  * The command line is the reference's (kma.c:351-1248) for the options this path implements; anything else is refused, loudly.
  * Stage 1 (kmahip_ingest_*: parse, trim, pack), the whole device run in one call (kmahip_run_se / _pe / _chain / _mt1: stage 2, 3a,
@@ -229,6 +230,10 @@ static void usage(void) {
 	                "        (runConClave2); in every run of one rank, not with -gpus N; -Mt1 runs no ConClave and ignores it)\n"
 	                "       (-deCon: decontamination, against <index prefix>.decon.comp.b (kmahip_index -deCon / kma index -deCon): a read that fits the contamination\n"
 	                "        better than any template has no record; in the -1t1 runs of one rank, not in the default mode, with -mem_mode, -Mt1 or -gpus N)\n"
+	                "       (-Sparse [-ss q|c|d]: sparse mapping against an index of `kma index -Sparse`: the k-mers of the reads are counted, the templates ranked on\n"
+	                "        the counts (-ss: by score q, coverage c or depth d) and named one by one; only <output prefix>.spa is written. -i takes a list of files,\n"
+	                "        -ipe / -int files are read as single-end files; -ID, -md, -e / -p, -t and the trimming options apply, the other mapping options are\n"
+	                "        taken and ignored; not with -deCon, -gpus N, -s1dev or -o --)\n"
 	                "(the options of kma 1.5.1 this path implements; -apm takes p or u; everything else is refused)\n");
 }
 
@@ -302,6 +307,47 @@ static int launch_ranks(int gpus, char **argv) {
 	return status;
 }
 
+/* `kma -Sparse` (kma.c:1483-1538 run_input_sparse, :1607-1612 save_kmers_sparse_batch): every input file is read as single-end records
+ * by the host's stage 1, batch by batch; a batch's k-mers are counted on the device against the sparse index (kmahip_sparse_count);
+ * then the templates are ranked, named and withdrawn, and <out>.spa is written. Nothing else is written. */
+static int run_sparse(const char *prefix, const char *out, char **files, int n_files, kmahip_trim trim, double ID_t, double Depth_t, double evalue, char ss) {
+	kmahip_sparse *sdb = NULL;
+	/* kma.c:1527-1529 and sparse.c:256-258: the end trimming is at least as strict as the masking and the average quality asked for */
+	if(trim.min_phred < trim.hardmask_q) trim.min_phred = trim.hardmask_q;
+	if(trim.min_phred < trim.min_q) trim.min_phred = trim.min_q;
+	if(kmahip_init(0) || kmahip_sparse_open(prefix, &sdb)) { fprintf(stderr, "kmahip_map: %s\n", kmahip_last_error()); return 1; }
+	const char *be = getenv("KMAHIP_MAP_BATCH_READS");
+	const int64_t batch_reads = be && atoll(be) > 0 ? atoll(be) : (int64_t) 1 << 20;
+	for(int f = 0; f < n_files; ++f) {
+		kmahip_ingest *ing = NULL;
+		kmahip_read_batch b;
+		int rc = kmahip_ingest_open(files[f], NULL, &trim, &ing);
+		while(!rc) {
+			rc = kmahip_ingest_next(ing, batch_reads, &b);
+			if(rc || b.reads.n_reads == 0) break;
+			rc = kmahip_sparse_count(sdb, &b.reads);
+		}
+		if(!rc) rc = kmahip_ingest_status(ing);
+		if(ing) kmahip_ingest_close(ing);
+		if(rc) { fprintf(stderr, "kmahip_map: %s: %s\n", files[f], kmahip_last_error()); kmahip_sparse_close(sdb); return 1; }
+	}
+	kmahip_sparse_opts so;
+	kmahip_sparse_default_opts(&so);
+	so.ID_t = ID_t; so.Depth_t = Depth_t; so.evalue = evalue; so.ss = ss;
+	char *path = malloc(strlen(out) + 8);
+	if(!path) { kmahip_sparse_close(sdb); return 1; }
+	sprintf(path, "%s.spa", out);
+	int rc = kmahip_sparse_write(sdb, &so, path);
+	free(path);
+	uint64_t hits[2] = {0, 0}, Ntot = 0;
+	if(!rc) rc = kmahip_sparse_scores(sdb, 0, NULL, NULL, hits);
+	if(!rc) rc = kmahip_sparse_counts(sdb, NULL, NULL, &Ntot);
+	if(rc) fprintf(stderr, "kmahip_map: %s\n", kmahip_last_error());
+	else fprintf(stderr, "# Total number of matches: %llu of %llu kmers\n", (unsigned long long) hits[1], (unsigned long long) Ntot);      /* sparse.c:649 */
+	kmahip_sparse_close(sdb);
+	return rc ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
 	const char *prefix = NULL, *input = NULL, *input2 = NULL, *out = NULL;
 	int Ts = -2, Tv = -2;          /* -transition / -transversion (kma.c:335-336) */
@@ -315,6 +361,7 @@ int main(int argc, char **argv) {
 	int matrix = 0, vcf = 0;                     /* -matrix (kma.c:667): <out>.mat.gz; -vcf [n] (kma.c:949-961): <out>.vcf.gz, n = 2 fills its FILTER column */
 	int proxi_opt = 0;                           /* -proxi / -ill given (for the refusals' wording; what counts is par.minFrac) */
 	int decon = 0;                               /* -deCon: map against <t_db>.decon.comp.b and drop what fits the contamination best */
+	int sparse = 0; char ss = 'q';               /* -Sparse (kma.c:684): count k-mers, write <out>.spa only; -ss q|c|d, the order its templates are named in */
 	int base_call = 0, sig_mode = 0, ref_fsa = 0, dense = 0;      /* as kmahip_assemble_opts.caller (0-2 here) / .sig90; printconsensus.c's ref_fsa */
 	double support = 0;                          /* -bc x: the variable the reference hands updateVcf (kma.c:747, vcf.c:195) ... */
 	double call_support = 0;                     /* ... and the threshold of significantAndSupport, a static that keeps the FIRST non-zero value it is given (assembly.c:153-157): -bc x, -ill and the presets -mint2 / -mint3 all give it one, and the two presets leave `support` alone (kma.c:1092, 1112) */
@@ -484,11 +531,35 @@ int main(int argc, char **argv) {
 		else if(!strcmp(o, "-transition")) Ts = -abs((int) need_int(argc, argv, &a, o));
 		else if(!strcmp(o, "-transversion")) Tv = -abs((int) need_int(argc, argv, &a, o));
 		else if(!strcmp(o, "-cge")) { par.scoreT = 0.5; cp.mrs = 0.5; par.rw.M = 1; par.rw.W1 = -5; par.rw.U = -1; par.rw.PE = 17; }      /* (its MM = -3 does not survive kma.c:1308) */
+		else if(!strcmp(o, "-Sparse")) sparse = 1;                                              /* kma.c:684 */
+		else if(!strcmp(o, "-ss")) {                                                            /* kma.c:724-735: a wrong value is named and the default kept */
+			if(a + 1 < argc) {
+				const char c = argv[++a][0];
+				if(c == 'q' || c == 'c' || c == 'd') ss = c;
+				else fprintf(stderr, "Invalid argument parsed to option: \"-ss\", using default.\n");
+			}
+		}
 		else if(!strcmp(o, "-gpus")) gpus = (int) need_int(argc, argv, &a, o);
 		else if(!strcmp(o, "-s1dev")) s1dev = 1;                                                /* (our own: kmahip_ingest_dev_* + kmahip_session_upload_dev) */
 		else { fprintf(stderr, "kmahip_map: option %s is not one this program implements\n", o); usage(); return 2; }
 	}
 	if(!prefix || !input || !out) { fprintf(stderr, "kmahip_map: -i (or -ipe / -int), -t_db and -o are required\n"); usage(); return 2; }
+	if(sparse) {
+		/* a pipeline of its own (kma.c:1483-1538, 1607-1612): the mapping options its path never reads are taken and ignored, as there */
+		const char *why = NULL;
+		if(decon) why = "-deCon (collect_Kmers_deCon is not built)";
+		else if(gpus > 1 || getenv("KMAHIP_RANK") || getenv("RANK")) why = "-gpus N (several ranks)";
+		else if(s1dev) why = "-s1dev";
+		else if(!strcmp(out, "--")) why = "-o -- (the rows on standard output)";
+		if(why) { fprintf(stderr, "kmahip_map: -Sparse is not built for %s: sparse mapping serves one rank, reads parsed on the host, and writes <out>.spa\n", why); return 2; }
+		char *files[512];
+		int n = 0;
+		for(int i = 0; i < n_files; ++i) { files[n++] = list1[i]; if(list2[i]) files[n++] = list2[i]; }
+		if(input2 && input2[0]) fprintf(stderr, "Paired end information is not considered in Sparse mode.\n");          /* kma.c:1514 */
+		else if(input2) fprintf(stderr, "Interleaved information is not considered in Sparse mode.\n");              /* kma.c:1525 */
+		if(threads) { char v[16]; snprintf(v, sizeof v, "%d", threads); setenv("KMAHIP_INGEST_THREADS", v, 1); }
+		return run_sparse(prefix, out, files, n, trim, ID_t, Depth_t, evalue, ss);
+	}
 	if(kmahip_set_cmp(cmp_mode)) { fprintf(stderr, "kmahip_map: %s\n", kmahip_last_error()); return 1; }
 	{	/* the substitution matrix (kma.c:1307-1328) */
 		par.rw.MM = (Ts + Tv - 1) / 2;

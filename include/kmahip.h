@@ -1048,6 +1048,73 @@ int kmahip_ws_set_timing(kmahip_ws *ws, int on);
 int kmahip_ws_get_timing(kmahip_ws *ws, int kernel /* 0 scan_se_kernel, 1 align_tasks_kernel, 2 scan_prefilter_kernel, 3 seed_tasks_kernel */,
                          double *total_ms, int64_t *launches);
 
+/* ---- sparse mapping (`kma -Sparse`, sparse.c:338-797): no alignment; the k-mers of the reads that the index holds are counted, the
+ * templates ranked on those counts and named one by one, a named template's k-mers withdrawn from all the others; one row per named
+ * template in <out>.spa. A pipeline of its own beside the mapping one (sparse.hip): kmahip_db_open keeps refusing sparse indexes.
+ *
+ * kmahip_sparse_open reads <prefix>.comp.b (hashed or direct-address form; prefix_len / prefix from its header, `-Sparse -` gives
+ * 0 / 1), <prefix>.length.b as load_DBs_Sparse does (sparse.c:133-177: the first array is skipped, then the lengths, then the unique
+ * lengths) and <prefix>.name; no .seq.b. On the device: a probe table k-mer -> k-mer id (the 32-byte buckets of the mapping index),
+ * the offset of every id's value list, the value lists, and one 32-bit count per id (the `int value` of HashMap_kmers,
+ * hashmapkmers.h:24-28). Refused with KMAHIP_EFORMAT and the reason in kmahip_last_error: an index without a prefix, k > 16,
+ * flag != 0 (minimizer / homopolymer indexes), a .length.b without unique lengths ("DB needs to sparse indexed, to run a sparse
+ * mapping.", sparse.c:172). Not built: -Sparse with -deCon (collect_Kmers_deCon), several ranks, building sparse indexes. */
+typedef struct kmahip_sparse kmahip_sparse;
+typedef struct kmahip_sparse_info {
+	uint32_t DB_size, kmersize, prefix_len, values_u16;
+	uint64_t prefix, n_kmers /* k-mers held (= ids) */, n_hdr /* the header's n: templates->n of sparse.c:685 */, n_values, total_bytes;
+} kmahip_sparse_info;
+int kmahip_sparse_open(const char *prefix, kmahip_sparse **out);
+void kmahip_sparse_close(kmahip_sparse *sdb);
+int kmahip_sparse_get_info(const kmahip_sparse *sdb, kmahip_sparse_info *info);
+/* template t's name (1 <= t < DB_size), its length and its unique length */
+int kmahip_sparse_template(const kmahip_sparse *sdb, int32_t t, const char **name, uint32_t *len, uint32_t *ulen);
+
+/* One batch of reads (host pointers; _dev: device pointers) added to the counts held by sdb: translateToKmersAndDump for flag == 0
+ * (sparse.c:50-131) over both strands, branch for branch -- with a prefix per N-free stretch behind the strict gate
+ * i < end - kmersize - prefix_len, the k-mer being the one that starts behind a prefix match; without one every k-mer of a stretch,
+ * the walk resuming kmersize + 1 bases behind an N (:124) -- and save_kmers_sparse (:232-244): every k-mer produced counts into Ntot,
+ * every one the index holds adds 1 to the count of its id. Undoes a collect: the scores are stale until the next one. */
+int kmahip_sparse_count(kmahip_sparse *sdb, const kmahip_reads *reads);
+int kmahip_sparse_count_dev(kmahip_sparse *sdb, const kmahip_reads *reads);
+/* for tests: keys[i] / counts[i] of k-mer id i (n_kmers each; either may be NULL) and Ntot */
+int kmahip_sparse_counts(kmahip_sparse *sdb, uint32_t *keys, uint32_t *counts, uint64_t *Ntot);
+/* collect_Kmers (hashtable.c:54-120): every k-mer with a count > 0 becomes live and adds 1 / its count to Scores / Scores_tot of each
+ * template of its list; Nhits.n / Nhits.tot. The working copies (w_Scores ...) start from these. */
+int kmahip_sparse_collect(kmahip_sparse *sdb);
+/* withDraw_Kmers (hashtable.c:224-270) on the working copies: every live k-mer whose list holds t by intpos_bin (:27-52, restated as
+ * it stands) takes 1 / its count off every template of its list and dies */
+int kmahip_sparse_withdraw(kmahip_sparse *sdb, int32_t t);
+/* which: 0 = Scores / Scores_tot / Nhits of the last collect, 1 = the working copies. DB_size elements each; hits[2] = n, tot */
+int kmahip_sparse_scores(kmahip_sparse *sdb, int which, uint32_t *scores, uint64_t *scores_tot, uint64_t hits[2]);
+
+typedef struct kmahip_sparse_opts {
+	double ID_t;       /* -ID (1.0) */
+	double Depth_t;    /* -md (0.0) */
+	double evalue;     /* -e / -p (0.05) */
+	int32_t ss;        /* -ss: 'q', 'c' or 'd' */
+	int32_t pad_;
+} kmahip_sparse_opts;
+void kmahip_sparse_default_opts(kmahip_sparse_opts *o);
+/* one row of <out>.spa (sparse.c:766-774); ulen is what its Template_length column prints (:773) */
+typedef struct kmahip_sparse_row {
+	int32_t tmpl, expected;
+	uint64_t score;
+	uint32_t ulen, pad_;
+	double query_cover, cover, depth, tot_query_cover, tot_cover, tot_depth, q_value, p_value;
+} kmahip_sparse_row;
+/* save_kmers_sparse_batch without decontamination (sparse.c:645-790): collect, then choose (host arithmetic in the host's libm on the
+ * two downloaded vectors: the three -ss orders, the -ID / -md gates, p_chisqr, SearchList) and withdraw (a kernel) until nothing is
+ * left. Up to cap rows are stored, *n_rows is their number (KMAHIP_EOVERFLOW when cap was too small). */
+int kmahip_sparse_rows(kmahip_sparse *sdb, const kmahip_sparse_opts *opts, kmahip_sparse_row *rows, int64_t cap, int64_t *n_rows);
+/* the rows as the reference prints them (header line, "%s\t%d\t%lu\t%d\t%d" and %8.2f columns, p_value %4.1e) into `path` */
+int kmahip_sparse_write(kmahip_sparse *sdb, const kmahip_sparse_opts *opts, const char *path);
+/* Timing and ablation. set_timing: event pairs around the kernels; get_timing sums them per kernel (0 count, 1 collect, 2 withdraw)
+ * and resets. set_noadd(1): the counting kernel keeps its probes and drops its adds -- timing only, the counts are wrong by design. */
+int kmahip_sparse_set_timing(kmahip_sparse *sdb, int on);
+int kmahip_sparse_get_timing(kmahip_sparse *sdb, int kernel, double *total_ms, int64_t *launches);
+int kmahip_sparse_set_noadd(kmahip_sparse *sdb, int on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1391,3 +1391,165 @@ class KmaHipDB:
             _check(rcode)
             return (mate[:n], rc[:n], rc_flag[:n], flag[:n], R_off, T[:R_off[n]]), h
         raise KmaHipError("map_pe: output capacity kept overflowing")
+
+
+class SparseInfo(C.Structure):
+    _fields_ = [("DB_size", C.c_uint32), ("kmersize", C.c_uint32), ("prefix_len", C.c_uint32), ("values_u16", C.c_uint32),
+                ("prefix", C.c_uint64), ("n_kmers", C.c_uint64), ("n_hdr", C.c_uint64), ("n_values", C.c_uint64), ("total_bytes", C.c_uint64)]
+
+
+class SparseOpts(C.Structure):
+    _fields_ = [("ID_t", C.c_double), ("Depth_t", C.c_double), ("evalue", C.c_double), ("ss", C.c_int32), ("pad_", C.c_int32)]
+
+
+class SparseRow(C.Structure):
+    _fields_ = [("tmpl", C.c_int32), ("expected", C.c_int32), ("score", C.c_uint64), ("ulen", C.c_uint32), ("pad_", C.c_uint32),
+                ("query_cover", C.c_double), ("cover", C.c_double), ("depth", C.c_double), ("tot_query_cover", C.c_double),
+                ("tot_cover", C.c_double), ("tot_depth", C.c_double), ("q_value", C.c_double), ("p_value", C.c_double)]
+
+
+class SparseDB:
+    """Sparse mapping (`kma -Sparse`; kmahip_sparse_*): a sparse index (`kma index -Sparse`) resident in HBM with the k-mer counts of
+    the reads given so far. count() adds a batch; rows() / write() rank and name the templates like save_kmers_sparse_batch."""
+
+    def __init__(self, prefix: str, device: int = 0):
+        L = lib()
+        if not hasattr(L, "kmahip_sparse_open"):
+            raise KmaHipError("this libkmahip.so has no sparse mapping (kmahip_sparse_open)")
+        L.kmahip_sparse_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+        L.kmahip_sparse_close.argtypes = [C.c_void_p]
+        L.kmahip_sparse_close.restype = None
+        L.kmahip_sparse_get_info.argtypes = [C.c_void_p, C.POINTER(SparseInfo)]
+        L.kmahip_sparse_template.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.kmahip_sparse_count.argtypes = [C.c_void_p, C.POINTER(Reads)]
+        L.kmahip_sparse_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.kmahip_sparse_collect.argtypes = [C.c_void_p]
+        L.kmahip_sparse_withdraw.argtypes = [C.c_void_p, C.c_int32]
+        L.kmahip_sparse_scores.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kmahip_sparse_default_opts.argtypes = [C.POINTER(SparseOpts)]
+        L.kmahip_sparse_default_opts.restype = None
+        L.kmahip_sparse_rows.argtypes = [C.c_void_p, C.POINTER(SparseOpts), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.kmahip_sparse_write.argtypes = [C.c_void_p, C.POINTER(SparseOpts), C.c_char_p]
+        L.kmahip_sparse_set_timing.argtypes = [C.c_void_p, C.c_int]
+        L.kmahip_sparse_get_timing.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        L.kmahip_sparse_set_noadd.argtypes = [C.c_void_p, C.c_int]
+        self.h = C.c_void_p()
+        _check(L.kmahip_init(device))
+        _check(L.kmahip_sparse_open(os.fsencode(prefix), C.byref(self.h)))
+        self.prefix = prefix
+        self.info = SparseInfo()
+        _check(L.kmahip_sparse_get_info(self.h, C.byref(self.info)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().kmahip_sparse_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def template(self, t):
+        """-> (name bytes, length, unique length) of template t"""
+        name, ln, ul = C.c_char_p(), C.c_uint32(), C.c_uint32()
+        _check(lib().kmahip_sparse_template(self.h, int(t), C.byref(name), C.byref(ln), C.byref(ul)))
+        return name.value, ln.value, ul.value
+
+    def count(self, batch):
+        """add the k-mers of a formats.ReadBatch (both strands) to the counts"""
+        n = batch.n
+        if n == 0:
+            return
+        seq = np.ascontiguousarray(batch.seq, np.uint64)
+        Nn = np.ascontiguousarray(batch.N if len(batch.N) else np.zeros(1, np.int32), np.int32)
+        seq_off, length, N_off = (np.ascontiguousarray(a, d) for a, d in ((batch.seq_off, np.int64), (batch.length, np.int32), (batch.N_off, np.int64)))
+        r = Reads(n, _p(seq), _p(seq_off), _p(length), _p(Nn), _p(N_off), len(seq), len(batch.N), int(length.max()))
+        _check(lib().kmahip_sparse_count(self.h, C.byref(r)))
+
+    def count_dev(self, seq, seq_off, length, N, N_off):
+        """count() on CUDA(HIP) torch tensors (u64 words as int64, int64, int32, int32, int64), every read followed by its pad word
+        (the layout of formats.ReadBatch); asynchronous on the null stream"""
+        n = length.numel()
+        if n == 0:
+            return
+        L = lib()
+        L.kmahip_sparse_count_dev.argtypes = [C.c_void_p, C.POINTER(Reads)]
+        r = Reads(n, seq.data_ptr(), seq_off.data_ptr(), length.data_ptr(), N.data_ptr(), N_off.data_ptr(), seq.numel(), N.numel(), 0)
+        _check(L.kmahip_sparse_count_dev(self.h, C.byref(r)))
+
+    def counts(self):
+        """-> (keys u32[n_kmers], counts u32[n_kmers], Ntot): the count of every k-mer of the index, in the order of its ids"""
+        n = int(self.info.n_kmers)
+        keys, cnt, ntot = np.zeros(max(1, n), np.uint32), np.zeros(max(1, n), np.uint32), C.c_uint64()
+        _check(lib().kmahip_sparse_counts(self.h, _p(keys), _p(cnt), C.byref(ntot)))
+        return keys[:n], cnt[:n], int(ntot.value)
+
+    def collect(self):
+        """collect_Kmers: the scores from the counts; the working copies start from them"""
+        _check(lib().kmahip_sparse_collect(self.h))
+
+    def withdraw(self, t):
+        """withDraw_Kmers on the working copies"""
+        _check(lib().kmahip_sparse_withdraw(self.h, int(t)))
+
+    def scores(self, working=False):
+        """-> (Scores u32[DB_size], Scores_tot u64[DB_size], (Nhits.n, Nhits.tot)) of the last collect(), or the working copies.
+        Collects first when the counts changed since."""
+        D = int(self.info.DB_size)
+        sc, tot, hits = np.zeros(D, np.uint32), np.zeros(D, np.uint64), np.zeros(2, np.uint64)
+        rc = lib().kmahip_sparse_scores(self.h, 1 if working else 0, _p(sc), _p(tot), _p(hits))
+        if rc == -1 and not working:
+            self.collect()
+            rc = lib().kmahip_sparse_scores(self.h, 0, _p(sc), _p(tot), _p(hits))
+        _check(rc)
+        return sc, tot, (int(hits[0]), int(hits[1]))
+
+    @staticmethod
+    def _opts(ss, id_t, depth_t, evalue):
+        o = SparseOpts()
+        lib().kmahip_sparse_default_opts(C.byref(o))
+        o.ss = ord(ss)
+        if id_t is not None:
+            o.ID_t = float(id_t)
+        if depth_t is not None:
+            o.Depth_t = float(depth_t)
+        if evalue is not None:
+            o.evalue = float(evalue)
+        return o
+
+    def rows(self, ss="q", id_t=None, depth_t=None, evalue=None):
+        """the rows of <out>.spa as tuples (template, score, expected, unique length, query cover, cover, depth, tot query cover,
+        tot cover, tot depth, q_value, p_value)"""
+        o = self._opts(ss, id_t, depth_t, evalue)
+        cap = int(self.info.DB_size)
+        buf = (SparseRow * max(1, cap))()
+        n = C.c_int64()
+        _check(lib().kmahip_sparse_rows(self.h, C.byref(o), buf, cap, C.byref(n)))
+        return [(r.tmpl, r.score, r.expected, r.ulen, r.query_cover, r.cover, r.depth, r.tot_query_cover, r.tot_cover, r.tot_depth, r.q_value, r.p_value)
+                for r in buf[:n.value]]
+
+    def write(self, path, ss="q", id_t=None, depth_t=None, evalue=None):
+        """<out>.spa, byte for byte the reference's"""
+        o = self._opts(ss, id_t, depth_t, evalue)
+        _check(lib().kmahip_sparse_write(self.h, C.byref(o), os.fsencode(path)))
+
+    def set_timing(self, on=True):
+        _check(lib().kmahip_sparse_set_timing(self.h, 1 if on else 0))
+
+    def get_timing(self, kernel):
+        """(milliseconds, launches) of kernel 0 count, 1 collect, 2 withdraw since the last call"""
+        ms, n = C.c_double(), C.c_int64()
+        _check(lib().kmahip_sparse_get_timing(self.h, int(kernel), C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def set_noadd(self, on=True):
+        """timing only: the counting kernel keeps its probes and drops its adds (the counts are wrong by design)"""
+        _check(lib().kmahip_sparse_set_noadd(self.h, 1 if on else 0))

@@ -205,21 +205,9 @@ __global__ __launch_bounds__(256) void tpos_insert_kernel(const unsigned long lo
 
 }  // namespace
 
-static int db_open(const char *prefix, bool decon, kmahip_db **out) {
-	if(!prefix || !out) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
-	*out = nullptr;
-	std::string base(prefix);
-	// KMAHIP_DEBUG_TIMING: where the time of opening an index goes
-	const bool dbg = getenv("KMAHIP_DEBUG_TIMING") != nullptr;
-	auto t_last = std::chrono::steady_clock::now();
-	auto stamp = [&](const char *what) {
-		if(!dbg) return;
-		const auto now = std::chrono::steady_clock::now();
-		fprintf(stderr, "[kmahip] db_open: %s %.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-		t_last = now;
-	};
-	// decontamination (kmers.c:76-80): the table with the pseudo-template DB_size in its lists; everything else is the same index
-	const std::string comp = base + (decon ? ".decon.comp.b" : ".comp.b");
+// <prefix>.comp.b (hashMapKMA_load, hashmapkma.c:276-460) into host arrays: the header, the value lists and the k-mers with the offsets of
+// their lists. allow_sparse: take an index with a prefix (`kma index -Sparse`, sparse.hip); kmahip_db_open refuses those by name.
+int kmahip_comp_read(const std::string &comp, bool allow_sparse, KmaComp *c) {
 	FILE *f = fopen(comp.c_str(), "rb");
 	if(!f) { kmahip_set_error("cannot open %s", comp.c_str()); return KMAHIP_EIO; }
 	uint32_t h32[3];
@@ -227,9 +215,10 @@ static int db_open(const char *prefix, bool decon, kmahip_db **out) {
 	if(!read_exact(f, h32, 12) || !read_exact(f, h64, 40)) { fclose(f); kmahip_set_error("short header in %s", comp.c_str()); return KMAHIP_EIO; }
 	const uint32_t DB_size = h32[0], mlen = h32[1];
 	const uint64_t size = h64[1], n_hdr = h64[2], v_index = h64[3];
+	c->DB_size = DB_size; c->mlen = mlen; c->prefix_len = h32[2]; c->prefix = h64[0]; c->n_hdr = n_hdr; c->v_index = v_index;
 	// `kma index -Sparse`: only the k-mers behind a prefix are stored and the reference maps with save_kmers_sparse, without
 	// stage 3 (kma.c:1499-1501); the -1t1 scan over such a table would be wrong without any error
-	if(h32[2] != 0 || h64[0] != 0) { fclose(f); kmahip_set_error("sparse index (prefix length %u) not supported", h32[2]); return KMAHIP_EFORMAT; }
+	if(!allow_sparse && (h32[2] != 0 || h64[0] != 0)) { fclose(f); kmahip_set_error("sparse index (prefix length %u) not supported", h32[2]); return KMAHIP_EFORMAT; }
 	if(mlen == 0 || mlen > 16) { fclose(f); kmahip_set_error("k-mer length %u needs 64-bit keys: not supported", mlen); return KMAHIP_EFORMAT; }
 	const uint64_t kmask = (1ull << (2 * mlen)) - 1;
 	// A direct-address index (`kma index -ME`, or any index whose table grew to 4^k slots, hashmap.c:204-209): exist[] holds one
@@ -237,14 +226,18 @@ static int db_open(const char *prefix, bool decon, kmahip_db **out) {
 	// there are no key / value-index arrays. The k-mers present are read out of it in ascending order; from there on the
 	// index is built like any other (the probe table below is what the kernels look k-mers up in).
 	const bool mega = size - 1 == kmask;
+	c->mega = mega;
 	uint64_t n = n_hdr;
 	if(size < n_hdr || n_hdr > 0xFFFFFFFFull || v_index >= 0xFFFFFFFFull || (n_hdr == 0 && !mega)) { fclose(f); kmahip_set_error("index too large or old format"); return KMAHIP_EFORMAT; }
 	const bool u16 = DB_size < 65535; // hashmapkma.c:340-348
+	c->u16 = u16;
 	// 8 zero elements of slack: the scan kernel fetches a list head as count + 7 ids
 	const size_t vbytes = v_index * (u16 ? 2 : 4);
-	std::vector<uint8_t> values(vbytes + 8 * 4, 0);
-	std::vector<uint32_t> keys, vidx;
-	uint32_t tail[2] = {mlen, 0};
+	std::vector<uint8_t> &values = c->values;
+	std::vector<uint32_t> &keys = c->keys, &vidx = c->vidx;
+	values.assign(vbytes + 8 * 4, 0);
+	uint32_t *tail = c->tail;
+	tail[0] = mlen; tail[1] = 0;
 	bool ok = true;
 	if(mega) {
 		std::vector<uint32_t> chunk(1u << 22);
@@ -266,9 +259,38 @@ static int db_open(const char *prefix, bool decon, kmahip_db **out) {
 	if(ok && read_exact(f, &tail[0], 4)) ok = read_exact(f, &tail[1], 4);
 	fclose(f);
 	if(!ok) { kmahip_set_error("truncated %s", comp.c_str()); return KMAHIP_EIO; }
-	stamp("read .comp.b");
 	if(tail[1] != 0) { kmahip_set_error("minimizer / homopolymer-compressed index (flag %u) not supported", tail[1]); return KMAHIP_EFORMAT; }
 	if(tail[0] != mlen) { kmahip_set_error("kmersize %u != mlen %u not supported", tail[0], mlen); return KMAHIP_EFORMAT; }
+
+	c->n = n;
+	return KMAHIP_OK;
+}
+
+static int db_open(const char *prefix, bool decon, kmahip_db **out) {
+	if(!prefix || !out) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	*out = nullptr;
+	std::string base(prefix);
+	// KMAHIP_DEBUG_TIMING: where the time of opening an index goes
+	const bool dbg = getenv("KMAHIP_DEBUG_TIMING") != nullptr;
+	auto t_last = std::chrono::steady_clock::now();
+	auto stamp = [&](const char *what) {
+		if(!dbg) return;
+		const auto now = std::chrono::steady_clock::now();
+		fprintf(stderr, "[kmahip] db_open: %s %.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
+		t_last = now;
+	};
+	// decontamination (kmers.c:76-80): the table with the pseudo-template DB_size in its lists; everything else is the same index
+	const std::string comp = base + (decon ? ".decon.comp.b" : ".comp.b");
+	KmaComp comp_;
+	if(int rc_ = kmahip_comp_read(comp, false, &comp_)) return rc_;
+	stamp("read .comp.b");
+	const uint32_t DB_size = comp_.DB_size, mlen = comp_.mlen;
+	const uint64_t n = comp_.n, v_index = comp_.v_index;
+	const bool u16 = comp_.u16;
+	std::vector<uint8_t> &values = comp_.values;
+	std::vector<uint32_t> &keys = comp_.keys, &vidx = comp_.vidx;
+	const uint32_t *tail = comp_.tail;
+	FILE *f = nullptr;
 
 	kmahip_db *db = new kmahip_db();
 	db->prefix = base;

@@ -167,6 +167,16 @@ struct kmahip_ws {
 struct KmaAnk { int score, weight, score_len, len_len; unsigned start, end; uint32_t values; int descend; };
 
 void kmahip_set_error(const char *fmt, ...);
+// <prefix>.comp.b as read from disk (db.hip: kmahip_comp_read): keys[i] is the i-th k-mer, vidx[i] the offset of its value list in
+// `values` (u16 or u32 elements: count, then the sorted template ids); n_hdr is the header's n, n the k-mers actually there
+struct KmaComp {
+	uint32_t DB_size = 0, mlen = 0, prefix_len = 0, tail[2] = {0, 0};      // tail: kmersize, flag
+	uint64_t prefix = 0, n_hdr = 0, n = 0, v_index = 0;
+	bool mega = false, u16 = false;
+	std::vector<uint8_t> values;
+	std::vector<uint32_t> keys, vidx;
+};
+int kmahip_comp_read(const std::string &comp, bool allow_sparse, KmaComp *c);
 int kmahip_cmp(bool t, bool q);          // conclave.hip: the reference's `cmp` (or / and / true, kmahip_set_cmp)
 #define HIP_TRY(expr) do { hipError_t e__ = (expr); if(e__ != hipSuccess) { \
 	kmahip_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); return KMAHIP_EDEVICE; } } while(0)
