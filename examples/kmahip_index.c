@@ -1,9 +1,11 @@
 /* kmahip_index.c -- `kma index -i templates.fsa [more.fsa ...] (or -batch list.txt) -o prefix [-k k] [-deCon host.fsa ...]` on an MI355X:
- * plain C99 over kmahip_index_build / kmahip_index_build_decon (the k-mers are sorted and made unique on the device). Writes
- * prefix.comp.b / .length.b / .seq.b / .name, which the reference and libkmahip load alike, and with -deCon prefix.decon.comp.b
- * beside them (what `kma ... -deCon` and `kmahip_map ... -deCon` map against).
+ * plain C99 over kmahip_index_build / kmahip_index_build_decon / kmahip_index_build_sparse (the k-mers are sorted and made unique on
+ * the device). Writes prefix.comp.b / .length.b / .seq.b / .name, which the reference and libkmahip load alike, and with -deCon
+ * prefix.decon.comp.b beside them (what `kma ... -deCon` and `kmahip_map ... -deCon` map against). With -Sparse the index is the
+ * sparse one (`kma -Sparse`, `kmahip_map -Sparse`): only the k-mers behind the prefix, of both strands; -ML is its length gate.
  *
  *     kmahip_index -i genes.fsa -o genes [-k 16] [-deCon host.fsa phix.fsa]
+ *     kmahip_index -i genes.fsa -o genes_sparse -Sparse TG [-ML 100]
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -11,9 +13,21 @@
 
 #include "kmahip.h"
 
+#define USAGE "usage: kmahip_index (-i <fasta> [<fasta> ...] | -batch <file of paths>) -o <index prefix> [-k <k-mer length, 4 ... 16>] " \
+              "[-deCon <fasta> [<fasta> ...]] [-Sparse [<prefix>|-] [-ML <minimum length>]]\n"
+
+/* index.c:451-474: the letters the reference's table maps to 0 ... 3; anything else, or nothing at all, is no prefix */
+static int valid_prefix(const char *s) {
+	if(!strcmp(s, "-")) return 1;
+	if(!*s) return 0;
+	for(; *s; ++s) if(!strchr("ARMDarmdCYBcybGSKVgskvTWHUtwhu", *s)) return 0;
+	return 1;
+}
+
 int main(int argc, char **argv) {
-	const char *inputs[256], *decon[256], *out = NULL;
-	int n_in = 0, n_decon = 0, decon_opt = 0, k = 16;
+	const char *inputs[256], *decon[256], *out = NULL, *sparse = NULL;
+	int n_in = 0, n_decon = 0, decon_opt = 0, k = 16, ml_opt = 0;
+	long min_len = 0;
 	for(int a = 1; a < argc; ++a) {
 		if(!strcmp(argv[a], "-i")) { while(a + 1 < argc && argv[a + 1][0] != '-' && n_in < 256) inputs[n_in++] = argv[++a]; }
 		else if(!strcmp(argv[a], "-batch") && a + 1 < argc) {          /* index.c:351-401: a file that lists the inputs, one path a line */
@@ -37,10 +51,26 @@ int main(int argc, char **argv) {
 		}
 		else if(!strcmp(argv[a], "-o") && a + 1 < argc) out = argv[++a];
 		else if(!strcmp(argv[a], "-k") && a + 1 < argc) k = atoi(argv[++a]);
-		else { fprintf(stderr, "usage: kmahip_index (-i <fasta> [<fasta> ...] | -batch <file of paths>) -o <index prefix> [-k <k-mer length, 4 ... 16>] [-deCon <fasta> [<fasta> ...]]\n"); return 2; }
+		else if(!strcmp(argv[a], "-Sparse")) {         /* index.c:451-474: the next argument whatever it is; none, or "-": no prefix */
+			sparse = a + 1 < argc ? argv[++a] : "-";
+			if(!valid_prefix(sparse)) { fprintf(stderr, "Invalid prefix.\n"); return 1; }
+		}
+		else if(!strcmp(argv[a], "-ML") && a + 1 < argc) {          /* index.c:315-326 */
+			char *end;
+			min_len = strtol(argv[++a], &end, 10);
+			ml_opt = 1;
+			if(*end) { fprintf(stderr, "# Invalid minimum length parsed\n"); return 1; }
+			if(min_len <= 0) { fprintf(stderr, "# Invalid minimum length parsed, using default\n"); min_len = 0; }
+			if(min_len > 0x7FFFFFFF) min_len = 0x7FFFFFFF;
+		}
+		else { fprintf(stderr, USAGE); return 2; }
 	}
+	/* what is not built is refused by name, before a file or the device is opened */
+	if(sparse && decon_opt) { fprintf(stderr, "kmahip_index: -Sparse is not built for -deCon (deConNode_sparse)\n"); return 2; }
+	if(ml_opt && !sparse) { fprintf(stderr, "kmahip_index: -ML is not built for a build without -Sparse\n"); return 2; }
 	if(!n_in || !out) { fprintf(stderr, "kmahip_index: -i and -o are required\n"); return 2; }
-	if(kmahip_init(0) || (decon_opt ? kmahip_index_build_decon(inputs, n_in, decon, n_decon, out, k) : kmahip_index_build(inputs, n_in, out, k))) {
+	if(kmahip_init(0) || (sparse ? kmahip_index_build_sparse(inputs, n_in, out, k, k, sparse, (int) min_len)
+	                      : decon_opt ? kmahip_index_build_decon(inputs, n_in, decon, n_decon, out, k) : kmahip_index_build(inputs, n_in, out, k))) {
 		fprintf(stderr, "kmahip_index: %s\n", kmahip_last_error()); return 1;
 	}
 	return 0;

@@ -616,7 +616,8 @@ int kmahip_chain_unpinned_reads(const int32_t *len, const int32_t *N, const int6
  * made unique there (rocPRIM); grouping, list sharing and the bucket directory are one pass on the host. The files hold the
  * same k-mer -> template-list mapping as the reference's (tests compare the two) and the reference maps against them with
  * identical results; bucket count, key order inside a bucket and list order are the builder's own. FASTA input, plain or .gz.
- * Not covered: -Sparse / prefixes, minimizers (-m), homopolymer compression (-hc), appending (-t_db); `-batch list` is the
+ * Not covered: minimizers (-m), homopolymer compression (-hc), appending (-t_db); -Sparse / prefixes have their own entry point,
+ * kmahip_index_build_sparse below; `-batch list` is the
  * host program's (examples/kmahip_index: the listed paths become fasta_paths). */
 int kmahip_index_build(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize);
 /* `kma index ... -deCon <fasta ...>` (index.c:676-729, decon.c:77-227): the four files of kmahip_index_build, byte for byte, and
@@ -626,6 +627,22 @@ int kmahip_index_build(const char *const *fasta_paths, int n_files, const char *
  * plain or .gz; "--" (standard input) is refused with KMAHIP_EINVAL. Appending to an existing index is not covered. */
 int kmahip_index_build_decon(const char *const *fasta_paths, int n_files, const char *const *decon_paths, int n_decon,
                              const char *out_prefix, int kmersize);
+/* `kma index ... -Sparse <prefix | -> [-ML n]` (index.c:451-474, 576-613; makeindex.c:46-48, 167-291; updateindex.c:79-199:
+ * updateDBs_sparse, updateAnnots_sparse; qualcheck.c:31-79: lengthCheck; hashmap.c:120-187): the index `kma -Sparse` and
+ * kmahip_sparse_open map against. A window is prefix_len + k bases of a trimmed template or of its reverse complement that hold no N
+ * and start with the prefix; its k-mer, the last k bases, is indexed. prefix_text "-": no prefix, every N-free k-mer of either strand
+ * (header fields prefix_len 0, prefix 1). A template stays when it is LONGER than MinLen = max(k, kmerindex), has MinKlen = 1
+ * windows at least (without a prefix (length - k + 1) * 2 stands for the count) and one window in any case; a template that goes
+ * gets no id, no name and no .seq.b words, and those behind it move up. min_len (-ML) > k + prefix_len + 1: MinLen = min_len,
+ * MinKlen = 2 * (min_len - k - prefix_len + 1), divided by 4 once per prefix base; any other value (0: the default) is ignored,
+ * as the reference ignores it. .length.b holds DB_size, lengths (slot 0: kmerindex), slengths (windows of both strands) and
+ * ulengths (distinct window k-mers); .comp.b the same k-mer -> ascending template list mapping as the reference's, in the
+ * builder's own bucket layout; .seq.b and .name as kmahip_index_build writes them, over the templates that stayed.
+ * kmersize <= 0: 16. kmerindex <= 0: kmersize (what -k sets). KMAHIP_EINVAL, the reason in kmahip_last_error: k outside 4 ... 16,
+ * a prefix of more than 16 bases, a null prefix, an empty one or one with a letter that is no A, C, G, T (IUPAC codes as the
+ * reference folds them) -- "Invalid prefix." as the reference says. Not covered: -deCon on a sparse index, -ht / -hq, appending. */
+int kmahip_index_build_sparse(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize, int kmerindex,
+                              const char *prefix_text, int min_len);
 
 /* ---- stage 1: FASTQ / FASTA ingest into packed read batches -------------------------------------------
  * Host code (zlib for .gz, plain files read as they are): the record parser of FileBuffgetFq / FileBuffgetFsa

@@ -371,12 +371,23 @@ def test_mapq(best, second, w):
     return out
 
 
-def index_build(fasta_paths, out_prefix, k=16, decon=None):
+def index_build(fasta_paths, out_prefix, k=16, decon=None, sparse=None, min_len=0):
     """kmahip_index_build: the four index files from FASTA file(s) (needs a GPU: the k-mers are sorted on the device).
-    decon: contamination FASTA file(s) (`kma index -deCon`) -> kmahip_index_build_decon, which writes <out_prefix>.decon.comp.b too"""
+    decon: contamination FASTA file(s) (`kma index -deCon`) -> kmahip_index_build_decon, which writes <out_prefix>.decon.comp.b too.
+    sparse: a prefix such as "TG", or "-" for none (`kma index -Sparse`) -> kmahip_index_build_sparse, the index SparseDB maps against;
+    min_len: its -ML (0: the default). A sparse decon index is not built, and -ML belongs to the sparse build alone."""
     paths = [os.fsencode(p) for p in ([fasta_paths] if isinstance(fasta_paths, (str, bytes)) else fasta_paths)]
     arr = (C.c_char_p * len(paths))(*paths)
     L = lib()
+    if sparse is not None:
+        if decon is not None:
+            raise ValueError("index_build: sparse with decon is not built")
+        L.kmahip_index_build_sparse.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int]
+        L.kmahip_index_build_sparse.restype = C.c_int
+        _check(L.kmahip_index_build_sparse(arr, len(paths), os.fsencode(out_prefix), int(k), int(k), os.fsencode(sparse), int(min_len)))
+        return
+    if min_len:
+        raise ValueError("index_build: min_len (-ML) is built for sparse indexes only")
     if decon is not None:
         dpaths = [os.fsencode(p) for p in ([decon] if isinstance(decon, (str, bytes)) else decon)]
         darr = (C.c_char_p * max(1, len(dpaths)))(*dpaths)

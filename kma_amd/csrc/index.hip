@@ -6,7 +6,9 @@
 // equal template lists, cut into buckets). The files hold the same k-mer -> template-list mapping as the reference's and load into
 // it; bucket count, key order inside a bucket and the order of the shared lists are the builder's own (the reference's follow
 // from the growth history of its in-memory hash table and carry no meaning for a reader).
-// Covered: the default hashed form, k <= 16, no prefix (-Sparse), no minimizers / homopolymer compression, no -batch.
+// Covered: the default hashed form, k <= 16, no minimizers / homopolymer compression, no -batch.
+// -Sparse (kmahip_index_build_sparse; index.c:451-474 / 576-613, updateindex.c:79-199, qualcheck.c:31-79): index_build_sparse below,
+// with its host side in index_host.h. The plain build's kernel, host pass and files are as they were.
 // -deCon (kmahip_index_build_decon; index.c:676-729, decon.c:77-227): every k-mer of either strand of the contamination records
 // becomes a key of the pseudo-template DB_size and joins the same sort; the host pass runs twice over the sorted pairs, once
 // without those keys (<prefix>.comp.b, as ever) and once with them (<prefix>.decon.comp.b), where a k-mer that only the
@@ -20,25 +22,9 @@
 #include <unordered_map>
 #include <vector>
 
+#include "index_host.h"          // Tmpl, RefTable (index.c:128-170), and the host side of the sparse build
+
 namespace {
-
-struct Tmpl {
-	std::string name;
-	size_t at = 0;       // first base in the concatenated code array
-	int len = 0;
-};
-
-// index.c:128-170
-struct RefTable {
-	uint8_t t[256];
-	RefTable() {
-		memset(t, 8, sizeof t);
-		t[(int) '\n'] = 16;
-		const char *codes[5] = {"ARMDrmd", "CYBcyb", "GSKVgskv", "TWHUtwhu", "NXnx"};
-		for(int c = 0; c < 5; ++c) for(const char *p = codes[c]; *p; ++p) t[(int) (unsigned char) *p] = (uint8_t) c;
-		t[(int) 'a'] = 0;
-	}
-};
 
 // one thread per base of the concatenated templates: the k-mer that starts there, if it lies inside one template and holds no N
 __global__ __launch_bounds__(256) void index_kmers_kernel(const uint8_t *codes, const int64_t *t_off, int n_t, int64_t total, int k,
@@ -81,6 +67,74 @@ __global__ __launch_bounds__(256) void index_decon_kmers_kernel(const uint8_t *c
 	keys[2 * p + 1] = rc;
 }
 
+// -Sparse (updateDBs_sparse, updateindex.c:79-167). One thread per base p of the concatenated templates reads the prefix_len + k bases
+// that start there, once, for both strands: when they lie inside one template and hold no N they are a window of the forward strand
+// if their first prefix_len bases equal the prefix (its k-mer: the last k bases), and a window of the reverse strand if the reverse
+// complement of their last prefix_len bases does (its k-mer: the reverse complement of the first k). keys[2 p], keys[2 p + 1]:
+// k-mer << 32 | template in file order, 1 .. n_t, or ~0. slen[t] gains the template's windows: where a wavefront lies inside one
+// template -- all but the few that hold a boundary -- it adds once, the population count of two ballots
+__global__ __launch_bounds__(256) void index_sparse_keys_kernel(const uint8_t *codes, const int64_t *t_off, int n_t, int64_t total, int k, int prefix_len,
+                                                                  unsigned long long prefix, unsigned long long *keys, unsigned *slen) {
+	const int64_t p = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	const bool live = p < total;
+	int lo = 0;
+	unsigned long long fw = ~0ull, rc = ~0ull;
+	if(live) {
+		int hi = n_t;                            // template holding p: last t with t_off[t] <= p
+		while(hi - lo > 1) { const int mid = (lo + hi) >> 1; if(t_off[mid] <= p) lo = mid; else hi = mid; }
+		const int w = prefix_len + k;            // <= 32 bases: one 64-bit word a strand
+		if(p + w <= t_off[lo + 1]) {
+			unsigned long long x = 0, y = 0;
+			bool ok = true;
+			for(int i = 0; i < w; ++i) {
+				const uint8_t c = codes[p + i];
+				ok = ok && c < 4;
+				x = (x << 2) | (c & 3);
+				y |= (unsigned long long) (3 - (c & 3)) << (2 * i);
+			}
+			if(ok) {
+				const unsigned long long kmask = (1ull << (2 * k)) - 1, id = (unsigned long long) (lo + 1);
+				if(prefix_len == 0 || (x >> (2 * k)) == prefix) fw = ((x & kmask) << 32) | id;
+				if(prefix_len == 0 || (y >> (2 * k)) == prefix) rc = ((y & kmask) << 32) | id;
+			}
+		}
+		keys[2 * p] = fw;
+		keys[2 * p + 1] = rc;
+	}
+	// (no thread has left: lane 0 of a wavefront is live whenever any of its lanes is, p rises with the lane)
+	const int lo0 = __builtin_amdgcn_readfirstlane(lo);
+	const bool has_fw = fw != ~0ull, has_rc = rc != ~0ull;
+	if(__all(!live || lo == lo0)) {
+		const unsigned c = (unsigned) (__popcll(__ballot(has_fw)) + __popcll(__ballot(has_rc)));
+		if((threadIdx.x & 63) == 0 && c) atomicAdd(&slen[lo0], c);
+	} else if(has_fw || has_rc) atomicAdd(&slen[lo], (unsigned) has_fw + (unsigned) has_rc);
+}
+
+// the keys of the templates that are skipped go, the others take their template's id in the index: new_id[t - 1], 0 = skipped
+__global__ __launch_bounds__(256) void index_sparse_remap_kernel(unsigned long long *keys, int64_t n, const uint32_t *new_id) {
+	const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if(i >= n) return;
+	const unsigned long long key = keys[i];
+	if(key == ~0ull) return;
+	const uint32_t id = new_id[(uint32_t) key - 1];
+	keys[i] = id ? (key & 0xFFFFFFFF00000000ull) | id : ~0ull;
+}
+
+// ulen[id] = the template's distinct window k-mers (what hashMap_add returned 1 for): its share of the unique (k-mer, id) pairs. The
+// pairs are sorted by k-mer, so a wavefront seldom holds one id alone; where it does (a database of a template or two) it adds once
+__global__ __launch_bounds__(256) void index_sparse_ulen_kernel(const unsigned long long *pairs, int64_t n, uint32_t DB_size, unsigned *ulen) {
+	const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	const unsigned long long key = i < n ? pairs[i] : ~0ull;
+	const bool has = key != ~0ull && (uint32_t) key < DB_size;
+	const uint32_t id = has ? (uint32_t) key : 0;
+	const unsigned long long m = __ballot(has);
+	if(m == 0) return;                           // (wave-uniform)
+	const uint32_t id0 = (uint32_t) __builtin_amdgcn_readfirstlane((int) __shfl((int) id, __ffsll((long long) m) - 1));
+	if(__all(!has || id == id0)) {
+		if((threadIdx.x & 63) == 0) atomicAdd(&ulen[id0], (unsigned) __popcll(m));
+	} else if(has) atomicAdd(&ulen[id], 1u);
+}
+
 struct SameKey { __device__ bool operator()(unsigned long long a, unsigned long long b) const { return a == b; } };
 
 int read_whole(const char *path, std::vector<uint8_t> &buf) {
@@ -101,8 +155,10 @@ int read_whole(const char *path, std::vector<uint8_t> &buf) {
 
 // host pass over the sorted (k-mer << 32 | template) pairs and the .comp.b image of what it finds: group by k-mer, share equal
 // lists (valuesHash, compress.c:218), lists laid out in the order they are first needed. with_decon = false: the pairs of the
-// pseudo-template DB_size are passed over; true: they stay, but a k-mer that holds nothing else is dropped
-int write_comp_b(const std::vector<unsigned long long> &pairs, uint32_t DB_size, int k, bool with_decon, const std::string &path) {
+// pseudo-template DB_size are passed over; true: they stay, but a k-mer that holds nothing else is dropped. prefix_len, prefix: the two
+// header fields of a sparse index (hashMapKMA_dump), 0 and 0 in every other
+int write_comp_b(const std::vector<unsigned long long> &pairs, uint32_t DB_size, int k, bool with_decon, const std::string &path, uint32_t prefix_len = 0,
+                 uint64_t prefix = 0) {
 	const bool u16 = DB_size < 65535;                               // hashmapkma.c:340-348
 	std::vector<uint32_t> ukm, vi_of_key;
 	std::vector<uint32_t> values;                                   // [cnt, t1 .. tcnt] per list
@@ -156,8 +212,8 @@ int write_comp_b(const std::vector<unsigned long long> &pairs, uint32_t DB_size,
 
 	FILE *f = fopen(path.c_str(), "wb");
 	if(!f) { kmahip_set_error("cannot create %s", path.c_str()); return KMAHIP_EIO; }
-	const uint32_t h32[3] = {DB_size, (uint32_t) k, 0};
-	const uint64_t h64[5] = {0, size, n, v_index, n};
+	const uint32_t h32[3] = {DB_size, (uint32_t) k, prefix_len};          // (a sparse index: its prefix; 0 and 0 otherwise)
+	const uint64_t h64[5] = {prefix, size, n, v_index, n};
 	bool ok = fwrite(h32, 4, 3, f) == 3 && fwrite(h64, 8, 5, f) == 5 && fwrite(exist.data(), 4, size, f) == size;
 	if(u16) {
 		std::vector<uint16_t> v16(values.begin(), values.end());
@@ -315,7 +371,101 @@ int index_build(const char *const *fasta_paths, int n_files, const char *const *
 	return KMAHIP_OK;
 }
 
+// `kma index -Sparse <prefix | -> [-ML n]`: which k-mers become keys, both strands, templates that go and the ids that move up behind
+// them, two more arrays in .length.b and the prefix in the .comp.b header. The rule is index_host.h's; the device finds the windows
+// under the ids of the file order (index_sparse_keys_kernel), the host picks the templates that stay from n_t window counts, the keys
+// are renumbered where a template went (index_sparse_remap_kernel) and go through the plain build's sort and unique, and the unique
+// pairs are counted per template (index_sparse_ulen_kernel)
+int index_build_sparse(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize, int kmerindex, const char *prefix_text, int min_len) {
+	if(!fasta_paths || n_files <= 0 || !out_prefix) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	static const RefTable T;
+	SparseRule rule;
+	rule.k = kmersize > 0 ? kmersize : 16;
+	rule.kmerindex = kmerindex > 0 ? kmerindex : rule.k;
+	if(rule.k < 4 || rule.k > 16) { kmahip_set_error("k-mer length %d: 4 ... 16 supported", rule.k); return KMAHIP_EINVAL; }
+	if(rule.kmerindex > 31) { kmahip_set_error("k-mer length of the position index %d: at most 31", rule.kmerindex); return KMAHIP_EINVAL; }
+	int rc = sparse_parse_prefix(prefix_text, T, rule);
+	if(rc) return rc;
+	sparse_set_gates(min_len, rule);
+	const int k = rule.k;
+	std::vector<Tmpl> tm;
+	std::vector<uint8_t> codes;
+	for(int fi = 0; fi < n_files; ++fi) {
+		std::vector<uint8_t> raw;
+		if((rc = read_whole(fasta_paths[fi], raw))) return rc;
+		if((rc = sparse_parse_fasta(raw, fasta_paths[fi], T, rule.MinLen, codes, tm))) return rc;
+	}
+	const int n_t = (int) tm.size();
+	if(n_t == 0) { kmahip_set_error("no template of more than %d bases", rule.MinLen); return KMAHIP_EFORMAT; }
+	const int64_t total = (int64_t) codes.size(), n_keys = 2 * total;
+	std::vector<int64_t> t_off((size_t) n_t + 1);
+	for(int t = 0; t < n_t; ++t) t_off[(size_t) t] = (int64_t) tm[(size_t) t].at;
+	t_off[(size_t) n_t] = total;
+
+	uint8_t *d_codes = nullptr; int64_t *d_off = nullptr; unsigned *d_slen = nullptr, *d_ulen = nullptr; uint32_t *d_newid = nullptr;
+	unsigned long long *d_keys = nullptr, *d_sorted = nullptr, *d_uniq = nullptr; size_t *d_count = nullptr; void *d_tmp = nullptr;
+	auto release = [&] { (void) hipFree(d_codes); (void) hipFree(d_off); (void) hipFree(d_slen); (void) hipFree(d_ulen); (void) hipFree(d_newid); (void) hipFree(d_keys);
+	                     (void) hipFree(d_sorted); (void) hipFree(d_uniq); (void) hipFree(d_count); (void) hipFree(d_tmp); };
+	struct Guard { decltype(release) &r; ~Guard() { r(); } } guard{release};
+	HIP_TRY(hipMalloc((void **) &d_codes, (size_t) total + 32));
+	HIP_TRY(hipMalloc((void **) &d_off, t_off.size() * 8));
+	HIP_TRY(hipMalloc((void **) &d_slen, (size_t) n_t * 4));
+	HIP_TRY(hipMalloc((void **) &d_keys, (size_t) n_keys * 8));
+	HIP_TRY(hipMemcpy(d_codes, codes.data(), (size_t) total, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(d_off, t_off.data(), t_off.size() * 8, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemset(d_slen, 0, (size_t) n_t * 4));
+	hipLaunchKernelGGL(index_sparse_keys_kernel, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, 0, d_codes, d_off, n_t, total, k, rule.prefix_len,
+	                   (unsigned long long) rule.prefix, d_keys, d_slen);
+	HIP_TRY(hipGetLastError());
+	std::vector<uint32_t> slen((size_t) n_t), new_id;
+	HIP_TRY(hipMemcpy(slen.data(), d_slen, (size_t) n_t * 4, hipMemcpyDeviceToHost));
+	const uint32_t n_kept = sparse_assign_ids(tm, slen, rule, new_id);
+	if(n_kept == 0) { kmahip_set_error("DB is empty: no template holds a k-mer behind the prefix"); return KMAHIP_EFORMAT; }
+	const uint32_t DB_size = n_kept + 1;
+	if(n_kept != (uint32_t) n_t) {
+		HIP_TRY(hipMalloc((void **) &d_newid, (size_t) n_t * 4));
+		HIP_TRY(hipMemcpy(d_newid, new_id.data(), (size_t) n_t * 4, hipMemcpyHostToDevice));
+		hipLaunchKernelGGL(index_sparse_remap_kernel, dim3((unsigned) ((n_keys + 255) / 256)), dim3(256), 0, 0, d_keys, n_keys, d_newid);
+		HIP_TRY(hipGetLastError());
+	}
+	HIP_TRY(hipMalloc((void **) &d_sorted, (size_t) n_keys * 8));
+	HIP_TRY(hipMalloc((void **) &d_uniq, (size_t) n_keys * 8));
+	HIP_TRY(hipMalloc((void **) &d_count, sizeof(size_t)));
+	HIP_TRY(hipMalloc((void **) &d_ulen, (size_t) DB_size * 4));
+	HIP_TRY(hipMemset(d_ulen, 0, (size_t) DB_size * 4));
+	size_t tmp_bytes = 0, tmp2 = 0;
+	if(rocprim::radix_sort_keys(nullptr, tmp_bytes, d_keys, d_sorted, (size_t) n_keys, 0, 64, 0) != hipSuccess ||
+	   rocprim::unique(nullptr, tmp2, d_sorted, d_uniq, d_count, (size_t) n_keys, SameKey(), 0) != hipSuccess) { kmahip_set_error("rocprim size query failed"); return KMAHIP_EDEVICE; }
+	tmp_bytes = std::max(tmp_bytes, tmp2);
+	HIP_TRY(hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16));
+	if(rocprim::radix_sort_keys(d_tmp, tmp_bytes, d_keys, d_sorted, (size_t) n_keys, 0, 64, 0) != hipSuccess ||
+	   rocprim::unique(d_tmp, tmp_bytes, d_sorted, d_uniq, d_count, (size_t) n_keys, SameKey(), 0) != hipSuccess) { kmahip_set_error("rocprim sort / unique failed"); return KMAHIP_EDEVICE; }
+	size_t n_pairs = 0;
+	HIP_TRY(hipMemcpy(&n_pairs, d_count, sizeof n_pairs, hipMemcpyDeviceToHost));
+	if(n_pairs > (size_t) n_keys) { kmahip_set_error("rocprim unique returned %zu of %lld keys", n_pairs, (long long) n_keys); return KMAHIP_EDEVICE; }
+	if(n_pairs) {
+		hipLaunchKernelGGL(index_sparse_ulen_kernel, dim3((unsigned) ((n_pairs + 255) / 256)), dim3(256), 0, 0, d_uniq, (int64_t) n_pairs, DB_size, d_ulen);
+		HIP_TRY(hipGetLastError());
+	}
+	std::vector<unsigned long long> pairs(n_pairs);
+	if(n_pairs) HIP_TRY(hipMemcpy(pairs.data(), d_uniq, n_pairs * 8, hipMemcpyDeviceToHost));
+	std::vector<uint32_t> ulen((size_t) DB_size);
+	HIP_TRY(hipMemcpy(ulen.data(), d_ulen, (size_t) DB_size * 4, hipMemcpyDeviceToHost));
+	if(n_pairs && pairs.back() == ~0ull) pairs.pop_back();         // the starts that hold no window sorted to the end
+	if(pairs.empty()) { kmahip_set_error("DB is empty: no template holds a k-mer behind the prefix"); return KMAHIP_EFORMAT; }
+
+	const std::string base(out_prefix);
+	if((rc = write_comp_b(pairs, DB_size, k, false, base + ".comp.b", (uint32_t) rule.prefix_len, rule.prefix))) return rc;
+	if((rc = sparse_write_length_b(base + ".length.b", tm, new_id, DB_size, rule.kmerindex, slen, ulen))) return rc;
+	return sparse_write_seq_and_names(base, tm, new_id, codes);
+}
+
 }  // namespace
+
+extern "C" int kmahip_index_build_sparse(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize, int kmerindex,
+                                         const char *prefix_text, int min_len) {
+	return index_build_sparse(fasta_paths, n_files, out_prefix, kmersize, kmerindex, prefix_text, min_len);
+}
 
 extern "C" int kmahip_index_build(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize) {
 	return index_build(fasta_paths, n_files, nullptr, 0, out_prefix, kmersize);

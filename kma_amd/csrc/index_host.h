@@ -1,0 +1,161 @@
+// index_host.h -- the host side of a sparse index build (`kma index -Sparse`), free of any device call so that it also compiles into a
+// plain C++ program: the letter table, the FASTA parser with the sparse build's length gate, the prefix and -ML arithmetic of
+// index.c:451-474 / 576-613, the choice of the templates that stay (makeindex.c:225, updateindex.c:79-167, qualcheck.c:31-79) and
+// the writers of .length.b / .seq.b / .name over the templates that stayed (updateAnnots_sparse, makeindex.c:262-276).
+#pragma once
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+#include <ctype.h>
+#include <string>
+#include <vector>
+#include "../../include/kmahip.h"
+
+void kmahip_set_error(const char *fmt, ...);
+
+namespace {
+
+struct Tmpl {
+	std::string name;
+	size_t at = 0;       // first base in the concatenated code array
+	int len = 0;
+};
+
+// index.c:128-170
+struct RefTable {
+	uint8_t t[256];
+	RefTable() {
+		memset(t, 8, sizeof t);
+		t[(int) '\n'] = 16;
+		const char *codes[5] = {"ARMDrmd", "CYBcyb", "GSKVgskv", "TWHUtwhu", "NXnx"};
+		for(int c = 0; c < 5; ++c) for(const char *p = codes[c]; *p; ++p) t[(int) (unsigned char) *p] = (uint8_t) c;
+		t[(int) 'a'] = 0;
+	}
+};
+
+// what -Sparse, -k and -ML come to (index.c:451-474, 576-613)
+struct SparseRule {
+	int k = 16, kmerindex = 16;
+	int prefix_len = 0;
+	uint64_t prefix = 1;        // the header's value: 1 stands for "no prefix"
+	int MinLen = 16;            // a template stays when MinLen < its length (lenCheck, makeindex.c:46-48)
+	int64_t MinKlen = 1;        // ... and when its windows (no prefix: its k-mer starts, twice) reach MinKlen (lengthCheck)
+};
+
+// "-" = no prefix; anything else: letters the table maps to 0 ... 3, at least one and at most 16 of them
+inline int sparse_parse_prefix(const char *text, const RefTable &T, SparseRule &r) {
+	if(!text) { kmahip_set_error("sparse index: null prefix (\"-\" stands for none)"); return KMAHIP_EINVAL; }
+	if(!strcmp(text, "-")) { r.prefix_len = 0; r.prefix = 1; return KMAHIP_OK; }
+	const size_t n = strlen(text);
+	if(n == 0) { kmahip_set_error("Invalid prefix."); return KMAHIP_EINVAL; }
+	if(n > 16) { kmahip_set_error("sparse index: a prefix of %zu bases: at most 16 supported", n); return KMAHIP_EINVAL; }
+	uint64_t p = 0;
+	for(size_t i = 0; i < n; ++i) {
+		const uint8_t c = T.t[(unsigned char) text[i]];
+		if(c > 3) { kmahip_set_error("Invalid prefix."); return KMAHIP_EINVAL; }
+		p = (p << 2) | c;
+	}
+	r.prefix_len = (int) n; r.prefix = p;
+	return KMAHIP_OK;
+}
+
+// index.c:599-606; min_len <= 0: no -ML
+inline void sparse_set_gates(int min_len, SparseRule &r) {
+	if(min_len > r.k + r.prefix_len + 1) {
+		r.MinLen = min_len;
+		r.MinKlen = 2 * ((int64_t) min_len - r.k - r.prefix_len + 1);
+		for(int i = 0; i < r.prefix_len; ++i) r.MinKlen /= 4;
+	} else {
+		r.MinLen = r.k > r.kmerindex ? r.k : r.kmerindex;
+		r.MinKlen = 1;
+	}
+}
+
+// One FASTA file already in memory -> its records behind `tm` / `codes`, as the plain build parses them (FileBuffgetFsa,
+// seqparse.c:66-159; compDNAref, compdna.c:129-147), with the sparse build's gate: a record of min_len bases or fewer goes
+int sparse_parse_fasta(const std::vector<uint8_t> &raw, const char *path, const RefTable &T, int min_len, std::vector<uint8_t> &codes, std::vector<Tmpl> &tm) {
+	if(raw.empty() || raw[0] != '>') { kmahip_set_error("%s is not a FASTA file", path); return KMAHIP_EFORMAT; }
+	size_t p = 0;
+	while(p < raw.size()) {
+		size_t e = p;
+		while(e < raw.size() && raw[e] != '\n') ++e;
+		size_t h = e;
+		while(h > p + 1 && isspace(raw[h - 1])) --h;
+		std::string name((const char *) raw.data() + p + 1, h - p - 1);
+		p = e < raw.size() ? e + 1 : e;
+		const size_t at = codes.size();
+		while(p < raw.size() && raw[p] != '>') { const uint8_t c = T.t[raw[p]]; if(c < 8) codes.push_back(c); ++p; }
+		size_t a = at, b = codes.size();
+		while(a < b && codes[a] == 4) ++a;
+		while(b > a && codes[b - 1] == 4) --b;
+		const int bias = (int) (a - at);
+		if(a > at) memmove(codes.data() + at, codes.data() + a, b - a);
+		codes.resize(at + (b - a));
+		const size_t len = b - a;
+		if(len > 0x7FFFFFFFu) { kmahip_set_error("%s: a template of %zu bases", path, len); return KMAHIP_EFORMAT; }
+		if(!((size_t) min_len < len)) { codes.resize(at); continue; }              // "# Skipped"
+		if(bias > 0) name += " B" + std::to_string(bias);
+		Tmpl t; t.name = name; t.at = at; t.len = (int) len;
+		tm.push_back(t);
+	}
+	return KMAHIP_OK;
+}
+
+// The templates that stay, from their window counts over both strands (slen[t], t = 0 .. n_t - 1 in file order): lengthCheck asks
+// for MinKlen windows (without a prefix: of (len - k + 1) * 2, whatever N's there are), update_DB for one at least. new_id[t] = the
+// id of the template in the index, 1 .. , or 0 when it is skipped; every template behind a skipped one moves up. -> how many stay
+inline uint32_t sparse_assign_ids(const std::vector<Tmpl> &tm, const std::vector<uint32_t> &slen, const SparseRule &r, std::vector<uint32_t> &new_id) {
+	new_id.assign(tm.size(), 0);
+	uint32_t next = 1;
+	for(size_t t = 0; t < tm.size(); ++t) {
+		const int64_t have = r.prefix_len ? (int64_t) slen[t] : ((int64_t) tm[t].len - r.k + 1) * 2;
+		if(have < r.MinKlen || slen[t] == 0) continue;
+		new_id[t] = next++;
+	}
+	return next - 1;
+}
+
+// .length.b of a sparse index (makeindex.c:262-270): DB_size, lengths (slot 0: kmerindex), slengths, ulengths (slot 0: 0).
+// slen by template in file order, ulen by the id in the index (DB_size entries, as the device counted them)
+int sparse_write_length_b(const std::string &path, const std::vector<Tmpl> &tm, const std::vector<uint32_t> &new_id, uint32_t DB_size, int kmerindex,
+                          const std::vector<uint32_t> &slen, const std::vector<uint32_t> &ulen) {
+	std::vector<uint32_t> out((size_t) 1 + 3 * (size_t) DB_size, 0);
+	out[0] = DB_size;
+	uint32_t *lens = out.data() + 1, *sl = lens + DB_size, *ul = sl + DB_size;
+	lens[0] = (uint32_t) kmerindex;
+	for(size_t t = 0; t < tm.size(); ++t) {
+		const uint32_t id = new_id[t];
+		if(!id) continue;
+		lens[id] = (uint32_t) tm[t].len; sl[id] = slen[t]; ul[id] = ulen[id];
+	}
+	FILE *f = fopen(path.c_str(), "wb");
+	if(!f) { kmahip_set_error("cannot create %s", path.c_str()); return KMAHIP_EIO; }
+	bool ok = fwrite(out.data(), 4, out.size(), f) == out.size();
+	ok = (fclose(f) == 0) && ok;
+	if(!ok) { kmahip_set_error("writing %s failed", path.c_str()); return KMAHIP_EIO; }
+	return KMAHIP_OK;
+}
+
+// .seq.b and .name over the templates that stayed: (len >> 5) + 1 words each, 32 bases a word from the top, N as A
+int sparse_write_seq_and_names(const std::string &base, const std::vector<Tmpl> &tm, const std::vector<uint32_t> &new_id, const std::vector<uint8_t> &codes) {
+	FILE *f = fopen((base + ".seq.b").c_str(), "wb");
+	if(!f) { kmahip_set_error("cannot create %s.seq.b", base.c_str()); return KMAHIP_EIO; }
+	bool ok = true;
+	std::vector<uint64_t> words;
+	for(size_t t = 0; t < tm.size(); ++t) {
+		if(!new_id[t]) continue;
+		const Tmpl &x = tm[t];
+		words.assign((size_t) (x.len >> 5) + 1, 0);
+		for(int i = 0; i < x.len; ++i) words[(size_t) i >> 5] |= (uint64_t) (codes[x.at + (size_t) i] & 3) << (62 - ((i & 31) << 1));
+		ok = fwrite(words.data(), 8, words.size(), f) == words.size() && ok;
+	}
+	ok = (fclose(f) == 0) && ok;
+	f = fopen((base + ".name").c_str(), "wb");
+	if(!f) { kmahip_set_error("cannot create %s.name", base.c_str()); return KMAHIP_EIO; }
+	for(size_t t = 0; t < tm.size(); ++t) if(new_id[t]) ok = fprintf(f, "%s\n", tm[t].name.c_str()) > 0 && ok;
+	ok = (fclose(f) == 0) && ok;
+	if(!ok) { kmahip_set_error("writing the index under %s failed", base.c_str()); return KMAHIP_EIO; }
+	return KMAHIP_OK;
+}
+
+}  // namespace
