@@ -799,6 +799,10 @@ int kmahip_sam_write(const char *path, kmahip_db *db, const kmahip_reads *reads,
  * log(best)) in double, 0 for best <= 0), evaluated ON THE DEVICE by the one function all of those kernels call, for n triples in HOST
  * arrays. Exposed for tests: the device's log against the libm the reference links. */
 int kmahip_test_mapq(const int32_t *best, const int32_t *second, const int32_t *w, int64_t n, uint32_t *out);
+/* The neighbour move of the cooperative DP sweep (a DPP row or wavefront shift in place of __shfl_down(x, 1, w)), on one wavefront:
+ * out[l] = what lane l receives of in[0..64), w = 8, 16, 32 or 64 lanes per segment. What the last lane of a segment receives is
+ * unspecified (the sweep never uses it). Exposed for tests. */
+int kmahip_test_lane_down(const int32_t *in, int w, int32_t *out);
 
 /* The single-end run in KMA's DEFAULT mode (no -1t1) on one batch: kmahip_scan_chain, then every S2 record -- a read, or its
  * reverse complement where the record prints that, with its query bounds -- goes through stage 3a, ConClave, the `.res`
@@ -1049,6 +1053,12 @@ int kmahip_ws_scan_overflow(kmahip_ws *ws, void *stream, unsigned long long out[
  * of them and files that hit's diagonal when fewer bases differ along it (KMAHIP_SCAN_REFINE=0 in the environment: never). Counted
  * only while kmahip_scan_set_stats is on; read it before another stage is launched on the workspace. */
 int kmahip_ws_scan_diag_replaced(kmahip_ws *ws, void *stream, unsigned long long *out);
+/* Stage 3a's device-wide queues after the last alignment launch on the workspace (the register-only route, which hands its DP
+ * problems of 2..63 query columns to four class queues that one kernel sweeps): out[0..3] entries of the classes of 33..63,
+ * 17..32, 9..16 and 2..8 columns, out[4] tasks that waited for queued problems (the last result to arrive finishes such a task),
+ * out[5] hand-ons to the general kernel over the queues: tasks that gave up behind a problem they had queued, plus entries that
+ * found no room (KMAHIP_ALIGN_DQ_CAP=<n> in the environment caps the entries per queue: tests and timing only). */
+int kmahip_ws_align_queue_counts(kmahip_ws *ws, void *stream, unsigned long long out[6]);
 
 /* work figures of the last long-read trace call on this workspace (kmahip_align_trace_mt1*, kmahip_run_mt1, or the trace stage
  * on reads over 1 kb): DP problems solved, their cells (rows x columns; rows x (band + 1) for banded ones), MEMs of the chained

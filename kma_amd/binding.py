@@ -205,6 +205,8 @@ def lib():
             L.kmahip_ws_scan_routes.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]
         if hasattr(L, "kmahip_ws_scan_diag_replaced"):
             L.kmahip_ws_scan_diag_replaced.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]
+        if hasattr(L, "kmahip_ws_align_queue_counts"):
+            L.kmahip_ws_align_queue_counts.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]
         L.kmahip_ws_set_timing.argtypes = [C.c_void_p, C.c_int]
         L.kmahip_ws_get_timing.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         L.kmahip_align_se_dev.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Reads), C.POINTER(Cands), C.POINTER(Params),
@@ -368,6 +370,18 @@ def test_mapq(best, second, w):
     L.kmahip_test_mapq.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.kmahip_test_mapq.restype = C.c_int
     _check(L.kmahip_test_mapq(_p(b), _p(s), _p(ww), len(b), _p(out)))
+    return out
+
+
+def test_lane_down(values, w):
+    """kmahip_test_lane_down (a test hook): what each of a wavefront's 64 lanes receives from the sweep's neighbour move"""
+    v = np.ascontiguousarray(values, np.int32)
+    assert v.shape == (64,)
+    out = np.zeros(64, np.int32)
+    L = lib()
+    L.kmahip_test_lane_down.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.kmahip_test_lane_down.restype = C.c_int
+    _check(L.kmahip_test_lane_down(_p(v), int(w), _p(out)))
     return out
 
 
@@ -753,6 +767,12 @@ class KmaHipDB:
         out = C.c_ulonglong(0)
         _check(lib().kmahip_ws_scan_diag_replaced(self.ws, C.c_void_p(stream or 0), C.byref(out)))
         return int(out.value)
+
+    def get_align_queue_counts(self, stream=None) -> dict:
+        """stage 3a's class queues after the last alignment launch: entries per class, pending tasks, hand-ons over the queues"""
+        out = (C.c_ulonglong * 6)()
+        _check(lib().kmahip_ws_align_queue_counts(self.ws, C.c_void_p(stream or 0), out))
+        return dict(zip(("wide", "mid", "narrow", "tiny", "pending", "handed_on"), (int(x) for x in out)))
 
     def get_align_stats(self, stream=None) -> AlignStats:
         st = AlignStats()

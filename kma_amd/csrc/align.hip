@@ -85,8 +85,7 @@ struct AlignArgs {
 	int64_t *slow_list;      // tasks align_fast_kernel hands on (counters[2] of them); the general kernel run over a list takes its tasks from it
 	int use_list;            // align_tasks_kernel: the tasks are slow_list[0 .. counters[2]), handed out through counters[8]
 	int *dq; int64_t dq_cap; // align_fast_kernel's DP problems: four class queues of dq_cap entries of QENT ints (counters[AC_DQ + class])
-	int32_t *pend;           // its tasks that wait for queued problems (counters[AC_PEND]) ...
-	int *part;               // ... and their sums so far, PART_INTS per TASK
+	int *part;               // its tasks that wait for queued problems: their sums so far and the problems still out, PART_INTS per TASK
 	int per_round;           // tasks a wavefront takes per round (64; fewer over the list, whose tasks all bring DP problems for the wave's queues)
 	int seed_diag;           // seed_tasks_kernel: short reads without N's take the diagonal route (seed_view_diag)
 };
@@ -511,6 +510,39 @@ __device__ __forceinline__ Aln nw_auto(const Lane &L, const uint64_t *ts, int t_
 // counters as nw_full; neighbours come by shuffles (cell (m, n+1) from lane n+1's last step, (m+1, n+1) from the
 // step before that). All 64 lanes call this; segment g solves entry `first + g` (if < count) and its lane 0
 // overwrites the entry with the result: e[2..6] = score, len, match, tGaps, qGaps.
+// Two cheaper forms of nw_coop's step, measured in round 8 and NOT the default, because the step came out 0.05 ms slower with them
+// (DESIGN 4, round 8): -DKMAHIP_NW_DPP=1 the six neighbour moves as DPP moves, -DKMAHIP_NW_SUBREG=1 the four substitution scores of
+// a lane's column in registers. Timing builds only.
+#ifndef KMAHIP_NW_DPP
+#define KMAHIP_NW_DPP 0
+#endif
+#ifndef KMAHIP_NW_SUBREG
+#define KMAHIP_NW_SUBREG 0
+#endif
+
+// The neighbour moves of nw_coop's sweep: lane l's value of x from lane l + 1, as __shfl_down(x, 1, W) gives it to every lane but the
+// last of a W-lane segment. A shuffle narrower than the wavefront is a ds_bpermute (a trip through the LDS crossbar); the DPP
+// controls move the value inside the register file: row_shl:1 (0x101) within rows of 16 lanes, wave_shl:1 (0x130) across the wavefront.
+// What the LAST lane of a segment receives differs from the shuffle (its own value there; here its own value at a row's or the
+// wavefront's end, else the next segment's first lane) and is never used: that lane owns column W - 1, which is a query column only
+// when q_len == W (classes of at most W columns; never with W = 64: q_len <= 63), and then it is the lane n == q_len - 1 whose six
+// neighbour values the boundary column overrides; otherwise it is no column at all and computes nothing.
+// tests/test_dp_queues_gpu.py pins direction and edges of the DPP form against the shuffle through kmahip_test_lane_down.
+template <int W>
+__device__ __forceinline__ int lane_down_dpp(int x) {
+	if(W <= 16) return __builtin_amdgcn_update_dpp(x, x, 0x101, 0xF, 0xF, false);
+	return __builtin_amdgcn_update_dpp(x, x, 0x130, 0xF, 0xF, false);
+}
+
+template <int W>
+__device__ __forceinline__ int lane_down(int x) {
+#if KMAHIP_NW_DPP
+	return lane_down_dpp<W>(x);
+#else
+	return __shfl_down(x, 1, W);
+#endif
+}
+
 template <int W>
 __device__ void nw_coop(const Lane &L, const DevDB &db, const AlignArgs &A, int *qu, int first, int count, uint8_t *tbuf_wave) {
 	constexpr int G = 64 / W;
@@ -540,6 +572,10 @@ __device__ void nw_coop(const Lane &L, const DevDB &db, const AlignArgs &A, int 
 	q.N = A.N + A.N_off[rd]; q.nN = (int) (A.N_off[rd + 1] - A.N_off[rd]);
 	const bool col = live && n < q_len;
 	const int qc = col ? qn(q, q_s + n) : 0;
+#if KMAHIP_NW_SUBREG
+	// the lane's query base is fixed for the sweep: the four scores its column can meet (a staged template base is 0..3), once
+	const int sub0 = L.d[qc], sub1 = L.d[5 + qc], sub2 = L.d[10 + qc], sub3 = L.d[15 + qc];
+#endif
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 	__builtin_amdgcn_wave_barrier();
 	// state: `last` = the row this lane computed most recently (start: boundary row m = t_len), `before` = the row before it
@@ -551,8 +587,8 @@ __device__ void nw_coop(const Lane &L, const DevDB &db, const AlignArgs &A, int 
 	int steps = live ? t_len + q_len - 1 : 0;
 	for(int o = 32; o > 0; o >>= 1) steps = max(steps, __shfl_xor(steps, o));
 	for(int d = 0; d < steps; ++d) {
-		int rD = __shfl_down(lD, 1, W), rQ = __shfl_down(lQ, 1, W), dD = __shfl_down(bD, 1, W);
-		uint32_t rTD = __shfl_down(lTD, 1, W), rTQ = __shfl_down(lTQ, 1, W), dTD = __shfl_down(bTD, 1, W);
+		int rD = lane_down<W>(lD), rQ = lane_down<W>(lQ), dD = lane_down<W>(bD);
+		uint32_t rTD = (uint32_t) lane_down<W>((int) lTD), rTQ = (uint32_t) lane_down<W>((int) lTQ), dTD = (uint32_t) lane_down<W>((int) bTD);
 		const int i = d - (q_len - 1 - n);
 		if(col && i >= 0 && i < t_len) {
 			const int m = t_len - 1 - i;
@@ -564,7 +600,7 @@ __device__ void nw_coop(const Lane &L, const DevDB &db, const AlignArgs &A, int 
 				if(m + 1 == t_len) { dD = 0; dTD = 0; }
 				else { dD = (0 < k) ? 0 : (W1 + (t_len - 2 - m) * U); dTD = (0 < k) ? 0u : QG * (uint32_t) (t_len - 1 - m); }
 			}
-			const int *drow = L.d + 5 * (int) tbuf[m];
+			const int tb = (int) tbuf[m];
 			int Q = rD + W1, P = lD + W1, D, mv;
 			bool ob = false;
 			if(Q < P) { D = P; mv = 4; } else { D = Q; mv = 2; }
@@ -572,7 +608,11 @@ __device__ void nw_coop(const Lane &L, const DevDB &db, const AlignArgs &A, int 
 			if(Q < x) { Q = x; if(D <= x) { D = x; mv = 3; } } else ob = true;
 			x = lP + U;
 			if(P < x) { P = x; if(D <= x) { D = x; mv = 5; } } else ob = true;
-			x = dD + drow[qc];
+#if KMAHIP_NW_SUBREG
+			x = dD + (tb == 0 ? sub0 : tb == 1 ? sub1 : tb == 2 ? sub2 : sub3);
+#else
+			x = dD + L.d[5 * tb + qc];
+#endif
 			if(D <= x) { D = x; mv = 1; }
 			const uint32_t TQ = TG + (ob ? rTD : rTQ);
 			const uint32_t TP = QG + (ob ? lTD : lTP);
@@ -1491,25 +1531,29 @@ __global__ __launch_bounds__(ATHREADS, 4) void align_tasks_kernel(const AlignArg
 // arguments of kma_score in private memory (1 136 B of scratch per lane, 128 VGPRs, 4 waves / SIMD; counter traffic 11x the
 // algorithmic bytes). But what nearly every task of a short-read sample needs is little: the <= SEEDS MEMs seed_tasks_kernel handed
 // over, chainSeeds over those few, and tails / links that are provably diagonal (nw_diagonal) or one column wide. Stage 3a is
-// therefore four launches:
+// therefore three launches:
 //   align_fast_kernel    a lane per task, the MEMs, the chain and the running sums in registers -- no scratch, nothing of KMA_score
 //                        in memory. A DP problem of 2..63 columns is not solved here: its descriptor goes to a DEVICE-WIDE queue
 //                        of its width class (results are only ever summed into the task's figures, so the walk goes on), the task's
-//                        sums so far to a row of `part`, the task to the pending list. Queue entries, pending and handed-on tasks
+//                        sums so far to a row of `part`, with the number of problems it waits for. Queue entries and handed-on tasks
 //                        are staged per wavefront in LDS and appended with one global atomic per list and flush (a lane's own
 //                        atomic per entry on one address would cost more than the kernel).
-//   dp_queue_kernel<W>   per width class, the cooperative anti-diagonal sweep nw_coop<W> over the whole queue -- dense: every
-//                        segment of every wavefront has a problem -- adding each result into its task's row of `part`.
-//   pend_finish_kernel   the filters of phase C for the pending tasks, from their rows.
+//   dp_queues_kernel     one launch over the four queues: a wavefront takes every n-th unit (a class, 64 / W entries) of one list,
+//                        widest class first, sweeps them with nw_coop<W> -- dense: every segment has a problem -- and adds each result
+//                        into its task's row of `part`; the arrival that counts the row's word down to zero runs the filters of phase C.
 //   align_tasks_kernel   the general kernel, over the list of tasks the first handed on: no MEMs from the seeding kernel (N-rich
 //                        or repeat-rich reads, > SEEDS MEMs), a strand tie, a problem of 64 and more columns or a banded one, a
 //                        chain that fails after queueing. It runs last and overwrites whatever the others left for such a task.
 // The join rule and the end bonuses are the functions of chain_dev.h that chain_seeds above calls too; the three windows are written
 // out here as in kma_score (their kernels' spill counts move through the header's functions, DESIGN.md "One chaining rule");
 // tests/test_align_gpu.py runs both routes against the oracle (KMAHIP_ALIGN_FAST=0: the general kernel for every task).
-constexpr int AC_DQ = 16, AC_PEND = 20, DQ_CLASSES = 4;      // counters: entries of the class queues (wide 33..63 columns, narrow 9..16, tiny 2..8, mid 17..32), pending tasks
-constexpr int DQ_STAGE = 96, PEND_STAGE = 96, PUNT_STAGE = 64;      // per wavefront, in LDS
-constexpr int PART_INTS = 16;                    // a pending task's row: S0 (6), S1 (6), kind, qlen0, qlen1, -
+// counters: entries of the class queues (wide 33..63 columns, narrow 9..16, tiny 2..8, mid 17..32), and two figures for diagnostics:
+// pending tasks, hand-ons that concern the queues (fast_flush)
+constexpr int AC_DQ = KMAHIP_C_ADQ, AC_PEND = AC_DQ + 4, AC_HAND = AC_DQ + 5, DQ_CLASSES = 4;
+constexpr int DQ_STAGE = 96, PUNT_STAGE = 64;      // per wavefront, in LDS
+// a pending task's row: S0 (6), S1 (6), kind, qlen0, qlen1, and the problems it still waits for -- or ROW_HANDED: the general kernel
+// has the task, no number of arrivals brings the word to zero
+constexpr int PART_INTS = 16, ROW_HANDED = 1 << 30;
 
 template <class T>
 __device__ __forceinline__ T sel4(const T (&a)[SEEDS], int i) { return i == 0 ? a[0] : i == 1 ? a[1] : i == 2 ? a[2] : a[3]; }
@@ -1517,7 +1561,7 @@ __device__ __forceinline__ T sel4(const T (&a)[SEEDS], int i) { return i == 0 ? 
 struct FastCtx {
 	const int *d;              // 25 ints in LDS
 	int M, MM, U, W1;
-	int *st_cnt;               // this wave's staging counters in LDS: [0] queue entries, [1] pending tasks, [2] handed-on tasks
+	int *st_cnt;               // this wave's staging counters in LDS: [0] queue entries, [2] handed-on tasks; counted only: [1] pending tasks, [3] tasks handed on behind a queued problem
 	int *st_dq;                // DQ_STAGE entries of QENT ints
 	int task32, at, mate, rc;  // the KMA_score call being run, for the queue entries
 	int64_t rd;
@@ -1666,11 +1710,11 @@ constexpr int FTHREADS = 256;
 #endif
 
 // the staged entries of a wavefront to the device-wide lists: one global atomic per list that has something. Called by all 64 lanes.
-__device__ void fast_flush(const AlignArgs &A, int *st_cnt, const int *st_dq, const int *st_pend, const int *st_punt) {
+__device__ void fast_flush(const AlignArgs &A, int *st_cnt, const int *st_dq, const int *st_punt) {
 	const int lane = (int) (threadIdx.x & 63);
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 	__builtin_amdgcn_wave_barrier();
-	const int nq = min(DQ_STAGE, st_cnt[0]), np = min(PEND_STAGE, st_cnt[1]), nu = min(PUNT_STAGE, st_cnt[2]);
+	const int nq = min(DQ_STAGE, st_cnt[0]), np = st_cnt[1], nu = min(PUNT_STAGE, st_cnt[2]), nh = st_cnt[3];
 	for(int c0 = 0; c0 < nq; c0 += 64) {
 		const int i = c0 + lane;
 		const int cls = i < nq ? (st_dq[i * QENT + 1] >> 1) : -1;
@@ -1689,21 +1733,17 @@ __device__ void fast_flush(const AlignArgs &A, int *st_cnt, const int *st_dq, co
 					dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2];
 				} else {
 					// no room (the host sized the queues for the usual sample): the general kernel takes the task, and its row -- written
-					// by this wavefront before it staged the entry -- says so to pend_finish_kernel
+					// by this wavefront before this store, with its count -- says so to every problem of the task that did find room
 					A.slow_list[atomicAdd(&A.counters[2], 1ull)] = st_dq[i * QENT];
-					A.part[(int64_t) st_dq[i * QENT] * PART_INTS + 15] = 1;
+					A.part[(int64_t) st_dq[i * QENT] * PART_INTS + 15] = ROW_HANDED;
+					atomicAdd(&A.counters[AC_HAND], 1ull);
 				}
 			}
 		}
 	}
-	for(int c0 = 0; c0 < np; c0 += 64) {
-		const int i = c0 + lane;
-		const unsigned long long m = __ballot(i < np);
-		unsigned long long first = 0;
-		if(lane == 0) first = atomicAdd(&A.counters[AC_PEND], (unsigned long long) __popcll(m));
-		first = __shfl(first, 0);
-		if(i < np) A.pend[first + lane] = st_pend[i];
-	}
+	// (diagnostics: tasks left pending; tasks punted behind a queued problem -- with the entries without room above: AC_HAND)
+	if(lane == 0 && np) atomicAdd(&A.counters[AC_PEND], (unsigned long long) np);
+	if(lane == 0 && nh) atomicAdd(&A.counters[AC_HAND], (unsigned long long) nh);
 	for(int c0 = 0; c0 < nu; c0 += 64) {
 		const int i = c0 + lane;
 		const unsigned long long m = __ballot(i < nu);
@@ -1714,7 +1754,7 @@ __device__ void fast_flush(const AlignArgs &A, int *st_cnt, const int *st_dq, co
 	}
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 	__builtin_amdgcn_wave_barrier();
-	if(lane < 3) st_cnt[lane] = 0;
+	if(lane < 4) st_cnt[lane] = 0;
 	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 	__builtin_amdgcn_wave_barrier();
 }
@@ -1724,13 +1764,12 @@ __global__ __launch_bounds__(FTHREADS, KMAHIP_FAST_WAVES) void align_fast_kernel
 	__shared__ int s_d[25];
 	__shared__ int s_cnt[(FTHREADS / 64) * 4];
 	__shared__ __attribute__((aligned(16))) int s_dq[(FTHREADS / 64) * DQ_STAGE * QENT];
-	__shared__ int s_pend[(FTHREADS / 64) * PEND_STAGE];
 	__shared__ int s_punt[(FTHREADS / 64) * PUNT_STAGE];
 	if(threadIdx.x < 25) s_d[threadIdx.x] = A.d[threadIdx.x];
 	if(threadIdx.x < (FTHREADS / 64) * 4) s_cnt[threadIdx.x] = 0;
 	__syncthreads();
 	const int wave = (int) (threadIdx.x >> 6), lane = (int) (threadIdx.x & 63);
-	int *const st_cnt = s_cnt + wave * 4, *const st_dq = s_dq + wave * DQ_STAGE * QENT, *const st_pend = s_pend + wave * PEND_STAGE, *const st_punt = s_punt + wave * PUNT_STAGE;
+	int *const st_cnt = s_cnt + wave * 4, *const st_dq = s_dq + wave * DQ_STAGE * QENT, *const st_punt = s_punt + wave * PUNT_STAGE;
 	FastCtx C;
 	C.d = s_d; C.M = A.M; C.MM = A.MM; C.U = A.U; C.W1 = A.W1; C.st_cnt = st_cnt; C.st_dq = st_dq;
 	C.task32 = 0; C.at = 0; C.mate = 0; C.rc = 0; C.rd = 0; C.n_queued = 0;
@@ -1831,69 +1870,104 @@ __global__ __launch_bounds__(FTHREADS, KMAHIP_FAST_WAVES) void align_fast_kernel
 					const int slot = atomicAdd(&st_cnt[2], 1);
 					if(slot < PUNT_STAGE) st_punt[slot] = (int) task;
 					else A.slow_list[atomicAdd(&A.counters[2], 1ull)] = task;
+					// what it has staged stays in the queues: its row says that the general kernel has the task, or the results would be
+					// added to whatever an earlier batch left there and could count a stale word down to zero
+					if(queued) { A.part[task * PART_INTS + 15] = ROW_HANDED; atomicAdd(&st_cnt[3], 1); }
 				} else if(queued) {
-					// the sums so far; the queues' results are added to this row, pend_finish_kernel filters it
+					// the sums so far and the number of queued problems: dp_queues_kernel adds each result to this row and counts down;
+					// the last arrival filters the row (one count for both mates of a couple)
 					int4 *row = (int4 *) (A.part + task * PART_INTS);
 					row[0] = make_int4(S0.score, S0.len, S0.pos, S0.match);
 					row[1] = make_int4(S0.tGaps, S0.qGaps, S1.score, S1.len);
 					row[2] = make_int4(S1.pos, S1.match, S1.tGaps, S1.qGaps);
-					row[3] = make_int4(kind, qlen0, qlen1, 0);
-					const int slot = atomicAdd(&st_cnt[1], 1);
-					if(slot < PEND_STAGE) st_pend[slot] = (int) task;
-					else A.pend[atomicAdd(&A.counters[AC_PEND], 1ull)] = (int) task;
+					row[3] = make_int4(kind, qlen0, qlen1, queued);
+					atomicAdd(&st_cnt[1], 1);
 				} else task_finish<PEM>(A, task, kind, S0, S1, tmpl_out, t_len, qlen0, qlen1, k);
 			}
 		}
 		// a round can stage 64 x 5 entries at most, usually one or two: flush when half full (a lane that finds no slot hands its task on)
 		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 		__builtin_amdgcn_wave_barrier();
-		if(st_cnt[0] >= DQ_STAGE / 2 || st_cnt[1] >= PEND_STAGE / 2 || st_cnt[2] >= PUNT_STAGE / 2 || base + stride >= n_tasks) fast_flush(A, st_cnt, st_dq, st_pend, st_punt);
+		if(st_cnt[0] >= DQ_STAGE / 2 || st_cnt[2] >= PUNT_STAGE / 2 || base + stride >= n_tasks) fast_flush(A, st_cnt, st_dq, st_punt);
 	}
 }
 
-// the queue of one width class: nw_coop<W> over every entry, the result added to the task's row
-template <int W>
-__global__ __launch_bounds__(256) void dp_queue_kernel(const AlignArgs A, int cls) {
+// one unit of dp_queues_kernel: the 64 / W entries of class `cls` from `first`, nw_coop<W> over them, each result added to its task's row.
+// The lane that holds a segment's result then counts the task's word down, once its adds are done, and the one arrival that brings
+// the word to zero filters the row (phase C), which it reads back with device-scope atomic loads: the other arrivals' adds were
+// device-scope atomics, a plain load could be served from a cache line this CU or this die's L2 holds.
+// Everything one arrival tells another goes through device-scope atomics on the row, which are carried out where the whole device
+// sees them; what the order needs is that the adds are DONE before the decrement is sent, and a returning decrement is done before
+// the loads behind it are sent. DQ_ORDER_ADDS waits for the acknowledgement of the adds (vmcnt counts atomics without a return
+// value) and keeps the compiler from moving memory operations across. A device-scope fence (__threadfence) in its place is correct
+// too and was measured: its release half writes the die's whole L2 back, once per arrival, and the step went from 12.0 to 15.8 ms
+// (-DKMAHIP_DQ_FENCE=1 builds that).
+// A row marked ROW_HANDED (no room in a queue, or the task punted behind a queued problem) never gets to zero: the general kernel,
+// which may run beside this one, owns that task's outputs. Couples: one row and one count for both mates, the entry's mate bit
+// selects the half the result is added to.
+#if KMAHIP_DQ_FENCE
+#define DQ_ORDER_ADDS() __threadfence()
+#else
+#define DQ_ORDER_ADDS() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#endif
+template <int W, bool PEM>
+__device__ __forceinline__ void dq_unit(const Lane &L, const AlignArgs &A, int cls, int first, int count, uint8_t *tbuf, int k) {
+	const int lane = (int) (threadIdx.x & 63);
+	int *const qu = A.dq + (size_t) cls * A.dq_cap * QENT - 1;          // (nw_coop counts its entries from qu + 1)
+	nw_coop<W>(L, A.db, A, qu, first, count, tbuf);
+	const int g = lane / W;
+	if((lane & (W - 1)) == 0 && first + g < count) {
+		const int *e = qu + 1 + (first + g) * QENT;
+		const int64_t task = e[0];
+		int *const row0 = A.part + task * PART_INTS, *const row = row0 + (e[1] & 1) * 6;
+		atomicAdd(&row[0], e[2]); atomicAdd(&row[1], e[3]); atomicAdd(&row[3], e[4]); atomicAdd(&row[4], e[5]); atomicAdd(&row[5], e[6]);
+		if(e[11] & 1) atomicAdd(&row[2], -(e[3] - e[5]));
+		DQ_ORDER_ADDS();
+		if(atomicSub(&row0[15], 1) == 1) {
+			int v[12];
+#pragma unroll
+			for(int i = 0; i < 12; ++i) v[i] = __hip_atomic_load(&row0[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			const Aln S0 = {v[0], v[1], v[2], v[3], v[4], v[5]}, S1 = {v[6], v[7], v[8], v[9], v[10], v[11]};
+			const int tmpl_out = A.T[task];
+			task_finish<PEM>(A, task, row0[12], S0, S1, tmpl_out, A.db.tlen[abs(tmpl_out)], row0[13], row0[14], k);
+		}
+	}
+	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+	__builtin_amdgcn_wave_barrier();          // (the staged template bases are the next problem's)
+}
+
+// The four class queues in one launch. A unit of work is a class and the first entry of a group of 64 / W; the units are numbered
+// widest class first (33..63 columns, 17..32, 9..16, 2..8), so that the long sweeps start first and the short ones fill the end, and
+// a wavefront takes every n_waves-th unit: with some ten units per wavefront, neighbours in the list -- alike in width -- go to
+// different wavefronts. No wavefront waits for another. (Units claimed one by one from a device-wide counter were measured and
+// taken out: 74 k returning atomics on one word took longer than the sweeps, 1.05 ms for the kernel whatever else changed, and
+// claims of four units or a counter for the last fifth only did no better: DESIGN 3.2, round 8.)
+#ifndef KMAHIP_DQ_WAVES
+#define KMAHIP_DQ_WAVES 8
+#endif
+template <bool PEM>
+__global__ __launch_bounds__(256, KMAHIP_DQ_WAVES) void dp_queues_kernel(const AlignArgs A) {
 	__shared__ int s_d[25];
 	__shared__ uint8_t s_tbuf[4 * TBUF];
 	if(threadIdx.x < 25) s_d[threadIdx.x] = A.d[threadIdx.x];
 	__syncthreads();
-	constexpr int G = 64 / W;
 	const int wave = (int) (threadIdx.x >> 6), lane = (int) (threadIdx.x & 63);
 	Lane L;
 	L.s32 = nullptr; L.s64 = nullptr; L.r32 = nullptr; L.r64 = nullptr; L.lanes = 0; L.cap1 = 0; L.ncols = 0;
 	L.d = s_d; L.M = A.M; L.MM = A.MM; L.U = A.U; L.W1 = A.W1; L.wide = nullptr; L.queue = nullptr; L.xq = nullptr; L.xq_cnt = nullptr; L.xq_cap = 0;
 	L.q_at = 0; L.q_mate = 0; L.q_rd = 0; L.ablate = 0; L.gap_m_max = A.gap_m_max; L.diag_uniform = 1; L.cnt = nullptr;
-	const int count = (int) min((unsigned long long) A.dq_cap, A.counters[AC_DQ + cls]);
-	int *const qu = A.dq + (size_t) cls * A.dq_cap * QENT - 1;          // (nw_coop counts its entries from qu + 1)
-	uint8_t *const tbuf = s_tbuf + wave * TBUF;
-	const int n_waves = (int) gridDim.x * 4;
-	for(int first = ((int) blockIdx.x * 4 + wave) * G; first < count; first += n_waves * G) {
-		nw_coop<W>(L, A.db, A, qu, first, count, tbuf);
-		const int g = lane / W;
-		if((lane & (W - 1)) == 0 && first + g < count) {
-			const int *e = qu + 1 + (first + g) * QENT;
-			int *row = A.part + (int64_t) e[0] * PART_INTS + (e[1] & 1) * 6;
-			atomicAdd(&row[0], e[2]); atomicAdd(&row[1], e[3]); atomicAdd(&row[3], e[4]); atomicAdd(&row[4], e[5]); atomicAdd(&row[5], e[6]);
-			if(e[11] & 1) atomicAdd(&row[2], -(e[3] - e[5]));
-		}
-		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-		__builtin_amdgcn_wave_barrier();          // (the staged template bases are the next problem's)
-	}
-}
-
-template <bool PEM>
-__global__ __launch_bounds__(256) void pend_finish_kernel(const AlignArgs A) {
-	const int64_t n = (int64_t) A.counters[AC_PEND];
 	const int k = (int) A.db.kmersize;
-	for(int64_t i = (int64_t) blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t) gridDim.x * 256) {
-		const int64_t task = A.pend[i];
-		const int4 *row = (const int4 *) (A.part + task * PART_INTS);
-		const int4 a = row[0], b = row[1], c = row[2], d = row[3];
-		if(d.w) continue;          // (handed on after all: a queue had no room)
-		const Aln S0 = {a.x, a.y, a.z, a.w, b.x, b.y}, S1 = {b.z, b.w, c.x, c.y, c.z, c.w};
-		const int tmpl_out = A.T[task];
-		task_finish<PEM>(A, task, d.x, S0, S1, tmpl_out, A.db.tlen[abs(tmpl_out)], d.y, d.z, k);
+	uint8_t *const tbuf = s_tbuf + wave * TBUF;
+	// entries per class (dq_cap <= 2^26: the units fit an int) and the first unit number after each class, in the order of the sweep
+	const int n_wide = (int) min((unsigned long long) A.dq_cap, A.counters[AC_DQ + 0]), n_mid = (int) min((unsigned long long) A.dq_cap, A.counters[AC_DQ + 3]);
+	const int n_narrow = (int) min((unsigned long long) A.dq_cap, A.counters[AC_DQ + 1]), n_tiny = (int) min((unsigned long long) A.dq_cap, A.counters[AC_DQ + 2]);
+	const int u_wide = n_wide, u_mid = u_wide + (n_mid + 1) / 2, u_narrow = u_mid + (n_narrow + 3) / 4, u_tiny = u_narrow + (n_tiny + 7) / 8;
+	const int n_waves = (int) gridDim.x * 4;
+	for(int unit = (int) blockIdx.x * 4 + wave; unit < u_tiny; unit += n_waves) {
+		if(unit < u_wide) dq_unit<64, PEM>(L, A, 0, unit, n_wide, tbuf, k);
+		else if(unit < u_mid) dq_unit<32, PEM>(L, A, 3, (unit - u_wide) * 2, n_mid, tbuf, k);
+		else if(unit < u_narrow) dq_unit<16, PEM>(L, A, 1, (unit - u_mid) * 4, n_narrow, tbuf, k);
+		else dq_unit<8, PEM>(L, A, 2, (unit - u_narrow) * 8, n_tiny, tbuf, k);
 	}
 }
 
@@ -2838,13 +2912,13 @@ static int launch_align(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 	if(ws->a_task_cap < tasks_cap) {
 		(void) hipFree(ws->a_task);
 		ws->a_task = nullptr;
-		// (per task: seeds 64 B, norm 8, hand-on list 8, eight int columns 32, pending list 4, row of sums 64, class queues 4 x 48 / 4)
-		HIP_TRY(hipMalloc((void **) &ws->a_task, (size_t) tasks_cap * (2 * SEEDS * 8 + 8 + 8 + 8 * 4 + 4 + PART_INTS * 4) + DQ_CLASSES * (size_t) (tasks_cap / 4 + 4096) * QENT * 4 + 64));
+		// (per task: seeds 64 B, norm 8, hand-on list 8, eight int columns 32, row of sums 64, class queues 4 x 48 / 4)
+		HIP_TRY(hipMalloc((void **) &ws->a_task, (size_t) tasks_cap * (2 * SEEDS * 8 + 8 + 8 + 8 * 4 + PART_INTS * 4) + DQ_CLASSES * (size_t) (tasks_cap / 4 + 4096) * QENT * 4 + 64));
 		ws->a_task_cap = tasks_cap;
 	}
 	if(!ws->counters) { HIP_TRY(hipMalloc((void **) &ws->counters, KMAHIP_N_COUNTERS * sizeof(unsigned long long))); HIP_TRY(hipMemset(ws->counters, 0, KMAHIP_N_COUNTERS * sizeof(unsigned long long))); }
 	HIP_TRY(hipMemsetAsync(ws->counters + 2, 0, 7 * sizeof(unsigned long long), stream));      // [2] .. [8]
-	HIP_TRY(hipMemsetAsync(ws->counters + AC_DQ, 0, (DQ_CLASSES + 1) * sizeof(unsigned long long), stream));  // the class queues and the pending list
+	HIP_TRY(hipMemsetAsync(ws->counters + AC_DQ, 0, (DQ_CLASSES + 2) * sizeof(unsigned long long), stream));  // the class queues, the two diagnostic counts
 
 	AlignArgs A;
 	A.db = db->dev;
@@ -2863,9 +2937,10 @@ static int launch_align(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 	A.slow_list = (int64_t *) (norm + tasks_cap); A.use_list = 0; A.per_round = 64;
 	A.part = (int *) (A.slow_list + tasks_cap);                         // (rows of 64 bytes, 16-byte aligned: everything before is)
 	A.dq_cap = std::min<int64_t>(tasks_cap / 4 + 4096, 1ll << 26);
+	// (KMAHIP_ALIGN_DQ_CAP=<n>: fewer entries per class queue, for tests and timing of the hand-on path)
+	if(const char *e = getenv("KMAHIP_ALIGN_DQ_CAP")) A.dq_cap = std::min<int64_t>(A.dq_cap, std::max(1, atoi(e)));
 	A.dq = A.part + (size_t) PART_INTS * tasks_cap;
 	int32_t *ti = (int32_t *) (A.dq + DQ_CLASSES * (size_t) (tasks_cap / 4 + 4096) * QENT);
-	A.pend = ti + 8 * tasks_cap;
 	A.t_norm = norm; A.t_score = ti; A.t_alen = ti + tasks_cap; A.t_start = ti + 2 * tasks_cap; A.t_end = ti + 3 * tasks_cap; A.t_tmpl = ti + 4 * tasks_cap;
 	int32_t *t_rec = ti + 5 * tasks_cap;
 	A.seed_slots = rec_mate ? 2 : 1;
@@ -2969,13 +3044,11 @@ static int launch_align(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 		} else if(A.pe_mode) hipLaunchKernelGGL((align_tasks_kernel<false, true, false>), agrid, dim3(ATHREADS), 0, gstream, A);
 		else hipLaunchKernelGGL((align_tasks_kernel<false, false, false>), agrid, dim3(ATHREADS), 0, gstream, A);
 		if(fast) {
-			const dim3 qgrid(1024);
-			hipLaunchKernelGGL((dp_queue_kernel<8>), qgrid, dim3(256), 0, stream, A, 2);
-			hipLaunchKernelGGL((dp_queue_kernel<16>), qgrid, dim3(256), 0, stream, A, 1);
-			hipLaunchKernelGGL((dp_queue_kernel<32>), qgrid, dim3(256), 0, stream, A, 3);
-			hipLaunchKernelGGL((dp_queue_kernel<64>), qgrid, dim3(256), 0, stream, A, 0);
-			if(A.pe_mode) hipLaunchKernelGGL((pend_finish_kernel<true>), dim3(512), dim3(256), 0, stream, A);
-			else hipLaunchKernelGGL((pend_finish_kernel<false>), dim3(512), dim3(256), 0, stream, A);
+			// 6 wavefronts / SIMD on 256 CUs: at 64 VGPRs the kernel could have 8, and measures the same alone; 6 leave a quarter of the
+			// registers to the general kernel's wavefronts beside it, which otherwise start when these end
+			const dim3 qgrid(256 * 6);
+			if(A.pe_mode) hipLaunchKernelGGL((dp_queues_kernel<true>), qgrid, dim3(256), 0, stream, A);
+			else hipLaunchKernelGGL((dp_queues_kernel<false>), qgrid, dim3(256), 0, stream, A);
 			if(gstream != stream) {
 				HIP_TRY(hipEventRecord(ws->a_ev[1], gstream));
 				HIP_TRY(hipStreamWaitEvent(stream, ws->a_ev[1], 0));
@@ -2985,10 +3058,10 @@ static int launch_align(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 			unsigned long long c[7];
 			HIP_TRY(hipStreamSynchronize(stream));
 			HIP_TRY(hipMemcpy(c, ws->counters + 2, sizeof c, hipMemcpyDeviceToHost));
-			unsigned long long q[DQ_CLASSES + 1];
+			unsigned long long q[DQ_CLASSES + 2];
 			HIP_TRY(hipMemcpy(q, ws->counters + AC_DQ, sizeof q, hipMemcpyDeviceToHost));
-			fprintf(stderr, "[kmahip] align: %llu tasks handed on to the general kernel (%d per wavefront round); %llu pending on queued problems: %llu wide, %llu mid, %llu narrow, %llu tiny (room for %lld each)\n",
-			        c[0], A.per_round, q[DQ_CLASSES], q[0], q[3], q[1], q[2], (long long) A.dq_cap);
+			fprintf(stderr, "[kmahip] align: %llu tasks handed on to the general kernel (%d per wavefront round), %llu of them over the queues; %llu pending on queued problems: %llu wide, %llu mid, %llu narrow, %llu tiny (room for %lld each)\n",
+			        c[0], A.per_round, q[AC_HAND - AC_DQ], q[AC_PEND - AC_DQ], q[0], q[3], q[1], q[2], (long long) A.dq_cap);
 		}
 		A.use_list = 0; A.per_round = 64;
 	}
@@ -3109,6 +3182,28 @@ extern "C" int kmahip_test_mapq(const int32_t *best, const int32_t *second, cons
 	if(e == hipSuccess) e = hipMemcpy(out, d + 3 * n, (size_t) n * 4, hipMemcpyDeviceToHost);
 	(void) hipFree(d);
 	if(e != hipSuccess) { kmahip_set_error("kmahip_test_mapq: %s", hipGetErrorString(e)); return KMAHIP_EDEVICE; }
+	return KMAHIP_OK;
+}
+
+// test hook: lane_down_dpp<W> -- the DPP form of the neighbour move of nw_coop's sweep -- on one wavefront: out[l] = what lane l receives of in[0..64)
+template <int W>
+static __global__ void test_lane_down_kernel(const int32_t *in, int32_t *out) { out[threadIdx.x] = lane_down_dpp<W>(in[threadIdx.x]); }
+
+extern "C" int kmahip_test_lane_down(const int32_t *in, int w, int32_t *out) {
+	if(!in || !out || (w != 8 && w != 16 && w != 32 && w != 64)) { kmahip_set_error("kmahip_test_lane_down: bad argument"); return KMAHIP_EINVAL; }
+	int32_t *d = nullptr;
+	if(hipMalloc((void **) &d, 128 * 4) != hipSuccess) { kmahip_set_error("kmahip_test_lane_down: no device memory"); return KMAHIP_ENOMEM; }
+	hipError_t e = hipMemcpy(d, in, 64 * 4, hipMemcpyHostToDevice);
+	if(e == hipSuccess) {
+		if(w == 8) hipLaunchKernelGGL(test_lane_down_kernel<8>, dim3(1), dim3(64), 0, 0, d, d + 64);
+		else if(w == 16) hipLaunchKernelGGL(test_lane_down_kernel<16>, dim3(1), dim3(64), 0, 0, d, d + 64);
+		else if(w == 32) hipLaunchKernelGGL(test_lane_down_kernel<32>, dim3(1), dim3(64), 0, 0, d, d + 64);
+		else hipLaunchKernelGGL(test_lane_down_kernel<64>, dim3(1), dim3(64), 0, 0, d, d + 64);
+		e = hipGetLastError();
+	}
+	if(e == hipSuccess) e = hipMemcpy(out, d + 64, 64 * 4, hipMemcpyDeviceToHost);
+	(void) hipFree(d);
+	if(e != hipSuccess) { kmahip_set_error("kmahip_test_lane_down: %s", hipGetErrorString(e)); return KMAHIP_EDEVICE; }
 	return KMAHIP_OK;
 }
 

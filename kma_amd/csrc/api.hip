@@ -136,6 +136,17 @@ extern "C" int kmahip_ws_scan_diag_replaced(kmahip_ws *ws, void *stream, unsigne
 	return KMAHIP_OK;
 }
 
+// stage 3a's class queues after the last alignment launch: entries of the classes wide (33..63 columns), mid (17..32), narrow (9..16)
+// and tiny (2..8), the tasks left pending on them, and the hand-ons over the queues
+extern "C" int kmahip_ws_align_queue_counts(kmahip_ws *ws, void *stream, unsigned long long out[6]) {
+	if(!ws || !out || !ws->counters) return KMAHIP_EINVAL;
+	unsigned long long c[6];
+	HIP_TRY(hipMemcpyAsync(c, ws->counters + KMAHIP_C_ADQ, sizeof c, hipMemcpyDeviceToHost, (hipStream_t) stream));
+	HIP_TRY(hipStreamSynchronize((hipStream_t) stream));
+	out[0] = c[0]; out[1] = c[3]; out[2] = c[1]; out[3] = c[2]; out[4] = c[4]; out[5] = c[5];
+	return KMAHIP_OK;
+}
+
 extern "C" int kmahip_align_get_stats(kmahip_ws *ws, kmahip_align_stats *st, void *stream) {
 	if(!ws || !st || !ws->counters) return KMAHIP_EINVAL;
 	unsigned long long c[8];

@@ -9,11 +9,14 @@
 
 #define KMAHIP_EMPTY_VI 0xFFFFFFFFu
 #define KMAHIP_BUCKET_SLOTS 4
-#define KMAHIP_N_COUNTERS 24
+#define KMAHIP_N_COUNTERS 32
 // slots of kmahip_ws::counters that scan.hip and api.hip both name: live strand items on the bare list, and as records
 #define KMAHIP_C_NACT 8
 #define KMAHIP_C_NREC 21
 #define KMAHIP_C_NREPL 22      // records whose diagonal the prefilter replaced by a better one (counted with the statistics on)
+// stage 3a's class queues (align.hip, api.hip): [+0..3] entries of the classes wide, narrow, tiny, mid; [+4] pending
+// tasks; [+5] hand-ons over the queues (tasks punted behind a queued problem, entries that found no room)
+#define KMAHIP_C_ADQ 24
 #define KMAHIP_KBITS_MUL 0x85EBCA6Bu      // device counter words per workspace
 
 // Probe table in HBM: open hashing over 32-byte buckets of 4 (key, position)
@@ -92,7 +95,7 @@ struct kmahip_ws {
 	int mem_scale;            // MEM slots per (read, template) = the usual 64 (reads up to 1 kb) x this; raised by the runs when a read
 	                          // full of repeats carries more (status 3), 0 = 1
 	// counters (KMAHIP_N_COUNTERS): [0] pool top, [1] status, [2] n_overflow, [3] probes, [4] value elems, [5] active strands,
-	// [6] hash probes, [7] pair pool top, [8] live strand items on the bare list, [9] prefilter probes, [21] records, [22] replaced diagonals
+	// [6] hash probes, [7] pair pool top, [8] live strand items on the bare list, [9] prefilter probes, [21] records, [22] replaced diagonals, [24..29] stage 3a's class queues (KMAHIP_C_ADQ)
 	unsigned long long *counters;
 	int64_t *overflow_items;
 	int64_t *active_items;    // strand items that passed the prefilter (device-wide compaction)
