@@ -106,6 +106,7 @@ struct ScanArgs {
 	uint64_t *recs;      // the prefilter's records of the plain live items (counters[C_NREC] of them, at most rec_cap); NULL: every
 	int64_t rec_cap;     // live item goes to active_items
 	int refine;          // the prefilter checks a record's diagonal against `cat` and tries ONE other when it finds two mismatches or more
+	int pf_stage_words;  // the prefilter copies a workgroup's reads into LDS when their words + 2 fit in this many (0: never)
 	double min_frac;     // proximity matching (-proxi, getProxiMatch savekmers.c:296-340): |minFrac|, read by the PROXI finishes only
 };
 
@@ -292,10 +293,19 @@ constexpr int PF_PLANES = 1;                               // lanes sharing one 
 constexpr int PF_BLOCK = THREADS / PF_PLANES;              // items per round
 constexpr int PF_ROUNDS = 512 / PF_BLOCK;
 constexpr int PF_ITEMS = PF_BLOCK * PF_ROUNDS;             // items per workgroup
-
+constexpr int PF_READS = PF_ITEMS / 2;                     // = consecutive reads per workgroup
+// The words of a workgroup's reads are ONE contiguous range of the batch (seq_off ascends, every read carries a pad word), copied
+// into LDS once with coalesced loads: an item's lane, its neighbour (the other strand) and the lane that writes its record then take
+// them from there instead of from global memory with every lane on a line of its own. PF_READS reads of (SW - 1) * 32 bases, the
+// longest that get a record, with their pad words; two guard words behind the range (win2 reads word + 1).
+constexpr int PF_STAGE_WORDS = PF_READS * SW + 2;
+// (eight wavefronts per SIMD: 64 VGPRs, and eight workgroups' LDS in a CU's 160 KiB)
 template <bool STATS>
-__global__ __launch_bounds__(THREADS) void scan_prefilter_kernel(const ScanArgs A) {
+__global__ __launch_bounds__(THREADS, 8) void scan_prefilter_kernel(const ScanArgs A) {
 	__shared__ int64_t s_list[PF_ITEMS];      // the bare entries from the front, the entries that become records from the back
+	__shared__ uint64_t s_words[PF_STAGE_WORDS];          // seq[seq_off[r0] .. seq_off[r1]) of the workgroup's reads r0 .. r1, + 2 guards
+	__shared__ int32_t s_len[PF_READS];                   // their lengths
+	__shared__ uint16_t s_woff[PF_READS];                 // staged: the word offset of each in s_words
 	__shared__ uint32_t s_n, s_nr, s_np, s_nt, s_nx, s_nrepl;
 	__shared__ unsigned long long s_base, s_rbase;
 	__shared__ uint32_t s_room;
@@ -303,18 +313,43 @@ __global__ __launch_bounds__(THREADS) void scan_prefilter_kernel(const ScanArgs 
 	const int tid = threadIdx.x;
 	const int k = (int) db.kmersize;
 	const int plane = tid & (PF_PLANES - 1);
+	const int64_t r0 = (int64_t) blockIdx.x * PF_READS;          // (< n_reads: the grid covers the items and no more)
 	if(tid == 0) { s_n = 0; s_nr = 0; s_np = 0; s_nt = 0; s_nx = 0; s_nrepl = 0; }
+	// ---- the reads of the workgroup: lengths always, words when the range fits (pf_stage_words: 0 = staging off). A range that is
+	// too long or negative, or a read whose words do not lie inside it, sends the WHOLE workgroup by the unstaged route: the same
+	// text below, its word accessor reading global memory.
+	const int64_t wbase = A.seq_off[r0], span = A.seq_off[min(r0 + (int64_t) PF_READS, A.n_reads)] - wbase;
+	bool staged;
+	{
+		int Lt = 0;
+		int64_t wo = 0;
+		if(r0 + tid < A.n_reads) { Lt = A.len[r0 + tid]; wo = A.seq_off[r0 + tid] - wbase; }
+		s_len[tid] = Lt;
+		const bool outside = wo < 0 || wo + ((max(Lt, 0) + 31) >> 5) + 1 > span + 2;
+		staged = !__syncthreads_or(outside || span < 0 || span + 2 > (int64_t) A.pf_stage_words);
+		if(staged) {
+			s_woff[tid] = (uint16_t) wo;
+			for(int w = tid; w < (int) span; w += THREADS) s_words[w] = A.seq[wbase + w];
+			if(tid < 2) s_words[span + tid] = 0ull;
+		}
+	}
 	__syncthreads();
+	auto lds_words = [&](int rl) -> const uint64_t * { return s_words + s_woff[rl]; };
+	auto global_words = [&](int rl) -> const uint64_t * { return A.seq + A.seq_off[r0 + rl]; };
+	// (a generic lambda, called once per route from a branch that is uniform in the workgroup: the compiler sees which memory the
+	// words are in, and there is one text)
+	auto body = [&](auto words_of) {
 	uint32_t nprobe = 0, ntable = 0;      // k-mers resolved / of them by a gather into the probe table
 	for(int rd = 0; rd < PF_ROUNDS; ++rd) {
-		const int64_t item = (int64_t) blockIdx.x * PF_ITEMS + rd * PF_BLOCK + (tid / PF_PLANES);
+		const int li = rd * PF_BLOCK + (tid / PF_PLANES);
+		const int64_t item = (int64_t) blockIdx.x * PF_ITEMS + li;
 		const int64_t r = item >> 1;
 		bool hit = false, plain = false;   // plain: the scan can take the item from a record
 		int64_t diag = DIAG_NONE;          // template diagonal of the hit: its position in `cat` minus its strand position in the read
 		if(r < A.n_reads) {
-			const int L = A.len[r], strand = (int) (item & 1), npos = L - k + 1;
+			const int L = s_len[li >> 1], strand = (int) (item & 1), npos = L - k + 1;
 			if(npos > 0) {
-				const uint64_t *rs = A.seq + A.seq_off[r];
+				const uint64_t *rs = words_of(li >> 1);
 				const int64_t no = A.N_off[r];
 				const int nN = (int) (A.N_off[r + 1] - no);
 				plain = A.recs && nN == 0 && L <= (SW - 1) * 32 && !A.exhaustive;
@@ -432,15 +467,18 @@ __global__ __launch_bounds__(THREADS) void scan_prefilter_kernel(const ScanArgs 
 	}
 	__syncthreads();
 	for(uint32_t i = tid; i < nact; i += THREADS) A.active_items[s_base + i] = s_list[i];
-	// the records, one lane each: the six words by the arithmetic of the scan's staging loop, then 64 contiguous bytes in 16-byte
-	// stores (the read's words were fetched by this workgroup a moment ago: they come from the caches)
 	const uint32_t room = s_room;
-	for(uint32_t i = tid; i < nrec; i += THREADS) {
+	// (the records that found no room: their entries, behind the bare ones)
+	for(uint32_t i = room + tid; i < nrec; i += THREADS) A.active_items[s_base + nact + (i - room)] = s_list[PF_ITEMS - 1 - i];
+	// the records, one lane each: the six words by the arithmetic of the scan's staging loop, from the workgroup's copy of the read,
+	// then 64 contiguous bytes in 16-byte stores. (Eight lanes per record, a word and a template window each, the counts summed by
+	// DPP moves and every store instruction writing whole records, took 0.15 ms off the step at 250 M more vector instructions per launch:
+	// short of the rule for a gain, and not kept. DESIGN section 3.1, round 9.)
+	for(uint32_t i = tid; i < room; i += THREADS) {
 		const int64_t ent = s_list[PF_ITEMS - 1 - i];
-		if(i >= room) { A.active_items[s_base + nact + (i - room)] = ent; continue; }
-		const int64_t it = ent & ITEM_MASK, r = it >> 1;
-		const int L = A.len[r], nw = (L + 31) >> 5;
-		const uint64_t *rs = A.seq + A.seq_off[r];
+		const int64_t it = ent & ITEM_MASK; const int li = (int) (ent & (PF_ITEMS - 1));
+		const int L = s_len[li >> 1], nw = (L + 31) >> 5;
+		const uint64_t *rs = words_of(li >> 1);
 		uint64_t w[REC_WORDS];
 		w[0] = (uint64_t) ent; w[1] = (uint64_t) (uint32_t) L;
 #pragma unroll
@@ -504,6 +542,9 @@ __global__ __launch_bounds__(THREADS) void scan_prefilter_kernel(const ScanArgs 
 		__syncthreads();
 		if(tid == 0 && s_nx) { atomicAdd(&A.counters[C_HASH], (unsigned long long) s_nx); atomicAdd(&A.counters[C_NREPL], (unsigned long long) s_nrepl); }
 	}
+	};
+	if(staged) body(lds_words);
+	else body(global_words);
 }
 
 // ---- scan: one workgroup = GROUP active strand items, 16 lanes each ----------------------------------------
@@ -2044,6 +2085,13 @@ static int scan_refine_on(int64_t cat_bases) {
 	return cat_bases > 0;
 }
 
+// Words of LDS the prefilter may fill with a workgroup's reads. KMAHIP_PF_STAGE_WORDS (read per launch): 0 sends every workgroup by
+// the unstaged route, a smaller value than the compiled capacity some of them (for the tests of both routes side by side).
+static int pf_stage_words() {
+	if(const char *e = getenv("KMAHIP_PF_STAGE_WORDS")) return std::max(0, std::min(PF_STAGE_WORDS, atoi(e)));
+	return PF_STAGE_WORDS;
+}
+
 // Does the prefilter write records for this batch? KMAHIP_SCAN_REC=0 (read per launch): never. Nor in the exhaustive mode, nor for
 // a batch whose caller declares a read beyond the record's 192 bases (kmahip_reads::max_len; 0 = not told): the bare list's
 // looping launch is for a short list -- with 35 spilled dwords it takes 3.8 ms more per 10 M reads than the straight-line kernel
@@ -2145,7 +2193,7 @@ int kmahip_launch_scan_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	if(kmahip_mem_mode() && (rc = kmahip_refuse_proxi(p, KMAHIP_PROXI_MEM))) return rc;
 	if(kmahip_mem_mode() && (rc = kmahip_refuse_decon(db, KMAHIP_DECON_MEM))) return rc;
 	A.recs = scan_records_on(ws, reads, p) ? ws->recs : nullptr; A.rec_cap = ws->rec_cap;
-	A.refine = scan_refine_on(A.cat_bases);
+	A.refine = scan_refine_on(A.cat_bases); A.pf_stage_words = pf_stage_words();
 	A.ablate = 0;
 #ifdef KMAHIP_DIAG
 	if(const char *e = getenv("KMAHIP_ABLATE_SCAN")) A.ablate = atoi(e);
@@ -2219,7 +2267,7 @@ int kmahip_launch_chain_anchors(kmahip_db *db, kmahip_ws *ws, const kmahip_reads
 	S.pool = ws->pool; S.pool_cap = ws->pool_cap; S.counters = ws->counters; S.overflow_items = ws->overflow_items;
 	S.dense = ws->dense; S.dense_slots = ws->dense_slots; S.active_items = ws->active_items;
 	S.mode = 0; S.pool_sc = nullptr; S.pool_tail0 = 2 * n * INL; S.ablate = 0; S.cat_bases = 0;
-	S.recs = nullptr; S.rec_cap = 0; S.refine = 0;          // (the anchor kernel takes every live item from the bare list)
+	S.recs = nullptr; S.rec_cap = 0; S.refine = 0; S.pf_stage_words = pf_stage_words();          // (the anchor kernel takes every live item from the bare list)
 	S.min_frac = 1.0;
 	S.in_items = ws->active_items; S.in_count = C_NACT; S.out_over = ws->overflow_items; S.out_count = C_NOVER;
 	A.pool = pool; A.pool_cap = pool_cap; A.a_off = a_off; A.a_n = a_n; A.slow = slow; A.cnt = cnt;
@@ -2263,7 +2311,7 @@ int kmahip_launch_scan_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	A.dense = ws->dense; A.dense_slots = ws->dense_slots; A.active_items = ws->active_items;
 	A.ablate = 0; A.mode = 1; A.pool_sc = ws->pool_sc; A.pool_tail0 = 0; A.cat_bases = diag_cat_bases(db);
 	A.recs = scan_records_on(ws, reads, p) ? ws->recs : nullptr; A.rec_cap = ws->rec_cap;
-	A.refine = scan_refine_on(A.cat_bases);
+	A.refine = scan_refine_on(A.cat_bases); A.pf_stage_words = pf_stage_words();
 	A.min_frac = 1.0;
 #ifdef KMAHIP_DIAG
 	if(const char *e = getenv("KMAHIP_ABLATE_SCAN")) A.ablate = atoi(e);
