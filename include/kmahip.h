@@ -1067,6 +1067,12 @@ typedef struct kmahip_trace_stats {
 	uint64_t problems, dp_cells, mems, reads;
 } kmahip_trace_stats;
 int kmahip_trace_get_stats(kmahip_ws *ws, kmahip_trace_stats *st);
+/* DP problems of the same call by the size class that solved them, summed over the call's passes: out[0..16] the wavefront classes
+ * (0-3 lt_dp_kernel of 8 / 16 / 32 / 64 columns; 4-7 lt_dpx_kernel with the move matrix in LDS: full 2 / 4 columns a lane, banded
+ * 2 / 4; 8 the one-lane kernel; 9-12 as 4-7 with the move matrix in HBM; 13, 14 unused; 15, 16 banded, 8 / 16 columns a lane),
+ * out[17..25] the lane classes 0..8 (rows of 16 / 32 / 48 / 64 / 128 / 256 cells, bands of up to 72 / 96 / 144). Degenerate joins
+ * (a pure insertion or deletion) are in no class. */
+int kmahip_trace_get_class_counts(kmahip_ws *ws, unsigned long long out[26]);
 
 /* Kernel timing: when on, every *_dev call records a HIP event pair around its
  * main kernels (scan_prefilter_kernel, scan_se_kernel, seed_tasks_kernel, align_tasks_kernel) on the caller's stream; get_timing waits

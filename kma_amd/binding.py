@@ -253,6 +253,8 @@ def lib():
         L.kmahip_frag_write2.argtypes = [C.c_char_p, C.c_void_p, C.POINTER(Reads), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int64, C.c_int, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64)]
         L.kmahip_trace_get_stats.argtypes = [C.c_void_p, C.POINTER(TraceStats)]
+        if hasattr(L, "kmahip_trace_get_class_counts"):          # (KMAHIP_LIB may name an older library, for side-by-side timing)
+            L.kmahip_trace_get_class_counts.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
         L.kmahip_trim_default.argtypes = [C.POINTER(Trim)]
         L.kmahip_trim_default.restype = None
         L.kmahip_ingest_open.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Trim), C.POINTER(C.c_void_p)]
@@ -783,6 +785,12 @@ class KmaHipDB:
         st = TraceStats()
         _check(lib().kmahip_trace_get_stats(self.ws, C.byref(st)))
         return st
+
+    def get_trace_class_counts(self) -> dict:
+        """DP problems of the last long-read trace call per size class: wave (17 wavefront classes), lane (9 lane classes)"""
+        out = (C.c_ulonglong * 26)()
+        _check(lib().kmahip_trace_get_class_counts(self.ws, out))
+        return dict(wave=[int(x) for x in out[:17]], lane=[int(x) for x in out[17:]])
 
     def set_timing(self, on: bool):
         _check(lib().kmahip_ws_set_timing(self.ws, int(on)))

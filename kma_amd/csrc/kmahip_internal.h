@@ -154,6 +154,7 @@ struct kmahip_ws {
 	void *lt_buf[20];
 	size_t lt_bytes[20];
 	unsigned long long lt_stats[4];   // of the last call: DP problems, DP cells, MEMs chained, reads
+	unsigned long long lt_class_counts[26];   // of the last call: problems per wavefront class 0..16, then per lane class 0..8
 	// slow-path dense scratch
 	int32_t *dense;
 	int64_t dense_slots;

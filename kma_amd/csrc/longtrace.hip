@@ -492,7 +492,11 @@ __device__ __forceinline__ int lt_class(int q_l, int t_l, int band, int k, int64
 	if(band & 1) ++band;
 	const int pitch = band ? band + 2 : q_l + 1;
 	// the reference's last-row scan (k == -2) reads cells of its row buffer beyond the boundary column when the band is cut
-	// there: only the one-lane form reproduces that
+	// there: only the one-lane form reproduces that.
+	// With CHAIN_BW = 64 no input gets here: k == -2 means lead_window left the template side whole (t_e <= 2 q_e and t_e <= q_e + 64),
+	// so d = q_l - t_l lies in [-64, 64] (64 when the query side was cut), band = |d| + 64 and cfin = floor(d / 2) + 1. The test below
+	// then asks for t_l <= 34 (d >= 0) or q_l <= 34 (d < 0), while a banded problem has both sides over its band of 64 or more. Kept as
+	// the guard it is for another CHAIN_BW.
 	const int cfin = ((t_l + q_l) >> 1) - (t_l - 1);
 	const bool stale_scan = band && k == -2 && !(cfin + (band >> 1) < q_l - 1);
 	if(q_l < 256 && !stale_scan && (int64_t) pitch * (t_l + 1) <= xe_cap)
@@ -2278,6 +2282,7 @@ int kmahip_launch_longtrace(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *re
 	unsigned long long *counters = (unsigned long long *) ws->lt_buf[7];
 	HIP_TRY(hipMemsetAsync(counters, 0, LCI(LC_N + 1) * 8, stream));
 	for(int i = 0; i < 4; ++i) ws->lt_stats[i] = 0;
+	for(int i = 0; i < LT_NCLS + LT_LCLS; ++i) ws->lt_class_counts[i] = 0;
 	LtArgs A;
 	A.db = db->dev;
 	A.seq = reads->seq; A.seq_off = reads->seq_off; A.len = reads->len; A.N = reads->N; A.N_off = reads->N_off;
@@ -2381,6 +2386,8 @@ int kmahip_launch_longtrace(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *re
 		const unsigned long long *cf = hc + (size_t) (2 + x) * LCI(LC_N);
 		if(cf[LCI(LC_STATUS)] == 10) { kmahip_set_error("long-read trace: a move matrix was left through a non-boundary cell (internal error)"); return KMAHIP_EDEVICE; }
 		ws->lt_stats[0] += cf[LCI(LC_PROB)]; ws->lt_stats[1] += cf[LCI(LC_CELLS)]; ws->lt_stats[2] += cf[LCI(LC_MEMS)]; ws->lt_stats[3] += (unsigned long long) fin_nb[x];
+		for(int i = 0; i < LT_NCLS; ++i) ws->lt_class_counts[i] += cf[LCI(LC_CNT + i)];
+		for(int j = 0; j < LT_LCLS; ++j) ws->lt_class_counts[LT_NCLS + j] += cf[LCI(LC_LCNT + j)];
 		if(cf[LCI(LC_STATUS)] == 8 || cf[LCI(LC_STATUS)] == 9) { kmahip_set_error("long-read trace: a DP problem or a read's run list beyond the scratch (status %llu)", cf[LCI(LC_STATUS)]); return KMAHIP_EDEVICE; }
 		return KMAHIP_OK;
 	};

@@ -88,6 +88,15 @@ typedef struct { int score, len, pos, match, tGaps, qGaps; } aln;
 
 /* call counters for tests: [0] full NW, [1] banded NW, [2] DP cells, [3] chain calls */
 int64_t orc_counters[4] = {0, 0, 0, 0};
+/* the DP problems solved since a test last set orc_dp_n to 0, four ints each: mode k, template rows, query columns, band as the
+ * caller computed it (0: full matrix); orc_dp_n counts on when the log is full */
+enum { ORC_DP_LOG = 256 };
+int32_t orc_dp_log[4 * ORC_DP_LOG];
+int32_t orc_dp_n = 0;
+static void dp_log(int k, int t_len, int q_len, int band) {
+	if(orc_dp_n < ORC_DP_LOG) { int32_t *e = orc_dp_log + 4 * orc_dp_n; e[0] = k; e[1] = t_len; e[2] = q_len; e[3] = band; }
+	++orc_dp_n;
+}
 
 static aln degenerate(int t_len, int q_len, const orc_rewards *rw) {
 	/* nw.c:662-684 */
@@ -192,6 +201,7 @@ static aln nw_score(aws *w, const uint64_t *tseq, const uint8_t *qorg, int k, in
 	const uint8_t *q = qorg + q_s;
 	if(t_len == 0 || q_len == 0) return tr ? degenerate_trace(t_len, q_len, rw, tr, tseq, t_e, q) : degenerate(t_len, q_len, rw);
 	orc_counters[0]++; orc_counters[2] += (int64_t) t_len * q_len;
+	dp_log(k, t_len, q_len, 0);
 	aws_rows(w, q_len + 2);
 	aws_E(w, (long) (q_len + 2) * (t_len + 2));
 	const long pitch = q_len + 1;
@@ -260,6 +270,7 @@ static aln nw_band_score(aws *w, const uint64_t *tseq, const uint8_t *qorg, int 
 	if(t_len < 0) t_len += tlen_total;
 	const uint8_t *q = qorg + q_s;
 	if(t_len == 0 || q_len == 0) return tr ? degenerate_trace(t_len, q_len, rw, tr, tseq, t_e, q) : degenerate(t_len, q_len, rw);
+	dp_log(k, t_len, q_len, band);
 	if(band & 1) ++band;
 	orc_counters[1]++; orc_counters[2] += (int64_t) t_len * (band + 1);
 	const int half = band >> 1, bq = band + 1;

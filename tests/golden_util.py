@@ -272,6 +272,52 @@ def load_mt1(tmp):
     return dict(dir=src, prefix=prefix, names=names, reads=reads, fastq=fq)
 
 
+def load_ltclass(tmp):
+    """tests/golden/ltclass (make_golden_ltclass.py): index unpacked into tmp; the raw reads (codes 0-4, file order) with their names;
+    cases = one dict per read in file order (cases.tsv, numbers as ints); schemes = {name: dict(M, MM, U, W1, lane_tq)};
+    sam = {scheme: {qname: (flag, rname, pos, mapq, cigar, AS)}}"""
+    src = os.path.join(GOLD, "ltclass")
+    tmp = str(tmp)
+    os.makedirs(tmp, exist_ok=True)
+    prefix = os.path.join(tmp, "db")
+    with lzma.open(os.path.join(src, "db.comp.b.xz"), "rb") as f, open(prefix + ".comp.b", "wb") as g:
+        shutil.copyfileobj(f, g)
+    for ext in (".length.b", ".seq.b", ".name"):
+        shutil.copy(os.path.join(src, "db" + ext), prefix + ext)
+    lut = np.full(256, 4, np.uint8)
+    for i, c in enumerate(b"ACGT"):
+        lut[c] = i
+    names, reads = [], []
+    lines = _gunzip(os.path.join(src, "reads.fq.gz")).split(b"\n")
+    for i in range(0, len(lines) - 3, 4):
+        names.append(lines[i][1:].decode())
+        reads.append(lut[np.frombuffer(lines[i + 1], np.uint8)])
+
+    def table(path):
+        with open(path) as f:
+            head = f.readline().rstrip("\n").split("\t")
+            return [{k: (int(v) if v.lstrip("-").isdigit() else v) for k, v in zip(head, line.rstrip("\n").split("\t"))} for line in f]
+    cases = table(os.path.join(src, "cases.tsv"))
+    assert [c["name"] for c in cases] == names
+    schemes = {r["scheme"]: r for r in table(os.path.join(src, "schemes.tsv"))}
+    sam = {}
+    for s in schemes:
+        with gzip.open(os.path.join(src, f"out.{s}.sam.tsv.gz"), "rt") as f:
+            rows = [line.rstrip("\n").split("\t") for line in f]
+        sam[s] = {c[0]: (int(c[1]), c[2], int(c[3]), int(c[4]), c[5], int(c[6])) for c in rows}
+        assert len(sam[s]) == len(rows) == len(names)
+    return dict(dir=src, prefix=prefix, names=names, reads=reads, cases=cases, schemes=schemes, sam=sam)
+
+
+def set_scheme(rw, scheme):
+    """a three-valued scoring scheme into a Rewards structure (the oracle's or the binding's), as kma.c:1308-1327 fills it: every
+    mismatch MM, N against anything 0"""
+    rw.M, rw.MM, rw.U, rw.W1 = scheme["M"], scheme["MM"], scheme["U"], scheme["W1"]
+    for i in range(5):
+        for j in range(5):
+            rw.d[i][j] = 0 if i == 4 or j == 4 else (scheme["M"] if i == j else scheme["MM"])
+
+
 def load_frag_rows(name):
     """`.frag.gz` rows in file order: (sequence, n_templates, score, start, end, template name, header)"""
     with gzip.open(os.path.join(GOLD, name, "out.frag.gz"), "rt") as f:

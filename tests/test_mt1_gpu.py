@@ -24,7 +24,12 @@ def test_mt1_traceback_matches_reference_sam(tmp_path):
     from kma_amd import binding
     g = golden_util.load_mt1(tmp_path / "mt1")
     db, batch, ((stats, off, nops, ops), rc) = _trace(g)
+    counts = db.get_trace_class_counts()
     db.close()
+    # the size classes this fixture's 7274 DP problems fall into under the default arrangement (kmahip_trace_get_class_counts), as first
+    # measured: a change to lt_class / lt_lane_class or to the windows shows here. The classes it leaves empty are the business of
+    # tests/test_ltclass_gpu.py
+    assert counts == dict(wave=[0, 0, 0, 0, 0, 0, 0, 6, 2, 0, 0, 0, 0, 0, 0, 0, 0], lane=[3185, 1830, 1048, 566, 104, 2, 456, 75, 0]), counts
     sam = golden_util.load_sam("mt1")
     mapped = 0
     for i, nm in enumerate(g["names"]):
