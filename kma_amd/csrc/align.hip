@@ -1461,7 +1461,7 @@ __global__ __launch_bounds__(ATHREADS, 4) void align_tasks_kernel(const AlignArg
 					else if(side > 0) { tmpl_out = at; S0 = kma_score<CIRC>(L, A.db, at, ts, t_len, q, A.mq, side, &status); }
 				}
 			}
-			if(status) atomicMax(&A.counters[1], 3ull);
+			if(status) atomicMax(&A.counters[1], KMAHIP_ST_SEED_MEMS);
 		}
 #ifdef KMAHIP_DIAG
 		if(have) atomicMax(&A.counters[13], ((wall_clock64() - dbg_t0) << 32) | (unsigned long long) (task & 0xFFFFFFFFll));      // slowest phase A (10 ns ticks) and its task
@@ -1975,7 +1975,7 @@ __global__ __launch_bounds__(256, KMAHIP_DQ_WAVES) void dp_queues_kernel(const A
 __global__ __launch_bounds__(256) void task_map_kernel(const int64_t *T_off, int64_t n, int32_t *t_rec, int64_t tasks_cap, unsigned long long *counters) {
 	const int64_t r = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
 	if(r >= n) return;
-	if(T_off[n] > tasks_cap) { if(r == 0) atomicMax(&counters[1], 2ull); return; }
+	if(T_off[n] > tasks_cap) { if(r == 0) atomicMax(&counters[1], KMAHIP_ST_CALLER_CAP); return; }
 	const int64_t e = T_off[r + 1];
 	for(int64_t t = T_off[r]; t < e; ++t) t_rec[t] = (int32_t) r;
 }
@@ -2751,7 +2751,7 @@ __global__ __launch_bounds__(256) void trace_kernel(const TraceArgs A) {      //
 				T.em.n = 0; T.em.over = false; T.status = 0;
 				S = kma_trace<FAST, CIRC>(T, A.db, t, ts, t_len, q, A.mq, cs, ce, mapQ);
 				if(T.status == 32 || (T.status == 1 && A.lds_bytes)) A.q_out[atomicAdd(&A.counters[A.q_out_cnt], 1ull)] = (int32_t) r;
-				else if(T.status || T.em.over) atomicMax(&A.counters[1], (unsigned long long) (T.em.over ? 4 : (T.status == 1 ? 8 : 16)));
+				else if(T.status || T.em.over) atomicMax(&A.counters[1], T.em.over ? KMAHIP_ST_TRACE_RUNS : (T.status == 1 ? KMAHIP_ST_TRACE_DP : KMAHIP_ST_TRACE_MEMS));
 				else {
 					// assemble_KMA, assembly.c:1931-1961
 					aln_len = S.len; start = S.pos;
@@ -2779,7 +2779,7 @@ __global__ __launch_bounds__(256) void trace_kernel(const TraceArgs A) {      //
 		base = __shfl(base, 63);
 		if(!keep && !drop) continue;
 		const int64_t o = (int64_t) base + incl - need;
-		if(o + T.em.n > A.ops_pool_cap) { atomicMax(&A.counters[1], 2ull); continue; }
+		if(o + T.em.n > A.ops_pool_cap) { atomicMax(&A.counters[1], KMAHIP_ST_CALLER_CAP); continue; }
 		for(int x = 0; x < T.em.n; ++x) A.ops[o + x] = T.em.at(x);
 		if(drop) {
 			int32_t *ds = A.d_stats + 6 * r;
@@ -2916,7 +2916,7 @@ static int launch_align(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 		HIP_TRY(hipMalloc((void **) &ws->a_task, (size_t) tasks_cap * (2 * SEEDS * 8 + 8 + 8 + 8 * 4 + PART_INTS * 4) + DQ_CLASSES * (size_t) (tasks_cap / 4 + 4096) * QENT * 4 + 64));
 		ws->a_task_cap = tasks_cap;
 	}
-	if(!ws->counters) { HIP_TRY(hipMalloc((void **) &ws->counters, KMAHIP_N_COUNTERS * sizeof(unsigned long long))); HIP_TRY(hipMemset(ws->counters, 0, KMAHIP_N_COUNTERS * sizeof(unsigned long long))); }
+	if(int rcc = kmahip_ws_counters(ws)) return rcc;
 	HIP_TRY(hipMemsetAsync(ws->counters + 2, 0, 7 * sizeof(unsigned long long), stream));      // [2] .. [8]
 	HIP_TRY(hipMemsetAsync(ws->counters + AC_DQ, 0, (DQ_CLASSES + 2) * sizeof(unsigned long long), stream));  // the class queues, the two diagnostic counts
 
@@ -3275,7 +3275,7 @@ int kmahip_launch_trace(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 	}
 	const int mem_cap = G.mem_cap, ncols = G.ncols, ops_cap = G.ops_cap;
 	const int64_t e_cap = G.e_cap, lanes = G.lanes;
-	if(!ws->counters) { HIP_TRY(hipMalloc((void **) &ws->counters, KMAHIP_N_COUNTERS * sizeof(unsigned long long))); HIP_TRY(hipMemset(ws->counters, 0, KMAHIP_N_COUNTERS * sizeof(unsigned long long))); }
+	if(int rcc = kmahip_ws_counters(ws)) return rcc;
 	HIP_TRY(hipMemsetAsync(ws->counters, 0, sizeof(unsigned long long), stream));
 	HIP_TRY(hipMemsetAsync(ws->counters + 3, 0, 2 * sizeof(unsigned long long), stream));
 	if(ws->t_queue_cap < n) {

@@ -1,6 +1,5 @@
 // api.hip -- extern "C" entry points of libkmahip.so (see include/kmahip.h).
-#include "kmahip_internal.h"
-void kmahip_devcache_flush();      // pipeline.hip
+#include "pipeline_util.h"
 #include <cstring>
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -59,34 +58,35 @@ extern "C" int kmahip_scan_se_dev(kmahip_db *db, kmahip_ws *ws, const kmahip_rea
 	return kmahip_launch_scan_se(db, ws, reads, p, out, (hipStream_t) stream);
 }
 
+// the one place where the entry points read the status word of a synchronised stage (read and cleared: ws_status): the candidate
+// pool doubles here when it is what ran out, and the caller repeats the call
+static int ws_classify(kmahip_ws *ws, unsigned long long *st, unsigned long long *c0) {
+	const int rc = ws_status(ws, st, c0);
+	if(!rc && *st == KMAHIP_ST_POOL) grow_pool(ws);
+	return rc;
+}
+
 extern "C" int kmahip_ws_status(kmahip_ws *ws, void *stream) {
 	if(!ws) return KMAHIP_EINVAL;
 	if(!ws->counters) return KMAHIP_OK;   // nothing launched yet
-	unsigned long long c[8];
-	HIP_TRY(hipMemcpyAsync(c, ws->counters, sizeof c, hipMemcpyDeviceToHost, (hipStream_t) stream));
 	HIP_TRY(hipStreamSynchronize((hipStream_t) stream));
-	if(c[1]) {
-		HIP_TRY(hipMemset(ws->counters + 1, 0, sizeof(unsigned long long)));
-		switch(c[1]) {
-			case 1:
-				// the library's own candidate pool (cap_reads * 16 * pool_scale ints), not a caller capacity: grown by the next launch
-				ws->pool_scale *= 2; ws->cap_reads = 0;
-				kmahip_set_error("internal candidate pool exhausted: the pool has been doubled, repeat the call");
-				break;
-			case 2: kmahip_set_error("output capacity (T_cap / ops_cap) too small: the offsets array holds the needed size; stage 3a was skipped"); break;
-			case 3: case 16: {
-				// more MEMs against one template than the scratch has slots per (read, template) pair (a read full of repeats): the
-				// capacity goes up fourfold with the next launch, like the candidate pool
-				const int cur = ws->mem_scale > 0 ? ws->mem_scale : 1;
-				if(cur < 64) { ws->mem_scale = cur * 4; kmahip_set_error("seed (MEM) capacity per read/template pair exceeded: it has been raised fourfold, repeat the %s call (with the score vectors zeroed again)", c[1] == 3 ? "align" : "trace"); }
-				else kmahip_set_error("seed (MEM) capacity per read/template pair exceeded");
-				break;
-			}
-			default: kmahip_set_error("a read needs more scratch than the workspace holds (status %llu)", c[1]); break;
-		}
-		return KMAHIP_EOVERFLOW;
+	unsigned long long st = 0;
+	if(int rc = ws_classify(ws, &st, nullptr)) return rc;
+	// (the codes: KmaStatus, kmahip_internal.h)
+	switch(st) {
+		case 0: return KMAHIP_OK;
+		// (the library's own candidate pool, not a caller capacity: grown by the next launch)
+		case KMAHIP_ST_POOL: kmahip_set_error("internal candidate pool exhausted: the pool has been doubled, repeat the call"); break;
+		case KMAHIP_ST_CALLER_CAP: kmahip_set_error("output capacity (T_cap / ops_cap) too small: the offsets array holds the needed size; stage 3a was skipped"); break;
+		case KMAHIP_ST_SEED_MEMS: case KMAHIP_ST_TRACE_MEMS:
+			// more MEMs against one template than the scratch has slots per (read, template) pair (a read full of repeats): the
+			// capacity goes up fourfold with the next launch, like the candidate pool
+			if(grow_mem_cap(ws)) kmahip_set_error("seed (MEM) capacity per read/template pair exceeded: it has been raised fourfold, repeat the %s call (with the score vectors zeroed again)", st == KMAHIP_ST_SEED_MEMS ? "align" : "trace");
+			else kmahip_set_error("seed (MEM) capacity per read/template pair exceeded");
+			break;
+		default: kmahip_set_error("a read needs more scratch than the workspace holds (status %llu)", st); break;
 	}
-	return KMAHIP_OK;
+	return KMAHIP_EOVERFLOW;
 }
 
 extern "C" int kmahip_scan_set_stats(kmahip_ws *ws, int on) {
@@ -167,29 +167,37 @@ static int stage_reserve(kmahip_ws *ws, int slot, size_t bytes) {
 	return KMAHIP_OK;
 }
 
+// a host batch's five read arrays in the staging slots 0 seq, 1 seq_off, 2 len, 3 N, 4 N_off; `pad` zero words behind the last read
+// keep the word+1 access in bounds. *d: the batch with DEVICE arrays
+static int stage_reads(kmahip_ws *ws, const kmahip_reads *reads, int pad, hipStream_t s, kmahip_reads *d) {
+	const int64_t n = reads->n_reads;
+	int rc;
+	if((rc = stage_reserve(ws, 0, (size_t) (reads->seq_words + pad) * 8)) || (rc = stage_reserve(ws, 1, (size_t) (n + 1) * 8)) || (rc = stage_reserve(ws, 2, (size_t) n * 4)) ||
+	   (rc = stage_reserve(ws, 3, (size_t) reads->N_total * 4)) || (rc = stage_reserve(ws, 4, (size_t) (n + 1) * 8))) return rc;
+	HIP_TRY(hipMemsetAsync((char *) ws->stage[0] + (size_t) reads->seq_words * 8, 0, (size_t) pad * 8, s));
+	if(reads->seq_words) HIP_TRY(hipMemcpyAsync(ws->stage[0], reads->seq, (size_t) reads->seq_words * 8, hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemcpyAsync(ws->stage[1], reads->seq_off, (size_t) (n + 1) * 8, hipMemcpyHostToDevice, s));
+	if(n) HIP_TRY(hipMemcpyAsync(ws->stage[2], reads->len, (size_t) n * 4, hipMemcpyHostToDevice, s));
+	if(reads->N_total) HIP_TRY(hipMemcpyAsync(ws->stage[3], reads->N, (size_t) reads->N_total * 4, hipMemcpyHostToDevice, s));
+	HIP_TRY(hipMemcpyAsync(ws->stage[4], reads->N_off, (size_t) (n + 1) * 8, hipMemcpyHostToDevice, s));
+	*d = *reads;
+	d->q_start = nullptr; d->q_end = nullptr;       // (host pointers, if any: these entry points map whole reads)
+	d->seq = (const uint64_t *) ws->stage[0]; d->seq_off = (const int64_t *) ws->stage[1]; d->len = (const int32_t *) ws->stage[2];
+	d->N = (const int32_t *) ws->stage[3]; d->N_off = (const int64_t *) ws->stage[4];
+	return KMAHIP_OK;
+}
+
 // host buffers in / out: reads are staged once; stage 3a optionally follows on the same staged batch
 static int run_host(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads, const kmahip_params *p,
                     kmahip_cands *out, kmahip_hits *hits) {
 	const int64_t n = reads->n_reads;
 	if(n < 0 || reads->seq_words < 0 || reads->N_total < 0) { kmahip_set_error("negative size"); return KMAHIP_EINVAL; }
 	int rc;
-	// stage inputs: 0 seq, 1 seq_off, 2 len, 3 N, 4 N_off; outputs: 5 rc_flag+flag, 6 T_off, 7 T
-	if((rc = stage_reserve(ws, 0, (size_t) (reads->seq_words + 1) * 8)) || (rc = stage_reserve(ws, 1, (size_t) (n + 1) * 8)) ||
-	   (rc = stage_reserve(ws, 2, (size_t) n * 4)) || (rc = stage_reserve(ws, 3, (size_t) reads->N_total * 4)) ||
-	   (rc = stage_reserve(ws, 4, (size_t) (n + 1) * 8)) || (rc = stage_reserve(ws, 5, (size_t) n * 8)) ||
-	   (rc = stage_reserve(ws, 6, (size_t) (n + 1) * 8)) || (rc = stage_reserve(ws, 7, (size_t) out->T_cap * 4))) return rc;
+	// the staged reads; outputs: 5 rc_flag+flag, 6 T_off, 7 T
 	hipStream_t s = 0;
-	// one zero pad word after the last read keeps the word+1 access in bounds
-	HIP_TRY(hipMemsetAsync((char *) ws->stage[0] + (size_t) reads->seq_words * 8, 0, 8, s));
-	if(reads->seq_words) HIP_TRY(hipMemcpyAsync(ws->stage[0], reads->seq, (size_t) reads->seq_words * 8, hipMemcpyHostToDevice, s));
-	HIP_TRY(hipMemcpyAsync(ws->stage[1], reads->seq_off, (size_t) (n + 1) * 8, hipMemcpyHostToDevice, s));
-	if(n) HIP_TRY(hipMemcpyAsync(ws->stage[2], reads->len, (size_t) n * 4, hipMemcpyHostToDevice, s));
-	if(reads->N_total) HIP_TRY(hipMemcpyAsync(ws->stage[3], reads->N, (size_t) reads->N_total * 4, hipMemcpyHostToDevice, s));
-	HIP_TRY(hipMemcpyAsync(ws->stage[4], reads->N_off, (size_t) (n + 1) * 8, hipMemcpyHostToDevice, s));
-	kmahip_reads d = *reads;
-	d.q_start = nullptr; d.q_end = nullptr;       // (host pointers, if any: this entry point maps whole reads)
-	d.seq = (const uint64_t *) ws->stage[0]; d.seq_off = (const int64_t *) ws->stage[1]; d.len = (const int32_t *) ws->stage[2];
-	d.N = (const int32_t *) ws->stage[3]; d.N_off = (const int64_t *) ws->stage[4];
+	kmahip_reads d;
+	if((rc = stage_reads(ws, reads, 1, s, &d)) || (rc = stage_reserve(ws, 5, (size_t) n * 8)) ||
+	   (rc = stage_reserve(ws, 6, (size_t) (n + 1) * 8)) || (rc = stage_reserve(ws, 7, (size_t) out->T_cap * 4))) return rc;
 	kmahip_cands o;
 	o.rc_flag = (int32_t *) ws->stage[5]; o.flag = o.rc_flag + n; o.T_off = (int64_t *) ws->stage[6];
 	o.T = (int32_t *) ws->stage[7]; o.T_cap = out->T_cap;
@@ -200,15 +208,10 @@ static int run_host(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads, con
 	}
 	HIP_TRY(hipMemcpyAsync(out->T_off, o.T_off, (size_t) (n + 1) * 8, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
-	unsigned long long c[8];
-	HIP_TRY(hipMemcpy(c, ws->counters, sizeof c, hipMemcpyDeviceToHost));
-	if(c[1]) HIP_TRY(hipMemset(ws->counters + 1, 0, sizeof(unsigned long long)));
-	if(c[1] == 1) {
-		// internal candidate pool too small: grow and let the caller retry
-		ws->pool_scale *= 2; ws->cap_reads = 0;
-		kmahip_set_error("internal candidate pool exhausted (retry grows it)");
-		return KMAHIP_EOVERFLOW;
-	}
+	unsigned long long st = 0;
+	if((rc = ws_classify(ws, &st, nullptr))) return rc;
+	// (internal candidate pool too small: it has grown, the caller retries)
+	if(st == KMAHIP_ST_POOL) { kmahip_set_error("internal candidate pool exhausted (retry grows it)"); return KMAHIP_EOVERFLOW; }
 	const int64_t total = out->T_off[n];
 	if(total > out->T_cap) { kmahip_set_error("T_cap %lld too small, need %lld", (long long) out->T_cap, (long long) total); return KMAHIP_EOVERFLOW; }
 	if(total) HIP_TRY(hipMemcpy(out->T, o.T, (size_t) total * 4, hipMemcpyDeviceToHost));
@@ -232,11 +235,7 @@ static int run_host(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads, con
 		hipError_t e = hipStreamSynchronize(s);
 		if(e != hipSuccess) { kmahip_set_error("align kernels failed: %s", hipGetErrorString(e)); rc = KMAHIP_EDEVICE; }
 	}
-	if(!rc) {
-		(void) hipMemcpy(c, ws->counters, sizeof c, hipMemcpyDeviceToHost);
-		if(c[1]) (void) hipMemset(ws->counters + 1, 0, sizeof(unsigned long long));
-		if(c[1] == 3) { kmahip_set_error("seed (MEM) capacity per read/template pair exceeded"); rc = KMAHIP_EOVERFLOW; }
-	}
+	if(!rc && !(rc = ws_classify(ws, &st, nullptr)) && st == KMAHIP_ST_SEED_MEMS) { kmahip_set_error("seed (MEM) capacity per read/template pair exceeded"); rc = KMAHIP_EOVERFLOW; }
 	if(!rc) {
 		(void) hipMemcpy(hits->n_hits, h.n_hits, (size_t) n * 4, hipMemcpyDeviceToHost);
 		(void) hipMemcpy(hits->best_score, h.best_score, (size_t) n * 4, hipMemcpyDeviceToHost);
@@ -340,21 +339,10 @@ static int run_host_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads, 
 	const int64_t n = reads->n_reads;
 	if(n < 0 || reads->seq_words < 0 || reads->N_total < 0) { kmahip_set_error("negative size"); return KMAHIP_EINVAL; }
 	int rc;
-	if((rc = stage_reserve(ws, 0, (size_t) (reads->seq_words + 1) * 8)) || (rc = stage_reserve(ws, 1, (size_t) (n + 1) * 8)) ||
-	   (rc = stage_reserve(ws, 2, (size_t) n * 4)) || (rc = stage_reserve(ws, 3, (size_t) reads->N_total * 4)) ||
-	   (rc = stage_reserve(ws, 4, (size_t) (n + 1) * 8)) || (rc = stage_reserve(ws, 5, (size_t) n * 16)) ||
-	   (rc = stage_reserve(ws, 6, (size_t) (n + 1) * 8)) || (rc = stage_reserve(ws, 7, (size_t) out->T_cap * 4))) return rc;
 	hipStream_t s = 0;
-	HIP_TRY(hipMemsetAsync((char *) ws->stage[0] + (size_t) reads->seq_words * 8, 0, 8, s));
-	if(reads->seq_words) HIP_TRY(hipMemcpyAsync(ws->stage[0], reads->seq, (size_t) reads->seq_words * 8, hipMemcpyHostToDevice, s));
-	HIP_TRY(hipMemcpyAsync(ws->stage[1], reads->seq_off, (size_t) (n + 1) * 8, hipMemcpyHostToDevice, s));
-	if(n) HIP_TRY(hipMemcpyAsync(ws->stage[2], reads->len, (size_t) n * 4, hipMemcpyHostToDevice, s));
-	if(reads->N_total) HIP_TRY(hipMemcpyAsync(ws->stage[3], reads->N, (size_t) reads->N_total * 4, hipMemcpyHostToDevice, s));
-	HIP_TRY(hipMemcpyAsync(ws->stage[4], reads->N_off, (size_t) (n + 1) * 8, hipMemcpyHostToDevice, s));
-	kmahip_reads d = *reads;
-	d.q_start = nullptr; d.q_end = nullptr;       // (host pointers, if any: this entry point maps whole reads)
-	d.seq = (const uint64_t *) ws->stage[0]; d.seq_off = (const int64_t *) ws->stage[1]; d.len = (const int32_t *) ws->stage[2];
-	d.N = (const int32_t *) ws->stage[3]; d.N_off = (const int64_t *) ws->stage[4];
+	kmahip_reads d;
+	if((rc = stage_reads(ws, reads, 1, s, &d)) || (rc = stage_reserve(ws, 5, (size_t) n * 16)) ||
+	   (rc = stage_reserve(ws, 6, (size_t) (n + 1) * 8)) || (rc = stage_reserve(ws, 7, (size_t) out->T_cap * 4))) return rc;
 	kmahip_pe_recs o;
 	int32_t *ip = (int32_t *) ws->stage[5];
 	o.mate = ip; o.rc = ip + n; o.rc_flag = ip + 2 * n; o.flag = ip + 3 * n;
@@ -368,10 +356,9 @@ static int run_host_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads, 
 	}
 	HIP_TRY(hipMemcpyAsync(out->R_off, o.R_off, (size_t) (n + 1) * 8, hipMemcpyDeviceToHost, s));
 	HIP_TRY(hipStreamSynchronize(s));
-	unsigned long long c[8];
-	HIP_TRY(hipMemcpy(c, ws->counters, sizeof c, hipMemcpyDeviceToHost));
-	if(c[1]) HIP_TRY(hipMemset(ws->counters + 1, 0, sizeof(unsigned long long)));
-	if(c[1] == 1) { ws->pool_scale *= 2; ws->cap_reads = 0; kmahip_set_error("internal candidate pool exhausted (retry grows it)"); return KMAHIP_EOVERFLOW; }
+	unsigned long long st = 0;
+	if((rc = ws_classify(ws, &st, nullptr))) return rc;
+	if(st == KMAHIP_ST_POOL) { kmahip_set_error("internal candidate pool exhausted (retry grows it)"); return KMAHIP_EOVERFLOW; }
 	const int64_t total = out->R_off[n];
 	if(total > out->T_cap) { kmahip_set_error("T_cap %lld too small, need %lld", (long long) out->T_cap, (long long) total); return KMAHIP_EOVERFLOW; }
 	if(total) HIP_TRY(hipMemcpy(out->T, o.T, (size_t) total * 4, hipMemcpyDeviceToHost));
@@ -396,11 +383,7 @@ static int run_host_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads, 
 		hipError_t e = hipStreamSynchronize(s);
 		if(e != hipSuccess) { kmahip_set_error("align kernels failed: %s", hipGetErrorString(e)); rc = KMAHIP_EDEVICE; }
 	}
-	if(!rc) {
-		(void) hipMemcpy(c, ws->counters, sizeof c, hipMemcpyDeviceToHost);
-		if(c[1]) (void) hipMemset(ws->counters + 1, 0, sizeof(unsigned long long));
-		if(c[1] == 3) { kmahip_set_error("seed (MEM) capacity per read/template pair exceeded"); rc = KMAHIP_EOVERFLOW; }
-	}
+	if(!rc && !(rc = ws_classify(ws, &st, nullptr)) && st == KMAHIP_ST_SEED_MEMS) { kmahip_set_error("seed (MEM) capacity per read/template pair exceeded"); rc = KMAHIP_EOVERFLOW; }
 	if(!rc) {
 		(void) hipMemcpy(hits->n_hits, h.n_hits, (size_t) n * 4, hipMemcpyDeviceToHost);
 		(void) hipMemcpy(hits->best_score, h.best_score, (size_t) n * 4, hipMemcpyDeviceToHost);
@@ -451,41 +434,29 @@ extern "C" int kmahip_align_trace(kmahip_db *db, kmahip_ws *ws, const kmahip_rea
 	if(n == 0) return KMAHIP_OK;
 	const size_t D = db->info.DB_size;
 	int rc;
-	if((rc = stage_reserve(ws, 0, (size_t) (reads->seq_words + 1) * 8)) || (rc = stage_reserve(ws, 1, (size_t) (n + 1) * 8)) ||
-	   (rc = stage_reserve(ws, 2, (size_t) n * 4)) || (rc = stage_reserve(ws, 3, (size_t) reads->N_total * 4)) ||
-	   (rc = stage_reserve(ws, 4, (size_t) (n + 1) * 8)) || (rc = stage_reserve(ws, 5, (size_t) n * 8 + D + 8)) ||
-	   (rc = stage_reserve(ws, 6, (size_t) n * (40 + 8 + 4) + 8)) || (rc = stage_reserve(ws, 7, (size_t) (out->ops_cap + 1) * 4))) return rc;
 	hipStream_t s = 0;
-	HIP_TRY(hipMemsetAsync((char *) ws->stage[0] + (size_t) reads->seq_words * 8, 0, 8, s));
-	if(reads->seq_words) HIP_TRY(hipMemcpyAsync(ws->stage[0], reads->seq, (size_t) reads->seq_words * 8, hipMemcpyHostToDevice, s));
-	HIP_TRY(hipMemcpyAsync(ws->stage[1], reads->seq_off, (size_t) (n + 1) * 8, hipMemcpyHostToDevice, s));
-	HIP_TRY(hipMemcpyAsync(ws->stage[2], reads->len, (size_t) n * 4, hipMemcpyHostToDevice, s));
-	if(reads->N_total) HIP_TRY(hipMemcpyAsync(ws->stage[3], reads->N, (size_t) reads->N_total * 4, hipMemcpyHostToDevice, s));
-	HIP_TRY(hipMemcpyAsync(ws->stage[4], reads->N_off, (size_t) (n + 1) * 8, hipMemcpyHostToDevice, s));
+	kmahip_reads d;
+	if((rc = stage_reads(ws, reads, 1, s, &d)) || (rc = stage_reserve(ws, 5, (size_t) n * 8 + D + 8)) ||
+	   (rc = stage_reserve(ws, 6, (size_t) n * (40 + 8 + 4) + 8)) || (rc = stage_reserve(ws, 7, (size_t) (out->ops_cap + 1) * 4))) return rc;
 	int32_t *d_flag = (int32_t *) ws->stage[5], *d_tmpl = d_flag + n;
 	uint8_t *d_ok = tmpl_ok ? (uint8_t *) (d_tmpl + n) : nullptr;
 	HIP_TRY(hipMemcpyAsync(d_flag, flag, (size_t) n * 4, hipMemcpyHostToDevice, s));
 	HIP_TRY(hipMemcpyAsync(d_tmpl, tmpl, (size_t) n * 4, hipMemcpyHostToDevice, s));
 	if(tmpl_ok) HIP_TRY(hipMemcpyAsync(d_ok, tmpl_ok, D, hipMemcpyHostToDevice, s));
-	kmahip_reads d = *reads;
-	d.q_start = nullptr; d.q_end = nullptr;       // (host pointers, if any: this entry point maps whole reads)
-	d.seq = (const uint64_t *) ws->stage[0]; d.seq_off = (const int64_t *) ws->stage[1]; d.len = (const int32_t *) ws->stage[2];
-	d.N = (const int32_t *) ws->stage[3]; d.N_off = (const int64_t *) ws->stage[4];
 	kmahip_traces o;
 	o.ops_off = (int64_t *) ws->stage[6]; o.stats = (int32_t *) (o.ops_off + n); o.n_ops = o.stats + 10 * n;
 	o.ops = (uint32_t *) ws->stage[7]; o.ops_cap = out->ops_cap;
 	if((rc = kmahip_launch_trace(db, ws, &d, d_flag, d_tmpl, d_ok, p, &o, s))) return rc;
 	HIP_TRY(hipStreamSynchronize(s));
-	unsigned long long c[8];
-	HIP_TRY(hipMemcpy(c, ws->counters, sizeof c, hipMemcpyDeviceToHost));
-	if(c[1]) HIP_TRY(hipMemset(ws->counters + 1, 0, sizeof(unsigned long long)));
-	if(ops_needed) *ops_needed = (int64_t) c[0];
-	if(c[1] == 2 || (int64_t) c[0] > out->ops_cap) { kmahip_set_error("ops_cap %lld too small, need %llu", (long long) out->ops_cap, c[0]); return KMAHIP_EOVERFLOW; }
-	if(c[1]) { kmahip_set_error("trace stage: a read needs more scratch than the workspace holds (status %llu)", c[1]); return KMAHIP_EDEVICE; }
+	unsigned long long st = 0, used = 0;
+	if((rc = ws_classify(ws, &st, &used))) return rc;
+	if(ops_needed) *ops_needed = (int64_t) used;
+	if(st == KMAHIP_ST_CALLER_CAP || (int64_t) used > out->ops_cap) { kmahip_set_error("ops_cap %lld too small, need %llu", (long long) out->ops_cap, used); return KMAHIP_EOVERFLOW; }
+	if(st) { kmahip_set_error("trace stage: a read needs more scratch than the workspace holds (status %llu)", st); return KMAHIP_EDEVICE; }
 	HIP_TRY(hipMemcpy(out->ops_off, o.ops_off, (size_t) n * 8, hipMemcpyDeviceToHost));
 	HIP_TRY(hipMemcpy(out->stats, o.stats, (size_t) n * 40, hipMemcpyDeviceToHost));
 	HIP_TRY(hipMemcpy(out->n_ops, o.n_ops, (size_t) n * 4, hipMemcpyDeviceToHost));
-	if(c[0]) HIP_TRY(hipMemcpy(out->ops, o.ops, (size_t) c[0] * 4, hipMemcpyDeviceToHost));
+	if(used) HIP_TRY(hipMemcpy(out->ops, o.ops, (size_t) used * 4, hipMemcpyDeviceToHost));
 	return KMAHIP_OK;
 }
 
@@ -503,37 +474,25 @@ extern "C" int kmahip_align_trace_mt1(kmahip_db *db, kmahip_ws *ws, const kmahip
 	if(ops_needed) *ops_needed = 0;
 	if(n == 0) return KMAHIP_OK;
 	int rc;
-	if((rc = stage_reserve(ws, 0, (size_t) (reads->seq_words + 2) * 8)) || (rc = stage_reserve(ws, 1, (size_t) (n + 1) * 8)) ||
-	   (rc = stage_reserve(ws, 2, (size_t) n * 4)) || (rc = stage_reserve(ws, 3, (size_t) reads->N_total * 4)) ||
-	   (rc = stage_reserve(ws, 4, (size_t) (n + 1) * 8)) || (rc = stage_reserve(ws, 5, (size_t) n * 4 + 8)) ||
-	   (rc = stage_reserve(ws, 6, (size_t) n * (40 + 8 + 4) + 8)) || (rc = stage_reserve(ws, 7, (size_t) (out->ops_cap + 1) * 4))) return rc;
 	hipStream_t s = 0;
-	HIP_TRY(hipMemsetAsync((char *) ws->stage[0] + (size_t) reads->seq_words * 8, 0, 16, s));
-	if(reads->seq_words) HIP_TRY(hipMemcpyAsync(ws->stage[0], reads->seq, (size_t) reads->seq_words * 8, hipMemcpyHostToDevice, s));
-	HIP_TRY(hipMemcpyAsync(ws->stage[1], reads->seq_off, (size_t) (n + 1) * 8, hipMemcpyHostToDevice, s));
-	HIP_TRY(hipMemcpyAsync(ws->stage[2], reads->len, (size_t) n * 4, hipMemcpyHostToDevice, s));
-	if(reads->N_total) HIP_TRY(hipMemcpyAsync(ws->stage[3], reads->N, (size_t) reads->N_total * 4, hipMemcpyHostToDevice, s));
-	HIP_TRY(hipMemcpyAsync(ws->stage[4], reads->N_off, (size_t) (n + 1) * 8, hipMemcpyHostToDevice, s));
-	kmahip_reads d = *reads;
-	d.q_start = nullptr; d.q_end = nullptr;       // (host pointers, if any: this entry point maps whole reads)
-	d.seq = (const uint64_t *) ws->stage[0]; d.seq_off = (const int64_t *) ws->stage[1]; d.len = (const int32_t *) ws->stage[2];
-	d.N = (const int32_t *) ws->stage[3]; d.N_off = (const int64_t *) ws->stage[4];
+	kmahip_reads d;
+	if((rc = stage_reads(ws, reads, 2, s, &d)) || (rc = stage_reserve(ws, 5, (size_t) n * 4 + 8)) ||
+	   (rc = stage_reserve(ws, 6, (size_t) n * (40 + 8 + 4) + 8)) || (rc = stage_reserve(ws, 7, (size_t) (out->ops_cap + 1) * 4))) return rc;
 	int32_t *d_rc = (int32_t *) ws->stage[5];
 	kmahip_traces o;
 	o.ops_off = (int64_t *) ws->stage[6]; o.stats = (int32_t *) (o.ops_off + n); o.n_ops = o.stats + 10 * n;
 	o.ops = (uint32_t *) ws->stage[7]; o.ops_cap = out->ops_cap;
 	if((rc = kmahip_launch_longtrace(db, ws, &d, nullptr, tmpl, nullptr, nullptr, one2one, p, &o, d_rc, s))) return rc;
 	HIP_TRY(hipStreamSynchronize(s));
-	unsigned long long c[2];
-	HIP_TRY(hipMemcpy(c, ws->counters, sizeof c, hipMemcpyDeviceToHost));
-	if(c[1]) HIP_TRY(hipMemset(ws->counters + 1, 0, sizeof(unsigned long long)));
-	if(ops_needed) *ops_needed = (int64_t) c[0];
-	if(c[1] == 2 || (int64_t) c[0] > out->ops_cap) { kmahip_set_error("ops_cap %lld too small, need %llu", (long long) out->ops_cap, c[0]); return KMAHIP_EOVERFLOW; }
+	unsigned long long st = 0, used = 0;
+	if((rc = ws_classify(ws, &st, &used))) return rc;
+	if(ops_needed) *ops_needed = (int64_t) used;
+	if(st == KMAHIP_ST_CALLER_CAP || (int64_t) used > out->ops_cap) { kmahip_set_error("ops_cap %lld too small, need %llu", (long long) out->ops_cap, used); return KMAHIP_EOVERFLOW; }
 	HIP_TRY(hipMemcpy(out->ops_off, o.ops_off, (size_t) n * 8, hipMemcpyDeviceToHost));
 	HIP_TRY(hipMemcpy(out->stats, o.stats, (size_t) n * 40, hipMemcpyDeviceToHost));
 	HIP_TRY(hipMemcpy(out->n_ops, o.n_ops, (size_t) n * 4, hipMemcpyDeviceToHost));
 	if(rc_out) HIP_TRY(hipMemcpy(rc_out, d_rc, (size_t) n * 4, hipMemcpyDeviceToHost));
-	if(c[0]) HIP_TRY(hipMemcpy(out->ops, o.ops, (size_t) c[0] * 4, hipMemcpyDeviceToHost));
+	if(used) HIP_TRY(hipMemcpy(out->ops, o.ops, (size_t) used * 4, hipMemcpyDeviceToHost));
 	return KMAHIP_OK;
 }
 

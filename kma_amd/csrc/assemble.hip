@@ -160,14 +160,14 @@ struct Walk {
 	__device__ int new_node(int bias, int b, int gaps) const {
 		if(LDS) {
 			const int id = (int) ++*s_nodes;
-			if(id > node_cap()) { atomicMax(&A.counters[1], 16ull); return 0; }
+			if(id > node_cap()) { atomicMax(&A.counters[1], KMAHIP_ST_PILE_LDS_COLS); return 0; }
 			uint32_t *c = &pile_lds[node_base() + 8 * (id - 1)];
 			for(int x = 0; x < 6; ++x) c[x] = 0;
 			c[5] = (uint32_t) bias; c[b] = 1; c[6] = 0; c[7] = (uint32_t) gaps;
 			return id;
 		}
 		const long long id = (long long) atomicAdd(&A.counters[2], 1ull) + 1;
-		if(id > A.node_cap) { atomicMax(&A.counters[1], 32ull); return 0; }
+		if(id > A.node_cap) { atomicMax(&A.counters[1], KMAHIP_ST_PILE_NODES); return 0; }
 		InsNode &nn = A.nodes[id - 1];
 		for(int x = 0; x < 6; ++x) nn.c[x] = 0;
 		nn.c[5] = (uint32_t) bias; nn.c[b] = 1; nn.next = 0; nn.gaps = gaps;
@@ -261,7 +261,7 @@ __global__ __launch_bounds__(256) void pile_count_kernel(const PileArgs A) {
 		const int t = abs(A.tmpl[r]);
 		c = visit_count(V, A.unit_base[t + 1] - A.unit_base[t]);
 		// (more turns than the sort key has room for: the host ends the call)
-		if(V.full >= (1 << PILE_TURN_BITS)) { atomicMax(&A.counters[1], 128ull); c = 0; }
+		if(V.full >= (1 << PILE_TURN_BITS)) { atomicMax(&A.counters[1], KMAHIP_ST_PILE_TURNS); c = 0; }
 		A.seg_start[t] = 0;
 	}
 	A.vis_cnt[r] = c;
@@ -409,7 +409,7 @@ struct SegWalk {
 	__device__ __forceinline__ int depth16_node(int h) const { int s = 0; for(int j = 0; j < 6; ++j) s += (int) min(pile_lds[node_base() + 8 * (h - 1) + j], 65535u); return s; }
 	__device__ int new_node(int bias, int b, int gaps) const {
 		const int id = (int) atomicAdd(s_nodes, 1u) + 1;
-		if(id > node_cap()) { atomicMax(&A.counters[1], 64ull); return 0; }
+		if(id > node_cap()) { atomicMax(&A.counters[1], KMAHIP_ST_PILE_SEG_COLS); return 0; }
 		uint32_t *c = &pile_lds[node_base() + 8 * (id - 1)];
 		for(int x = 0; x < 6; ++x) c[x] = 0;
 		c[5] = (uint32_t) bias; c[b] = 1; c[6] = 0; c[7] = (uint32_t) gaps;
@@ -751,7 +751,7 @@ __global__ __launch_bounds__(PILE_THREADS) void pileup_kernel(const PileArgs A, 
 			if(tid == 0) s_pool = n_nodes ? (long long) atomicAdd(&A.counters[2], (unsigned long long) n_nodes) : 0;
 			__syncthreads();
 			const long long base = s_pool;
-			if(base + n_nodes > A.node_cap) { if(tid == 0) atomicMax(&A.counters[1], 32ull); }
+			if(base + n_nodes > A.node_cap) { if(tid == 0) atomicMax(&A.counters[1], KMAHIP_ST_PILE_NODES); }
 			else {
 				for(int i = tid; i < 6 * (hi - lo); i += (int) blockDim.x) A.counts[6 * (tbase + lo) + i] = pile_lds[6 + i];
 				for(int i = tid; i < hi - lo; i += (int) blockDim.x) { const int h = (int) pile_lds[6 * ncol + 1 + i]; A.chain_head[tbase + lo + i] = h ? (int32_t) (base + h) : 0; }
@@ -777,7 +777,7 @@ __global__ __launch_bounds__(PILE_THREADS) void pileup_kernel(const PileArgs A, 
 			if(tid == 0) s_pool = n_nodes ? (long long) atomicAdd(&A.counters[2], (unsigned long long) n_nodes) : 0;
 			__syncthreads();
 			const long long base = s_pool;
-			if(base + n_nodes > A.node_cap) { if(tid == 0) atomicMax(&A.counters[1], 32ull); }
+			if(base + n_nodes > A.node_cap) { if(tid == 0) atomicMax(&A.counters[1], KMAHIP_ST_PILE_NODES); }
 			else {
 				for(int i = tid; i < 6 * t_len; i += (int) blockDim.x) A.counts[6 * tbase + i] = pile_lds[i];
 				for(int i = tid; i < t_len; i += (int) blockDim.x) { const int h = (int) pile_lds[6 * t_len + i]; A.chain_head[tbase + i] = h ? (int32_t) (base + h) : 0; }
@@ -981,7 +981,7 @@ static int assemble_scratch(kmahip_db *db, kmahip_ws *ws, int64_t n_reads, int64
 		HIP_TRY(hipMalloc((void **) &ws->p_rank, (size_t) n_reads * 2 * sizeof(int64_t)));
 		ws->p_reads_cap = n_reads;
 	}
-	if(!ws->counters) { HIP_TRY(hipMalloc((void **) &ws->counters, KMAHIP_N_COUNTERS * sizeof(unsigned long long))); HIP_TRY(hipMemset(ws->counters, 0, KMAHIP_N_COUNTERS * sizeof(unsigned long long))); }
+	if(int rcc = kmahip_ws_counters(ws)) return rcc;
 	return KMAHIP_OK;
 }
 
@@ -1246,15 +1246,15 @@ static int pileup_device(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads
 		if(dbg) fprintf(stderr, "[kmahip] pile-up: launch of %lld units, %d columns per segment, %s LDS, whole templates %s, %s\n", (long long) n_units, seg_cols,
 		                half ? "half" : "full", lds_cols ? "in LDS" : "on HBM", A.ck_j ? "run checkpoints" : "no run checkpoints");
 		HIP_TRY(hipMemcpy(c, ws->counters, sizeof c, hipMemcpyDeviceToHost));
-		if(c[1] == 64 && half && seg_cols > 256) { seg_cols >>= 1; if(dbg) fprintf(stderr, "[kmahip] pile-up: a segment ran out of its half of the LDS, again with %d columns per segment\n", seg_cols); continue; }
-		if((c[1] == 16 || c[1] == 64) && half) { lds_half = false; if(dbg) fprintf(stderr, "[kmahip] pile-up: half the LDS did not hold a unit's insertion columns, again with all of it\n"); continue; }
-		if(c[1] == 64 && seg_cols > 64) { seg_cols >>= 1; if(dbg) fprintf(stderr, "[kmahip] pile-up: a segment ran out of LDS room, again with %d columns per segment\n", seg_cols); continue; }
-		if(c[1] == 16 && lds_cols) { lds_cols = 0; if(dbg) fprintf(stderr, "[kmahip] pile-up: the LDS did not hold a template's insertion columns, again with whole templates on HBM\n"); continue; }
+		if(c[1] == KMAHIP_ST_PILE_SEG_COLS && half && seg_cols > 256) { seg_cols >>= 1; if(dbg) fprintf(stderr, "[kmahip] pile-up: a segment ran out of its half of the LDS, again with %d columns per segment\n", seg_cols); continue; }
+		if((c[1] == KMAHIP_ST_PILE_LDS_COLS || c[1] == KMAHIP_ST_PILE_SEG_COLS) && half) { lds_half = false; if(dbg) fprintf(stderr, "[kmahip] pile-up: half the LDS did not hold a unit's insertion columns, again with all of it\n"); continue; }
+		if(c[1] == KMAHIP_ST_PILE_SEG_COLS && seg_cols > 64) { seg_cols >>= 1; if(dbg) fprintf(stderr, "[kmahip] pile-up: a segment ran out of LDS room, again with %d columns per segment\n", seg_cols); continue; }
+		if(c[1] == KMAHIP_ST_PILE_LDS_COLS && lds_cols) { lds_cols = 0; if(dbg) fprintf(stderr, "[kmahip] pile-up: the LDS did not hold a template's insertion columns, again with whole templates on HBM\n"); continue; }
 		break;
 	}
 	if(c[1]) {
 		HIP_TRY(hipMemset(ws->counters + 1, 0, sizeof(unsigned long long)));
-		if(c[1] >= 128) {
+		if(c[1] >= KMAHIP_ST_PILE_TURNS) {
 			kmahip_set_error("pile-up: a read goes round a template cut into units more than %d times", 1 << PILE_TURN_BITS);
 			return KMAHIP_EINVAL;
 		}

@@ -653,7 +653,7 @@ template <class CLane> __device__ void emit_record(CLane &L, Emit &E, int rc_fla
 	const unsigned lo2 = (unsigned) __builtin_amdgcn_readfirstlane((int) (toff0 & 0xFFFFFFFFull)), hi2 = (unsigned) __builtin_amdgcn_readfirstlane((int) (toff0 >> 32));
 	const unsigned long long slot = (((unsigned long long) hi0 << 32) | lo0) + (unsigned long long) __popcll(below);
 	const unsigned long long toff = (((unsigned long long) hi2 << 32) | lo2) + pre;
-	if((int64_t) slot >= A.rec_cap || (int64_t) (toff + nT) > A.T_cap) { atomicMax(&A.counters[1], 2ull); ++E.ordinal; return; }
+	if((int64_t) slot >= A.rec_cap || (int64_t) (toff + nT) > A.T_cap) { atomicMax(&A.counters[1], KMAHIP_ST_CALLER_CAP); ++E.ordinal; return; }
 	KMAHIP_GLOBAL int32_t *r = (KMAHIP_GLOBAL int32_t *) A.rec + 8 * slot;
 	r[0] = (int32_t) (E.read & 0xFFFFFFFFll); r[1] = (int32_t) (E.read >> 32); r[2] = E.ordinal++; r[3] = rc_flag; r[4] = emit_rc;
 	r[5] = q_start; r[6] = q_end; r[7] = nT;
@@ -942,7 +942,7 @@ __global__ __launch_bounds__(64, CHAIN_MIN_WAVES) void chain_kernel(const ChainA
 		chain_read(L, A, list ? list[x] : x);
 		if(L.status) {
 			// leave the per-template arrays clean for the next read of this lane, and say so
-			atomicMax(&A.counters[1], 40ull);
+			atomicMax(&A.counters[1], KMAHIP_ST_CHAIN_CAP);
 			for(int64_t t = 0; t <= D; ++t) { L.tm.Score[t] = 0; L.tm.extend[t] = 0; L.tm.include[t] = 0; }
 			L.status = 0;
 		}
@@ -1182,7 +1182,7 @@ __global__ __launch_bounds__(64, CHAIN_MIN_WAVES) void chain_long_tail_kernel(co
 		L.VR = L.VF + (seqlen - L.k + 2);
 		chain_read_tail(L, A, r, seqlen, (unsigned) hitF, (unsigned) hitR);
 		if(L.status) {
-			atomicMax(&A.counters[1], 40ull);
+			atomicMax(&A.counters[1], KMAHIP_ST_CHAIN_CAP);
 			for(int64_t t = 0; t <= D; ++t) { L.tm.Score[t] = 0; L.tm.extend[t] = 0; L.tm.include[t] = 0; }
 			L.status = 0;
 		}
@@ -1554,8 +1554,8 @@ int kmahip_chain_device(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *d, con
 	HIP_TRY(hipMemcpy(c, A.counters, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
 	HIP_TRY(hipMemcpy(&c[2], A.counters + CH_T, sizeof(unsigned long long), hipMemcpyDeviceToHost));
 	*n_recs = (int64_t) c[0]; *n_T = (int64_t) c[2];
-	if(c[1] == 40) { kmahip_set_error("default template finder: a per-read capacity ran out (more than %d chains in a read, or chains nested deeper than %d in the tree of covered stretches)", s_cap_of_len / 2, SEG_DEPTH); return KMAHIP_EOVERFLOW; }
-	if(c[1] == 2 || (int64_t) c[0] > rec_cap || (int64_t) c[2] > T_cap) { kmahip_set_error("record capacity: %llu records with %llu templates", c[0], c[2]); return KMAHIP_EOVERFLOW; }
+	if(c[1] == KMAHIP_ST_CHAIN_CAP) { kmahip_set_error("default template finder: a per-read capacity ran out (more than %d chains in a read, or chains nested deeper than %d in the tree of covered stretches)", s_cap_of_len / 2, SEG_DEPTH); return KMAHIP_EOVERFLOW; }
+	if(c[1] == KMAHIP_ST_CALLER_CAP || (int64_t) c[0] > rec_cap || (int64_t) c[2] > T_cap) { kmahip_set_error("record capacity: %llu records with %llu templates", c[0], c[2]); return KMAHIP_EOVERFLOW; }
 	return KMAHIP_OK;
 }
 

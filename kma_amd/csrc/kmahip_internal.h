@@ -18,6 +18,23 @@
 // tasks; [+5] hand-ons over the queues (tasks punted behind a queued problem, entries that found no room)
 #define KMAHIP_C_ADQ 24
 #define KMAHIP_KBITS_MUL 0x85EBCA6Bu      // device counter words per workspace
+// The status word, counters[1] of a workspace (and of the chain finder's own counter block): the kernels raise it with atomicMax, so
+// the largest code of a launch is what the host reads, and clears, once the stage is synchronised (pipeline_util.h: ws_status and the
+// three retries; api.hip: ws_classify; assemble.hip keeps the pile-up's codes to itself). The traceback and the pile-up never run
+// between two reads of the word, so they share the value 16.
+enum KmaStatus : unsigned long long {
+	KMAHIP_ST_POOL = 1,             // stage 2: the library's candidate pool ran out (kmahip_ws::pool_scale doubles, the scan is repeated)
+	KMAHIP_ST_CALLER_CAP = 2,       // a capacity the caller chose is too small (T_cap, ops_cap, the chain finder's record room): the needed size is reported
+	KMAHIP_ST_SEED_MEMS = 3,        // stage 3a: more MEMs between a read and a template than kmahip_ws::mem_scale gives slots for
+	KMAHIP_ST_TRACE_RUNS = 4,       // traceback: a read's runs outgrew the lane's buffer
+	KMAHIP_ST_TRACE_DP = 8,         // traceback: a DP problem outgrew the lane's scratch
+	KMAHIP_ST_TRACE_MEMS = 16,      // traceback: as KMAHIP_ST_SEED_MEMS
+	KMAHIP_ST_PILE_LDS_COLS = 16,   // pile-up: the LDS did not hold a template's (or a unit's) insertion columns
+	KMAHIP_ST_PILE_NODES = 32,      // pile-up: the pool of insertion columns in HBM ran out
+	KMAHIP_ST_CHAIN_CAP = 40,       // chain finder: a per-read capacity ran out (chains per read, depth of the tree of covered stretches)
+	KMAHIP_ST_PILE_SEG_COLS = 64,   // pile-up: a segment's insertion columns outgrew its share of the LDS
+	KMAHIP_ST_PILE_TURNS = 128      // pile-up: a read goes round a template cut into units too often
+};
 
 // Probe table in HBM: open hashing over 32-byte buckets of 4 (key, position)
 // slots. bucket(key) = (key * GOLD) >> (32 - nb_log2); a key lives in the first
@@ -91,9 +108,9 @@ struct kmahip_ws {
 	// candidate pool
 	int32_t *pool;
 	int64_t pool_cap;
-	int64_t pool_scale;       // pool = cap_reads * 16 * pool_scale ints; doubled after an overflow
+	int64_t pool_scale;       // pool = cap_reads * 16 (KMAHIP_SCAN_POOL_PER_READ) * pool_scale ints; doubled after an overflow (grow_pool)
 	int mem_scale;            // MEM slots per (read, template) = the usual 64 (reads up to 1 kb) x this; raised by the runs when a read
-	                          // full of repeats carries more (status 3), 0 = 1
+	                          // full of repeats carries more (KMAHIP_ST_SEED_MEMS, KMAHIP_ST_TRACE_MEMS), 0 = 1
 	// counters (KMAHIP_N_COUNTERS): [0] pool top, [1] status, [2] n_overflow, [3] probes, [4] value elems, [5] active strands,
 	// [6] hash probes, [7] pair pool top, [8] live strand items on the bare list, [9] prefilter probes, [21] records, [22] replaced diagonals, [24..29] stage 3a's class queues (KMAHIP_C_ADQ)
 	unsigned long long *counters;
@@ -184,6 +201,13 @@ int kmahip_comp_read(const std::string &comp, bool allow_sparse, KmaComp *c);
 int kmahip_cmp(bool t, bool q);          // conclave.hip: the reference's `cmp` (or / and / true, kmahip_set_cmp)
 #define HIP_TRY(expr) do { hipError_t e__ = (expr); if(e__ != hipSuccess) { \
 	kmahip_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); return KMAHIP_EDEVICE; } } while(0)
+// the workspace's counter block, made (and zeroed) by whichever stage runs first
+static inline int kmahip_ws_counters(kmahip_ws *ws) {
+	if(ws->counters) return KMAHIP_OK;
+	HIP_TRY(hipMalloc((void **) &ws->counters, KMAHIP_N_COUNTERS * sizeof(unsigned long long)));
+	HIP_TRY(hipMemset(ws->counters, 0, KMAHIP_N_COUNTERS * sizeof(unsigned long long)));
+	return KMAHIP_OK;
+}
 
 // Proximity matching (-proxi: kmahip_params.minFrac other than 1 and -1, kma.c:708) is built for the single-end -1t1 run, stages 2
 // and 3a (getProxiMatch, update_Scores). Every other entry point refuses it by name: KMAHIP_EINVAL, `what` = what is not built.

@@ -2589,8 +2589,8 @@ int kmahip_launch_longtrace(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *re
 	if(score_mode) return KMAHIP_OK;          // (no runs; the workspace's status word is stage 3a's)
 	unsigned long long fin[2] = {0, 0};
 	HIP_TRY(hipMemcpy(&fin[0], counters + LCI(LC_OUT), 8, hipMemcpyDeviceToHost));
-	if((int64_t) fin[0] > out->ops_cap) fin[1] = 2;
-	if(!ws->counters) { HIP_TRY(hipMalloc((void **) &ws->counters, KMAHIP_N_COUNTERS * sizeof(unsigned long long))); HIP_TRY(hipMemset(ws->counters, 0, KMAHIP_N_COUNTERS * sizeof(unsigned long long))); }
+	if((int64_t) fin[0] > out->ops_cap) fin[1] = KMAHIP_ST_CALLER_CAP;
+	if(int rcc = kmahip_ws_counters(ws)) return rcc;
 	HIP_TRY(hipMemcpy(ws->counters, fin, sizeof fin, hipMemcpyHostToDevice));
 	return KMAHIP_OK;
 }

@@ -191,19 +191,14 @@ static int run_after_stage2(kmahip_db *db, kmahip_ws *ws, DevBlock &B, const kma
 	int rc;
 	// stage 3a
 	kmahip_hits h;
-	if((rc = B.get((size_t) n + 1, &h.n_hits, true)) || (rc = B.get((size_t) n + 1, &h.best_score, true)) || (rc = B.get((size_t) n + 1, &h.flag, true)) ||
-	   (rc = B.get((size_t) n + 1, &h.rc, true)) || (rc = B.get((size_t) total + 1, &h.tmpl, true)) || (rc = B.get((size_t) total + 1, &h.score, true)) ||
-	   (rc = B.get((size_t) total + 1, &h.start, true)) || (rc = B.get((size_t) total + 1, &h.end, true)) ||
-	   (rc = B.get(D, &h.alignment_scores, true)) || (rc = B.get(D, &h.uniq_alignment_scores, true))) return rc;
+	if((rc = carve_hits((size_t) n, (size_t) total, &h, [&](size_t k, int32_t **a) { return B.get(k, a, true); })) ||
+	   (rc = B.get(D, &h.alignment_scores)) || (rc = B.get(D, &h.uniq_alignment_scores))) return rc;
 	if(dbg) { auto t2 = t; fprintf(stderr, "[kmahip] run_se: stage 3a buffers after %.2f ms\n", since(t2)); }
-	for(;;) {
-		if(n && (rc = kmahip_stage3a_se(db, ws, &d, &c, p, &h, s))) return rc;
+	if((rc = retry_seed_room(ws, s, h.alignment_scores, h.uniq_alignment_scores, D * 8, [&] {
+		const int rl = n ? kmahip_stage3a_se(db, ws, &d, &c, p, &h, s) : KMAHIP_OK;
 		if(dbg) { auto t2 = t; fprintf(stderr, "[kmahip] run_se: stage 3a launched after %.2f ms\n", since(t2)); }
-		HIP_TRY(hipStreamSynchronize(s));
-		if(ws_status(ws, nullptr) != 3) break;
-		if(!grow_mem_cap(ws)) { kmahip_set_error("seed (MEM) capacity per read/template pair exceeded"); return KMAHIP_EOVERFLOW; }
-		HIP_TRY(hipMemsetAsync(h.alignment_scores, 0, D * 8, s)); HIP_TRY(hipMemsetAsync(h.uniq_alignment_scores, 0, D * 8, s));
-	}
+		return rl;
+	}))) return rc;
 	out->ms[1] = since(t);
 
 	// stage 3b + the `.res` statistics (host arithmetic on one u64 per template)
@@ -232,24 +227,11 @@ static int run_after_stage2(kmahip_db *db, kmahip_ws *ws, DevBlock &B, const kma
 	out->ms[2] = since(t);
 
 	// stage 3c per read; the run pool is sized for a handful of runs per read and grown on demand
-	kmahip_traces tr;
+	kmahip_traces tr{};
 	if((rc = B.get((size_t) 10 * n + 10, &tr.stats)) || (rc = B.get((size_t) n + 1, &tr.ops_off)) || (rc = B.get((size_t) n + 1, &tr.n_ops))) return rc;
-	tr.ops_cap = 6 * n + (1 << 20);
-	for(int attempt = 0; n; ++attempt) {
-		if((rc = B.get((size_t) tr.ops_cap, &tr.ops))) return rc;
-		if((rc = kmahip_launch_trace(db, ws, &d, h.rc, cc.tmpl, d_ok, p, &tr, s))) return rc;
-		HIP_TRY(hipStreamSynchronize(s));
-		unsigned long long used = 0;
-		const int st = ws_status(ws, &used);
-		if(st == 2 || (int64_t) used > tr.ops_cap) {
-			if(attempt >= 2) { kmahip_set_error("alignment run pool: %llu runs needed", used); return KMAHIP_EOVERFLOW; }
-			tr.ops_cap = (int64_t) used + (1 << 20);
-			continue;
-		}
-		if(st == 16 && grow_mem_cap(ws)) { --attempt; continue; }
-		if(st) { kmahip_set_error("trace stage: a read needs more scratch than the workspace holds (status %d)", st); return KMAHIP_EDEVICE; }
-		break;
-	}
+	unsigned long long used = 0;
+	if(n && (rc = retry_run_room(ws, s, 6 * n + (1 << 20), 1 << 20, true, &used, run_pool_in(B, tr),
+	                             [&] { return kmahip_launch_trace(db, ws, &d, h.rc, cc.tmpl, d_ok, p, &tr, s); }))) return rc;
 	out->ms[3] = since(t);
 
 	// stage 3c per template
@@ -285,11 +267,8 @@ extern "C" int kmahip_run_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *r
 
 	// the batch, once (the slabs are sized for what a run of n reads usually needs: ~230 bytes per read next to the reads)
 	B.expect((size_t) reads->seq_words * 8 + (size_t) reads->N_total * 4 + (size_t) n * 280 + (64u << 20));
-	kmahip_reads d = *reads;
-	d.q_start = nullptr; d.q_end = nullptr;       // (host pointers, if any: this entry point maps whole reads)
-	if((rc = B.up(reads->seq, (size_t) reads->seq_words, 2, &d.seq)) || (rc = B.up(reads->seq_off, (size_t) n + 1, 0, &d.seq_off)) ||
-	   (rc = B.up(reads->len, (size_t) n, 1, &d.len)) || (rc = B.up(reads->N, (size_t) reads->N_total, 1, &d.N)) ||
-	   (rc = B.up(reads->N_off, (size_t) n + 1, 0, &d.N_off))) return rc;
+	kmahip_reads d;
+	if((rc = upload_reads(B, *reads, &d))) return rc;
 	HIP_TRY(hipStreamSynchronize(s));
 	out->ms[0] = since(t);
 
@@ -297,23 +276,9 @@ extern "C" int kmahip_run_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *r
 	kmahip_cands c;
 	if((rc = B.get((size_t) n + 1, &c.rc_flag)) || (rc = B.get((size_t) n + 1, &c.flag)) || (rc = B.get((size_t) n + 1, &c.T_off))) return rc;
 	int64_t total = 0;
-	c.T_cap = 2 * n + 4096;
-	for(int attempt = 0;; ++attempt) {
-		if((rc = B.get((size_t) c.T_cap, &c.T))) return rc;
-		if((rc = kmahip_launch_scan_se(db, ws, &d, p, &c, s))) return rc;
-		HIP_TRY(hipStreamSynchronize(s));
-		const int st = ws_status(ws, nullptr);
-		if(st == 1) {
-			if(attempt >= 4) { kmahip_set_error("internal candidate pool exhausted"); return KMAHIP_EOVERFLOW; }
-			ws->pool_scale *= 2; ws->cap_reads = 0;     // grown by the next launch
-			continue;
-		}
-		HIP_TRY(hipMemcpy(&total, c.T_off + n, sizeof total, hipMemcpyDeviceToHost));
-		if(dbg) { auto t2 = t; fprintf(stderr, "[kmahip] run_se: scan attempt %d: %.1f ms, %lld candidates (cap %lld)\n", attempt, since(t2), (long long) total, (long long) c.T_cap); }
-		if(total <= c.T_cap) break;
-		c.T_cap = total + 1024;
-	}
-	if(dbg) { auto t2 = t; fprintf(stderr, "[kmahip] run_se: stage 2 done after %.1f ms\n", since(t2)); }
+	if((rc = retry_cand_room(ws, s, 2 * n + 4096, 1024, c.T_off + n, &total, [&](int64_t cap) { c.T_cap = cap; return B.get((size_t) cap, &c.T); },
+	                         [&] { return kmahip_launch_scan_se(db, ws, &d, p, &c, s); }))) return rc;
+	if(dbg) { auto t2 = t; fprintf(stderr, "[kmahip] run_se: stage 2 done after %.1f ms, %lld candidates (cap %lld)\n", since(t2), (long long) total, (long long) c.T_cap); }
 
 	PerRead pr = {out->tmpl, out->n_hits, out->rc, out->trace_stats};
 	return run_after_stage2(db, ws, B, d, c, total, p, evalue, bcd, max_frag, out, pr, t);
@@ -664,8 +629,7 @@ static int run_pe_impl(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *ba
 	B.expect((size_t) R.seq_words * 16 + (size_t) R.N_total * 8 + (size_t) n * 420 + (64u << 20));
 	kmahip_reads dR = R;
 	dR.q_start = nullptr; dR.q_end = nullptr;
-	if(!pd && ((rc = B.up(R.seq, (size_t) R.seq_words, 2, &dR.seq)) || (rc = B.up(R.seq_off, (size_t) n + 1, 0, &dR.seq_off)) ||
-	   (rc = B.up(R.len, (size_t) n, 1, &dR.len)) || (rc = B.up(R.N, (size_t) R.N_total, 1, &dR.N)) || (rc = B.up(R.N_off, (size_t) n + 1, 0, &dR.N_off)))) return rc;
+	if(!pd && (rc = upload_reads(B, R, &dR))) return rc;
 	kmahip_reads dP = dR, dS = dR;
 	dS.n_reads = 0;
 	std::vector<int64_t> s_idx;
@@ -699,20 +663,8 @@ static int run_pe_impl(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *ba
 	   (rc = B.get((size_t) 2 * np + 2, &recs.flag)) || (rc = B.get((size_t) 2 * np + 2, &recs.R_off, true))) return rc;
 	int64_t totP = 0, totS = 0;
 	recs.T_cap = 4 * np + 4096; recs.T = nullptr;
-	for(int attempt = 0; np > 0; ++attempt) {
-		if((rc = B.get((size_t) recs.T_cap, &recs.T))) return rc;
-		if((rc = kmahip_launch_scan_pe(db, ws, &dP, p, &recs, s))) return rc;
-		HIP_TRY(hipStreamSynchronize(s));
-		if(ws_status(ws, nullptr) == 1) {
-			if(attempt >= 4) { kmahip_set_error("internal candidate pool exhausted"); return KMAHIP_EOVERFLOW; }
-			ws->pool_scale *= 2; ws->cap_reads = 0;
-			continue;
-		}
-		HIP_TRY(hipMemcpy(&totP, recs.R_off + 2 * np, sizeof totP, hipMemcpyDeviceToHost));
-		if(totP <= recs.T_cap) break;
-		if(attempt >= 6) { kmahip_set_error("candidate lists keep growing"); return KMAHIP_EOVERFLOW; }
-		recs.T_cap = totP + 1024;
-	}
+	if(np > 0 && (rc = retry_cand_room(ws, s, 4 * np + 4096, 1024, recs.R_off + 2 * np, &totP, [&](int64_t cap) { recs.T_cap = cap; return B.get((size_t) cap, &recs.T); },
+	                                   [&] { return kmahip_launch_scan_pe(db, ws, &dP, p, &recs, s); }))) return rc;
 	stamp("stage 2 of the pairs");
 	kmahip_cands cd;
 	if((rc = B.get((size_t) ns + 1, &cd.rc_flag)) || (rc = B.get((size_t) ns + 1, &cd.flag)) || (rc = B.get((size_t) ns + 1, &cd.T_off, true))) return rc;
@@ -746,20 +698,8 @@ static int run_pe_impl(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *ba
 	const int64_t n_slots = 2 * U;
 	const int32_t *d_first = nullptr, *d_uidx = nullptr;
 	if((rc = B.up(u_first.get(), (size_t) U + 1, 1, &d_first)) || (rc = B.up(u_idx.get(), (size_t) U + 1, 1, &d_uidx))) return rc;
-	for(int attempt = 0; ns > 0 && !cp; ++attempt) {
-		if((rc = B.get((size_t) cd.T_cap, &cd.T))) return rc;
-		if((rc = kmahip_launch_scan_se(db, ws, &dS, p, &cd, s))) return rc;
-		HIP_TRY(hipStreamSynchronize(s));
-		if(ws_status(ws, nullptr) == 1) {
-			if(attempt >= 4) { kmahip_set_error("internal candidate pool exhausted"); return KMAHIP_EOVERFLOW; }
-			ws->pool_scale *= 2; ws->cap_reads = 0;
-			continue;
-		}
-		HIP_TRY(hipMemcpy(&totS, cd.T_off + ns, sizeof totS, hipMemcpyDeviceToHost));
-		if(totS <= cd.T_cap) break;
-		if(attempt >= 6) { kmahip_set_error("candidate lists keep growing"); return KMAHIP_EOVERFLOW; }
-		cd.T_cap = totS + 1024;
-	}
+	if(ns > 0 && !cp && (rc = retry_cand_room(ws, s, 2 * ns + 4096, 1024, cd.T_off + ns, &totS, [&](int64_t cap) { cd.T_cap = cap; return B.get((size_t) cap, &cd.T); },
+	                                          [&] { return kmahip_launch_scan_se(db, ws, &dS, p, &cd, s); }))) return rc;
 
 	// stage 3a: one set of hit arrays (the pairs' lists first), one pair of ConClave vectors
 	const size_t H = (size_t) totP + (size_t) totS + 2;
@@ -772,26 +712,20 @@ static int run_pe_impl(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *ba
 	   (rc = B.get((size_t) ns + 1, &sh.n_hits, true)) || (rc = B.get((size_t) ns + 1, &sh.best_score, true)) || (rc = B.get((size_t) ns + 1, &sh.flag, true)) ||
 	   (rc = B.get((size_t) ns + 1, &sh.rc, true)) ||
 	   (rc = B.get(H, &H_tmpl, true)) || (rc = B.get(H, &H_score, true)) || (rc = B.get(H, &H_start, true)) || (rc = B.get(H, &H_end, true)) ||
-	   (rc = B.get(D, &AS, true)) || (rc = B.get(D, &US, true))) return rc;
+	   (rc = B.get(D, &AS)) || (rc = B.get(D, &US))) return rc;
 	ph.tmpl = H_tmpl; ph.score = H_score; ph.start = H_start; ph.end = H_end; ph.alignment_scores = AS; ph.uniq_alignment_scores = US;
 	sh.tmpl = H_tmpl + s_base; sh.score = H_score + s_base; sh.start = H_start + s_base; sh.end = H_end + s_base; sh.alignment_scores = AS; sh.uniq_alignment_scores = US;
-	for(;;) {
-		bool again = false;
+	// (both stages add into the two vectors; the status word is raised, never lowered, so one look behind the two tells of either)
+	if((rc = retry_seed_room(ws, s, AS, US, D * 8, [&] {
+		int rl = KMAHIP_OK;
 		if(np > 0) {
-			if((rc = kmahip_stage3a_pe(db, ws, &dP, &recs, p, &ph, kind, s))) return rc;
-			HIP_TRY(hipStreamSynchronize(s));
-			again = ws_status(ws, nullptr) == 3;
+			if((rl = kmahip_stage3a_pe(db, ws, &dP, &recs, p, &ph, kind, s))) return rl;
+			if(hipStreamSynchronize(s) != hipSuccess) { kmahip_set_error("stage 3a of the pairs failed"); return (int) KMAHIP_EDEVICE; }
 		}
 		stamp("stage 3a of the pairs");
-		if(ns > 0 && !again) {
-			if((rc = kmahip_stage3a_se(db, ws, &dS, &cd, p, &sh, s))) return rc;
-			HIP_TRY(hipStreamSynchronize(s));
-			again = ws_status(ws, nullptr) == 3;
-		}
-		if(!again) break;
-		if(!grow_mem_cap(ws)) { kmahip_set_error("seed (MEM) capacity per read/template pair exceeded"); return KMAHIP_EOVERFLOW; }
-		HIP_TRY(hipMemsetAsync(AS, 0, D * 8, s)); HIP_TRY(hipMemsetAsync(US, 0, D * 8, s));          // (both stages add into them)
-	}
+		if(ns > 0) rl = kmahip_stage3a_se(db, ws, &dS, &cd, p, &sh, s);
+		return rl;
+	}))) return rc;
 	out->ms[1] = since(t);
 	if(sc && ((rc = shard_allreduce(sc, AS, D)) || (rc = shard_allreduce(sc, US, D)))) return rc;          // exchange 1
 
@@ -922,26 +856,13 @@ static int run_pe_impl(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *ba
 		stamp("fragment batch");
 		// stage 3c per fragment; the run pool is sized for a handful of runs per read and grown on demand
 		if((rc = B.get((size_t) 10 * nf + 10, &tr.stats)) || (rc = B.get((size_t) nf + 1, &tr.ops_off)) || (rc = B.get((size_t) nf + 1, &tr.n_ops))) return rc;
-		tr.ops_cap = 6 * nf + (1 << 20);
 		if(sam_level && !(sam_level & 2096)) {
 			if((rc = B.get((size_t) 6 * nf + 6, &drops.stats, true)) || (rc = B.get((size_t) nf + 1, &drops.ops_off, true)) || (rc = B.get((size_t) nf + 1, &drops.n_ops, true)) ||
 			   (rc = kmahip_ws_set_trace_drops(ws, &drops))) return rc;
 		}
-		for(int attempt = 0;; ++attempt) {
-			if((rc = B.get((size_t) tr.ops_cap, &tr.ops))) return rc;
-			if((rc = kmahip_launch_trace(db, ws, &dF, f_rc, f_t, d_ok, p, &tr, s))) return rc;
-			HIP_TRY(hipStreamSynchronize(s));
-			unsigned long long used = 0;
-			const int st = ws_status(ws, &used);
-			if(st == 2 || (int64_t) used > tr.ops_cap) {
-				if(attempt >= 2) { kmahip_set_error("alignment run pool: %llu runs needed", used); return KMAHIP_EOVERFLOW; }
-				tr.ops_cap = (int64_t) used + (1 << 20);
-				continue;
-			}
-			if(st == 16 && grow_mem_cap(ws)) { --attempt; continue; }
-			if(st) { kmahip_set_error("trace stage: a read needs more scratch than the workspace holds (status %d)", st); return KMAHIP_EDEVICE; }
-			break;
-		}
+		unsigned long long used = 0;
+		if((rc = retry_run_room(ws, s, 6 * nf + (1 << 20), 1 << 20, true, &used, run_pool_in(B, tr),
+		                        [&] { return kmahip_launch_trace(db, ws, &dF, f_rc, f_t, d_ok, p, &tr, s); }))) return rc;
 	}
 	out->ms[3] = since(t);
 	if(sc) {
@@ -1186,11 +1107,8 @@ extern "C" int kmahip_run_chain(kmahip_db *db, kmahip_ws *ws, const kmahip_reads
 	// the batch, once
 	DevBlock B;
 	B.expect((size_t) reads->seq_words * 16 + (size_t) reads->N_total * 8 + (size_t) n * 480 + (64u << 20));
-	kmahip_reads dR = *reads;
-	dR.q_start = nullptr; dR.q_end = nullptr;
-	if((rc = B.up(reads->seq, (size_t) reads->seq_words, 2, &dR.seq)) || (rc = B.up(reads->seq_off, (size_t) n + 1, 0, &dR.seq_off)) ||
-	   (rc = B.up(reads->len, (size_t) n, 1, &dR.len)) || (rc = B.up(reads->N, (size_t) reads->N_total, 1, &dR.N)) ||
-	   (rc = B.up(reads->N_off, (size_t) n + 1, 0, &dR.N_off))) return rc;
+	kmahip_reads dR;
+	if((rc = upload_reads(B, *reads, &dR))) return rc;
 	HIP_TRY(hipStreamSynchronize(s));
 	out->ms[0] = since(t);
 	lap("reads uploaded");
@@ -1254,33 +1172,20 @@ extern "C" int kmahip_run_mt1(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *
 	DevBlock B;
 	int rc;
 	auto t = std::chrono::steady_clock::now();
-	kmahip_reads d = *reads;
-	d.q_start = nullptr; d.q_end = nullptr;       // (host pointers, if any: this entry point maps whole reads)
-	if((rc = B.up(reads->seq, (size_t) reads->seq_words, 2, &d.seq)) || (rc = B.up(reads->seq_off, (size_t) n + 1, 0, &d.seq_off)) ||
-	   (rc = B.up(reads->len, (size_t) n, 1, &d.len)) || (rc = B.up(reads->N, (size_t) reads->N_total, 1, &d.N)) ||
-	   (rc = B.up(reads->N_off, (size_t) n + 1, 0, &d.N_off))) return rc;
+	kmahip_reads d;
+	if((rc = upload_reads(B, *reads, &d))) return rc;
 	HIP_TRY(hipStreamSynchronize(s));
 	out->ms[0] = since(t);
 	// stage 3c per read: strand + traceback; the run pool grows on demand
-	kmahip_traces tr;
+	kmahip_traces tr{};
 	int32_t *d_rc = nullptr, *d_tmpl = nullptr;
 	if((rc = B.get((size_t) 10 * n + 10, &tr.stats)) || (rc = B.get((size_t) n + 1, &tr.ops_off)) || (rc = B.get((size_t) n + 1, &tr.n_ops)) ||
 	   (rc = B.get((size_t) n + 1, &d_rc)) || (rc = B.get((size_t) n + 1, &d_tmpl))) return rc;
 	int64_t total_bases = 0;
 	for(int64_t i = 0; i < n; ++i) total_bases += reads->len[i];
-	tr.ops_cap = total_bases / 3 + 8 * n + (1 << 16);
-	for(int attempt = 0; n; ++attempt) {
-		if((rc = B.get((size_t) tr.ops_cap, &tr.ops))) return rc;
-		if((rc = kmahip_launch_longtrace(db, ws, &d, nullptr, tmpl, nullptr, nullptr, one2one, p, &tr, d_rc, s))) return rc;
-		unsigned long long used = 0;
-		const int st = ws_status(ws, &used);
-		if(st == 2 || (int64_t) used > tr.ops_cap) {
-			if(attempt >= 2) { kmahip_set_error("alignment run pool: %llu runs needed", used); return KMAHIP_EOVERFLOW; }
-			tr.ops_cap = (int64_t) used + (1 << 16);
-			continue;
-		}
-		break;
-	}
+	unsigned long long used = 0;
+	if(n && (rc = retry_run_room(ws, s, total_bases / 3 + 8 * n + (1 << 16), 1 << 16, false, &used, run_pool_in(B, tr),
+	                             [&] { return kmahip_launch_longtrace(db, ws, &d, nullptr, tmpl, nullptr, nullptr, one2one, p, &tr, d_rc, s); }))) return rc;
 	out->ms[3] = since(t);
 	// the per-read figures: Score of the `.res` row = sum of KMA()'s own scores of the kept reads (alnToMat, assembly.c:1328-1334),
 	// i.e. without the end bonus the read filter added
@@ -1853,17 +1758,9 @@ static int sharded_after_stage2(kmahip_db *db, kmahip_ws *ws, kmahip_comm *comm,
 	if(!c.T && (rc = B.get(16, &c.T))) return rc;
 	kmahip_hits h;
 	uint64_t *AS = nullptr;
-	if((rc = B.get((size_t) n + 1, &h.n_hits, true)) || (rc = B.get((size_t) n + 1, &h.best_score, true)) || (rc = B.get((size_t) n + 1, &h.flag, true)) ||
-	   (rc = B.get((size_t) n + 1, &h.rc, true)) || (rc = B.get((size_t) total + 1, &h.tmpl, true)) || (rc = B.get((size_t) total + 1, &h.score, true)) ||
-	   (rc = B.get((size_t) total + 1, &h.start, true)) || (rc = B.get((size_t) total + 1, &h.end, true)) || (rc = B.get(2 * D, &AS, true))) return rc;
+	if((rc = carve_hits((size_t) n, (size_t) total, &h, [&](size_t k, int32_t **a) { return B.get(k, a, true); })) || (rc = B.get(2 * D, &AS))) return rc;
 	h.alignment_scores = AS; h.uniq_alignment_scores = AS + D;
-	for(;;) {
-		if(n && (rc = kmahip_stage3a_se(db, ws, &d, &c, p, &h, s))) return rc;
-		HIP_TRY(hipStreamSynchronize(s));
-		if(ws_status(ws, nullptr) != 3) break;
-		if(!grow_mem_cap(ws)) { kmahip_set_error("seed (MEM) capacity per read/template pair exceeded"); return KMAHIP_EOVERFLOW; }
-		HIP_TRY(hipMemsetAsync(AS, 0, 2 * D * 8, s));
-	}
+	if((rc = retry_seed_room(ws, s, AS, nullptr, 2 * D * 8, [&] { return n ? kmahip_stage3a_se(db, ws, &d, &c, p, &h, s) : KMAHIP_OK; }))) return rc;
 	ms[1] = since(t);
 
 	// exchange 1: the two score vectors summed over the shards; ConClave on them; exchange 2: its per-template outputs summed
@@ -1892,21 +1789,9 @@ static int sharded_after_stage2(kmahip_db *db, kmahip_ws *ws, kmahip_comm *comm,
 	kmahip_traces tr;
 	if((rc = B.get((size_t) 10 * n + 10, &tr.stats, true)) || (rc = B.get((size_t) n + 1, &tr.ops_off, true)) || (rc = B.get((size_t) n + 1, &tr.n_ops, true))) return rc;
 	tr.ops_cap = 6 * n + (1 << 20); tr.ops = nullptr;
-	for(int attempt = 0; n; ++attempt) {
-		if((rc = B.get((size_t) tr.ops_cap, &tr.ops))) return rc;
-		if((rc = kmahip_launch_trace(db, ws, &d, h.rc, cc.tmpl, d_ok, p, &tr, s))) return rc;
-		HIP_TRY(hipStreamSynchronize(s));
-		unsigned long long used = 0;
-		const int st = ws_status(ws, &used);
-		if(st == 2 || (int64_t) used > tr.ops_cap) {
-			if(attempt >= 2) { kmahip_set_error("alignment run pool: %llu runs needed", used); return KMAHIP_EOVERFLOW; }
-			tr.ops_cap = (int64_t) used + (1 << 20);
-			continue;
-		}
-		if(st == 16 && grow_mem_cap(ws)) { --attempt; continue; }
-		if(st) { kmahip_set_error("trace stage: a read needs more scratch than the workspace holds (status %d)", st); return KMAHIP_EDEVICE; }
-		break;
-	}
+	unsigned long long used = 0;
+	if(n && (rc = retry_run_room(ws, s, 6 * n + (1 << 20), 1 << 20, true, &used, run_pool_in(B, tr),
+	                             [&] { return kmahip_launch_trace(db, ws, &d, h.rc, cc.tmpl, d_ok, p, &tr, s); }))) return rc;
 	if(!tr.ops && (rc = B.get(16, &tr.ops))) return rc;
 	ms[3] = since(t);
 
@@ -1946,10 +1831,8 @@ extern "C" int kmahip_run_se_sharded(kmahip_db *db, kmahip_ws *ws, kmahip_comm *
 
 	// the shard, once
 	B.expect((size_t) R.seq_words * 8 + (size_t) R.N_total * 4 + (size_t) n * 320 + (64u << 20));
-	kmahip_reads d = R;
-	d.q_start = nullptr; d.q_end = nullptr;
-	if((rc = B.up(R.seq, (size_t) R.seq_words, 2, &d.seq)) || (rc = B.up(R.seq_off, (size_t) n + 1, 0, &d.seq_off)) || (rc = B.up(R.len, (size_t) n, 1, &d.len)) ||
-	   (rc = B.up(R.N, (size_t) R.N_total, 1, &d.N)) || (rc = B.up(R.N_off, (size_t) n + 1, 0, &d.N_off))) return rc;
+	kmahip_reads d;
+	if((rc = upload_reads(B, R, &d))) return rc;
 	HIP_TRY(hipStreamSynchronize(s));
 	ms[0] = since(t);
 
@@ -1958,20 +1841,8 @@ extern "C" int kmahip_run_se_sharded(kmahip_db *db, kmahip_ws *ws, kmahip_comm *
 	if((rc = B.get((size_t) n + 1, &c.rc_flag)) || (rc = B.get((size_t) n + 1, &c.flag)) || (rc = B.get((size_t) n + 1, &c.T_off, true))) return rc;
 	int64_t total = 0;
 	c.T_cap = 2 * n + 4096; c.T = nullptr;
-	for(int attempt = 0; n > 0; ++attempt) {
-		if((rc = B.get((size_t) c.T_cap, &c.T))) return rc;
-		if((rc = kmahip_launch_scan_se(db, ws, &d, p, &c, s))) return rc;
-		HIP_TRY(hipStreamSynchronize(s));
-		if(ws_status(ws, nullptr) == 1) {
-			if(attempt >= 4) { kmahip_set_error("internal candidate pool exhausted"); return KMAHIP_EOVERFLOW; }
-			ws->pool_scale *= 2; ws->cap_reads = 0;
-			continue;
-		}
-		HIP_TRY(hipMemcpy(&total, c.T_off + n, sizeof total, hipMemcpyDeviceToHost));
-		if(total <= c.T_cap) break;
-		if(attempt >= 6) { kmahip_set_error("candidate lists keep growing"); return KMAHIP_EOVERFLOW; }
-		c.T_cap = total + 1024;
-	}
+	if(n > 0 && (rc = retry_cand_room(ws, s, 2 * n + 4096, 1024, c.T_off + n, &total, [&](int64_t cap) { c.T_cap = cap; return B.get((size_t) cap, &c.T); },
+	                                  [&] { return kmahip_launch_scan_se(db, ws, &d, p, &c, s); }))) return rc;
 	return sharded_after_stage2(db, ws, comm, B, batch, d, c, total, nullptr, p, opts, out_prefix, ms, t);
 }
 
@@ -1996,10 +1867,8 @@ extern "C" int kmahip_run_chain_sharded(kmahip_db *db, kmahip_ws *ws, kmahip_com
 	auto t = std::chrono::steady_clock::now();
 	if((rc = kmahip_db_load_names(db))) return rc;
 	B.expect((size_t) R.seq_words * 16 + (size_t) R.N_total * 8 + (size_t) n * 520 + (64u << 20));
-	kmahip_reads dR = R;
-	dR.q_start = nullptr; dR.q_end = nullptr;
-	if((rc = B.up(R.seq, (size_t) R.seq_words, 2, &dR.seq)) || (rc = B.up(R.seq_off, (size_t) n + 1, 0, &dR.seq_off)) || (rc = B.up(R.len, (size_t) n, 1, &dR.len)) ||
-	   (rc = B.up(R.N, (size_t) R.N_total, 1, &dR.N)) || (rc = B.up(R.N_off, (size_t) n + 1, 0, &dR.N_off))) return rc;
+	kmahip_reads dR;
+	if((rc = upload_reads(B, R, &dR))) return rc;
 	HIP_TRY(hipStreamSynchronize(s));
 	ms[0] = since(t);
 	ChainRecs CR;
@@ -2056,10 +1925,8 @@ extern "C" int kmahip_run_mt1_sharded(kmahip_db *db, kmahip_ws *ws, kmahip_comm 
 	int rc;
 	auto t = std::chrono::steady_clock::now();
 	if((rc = kmahip_db_load_names(db))) return rc;
-	kmahip_reads d = R;
-	d.q_start = nullptr; d.q_end = nullptr;
-	if((rc = B.up(R.seq, (size_t) R.seq_words, 2, &d.seq)) || (rc = B.up(R.seq_off, (size_t) n + 1, 0, &d.seq_off)) || (rc = B.up(R.len, (size_t) n, 1, &d.len)) ||
-	   (rc = B.up(R.N, (size_t) R.N_total, 1, &d.N)) || (rc = B.up(R.N_off, (size_t) n + 1, 0, &d.N_off))) return rc;
+	kmahip_reads d;
+	if((rc = upload_reads(B, R, &d))) return rc;
 	HIP_TRY(hipStreamSynchronize(s));
 	ms[0] = since(t);
 	// the traceback on the rank's own reads: strand by anker_rc, runs; the run pool grows on demand
@@ -2073,18 +1940,9 @@ extern "C" int kmahip_run_mt1_sharded(kmahip_db *db, kmahip_ws *ws, kmahip_comm 
 	int64_t total_bases = 0;
 	for(int64_t i = 0; i < n; ++i) total_bases += R.len[i];
 	tr.ops_cap = total_bases / 3 + 8 * n + (1 << 16); tr.ops = nullptr;
-	for(int attempt = 0; n; ++attempt) {
-		if((rc = B.get((size_t) tr.ops_cap, &tr.ops))) return rc;
-		if((rc = kmahip_launch_longtrace(db, ws, &d, nullptr, tmpl, nullptr, nullptr, one2one, p, &tr, d_rc, s))) return rc;
-		unsigned long long used = 0;
-		const int st = ws_status(ws, &used);
-		if(st == 2 || (int64_t) used > tr.ops_cap) {
-			if(attempt >= 2) { kmahip_set_error("alignment run pool: %llu runs needed", used); return KMAHIP_EOVERFLOW; }
-			tr.ops_cap = (int64_t) used + (1 << 16);
-			continue;
-		}
-		break;
-	}
+	unsigned long long used = 0;
+	if(n && (rc = retry_run_room(ws, s, total_bases / 3 + 8 * n + (1 << 16), 1 << 16, false, &used, run_pool_in(B, tr),
+	                             [&] { return kmahip_launch_longtrace(db, ws, &d, nullptr, tmpl, nullptr, nullptr, one2one, p, &tr, d_rc, s); }))) return rc;
 	if(!tr.ops && (rc = B.get(16, &tr.ops))) return rc;
 	ms[3] = since(t);
 	// the `.res` row: Score and the number of kept reads summed over the shards; a read's position among the kept reads of the stream

@@ -102,23 +102,106 @@ struct HostCols {
 	~HostCols() { wait(); for(auto &b : bufs) free(b.first); }
 };
 
-// status word of the workspace after a synchronised stage (and the first counter, the pool / run top)
-int ws_status(kmahip_ws *ws, unsigned long long *c0) {
-	unsigned long long c[2];
-	if(hipMemcpy(c, ws->counters, sizeof c, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-	if(c[1]) (void) hipMemset(ws->counters + 1, 0, sizeof(unsigned long long));
+// status word of the workspace after a synchronised stage (KmaStatus, kmahip_internal.h), read and cleared, and the first counter
+// (the pool / run top)
+int ws_status(kmahip_ws *ws, unsigned long long *st, unsigned long long *c0) {
+	unsigned long long c[2] = {0, 0};
+	if(ws->counters) HIP_TRY(hipMemcpy(c, ws->counters, sizeof c, hipMemcpyDeviceToHost));          // (none yet: nothing has been launched)
+	if(c[1]) HIP_TRY(hipMemset(ws->counters + 1, 0, sizeof(unsigned long long)));
 	if(c0) *c0 = c[0];
-	return (int) c[1];
+	*st = c[1];
+	return KMAHIP_OK;
 }
 
 // a read full of repeats can carry more MEMs against a template than the scratch holds slots for (64 for reads up to 1 kb;
-// status 3 from stage 3a, 16 from the traceback): the capacity goes up fourfold and the stage is run again
+// KMAHIP_ST_SEED_MEMS from stage 3a, KMAHIP_ST_TRACE_MEMS from the traceback): the capacity goes up fourfold and the stage is run again
 bool grow_mem_cap(kmahip_ws *ws) {
 	const int cur = ws->mem_scale > 0 ? ws->mem_scale : 1;
 	if(cur >= 64) return false;
 	ws->mem_scale = cur * 4;
 	if(getenv("KMAHIP_DEBUG_TIMING")) fprintf(stderr, "[kmahip] seed (MEM) capacity per read and template raised to %d x the usual\n", ws->mem_scale);
 	return true;
+}
+
+// KMAHIP_ST_POOL: the library's candidate pool (cap_reads x ints per read x pool_scale) doubles with the next scan launch
+void grow_pool(kmahip_ws *ws) {
+	ws->pool_scale *= 2; ws->cap_reads = 0;
+	if(getenv("KMAHIP_DEBUG_TIMING")) fprintf(stderr, "[kmahip] candidate pool raised to %lld x its usual size\n", (long long) ws->pool_scale);
+}
+
+// ---- the three capacities a run cannot know in advance. Each helper launches, synchronises, reads the status word and repeats with
+// more room: `launch` is the call site's launch (it returns a KMAHIP_* code), `alloc(cap)` makes room for `cap` entries and points
+// the launch's arguments at it. The bounds are the same on every run path: four pool doublings, six list regrows, three run-pool
+// regrows; MEM capacity up to 64 x (grow_mem_cap). KMAHIP_CAP_START=<n> replaces the starting guess of the lists and of the run pool
+// (for the tests: the regrows at test size).
+int64_t cap_start(int64_t guess) {
+	const char *e = getenv("KMAHIP_CAP_START");
+	return e ? std::max<int64_t>(1, atoll(e)) : guess;
+}
+void cap_note(const char *what, int64_t cap) {
+	if(getenv("KMAHIP_DEBUG_TIMING")) fprintf(stderr, "[kmahip] %s raised to %lld entries\n", what, (long long) cap);
+}
+
+// candidate lists of stage 2: `start` entries, then what the scan says it needs (d_total: the last offset, on the device) + slack
+template <class Alloc, class Launch>
+int retry_cand_room(kmahip_ws *ws, hipStream_t s, int64_t start, int64_t slack, const int64_t *d_total, int64_t *total, Alloc alloc, Launch launch) {
+	int64_t cap = cap_start(start);
+	for(int doubled = 0, regrown = 0;;) {
+		int rc;
+		unsigned long long st = 0;
+		if((rc = alloc(cap)) || (rc = launch())) return rc;
+		HIP_TRY(hipStreamSynchronize(s));
+		if((rc = ws_status(ws, &st, nullptr))) return rc;
+		if(st == KMAHIP_ST_POOL) {
+			if(doubled++ >= 4) { kmahip_set_error("internal candidate pool exhausted"); return KMAHIP_EOVERFLOW; }
+			grow_pool(ws);
+			continue;
+		}
+		HIP_TRY(hipMemcpy(total, d_total, sizeof *total, hipMemcpyDeviceToHost));
+		if(*total <= cap) return KMAHIP_OK;
+		if(regrown++ >= 6) { kmahip_set_error("candidate lists keep growing"); return KMAHIP_EOVERFLOW; }
+		cap = *total + slack;
+		cap_note("candidate lists", cap);
+	}
+}
+
+// seed (MEM) room of stage 3a: the launch adds into the score vectors, so they are zeroed before every launch (`bytes` each; v1 may be NULL)
+template <class Launch>
+int retry_seed_room(kmahip_ws *ws, hipStream_t s, uint64_t *v0, uint64_t *v1, size_t bytes, Launch launch) {
+	for(;;) {
+		int rc;
+		unsigned long long st = 0;
+		HIP_TRY(hipMemsetAsync(v0, 0, bytes, s));
+		if(v1) HIP_TRY(hipMemsetAsync(v1, 0, bytes, s));
+		if((rc = launch())) return rc;
+		HIP_TRY(hipStreamSynchronize(s));
+		if((rc = ws_status(ws, &st, nullptr))) return rc;
+		if(st != KMAHIP_ST_SEED_MEMS) return KMAHIP_OK;
+		if(!grow_mem_cap(ws)) { kmahip_set_error("seed (MEM) capacity per read/template pair exceeded"); return KMAHIP_EOVERFLOW; }
+	}
+}
+
+// run pool of a traceback: `start` runs, then what the kernels say they used + slack. mems: the launch can report KMAHIP_ST_TRACE_MEMS
+// (kmahip_launch_trace; kmahip_launch_longtrace grows its MEM arrays itself), which costs no attempt
+template <class Alloc, class Launch>
+int retry_run_room(kmahip_ws *ws, hipStream_t s, int64_t start, int64_t slack, bool mems, unsigned long long *used, Alloc alloc, Launch launch) {
+	int64_t cap = cap_start(start);
+	for(int regrown = 0;;) {
+		int rc;
+		unsigned long long st = 0;
+		if((rc = alloc(&cap)) || (rc = launch())) return rc;
+		HIP_TRY(hipStreamSynchronize(s));
+		if((rc = ws_status(ws, &st, used))) return rc;
+		if(st == KMAHIP_ST_CALLER_CAP || (int64_t) *used > cap) {
+			if(regrown++ >= 3) { kmahip_set_error("alignment run pool: %llu runs needed", *used); return KMAHIP_EOVERFLOW; }
+			cap = (int64_t) *used + slack;
+			cap_note("alignment run pool", cap);
+			continue;
+		}
+		if(mems && st == KMAHIP_ST_TRACE_MEMS && grow_mem_cap(ws)) continue;
+		if(st) { kmahip_set_error("trace stage: a read needs more scratch than the workspace holds (status %llu)", st); return KMAHIP_EDEVICE; }
+		return KMAHIP_OK;
+	}
 }
 
 
@@ -136,5 +219,30 @@ int scan_i64(DevBlock &B, const int64_t *in, int64_t *out, size_t n, hipStream_t
 	return KMAHIP_OK;
 }
 
+// retry_run_room's `alloc` for a run pool that lives in a block
+auto run_pool_in(DevBlock &B, kmahip_traces &tr) {
+	return [&B, &tr](int64_t *cap) { tr.ops_cap = *cap; return B.get((size_t) *cap, &tr.ops); };
+}
+
+// a host batch's five read arrays in a block, padded the way the kernels read them (two words behind the bases, one entry behind the
+// lengths and the N positions); *d is the batch with DEVICE arrays, without query bounds
+int upload_reads(DevBlock &B, const kmahip_reads &reads, kmahip_reads *d) {
+	const size_t n = (size_t) reads.n_reads;
+	int rc;
+	*d = reads;
+	d->q_start = nullptr; d->q_end = nullptr;       // (host pointers, if any: the entry points that upload map whole reads)
+	if((rc = B.up(reads.seq, (size_t) reads.seq_words, 2, &d->seq)) || (rc = B.up(reads.seq_off, n + 1, 0, &d->seq_off)) || (rc = B.up(reads.len, n, 1, &d->len)) ||
+	   (rc = B.up(reads.N, (size_t) reads.N_total, 1, &d->N)) || (rc = B.up(reads.N_off, n + 1, 0, &d->N_off))) return rc;
+	return KMAHIP_OK;
+}
+
+// stage 3a's outputs for n reads whose lists hold `total` entries: get(count, &array) makes a zeroed array (the two score vectors
+// are the caller's)
+template <class Get> int carve_hits(size_t n, size_t total, kmahip_hits *h, Get get) {
+	int rc;
+	for(int32_t **p : {&h->n_hits, &h->best_score, &h->flag, &h->rc}) if((rc = get(n + 1, p))) return rc;
+	for(int32_t **p : {&h->tmpl, &h->score, &h->start, &h->end}) if((rc = get(total + 1, p))) return rc;
+	return KMAHIP_OK;
+}
 
 }  // namespace

@@ -488,11 +488,8 @@ extern "C" int kmahip_sam_write(const char *path, kmahip_db *db, const kmahip_re
 	if(n == 0) return KMAHIP_OK;
 	int rc;
 	DevBlock B;
-	kmahip_reads W = *reads;
-	W.q_start = nullptr; W.q_end = nullptr;
-	const int32_t zero = 0;
-	if((rc = B.up(reads->seq, (size_t) reads->seq_words, 2, &W.seq)) || (rc = B.up(reads->seq_off, (size_t) n + 1, 0, &W.seq_off)) || (rc = B.up(reads->len, (size_t) n, 1, &W.len)) ||
-	   (rc = B.up(reads->N_total ? reads->N : &zero, (size_t) std::max<int64_t>(1, reads->N_total), 0, &W.N)) || (rc = B.up(reads->N_off, (size_t) n + 1, 0, &W.N_off))) return rc;
+	kmahip_reads W;
+	if((rc = upload_reads(B, *reads, &W))) return rc;
 	KmaSamIn in{};
 	kmahip_traces tr{};
 	kmahip_trace_drops dr{};

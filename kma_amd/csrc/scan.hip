@@ -1136,7 +1136,7 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 				if(nb) off = want ? A.pool_tail0 + (int64_t) pbase + (incl - want) : item * INL;
 				// (pool exhausted: the host repeats the call with a larger one; the item is left without a list, so that nothing
 				// downstream follows an offset behind the pool)
-				if(nb && off + nb > A.pool_cap) { atomicMax(&A.counters[C_STATUS], 1ull); s_off[g] = -1; nb = 0; off = 0; }
+				if(nb && off + nb > A.pool_cap) { atomicMax(&A.counters[C_STATUS], KMAHIP_ST_POOL); s_off[g] = -1; nb = 0; off = 0; }
 				else s_off[g] = nb ? off : -1;
 			}
 			if(mine) {
@@ -1273,7 +1273,7 @@ __global__ __launch_bounds__(64) void scan_dense_kernel(const ScanArgs A) {
 			off = __shfl(off, 0);
 			if(off + nb <= A.pool_cap) {
 				for(int e = lane; e < nlist; e += 64) { A.pool[off + e] = list[e]; A.pool_sc[off + e] = max(0, (int) score[list[e]]); }
-			} else { if(lane == 0) atomicMax(&A.counters[C_STATUS], 1ull); nb = 0; off = 0; }
+			} else { if(lane == 0) atomicMax(&A.counters[C_STATUS], KMAHIP_ST_POOL); nb = 0; off = 0; }
 		} else if(hits) {
 			for(int e = lane; e < nlist; e += 64) best = max(best, max(0, (int) score[list[e]]));
 			for(int d = 32; d; d >>= 1) best = max(best, __shfl_xor(best, d));
@@ -1295,7 +1295,7 @@ __global__ __launch_bounds__(64) void scan_dense_kernel(const ScanArgs A) {
 						if(is) A.pool[off + w + __popcll(m & below)] = list[e];
 						w += __popcll(m);
 					}
-				} else { if(lane == 0) atomicMax(&A.counters[C_STATUS], 1ull); nb = 0; off = 0; }
+				} else { if(lane == 0) atomicMax(&A.counters[C_STATUS], KMAHIP_ST_POOL); nb = 0; off = 0; }
 			} else nb = 0;
 		}
 		for(int e = lane; e < nlist; e += 64) { const int t = list[e]; score[t] = 0; ext[t] = -1; }
@@ -1455,7 +1455,7 @@ __global__ __launch_bounds__(CB) void combine_write_kernel(const ScanArgs A, con
 	T_off[r + 1] = end;
 	if(r == 0) T_off[0] = 0;
 	if(nT == 0) return;
-	if(end > T_cap) { atomicMax(&A.counters[C_STATUS], 2ull); return; }
+	if(end > T_cap) { atomicMax(&A.counters[C_STATUS], KMAHIP_ST_CALLER_CAP); return; }
 	const int rf = rc_flag[r], fl = flag[r];
 	int64_t w = beg;
 	if(DECON) {
@@ -1529,7 +1529,7 @@ __global__ __launch_bounds__(256) void pair_penalty_kernel(const PairArgs P) {
 	int64_t base = 0;
 	if(need) {
 		base = (int64_t) atomicAdd(&A.counters[C_PPOOL], (unsigned long long) need);
-		if(base + need > P.ppool_cap) { atomicMax(&A.counters[C_STATUS], 1ull); return; }
+		if(base + need > P.ppool_cap) { atomicMax(&A.counters[C_STATUS], KMAHIP_ST_POOL); return; }
 	}
 	int32_t *regT = P.ppool + base, *bT = regT + max(n1, n2);
 	auto regS = [&](int i) { return i < F1.n ? F1.s[i] : R1.s[i - F1.n]; };
@@ -1662,7 +1662,7 @@ __global__ __launch_bounds__(256) void pair_union_kernel(const PairArgs P) {
 	int64_t base = 0;
 	if(need) {
 		base = (int64_t) atomicAdd(&A.counters[C_PPOOL], (unsigned long long) need);
-		if(base + need > P.ppool_cap) { atomicMax(&A.counters[C_STATUS], 1ull); return; }
+		if(base + need > P.ppool_cap) { atomicMax(&A.counters[C_STATUS], KMAHIP_ST_POOL); return; }
 	}
 	int32_t *regT = P.ppool + base, *bT = regT + max(n1, n2);
 	// getF_Best: the best score over both strands' candidates and the templates that reach it, forward ones first
@@ -1767,7 +1767,7 @@ __global__ __launch_bounds__(256) void pair_force_kernel(const PairArgs P) {
 	const int n1 = F1.n + R1.n;
 	if(hc1 && hc2 && n1) {          // (without a hit of mate 1 the reference does not even scan mate 2: no record either way)
 		const int64_t base = (int64_t) atomicAdd(&A.counters[C_PPOOL], (unsigned long long) n1);
-		if(base + n1 > P.ppool_cap) { atomicMax(&A.counters[C_STATUS], 1ull); return; }
+		if(base + n1 > P.ppool_cap) { atomicMax(&A.counters[C_STATUS], KMAHIP_ST_POOL); return; }
 		int32_t *regT = P.ppool + base;
 		// getSecondBestForce over getFirstForce's list (mate 1's forward candidates, then its reverse ones as negative ids)
 		int best = 0, hits = 0;
@@ -1838,7 +1838,7 @@ __global__ __launch_bounds__(CB) void rec_write_kernel(const int32_t *cnt, const
 	out_off[r + 1] = end;
 	if(r == 0) out_off[0] = 0;
 	if(c == 0) return;
-	if(end > out_cap) { atomicMax(&counters[C_STATUS], 2ull); return; }
+	if(end > out_cap) { atomicMax(&counters[C_STATUS], KMAHIP_ST_CALLER_CAP); return; }
 	const int64_t so = src_off[r];
 	for(int64_t i = 0; i < c; ++i) out[beg + i] = src[so + i];
 }
@@ -2144,7 +2144,10 @@ static int ws_reserve(kmahip_ws *ws, int64_t n_reads) {
 		HIP_TRY(hipMalloc((void **) &ws->item_n, cap * 2 * sizeof(int32_t)));
 		HIP_TRY(hipMalloc((void **) &ws->item_off, cap * 2 * sizeof(int64_t)));
 		if(ws->pool_scale < 1) ws->pool_scale = 1;
-		ws->pool_cap = cap * 16 * ws->pool_scale;
+		// (KMAHIP_SCAN_POOL_PER_READ: the pool's ints per read, 16 unless set -- for the tests of the pool's doubling)
+		int64_t per_read = 16;
+		if(const char *e = getenv("KMAHIP_SCAN_POOL_PER_READ")) per_read = std::max<int64_t>(1, atoll(e));
+		ws->pool_cap = cap * per_read * ws->pool_scale;
 		HIP_TRY(hipMalloc((void **) &ws->pool, ws->pool_cap * sizeof(int32_t)));
 		HIP_TRY(hipMalloc((void **) &ws->overflow_items, cap * 4 * sizeof(int64_t)));       // first-tier list + second-tier list
 		HIP_TRY(hipMalloc((void **) &ws->active_items, cap * 2 * sizeof(int64_t)));
@@ -2156,7 +2159,7 @@ static int ws_reserve(kmahip_ws *ws, int64_t n_reads) {
 	// (KMAHIP_SCAN_REC_CAP: fewer records than the buffer holds, for the tests of the spill to the bare list)
 	ws->rec_cap = ws->cap_reads;
 	if(const char *e = getenv("KMAHIP_SCAN_REC_CAP")) ws->rec_cap = std::max<int64_t>(0, std::min<int64_t>(ws->cap_reads, atoll(e)));
-	if(!ws->counters) { HIP_TRY(hipMalloc((void **) &ws->counters, N_COUNTERS * sizeof(unsigned long long))); HIP_TRY(hipMemset(ws->counters, 0, N_COUNTERS * sizeof(unsigned long long))); }
+	if(int rcc = kmahip_ws_counters(ws)) return rcc;
 	if(!ws->dense) {
 		// overflow scratch: up to 4096 concurrent items, bounded to 1 GiB
 		int64_t slots = 4096;

@@ -46,18 +46,31 @@ struct DevArr {
 	template <class T> T *as() const { return (T *) p; }
 };
 
-struct Batch {
+struct BatchView {
 	int64_t r0 = 0, n = 0, total = 0;
 	int max_len = 0;
 	kmahip_cands c{};
 	kmahip_hits h{};
-	std::vector<void *> owned;
 	// the default mode: the batch's READS wait here (their own arrays) until kmahip_session_map has made the records out of them
 	kmahip_reads tmp{};
-	std::vector<void *> tmp_owned;
 	int64_t read0 = 0;             // first read of the batch among all reads (its headers' index)
 	int64_t words = 0;             // packed words of the batch's reads
+};
+// what a batch holds on the device is its own: released with it, and handed on by a move that leaves the source empty
+struct Batch : BatchView {
+	std::vector<void *> owned, tmp_owned;
 	KmaChainRecs cr;               // the records' template lists live in its block
+	Batch() = default;
+	Batch(Batch &&o) noexcept { *this = std::move(o); }
+	Batch &operator=(Batch &&o) noexcept {
+		if(this == &o) return *this;
+		release();
+		BatchView::operator=(o);
+		owned.swap(o.owned); tmp_owned.swap(o.tmp_owned);
+		cr = o.cr; o.cr = KmaChainRecs{};
+		return *this;
+	}
+	~Batch() { release(); }
 	void release_tmp() { for(void *q : tmp_owned) (void) hipFree(q); tmp_owned.clear(); }
 	void release() { for(void *q : owned) (void) hipFree(q); owned.clear(); release_tmp(); kmahip_chain_records_free(&cr); }
 };
@@ -254,8 +267,6 @@ struct kmahip_session {
 	int vcf = 0;
 	std::string vcf_tdb;
 	~kmahip_session() {
-		for(Batch &b : batches) b.release();
-		for(Batch &b : uploaded) b.release();
 		if(AS) (void) hipFree(AS);
 		if(AS_batch) (void) hipFree(AS_batch);
 		if(frag_thread.joinable()) frag_thread.join();
@@ -400,7 +411,7 @@ extern "C" int kmahip_session_upload(kmahip_session *S, const kmahip_read_batch 
 		int64_t *d_so = nullptr, *d_no = nullptr;
 		int32_t *d_len = nullptr, *d_N = nullptr;
 		if((rc = dev_new(U.tmp_owned, (size_t) R.seq_words + 2, &d_seq, false, s)) || (rc = dev_new(U.tmp_owned, (size_t) nb + 1, &d_so, false, s)) || (rc = dev_new(U.tmp_owned, (size_t) nb + 1, &d_len, false, s)) ||
-		   (rc = dev_new(U.tmp_owned, (size_t) R.N_total + 1, &d_N, false, s)) || (rc = dev_new(U.tmp_owned, (size_t) nb + 1, &d_no, false, s))) { U.release(); return rc; }
+		   (rc = dev_new(U.tmp_owned, (size_t) R.N_total + 1, &d_N, false, s)) || (rc = dev_new(U.tmp_owned, (size_t) nb + 1, &d_no, false, s))) return rc;
 		if(R.seq_words) HIP_TRY(hipMemcpyAsync(d_seq, R.seq, (size_t) R.seq_words * 8, hipMemcpyHostToDevice, s));
 		HIP_TRY(hipMemsetAsync(d_seq + R.seq_words, 0, 16, s));
 		HIP_TRY(hipMemcpyAsync(d_so, R.seq_off, (size_t) (nb + 1) * 8, hipMemcpyHostToDevice, s));
@@ -595,23 +606,16 @@ static int session_map_mt1(kmahip_session *S, Batch &B, const kmahip_reads &d) {
 	HIP_TRY(hipMemsetAsync(S->t_rc.as<int32_t>() + r0, 0, (size_t) nb * 4, s));
 	mt1_frag_start(S);          // (the batch before: nothing it reads is moved or written from here on)
 	// (the run pool: a guess from the batch's bases, redone with the count the kernels report if short)
-	int64_t room = B.words * 32 / 3 + 8 * nb + (1 << 16);
+	const int64_t room = B.words * 32 / 3 + 8 * nb + (1 << 16);
 	unsigned long long used = 0;
-	for(int attempt = 0;; ++attempt) {
-		if((rc = S->t_pool.ensure((size_t) (S->pool_used + room) * 4, (size_t) S->pool_used * 4, s))) return rc;
-		kmahip_traces tr;
-		tr.stats = S->t_stats.as<int32_t>() + 10 * r0; tr.ops_off = S->t_off.as<int64_t>() + r0; tr.n_ops = S->t_nops.as<int32_t>() + r0;
-		tr.ops = S->t_pool.as<uint32_t>() + S->pool_used; tr.ops_cap = (int64_t) (S->t_pool.cap / 4) - S->pool_used;
-		if((rc = kmahip_launch_longtrace(S->db, S->ws, &d, nullptr, S->mt1, nullptr, nullptr, S->mt1_one2one, &S->par, &tr, S->t_rc.as<int32_t>() + r0, s))) return rc;
-		used = 0;
-		const int st = ws_status(S->ws, &used);
-		if(st == 2 || (int64_t) used > tr.ops_cap) {
-			if(attempt >= 2) { kmahip_set_error("alignment run pool: %llu runs needed", used); return KMAHIP_EOVERFLOW; }
-			room = (int64_t) used + (1 << 16);
-			continue;
-		}
-		break;
-	}
+	kmahip_traces tr{};
+	tr.stats = S->t_stats.as<int32_t>() + 10 * r0; tr.ops_off = S->t_off.as<int64_t>() + r0; tr.n_ops = S->t_nops.as<int32_t>() + r0;
+	if((rc = retry_run_room(S->ws, s, room, 1 << 16, false, &used, [&](int64_t *cap) {
+		// (behind the runs of the batches before; the array grows by doubling, and the launch may use all of it)
+		const int ra = S->t_pool.ensure((size_t) (S->pool_used + *cap) * 4, (size_t) S->pool_used * 4, s);
+		tr.ops = S->t_pool.as<uint32_t>() + S->pool_used; tr.ops_cap = *cap = (int64_t) (S->t_pool.cap / 4) - S->pool_used;
+		return ra;
+	}, [&] { return kmahip_launch_longtrace(S->db, S->ws, &d, nullptr, S->mt1, nullptr, nullptr, S->mt1_one2one, &S->par, &tr, S->t_rc.as<int32_t>() + r0, s); }))) return rc;
 	// (the runs of a read are addressed from the start of the pool)
 	if(S->pool_used) hipLaunchKernelGGL(add_off_kernel, dim3((unsigned) ((nb + 255) / 256)), dim3(256), 0, s, nb, S->t_off.as<int64_t>() + r0, S->pool_used);
 	// the kept reads, their part of the `.res` row's Score
@@ -636,7 +640,7 @@ static int session_map_one(kmahip_session *S, Batch &B) {
 	if(S->chain) {
 		// stage 2 of the default mode: the chain finder on the batch's reads; its records -- in stream order -- go behind the records
 		// of the batches before, with their bounds and the read whose header they carry
-		if((rc = kmahip_chain_records_dev(db, ws, &B.tmp, &S->par, &S->cp, &B.cr))) { B.release(); return rc; }
+		if((rc = kmahip_chain_records_dev(db, ws, &B.tmp, &S->par, &S->cp, &B.cr))) return rc;
 		const int64_t m = B.cr.m;
 		B.r0 = S->n; B.n = m;
 		if(m) {
@@ -644,7 +648,7 @@ static int session_map_one(kmahip_session *S, Batch &B) {
 			if((rc = S->seq.ensure((size_t) (S->words + c.seq_words + 2) * 8, (size_t) S->words * 8, s)) || (rc = S->seq_off.ensure((size_t) (S->n + m + 1) * 8, (size_t) (S->n + 1) * 8, s)) ||
 			   (rc = S->len.ensure((size_t) (S->n + m + 1) * 4, (size_t) S->n * 4, s)) || (rc = S->N.ensure((size_t) (S->nN + c.N_total + 1) * 4, (size_t) S->nN * 4, s)) ||
 			   (rc = S->N_off.ensure((size_t) (S->n + m + 1) * 8, (size_t) (S->n + 1) * 8, s)) || (rc = S->qs.ensure((size_t) (S->n + m + 1) * 4, (size_t) S->n * 4, s)) ||
-			   (rc = S->qe.ensure((size_t) (S->n + m + 1) * 4, (size_t) S->n * 4, s)) || (rc = S->rread.ensure((size_t) (S->n + m + 1) * 8, (size_t) S->n * 8, s))) { B.release(); return rc; }
+			   (rc = S->qe.ensure((size_t) (S->n + m + 1) * 4, (size_t) S->n * 4, s)) || (rc = S->rread.ensure((size_t) (S->n + m + 1) * 8, (size_t) S->n * 8, s))) return rc;
 			bool ok = true;
 			ok = ok && (!c.seq_words || hipMemcpyAsync(S->seq.as<uint64_t>() + S->words, c.seq, (size_t) c.seq_words * 8, hipMemcpyDeviceToDevice, s) == hipSuccess);
 			ok = ok && hipMemsetAsync(S->seq.as<uint64_t>() + S->words + c.seq_words, 0, 16, s) == hipSuccess;
@@ -655,12 +659,12 @@ static int session_map_one(kmahip_session *S, Batch &B) {
 			ok = ok && hipMemcpyAsync(S->qs.as<int32_t>() + S->n, c.q_start, (size_t) m * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
 			ok = ok && hipMemcpyAsync(S->qe.as<int32_t>() + S->n, c.q_end, (size_t) m * 4, hipMemcpyDeviceToDevice, s) == hipSuccess;
 			ok = ok && hipMemcpyAsync(S->rread.as<int64_t>() + S->n, B.cr.o_read, (size_t) m * 8, hipMemcpyDeviceToDevice, s) == hipSuccess;
-			if(!ok) { B.release(); kmahip_set_error("device copy failed"); return KMAHIP_EDEVICE; }
+			if(!ok) { kmahip_set_error("device copy failed"); return KMAHIP_EDEVICE; }
 			const unsigned g1 = (unsigned) ((m + 1 + 255) / 256);
 			if(S->words) hipLaunchKernelGGL(add_off_kernel, dim3(g1), dim3(256), 0, s, m + 1, S->seq_off.as<int64_t>() + S->n, S->words);
 			if(S->nN) hipLaunchKernelGGL(add_off_kernel, dim3(g1), dim3(256), 0, s, m + 1, S->N_off.as<int64_t>() + S->n, S->nN);
 			if(B.read0) hipLaunchKernelGGL(add_off_kernel, dim3(g1), dim3(256), 0, s, m, S->rread.as<int64_t>() + S->n, B.read0);
-			if(hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { B.release(); kmahip_set_error("device copy failed"); return KMAHIP_EDEVICE; }
+			if(hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { kmahip_set_error("device copy failed"); return KMAHIP_EDEVICE; }
 			B.c = B.cr.c; B.total = B.cr.n_T;
 			S->n += m; S->words += c.seq_words; S->nN += c.N_total;
 		}
@@ -680,36 +684,17 @@ static int session_map_one(kmahip_session *S, Batch &B) {
 	}
 	// stage 2 (the candidate lists have no bound known in advance: two per read, redone with the exact size if short)
 	if(!S->chain) {
-	if((rc = dev_new(B.owned, (size_t) nb + 1, &B.c.rc_flag, false, s)) || (rc = dev_new(B.owned, (size_t) nb + 1, &B.c.flag, false, s)) || (rc = dev_new(B.owned, (size_t) nb + 1, &B.c.T_off, true, s))) { B.release(); return rc; }
-	B.c.T_cap = 2 * nb + 4096;
-	for(int attempt = 0;; ++attempt) {
-		if((rc = dev_new(B.owned, (size_t) B.c.T_cap, &B.c.T, false, s)) || (rc = kmahip_launch_scan_se(db, ws, &d, &S->par, &B.c, s))) { B.release(); return rc; }
-		if(hipStreamSynchronize(s) != hipSuccess) { B.release(); kmahip_set_error("stage 2 failed"); return KMAHIP_EDEVICE; }
-		if(ws_status(ws, nullptr) == 1) {
-			if(attempt >= 4) { B.release(); kmahip_set_error("internal candidate pool exhausted"); return KMAHIP_EOVERFLOW; }
-			ws->pool_scale *= 2; ws->cap_reads = 0;
-			continue;
-		}
-		if(hipMemcpy(&B.total, B.c.T_off + nb, 8, hipMemcpyDeviceToHost) != hipSuccess) { B.release(); kmahip_set_error("hipMemcpy failed"); return KMAHIP_EDEVICE; }
-		if(B.total <= B.c.T_cap) break;
-		if(attempt >= 6) { B.release(); kmahip_set_error("candidate lists keep growing"); return KMAHIP_EOVERFLOW; }
-		B.c.T_cap = B.total + 1024;
-	}
+	if((rc = dev_new(B.owned, (size_t) nb + 1, &B.c.rc_flag, false, s)) || (rc = dev_new(B.owned, (size_t) nb + 1, &B.c.flag, false, s)) || (rc = dev_new(B.owned, (size_t) nb + 1, &B.c.T_off, true, s)) ||
+	   (rc = retry_cand_room(ws, s, 2 * nb + 4096, 1024, B.c.T_off + nb, &B.total, [&](int64_t cap) { B.c.T_cap = cap; return dev_new(B.owned, (size_t) cap, &B.c.T, false, s); },
+	                         [&] { return kmahip_launch_scan_se(db, ws, &d, &S->par, &B.c, s); }))) return rc;
 	}
 	// stage 3a into vectors of the batch's own (a run that has to be repeated with more room for seeds starts them afresh), then added
 	kmahip_hits &h = B.h;
-	if((rc = dev_new(B.owned, (size_t) nb + 1, &h.n_hits, true, s)) || (rc = dev_new(B.owned, (size_t) nb + 1, &h.best_score, true, s)) || (rc = dev_new(B.owned, (size_t) nb + 1, &h.flag, true, s)) ||
-	   (rc = dev_new(B.owned, (size_t) nb + 1, &h.rc, true, s)) || (rc = dev_new(B.owned, (size_t) B.total + 1, &h.tmpl, true, s)) || (rc = dev_new(B.owned, (size_t) B.total + 1, &h.score, true, s)) ||
-	   (rc = dev_new(B.owned, (size_t) B.total + 1, &h.start, true, s)) || (rc = dev_new(B.owned, (size_t) B.total + 1, &h.end, true, s))) { B.release(); return rc; }
+	if((rc = carve_hits((size_t) nb, (size_t) B.total, &h, [&](size_t k, int32_t **a) { return dev_new(B.owned, k, a, true, s); }))) return rc;
 	h.alignment_scores = S->AS_batch; h.uniq_alignment_scores = S->AS_batch + D;
-	for(;;) {
-		if(hipMemsetAsync(S->AS_batch, 0, 2 * D * 8, s) != hipSuccess || (rc = kmahip_stage3a_se(db, ws, &d, &B.c, &S->par, &h, s))) { B.release(); return rc ? rc : KMAHIP_EDEVICE; }
-		if(hipStreamSynchronize(s) != hipSuccess) { B.release(); kmahip_set_error("stage 3a failed"); return KMAHIP_EDEVICE; }
-		if(ws_status(ws, nullptr) != 3) break;
-		if(!grow_mem_cap(ws)) { B.release(); kmahip_set_error("seed (MEM) capacity per read/template pair exceeded"); return KMAHIP_EOVERFLOW; }
-	}
+	if((rc = retry_seed_room(ws, s, S->AS_batch, nullptr, 2 * D * 8, [&] { return kmahip_stage3a_se(db, ws, &d, &B.c, &S->par, &h, s); }))) return rc;
 	hipLaunchKernelGGL(add_u64_kernel, dim3((unsigned) ((2 * D + 255) / 256)), dim3(256), 0, s, (int64_t) (2 * D), (const unsigned long long *) S->AS_batch, (unsigned long long *) S->AS);
-	if(hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { B.release(); kmahip_set_error("stage 3a failed"); return KMAHIP_EDEVICE; }
+	if(hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { kmahip_set_error("stage 3a failed"); return KMAHIP_EDEVICE; }
 	h.alignment_scores = S->AS; h.uniq_alignment_scores = S->AS + D;
 	const int64_t first_reads = S->batches.empty() ? B.n : 0;
 	const int first_len = B.max_len;
@@ -1113,23 +1098,16 @@ extern "C" int kmahip_session_finish(kmahip_session *S, const char *out_prefix, 
 	struct DropsOff { kmahip_ws *ws; ~DropsOff() { (void) kmahip_ws_set_trace_drops(ws, nullptr); } } drops_off{ws};
 	DevArr pool;
 	// (runs: a handful per short read; long reads with their errors leave one every few bases)
-	if((rc = pool.ensure((size_t) (6 * n + (1 << 20) + (S->max_len > 1024 ? S->words * 32 / 3 : 0)) * 4, 0, s))) return rc;
-	for(int attempt = 0; n; ++attempt) {
-		tr.ops = pool.as<uint32_t>(); tr.ops_cap = (int64_t) (pool.cap / 4);
-		if((rc = kmahip_launch_trace(db, ws, &W, rc_all, cc.tmpl, d_ok, p, &tr, s))) return rc;
-		HIP_TRY(hipStreamSynchronize(s));
-		unsigned long long used = 0;
-		const int st = ws_status(ws, &used);
-		if(st == 2 || (int64_t) used > tr.ops_cap) {
-			if(attempt >= 3) { kmahip_set_error("alignment run pool: %llu runs needed", used); return KMAHIP_EOVERFLOW; }
-			if((rc = pool.ensure((size_t) ((int64_t) used + (1 << 20)) * 4, 0, s))) return rc;
-			continue;
-		}
-		if(st == 16 && grow_mem_cap(ws)) { --attempt; continue; }
-		if(st) { kmahip_set_error("trace stage: a read needs more scratch than the workspace holds (status %d)", st); return KMAHIP_EDEVICE; }
-		break;
-	}
-	tr.ops = pool.as<uint32_t>(); tr.ops_cap = (int64_t) (pool.cap / 4);
+	const auto pool_room = [&](int64_t *cap) {
+		const int ra = pool.ensure((size_t) *cap * 4, 0, s);
+		tr.ops = pool.as<uint32_t>(); tr.ops_cap = *cap = (int64_t) (pool.cap / 4);
+		return ra;
+	};
+	unsigned long long runs_used = 0;
+	if(n) rc = retry_run_room(ws, s, 6 * n + (1 << 20) + (S->max_len > 1024 ? S->words * 32 / 3 : 0), 1 << 20, true, &runs_used, pool_room,
+	                          [&] { return kmahip_launch_trace(db, ws, &W, rc_all, cc.tmpl, d_ok, p, &tr, s); });
+	else { int64_t cap = 1 << 20; rc = pool_room(&cap); }
+	if(rc) return rc;
 	ms[3] = since(t);
 
 	// stage 3c per template over everything
