@@ -1073,6 +1073,12 @@ int kmahip_trace_get_stats(kmahip_ws *ws, kmahip_trace_stats *st);
  * out[17..25] the lane classes 0..8 (rows of 16 / 32 / 48 / 64 / 128 / 256 cells, bands of up to 72 / 96 / 144). Degenerate joins
  * (a pure insertion or deletion) are in no class. */
 int kmahip_trace_get_class_counts(kmahip_ws *ws, unsigned long long out[26]);
+/* which route the reads of the last default-mode stage 2 call on this workspace took (kmahip_scan_chain, or stage 2 of a whole run
+ * without -1t1): out[0] reads of the call; out[1] reads chain_anchor_kernel handed over (N's, more than 288 k-mer starts, more than 32
+ * anchors on a strand); out[2] reads chain_fast_kernel gave up (more candidate templates than its LDS table holds); out[3] reads the
+ * long-read route took; out[4] reads chain_kernel took. out[1] + out[2] == out[3] + out[4]; with KMAHIP_CHAIN=slow out[4] == out[0]
+ * and the rest is 0. */
+int kmahip_chain_get_route_counts(kmahip_ws *ws, unsigned long long out[5]);
 
 /* Kernel timing: when on, every *_dev call records a HIP event pair around its
  * main kernels (scan_prefilter_kernel, scan_se_kernel, seed_tasks_kernel, align_tasks_kernel) on the caller's stream; get_timing waits

@@ -255,6 +255,8 @@ def lib():
         L.kmahip_trace_get_stats.argtypes = [C.c_void_p, C.POINTER(TraceStats)]
         if hasattr(L, "kmahip_trace_get_class_counts"):          # (KMAHIP_LIB may name an older library, for side-by-side timing)
             L.kmahip_trace_get_class_counts.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+        if hasattr(L, "kmahip_chain_get_route_counts"):
+            L.kmahip_chain_get_route_counts.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
         L.kmahip_trim_default.argtypes = [C.POINTER(Trim)]
         L.kmahip_trim_default.restype = None
         L.kmahip_ingest_open.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Trim), C.POINTER(C.c_void_p)]
@@ -791,6 +793,13 @@ class KmaHipDB:
         out = (C.c_ulonglong * 26)()
         _check(lib().kmahip_trace_get_class_counts(self.ws, out))
         return dict(wave=[int(x) for x in out[:17]], lane=[int(x) for x in out[17:]])
+
+    def get_chain_route_counts(self) -> dict:
+        """reads of the last scan_chain call by route: reads, marked (chain_anchor_kernel handed them over), given_up (chain_fast_kernel
+        found its template table full), long (the long-read route took them), lane (chain_kernel took them)"""
+        out = (C.c_ulonglong * 5)()
+        _check(lib().kmahip_chain_get_route_counts(self.ws, out))
+        return dict(zip(("reads", "marked", "given_up", "long", "lane"), (int(x) for x in out)))
 
     def set_timing(self, on: bool):
         _check(lib().kmahip_ws_set_timing(self.ws, int(on)))

@@ -508,6 +508,12 @@ extern "C" int kmahip_trace_get_class_counts(kmahip_ws *ws, unsigned long long o
 	return KMAHIP_OK;
 }
 
+extern "C" int kmahip_chain_get_route_counts(kmahip_ws *ws, unsigned long long out[5]) {
+	if(!ws || !out) return KMAHIP_EINVAL;
+	for(int i = 0; i < 5; ++i) out[i] = ws->chain_route_counts[i];
+	return KMAHIP_OK;
+}
+
 // kmahip.h: reads of the default mode whose result the reference takes from memory it never cleared
 extern "C" int kmahip_chain_unpinned_reads(const int32_t *len, const int32_t *N, const int64_t *N_off, int64_t n_reads, int k,
                                            int32_t longest_before, int32_t *longest_after, int64_t *count) {

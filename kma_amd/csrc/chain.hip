@@ -1249,10 +1249,12 @@ __global__ __launch_bounds__(64, CHAIN_FAST_WAVES) void chain_fast_kernel(const 
 }
 
 // the reads the fast route left: those without N's from the front of `list` (count[0]: the long-read route takes them when `split`), the
-// others from its end (count[1]: chain_kernel)
+// others from its end (count[1]: chain_kernel). count[2], count[3]: the reads chain_anchor_kernel marked (slow == 1) and those
+// chain_fast_kernel gave up (slow == 2), for kmahip_chain_get_route_counts
 __global__ __launch_bounds__(256) void slow_list_kernel(int64_t n, const uint8_t *slow, const int64_t *N_off, int split, int64_t *list, unsigned long long *count) {
 	const int64_t r = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
 	if(r >= n || !slow[r]) return;
+	atomicAdd(&count[slow[r] == 2 ? 3 : 2], 1ull);
 	if(split && N_off[r + 1] == N_off[r]) list[atomicAdd(&count[0], 1ull)] = r;
 	else list[n - 1 - (int64_t) atomicAdd(&count[1], 1ull)] = r;
 }
@@ -1275,11 +1277,12 @@ void kmahip_devcache_flush();
 //   fast   prefilter + chain_anchor_kernel (scan.hip: the anchors of every live strand, 16 lanes per strand) -> chain_fast_kernel
 //          (a lane per read on ready anchors, per-template state in LDS), chunks of 2 M reads through one anchor pool;
 //   slow   chain_kernel, a lane per read on DB_size-wide scratch, for the reads the fast route does not take (N's, more than 288
-//          k-mer starts, more than 64 anchors on a strand, more candidate templates than the LDS table holds). -------------------
+//          k-mer starts, more than 32 anchors on a strand, more candidate templates than the LDS table holds). -------------------
 int kmahip_chain_device(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *d, const kmahip_params *p, const kmahip_chain_params *cp, int32_t *rec,
                         int64_t *rec_T, int32_t *T, int64_t rec_cap, int64_t T_cap, int64_t *n_recs, int64_t *n_T) {
 	const int64_t n = d->n_reads;
 	*n_recs = 0; *n_T = 0;
+	for(int i = 0; i < 5; ++i) ws->chain_route_counts[i] = 0;
 	if(int rcp = kmahip_refuse_proxi(p, KMAHIP_PROXI_CHAIN)) return rcp;
 	if(int rcd = kmahip_refuse_decon(db, KMAHIP_DECON_CHAIN)) return rcd;
 	if(n <= 0) return KMAHIP_OK;
@@ -1348,6 +1351,7 @@ int kmahip_chain_device(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *d, con
 	uint8_t *slow = nullptr;
 	int64_t *slow_list = nullptr, *long_list = nullptr;
 	int64_t n_slow = all_slow ? n : 0, n_long = 0;
+	unsigned long long n_marked = 0, n_given_up = 0;
 	if(!all_slow) {
 		// (KMAHIP_CHAIN_CHUNK: reads per chunk, for the tests: many chunks out of a few thousand reads)
 		const int64_t CHUNK = getenv("KMAHIP_CHAIN_CHUNK") ? std::max<int64_t>(64, atoll(getenv("KMAHIP_CHAIN_CHUNK"))) : 2000000;
@@ -1368,7 +1372,7 @@ int kmahip_chain_device(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *d, con
 		if((rc = dev((size_t) n, (void **) &slow))) return rc;
 		for(int x = 0; x < nbuf; ++x) {
 			buf[x].pool_cap = m_max * 40 + 4096;
-			if((rc = dev((size_t) m_max * 16, (void **) &buf[x].a_off)) || (rc = dev((size_t) m_max * 8, (void **) &buf[x].a_n)) || (rc = dev(16, (void **) &buf[x].cnt)) ||
+			if((rc = dev((size_t) m_max * 16, (void **) &buf[x].a_off)) || (rc = dev((size_t) m_max * 8, (void **) &buf[x].a_n)) || (rc = dev(32, (void **) &buf[x].cnt)) ||
 			   (rc = dev((size_t) buf[x].pool_cap * sizeof(CAnk), (void **) &buf[x].pool))) return rc;
 		}
 		// per-lane scratch of the fast kernel: two dummy anchors, the two template lists, the tree
@@ -1445,18 +1449,22 @@ int kmahip_chain_device(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *d, con
 		// what is left for the lane-per-read kernel
 		unsigned long long *cnt2 = cnt;
 		if((rc = dev((size_t) n * 8, (void **) &slow_list))) return rc;
-		HIP_TRY(hipMemsetAsync(cnt2, 0, 16, 0));
+		HIP_TRY(hipMemsetAsync(cnt2, 0, 32, 0));
 		// (KMAHIP_CHAIN_LONG=0: no long-read route, chain_kernel takes everything the fast route left)
 		const int split = !(getenv("KMAHIP_CHAIN_LONG") && !atoi(getenv("KMAHIP_CHAIN_LONG")));
 		hipLaunchKernelGGL(slow_list_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, n, slow, d->N_off, split, slow_list, cnt2);
-		unsigned long long ns[2] = {0, 0};
-		HIP_TRY(hipMemcpy(ns, cnt2, 16, hipMemcpyDeviceToHost));
+		unsigned long long ns[4] = {0, 0, 0, 0};
+		HIP_TRY(hipMemcpy(ns, cnt2, 32, hipMemcpyDeviceToHost));
 		n_long = (int64_t) ns[0];
 		n_slow = (int64_t) ns[1];
+		n_marked = ns[2]; n_given_up = ns[3];
 		long_list = slow_list;
 		slow_list += n - n_slow;
 		if(dbg) fprintf(stderr, "[kmahip] scan_chain: of %lld reads %lld left to the long-read route, %lld to the lane-per-read kernel\n", (long long) n, (long long) n_long, (long long) n_slow);
 	}
+	// (kmahip_chain_get_route_counts: which route the reads of this call took)
+	ws->chain_route_counts[0] = (unsigned long long) n; ws->chain_route_counts[1] = n_marked; ws->chain_route_counts[2] = n_given_up;
+	ws->chain_route_counts[3] = (unsigned long long) n_long; ws->chain_route_counts[4] = (unsigned long long) n_slow;
 	if(n_long > 0) {
 		// ---- the long-read route: chain_long_anchor_kernel (a wavefront per read and strand) + chain_long_tail_kernel (a lane per read) ----
 		const int k = (int) db->info.kmersize;

@@ -171,6 +171,8 @@ struct kmahip_ws {
 	void *lt_buf[20];
 	size_t lt_bytes[20];
 	unsigned long long lt_stats[4];   // of the last call: DP problems, DP cells, MEMs chained, reads
+	unsigned long long chain_route_counts[5]; // of the last kmahip_chain_device call: reads, marked by chain_anchor_kernel, given up by chain_fast_kernel,
+	                                          // taken by the long-read route, taken by chain_kernel
 	unsigned long long lt_class_counts[26];   // of the last call: problems per wavefront class 0..16, then per lane class 0..8
 	// slow-path dense scratch
 	int32_t *dense;

@@ -312,6 +312,11 @@ static int build_ankers(const orc_db *db, const orc_rewards *rw, int exhaustive,
 	return hits;
 }
 
+/* what the reads since the caller last cleared it went through (the directed fixture tests/golden/chainroute aims at these):
+ * [0] records, [1] records that carry both strands (a strand tie: the reverse strand's templates follow negated), [2] tie anchors whose
+ * templates were added to a record's, [3] reads with more than one record */
+int orc_chain_log[4];
+
 int orc_scan_chain(const orc_db *db, const orc_rewards *rw, int exhaustive, int minlen, double coverT, double mrs,
                    const uint64_t *seq, int seqlen, const int *N /* N[0] = count */, orc_chain_rec *out, int out_cap, int *T_pool, int T_cap) {
 	const int k = (int) db->kmersize, D = (int) db->DB_size;
@@ -450,6 +455,7 @@ int orc_scan_chain(const orc_db *db, const orc_rewards *rw, int exhaustive, int 
 						const int keep = *tail;
 						*tail = 0;
 						chain_templates(&c, V, v, tail);
+						++orc_chain_log[2];
 						bt[0] += *tail;
 						*tail = keep;
 					}
@@ -468,6 +474,7 @@ int orc_scan_chain(const orc_db *db, const orc_rewards *rw, int exhaustive, int 
 				R->q_start = start; R->q_end = start + len;
 				if(rc & 2) {
 					int j = bestT[0];
+					++orc_chain_log[1];
 					for(int i = 1; i <= bestT_r[0]; ++i) bestT[++j] = -bestT_r[i];
 					bestT[0] += bestT_r[0];
 					VF[bi].score = -VF[bi].score;
@@ -487,6 +494,8 @@ int orc_scan_chain(const orc_db *db, const orc_rewards *rw, int exhaustive, int 
 			R->rc_flag = score; R->nT = nT; R->T = T_pool + T_used;
 			T_used += nT;
 			bt[0] = 0;
+			++orc_chain_log[0];
+			if(n_out == 1) ++orc_chain_log[3];
 			++n_out;
 		}
 		/* next chain of either strand (savekmers.c:5827-5925) */
