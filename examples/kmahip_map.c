@@ -216,7 +216,7 @@ static void *xcalloc(size_t n, size_t sz) { void *p = calloc(n ? n : 1, sz); if(
 static void usage(void) {
 	fprintf(stderr, "usage: kmahip_map (-i reads.fq[.gz] | -ipe r1.fq[.gz] r2.fq[.gz] [-apm p|u] | -int interleaved.fq[.gz] [-apm p|u]) -t_db <index prefix> -o <output prefix> [-1t1] [-Mt1 <template>] [-bcNano] [-bc90] [-bc <support>] [-bcg] [-ref_fsa [n]] [-dense]\n"
 	                "       [-t threads] [-nc] [-na] [-nf] [-mf fragments] [-ml len] [-xl len] [-mp phred] [-mi phred] [-eq q] [-mq q] [-ts bases] [-mrs f] [-mrc f] [-mct f]\n"
-	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev] [-sam n] [-ef [n]] [-matrix] [-vcf [n]] [-proxi f] [-ill] [-ca] [-mint2] [-mint3] [-ConClave n] [-deCon]\n"
+	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev] [-sam n] [-ef [n]] [-matrix] [-vcf [n]] [-proxi f] [-ill] [-ca] [-ck] [-mint2] [-mint3] [-ConClave n] [-deCon]\n"
 	                "       [-reward n] [-gapopen n] [-gapextend n] [-localopen n] [-Npenalty n] [-per n] [-transition n] [-transversion n] [-penalty n] [-cge]\n"
 	                "       (-s1dev, like -gpus not an option of kma: stage 1 of plain FASTQ input on the device; one rank, -1t1 only; its batches close at a quarter\n"
 	                "        of a gigabase of their own accord, KMAHIP_MAP_BATCH_BASES does not apply to them)\n"
@@ -225,6 +225,9 @@ static void usage(void) {
 	                "       (-ca: circular alignments, the seeds of every aligner chained across the template's origin (chainSeeds_circular), in every mode served;\n"
 	                "        the presets -mint2 = -1t1 -mem_mode -ca -cge -mrs 0.75 -mq 1 -ref_fsa 2 -dense -bcg -bcd 10 -bc 0.9 -vcf -ef and\n"
 	                "        -mint3 = -1t1 -mem_mode -ca -mq 1 -ref_fsa 2 -dense -bcNano -bcd 10 -bc 0.7 -vcf -ef, applied where they stand)\n"
+	                "       (-ck: count k-mers over pseudo alignment: stage 2 gives a template one point per k-mer of the read it holds (save_kmers_count,\n"
+	                "        get_kmers_for_pair_count) in the single-end -1t1 run and in every paired run; taken without effect, like kma, on single-end input\n"
+	                "        without -1t1, with -Mt1 and with -Sparse)\n"
 	                "       (-ConClave n: 1, the default, gives every read to the best template of its list (runConClave); 2 drops the templates that are not\n"
 	                "        significant, credits the reads unique among the rest and draws a template for every other read in proportion to those unique scores\n"
 	                "        (runConClave2); in every run of one rank, not with -gpus N; -Mt1 runs no ConClave and ignores it)\n"
@@ -361,6 +364,7 @@ int main(int argc, char **argv) {
 	int matrix = 0, vcf = 0;                     /* -matrix (kma.c:667): <out>.mat.gz; -vcf [n] (kma.c:949-961): <out>.vcf.gz, n = 2 fills its FILTER column */
 	int proxi_opt = 0;                           /* -proxi / -ill given (for the refusals' wording; what counts is par.minFrac) */
 	int decon = 0;                               /* -deCon: map against <t_db>.decon.comp.b and drop what fits the contamination best */
+	int ck = 0;                                  /* -ck (kma.c:689): stage 2 counts k-mers, kmahip_ws_set_count_kmers on the run's workspace */
 	int sparse = 0; char ss = 'q';               /* -Sparse (kma.c:684): count k-mers, write <out>.spa only; -ss q|c|d, the order its templates are named in */
 	int base_call = 0, sig_mode = 0, ref_fsa = 0, dense = 0;      /* as kmahip_assemble_opts.caller (0-2 here) / .sig90; printconsensus.c's ref_fsa */
 	double support = 0;                          /* -bc x: the variable the reference hands updateVcf (kma.c:747, vcf.c:195) ... */
@@ -502,6 +506,7 @@ int main(int argc, char **argv) {
 		}
 		else if(!strcmp(o, "-deCon")) decon = 1;                                                /* kma.c:511-513: deConPrint / deConPrintPair, <t_db>.decon.comp.b */
 		else if(!strcmp(o, "-ca")) par.ca = 1;                                                  /* kma.c:722-723: chainSeedsPtr = &chainSeeds_circular */
+		else if(!strcmp(o, "-ck")) ck = 1;                                                      /* kma.c:689-690, 1272-1276: get_kmers_for_pair_count, and save_kmers_count under -1t1 */
 		else if(!strcmp(o, "-mint2")) {                                                         /* kma.c:1069-1094: a preset, applied where it stands */
 			one2one = 1; mem_mode = 1; par.ca = 1;                                              /* -1t1 -mem_mode -ca */
 			par.scoreT = 0.75; cp.mrs = 0.75;                                                   /* (not the 0.5 of -cge) */
@@ -744,7 +749,7 @@ int main(int argc, char **argv) {
 		pthread_t reader;
 		if(pthread_create(&reader, NULL, stream_main, &sj)) fail("cannot start a thread");
 		kmahip_db *db; kmahip_ws *ws;
-		if(kmahip_init(local) || (decon ? kmahip_db_open_decon(prefix, &db) : kmahip_db_open(prefix, &db)) || kmahip_ws_create(db, &ws)) die("open");
+		if(kmahip_init(local) || (decon ? kmahip_db_open_decon(prefix, &db) : kmahip_db_open(prefix, &db)) || kmahip_ws_create(db, &ws) || kmahip_ws_set_count_kmers(ws, ck)) die("open");
 		if(pe_chain && kmahip_ws_set_pe_chain(ws, &cp)) die("open");
 		const double t_open = now_s();
 		kmahip_shard_opts so;
@@ -849,7 +854,7 @@ int main(int argc, char **argv) {
 	if(pthread_create(&ingest_thread, NULL, ingest_main, &job)) fail("cannot start a thread");
 
 	kmahip_db *db; kmahip_ws *ws; kmahip_db_info info;
-	if(kmahip_init(local) || kmahip_db_open(prefix, &db) || kmahip_ws_create(db, &ws) || kmahip_db_get_info(db, &info)) die("open");
+	if(kmahip_init(local) || kmahip_db_open(prefix, &db) || kmahip_ws_create(db, &ws) || kmahip_ws_set_count_kmers(ws, ck) || kmahip_db_get_info(db, &info)) die("open");
 	if(pe_chain && kmahip_ws_set_pe_chain(ws, &cp)) die("open");
 	kmahip_comm *comm = NULL;
 	if(world > 1 || force_comm) {

@@ -833,6 +833,17 @@ int kmahip_run_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_read_batch *batch, 
  * the traceback and the `.frag.gz` like a record of kmahip_run_chain. NULL: back to -1t1 (single records through save_kmers). */
 int kmahip_ws_set_pe_chain(kmahip_ws *ws, const kmahip_chain_params *cp);
 
+/* -ck, "count k-mers over pseudo alignment" (kma.c:689), off on a new workspace. on != 0: stage 2 of every run on this workspace that
+ * scans k-mers for the single-end -1t1 run or for pairs scores a template by ONE point per k-mer start of the read whose value list
+ * holds it -- save_kmers_count (savekmers.c:3067-3365) in place of save_kmers (:2442-3065), get_kmers_for_pair_count (:690-824) in
+ * place of get_kmers_for_pair (:427-688), chosen at kma.c:1272-1276 -- on the device by scan_count_kernel. A single-end record is
+ * written when kmersize <= the best count of either strand (:3343); the pairing functions, kmahip_params::minFrac on single-end
+ * input, the decon filter and every stage behind stage 2 are the same. Read by kmahip_scan_se* / kmahip_scan_pe* and everything
+ * that runs them (kmahip_map_se / _pe, kmahip_run_se / _pe, the sessions, the sharded runs); kmahip_scan_chain and the chain runs
+ * (the default mode on single-end input) and kmahip_run_mt1 do not read it, like the reference. The setting lives on the workspace
+ * and not in kmahip_params, whose layout stays as it is. */
+int kmahip_ws_set_count_kmers(kmahip_ws *ws, int on);
+
 /* Multi-GPU (one process per GPU): in-place SUM over all ranks of the two ConClave
  * vectors on `stream`, through RCCL (ncclAllReduce, ncclUint64, ncclSum).
  * `nccl_comm` is an ncclComm_t the host program created (ncclCommInitRank);

@@ -559,14 +559,22 @@ class Session:
     """A kmahip_session on a database, as far as choosing its mode goes: set_sam (kmahip_session_set_sam) beside set_chain / set_mt1 /
     set_pe, each before the first batch. Feeding batches and finishing the run is the host program's (examples/kmahip_map.c)."""
 
-    def __init__(self, db, evalue=0.05, bcd=1, max_frag=0, reads_hint=0, conclave=1):
+    def __init__(self, db, evalue=0.05, bcd=1, max_frag=0, reads_hint=0, conclave=1, count_kmers=False):
         self._db = db
         self._h = C.c_void_p()
         self._conclave_was = _conclave_now          # (-ConClave: one setting per process, read when the session finishes; close() puts it back)
         set_conclave_version(conclave)
         so = ShardOpts(evalue, bcd, 0, 0, int(max_frag), 1.0, 0.0, 0.0, 0, 1)
         p = Params.from_buffer_copy(db.params)
-        _check(lib().kmahip_session_open(db.h, db.ws, C.byref(p), C.byref(so), int(reads_hint), C.byref(self._h)))
+        self._ck_was = db.count_kmers          # (-ck: the counting scan in every run of the session that scans k-mers; close() puts it back)
+        if count_kmers:
+            db.set_count_kmers(True)
+        try:
+            _check(lib().kmahip_session_open(db.h, db.ws, C.byref(p), C.byref(so), int(reads_hint), C.byref(self._h)))
+        except Exception:
+            db.set_count_kmers(self._ck_was)          # (no session: the workspace and the process are left as they were found)
+            set_conclave_version(self._conclave_was)
+            raise
 
     def set_sam(self, level=1, path="-", program="kmahip", cmdline=None):
         _check(lib().kmahip_session_set_sam(self._h, int(level), os.fsencode(path), program.encode(), None if cmdline is None else cmdline.encode()))
@@ -597,6 +605,7 @@ class Session:
             lib().kmahip_session_close(self._h)
             self._h = C.c_void_p()
             set_conclave_version(self._conclave_was)
+            self._db.set_count_kmers(self._ck_was)
 
     def __enter__(self):
         return self
@@ -651,6 +660,29 @@ class KmaHipDB:
         self.info = DBInfo()
         _check(L.kmahip_db_get_info(self.h, C.byref(self.info)))
         self.params = default_params()
+        self.count_kmers = False
+
+    def set_count_kmers(self, on=True):
+        """`-ck` for every later stage-2 call on this workspace (kmahip_ws_set_count_kmers): a template scores one point per k-mer of the
+        read it holds (save_kmers_count savekmers.c:3067, get_kmers_for_pair_count :690), not a pseudo-alignment. The chain finder and
+        -Mt1 do not read it."""
+        L = lib()
+        L.kmahip_ws_set_count_kmers.argtypes = [C.c_void_p, C.c_int]
+        L.kmahip_ws_set_count_kmers.restype = C.c_int
+        _check(L.kmahip_ws_set_count_kmers(self.ws, 1 if on else 0))
+        self.count_kmers = bool(on)
+
+    @contextlib.contextmanager
+    def _counting(self, on):
+        """count_kmers=True of one call: the workspace's setting for its duration, the earlier one after it"""
+        was = self.count_kmers
+        if on and not was:
+            self.set_count_kmers(True)
+        try:
+            yield
+        finally:
+            if self.count_kmers != was:
+                self.set_count_kmers(was)
 
     def close(self):
         if getattr(self, "ws", None):
@@ -667,9 +699,10 @@ class KmaHipDB:
             pass
 
     # -- host buffers in / out ------------------------------------------------
-    def scan_se(self, batch, exhaustive=0, t_cap=None, min_frac=1.0):
+    def scan_se(self, batch, exhaustive=0, t_cap=None, min_frac=1.0, count_kmers=False):
         """Stage 2 of the -1t1 run -> (rc_flag, flag, T_off, T). min_frac: proximity matching (-proxi): every template within that
-        fraction of a strand's best k-mer score is handed on, not only the ties (stage 2 takes its absolute value)"""
+        fraction of a strand's best k-mer score is handed on, not only the ties (stage 2 takes its absolute value). count_kmers (-ck):
+        a template scores one point per k-mer of the read it holds (save_kmers_count), not a pseudo-alignment"""
         n = batch.n
         seq = np.ascontiguousarray(batch.seq, np.uint64)
         Nn = np.ascontiguousarray(batch.N if len(batch.N) else np.zeros(1, np.int32), np.int32)
@@ -686,7 +719,8 @@ class KmaHipDB:
         for _ in range(8):
             T = np.zeros(cap, np.int32)
             out = Cands(_p(rc_flag), _p(flag), _p(T_off), _p(T), cap)
-            rc = lib().kmahip_scan_se(self.h, self.ws, C.byref(r), C.byref(p), C.byref(out))
+            with self._counting(count_kmers):
+                rc = lib().kmahip_scan_se(self.h, self.ws, C.byref(r), C.byref(p), C.byref(out))
             if rc == -6:  # KMAHIP_EOVERFLOW
                 cap = max(cap * 2, int(T_off[n]) + 16)
                 continue
@@ -811,7 +845,7 @@ class KmaHipDB:
         return ms.value, n.value
 
     # -- stages 2 + 3a, host buffers ------------------------------------------
-    def map_se(self, batch, exhaustive=0, t_cap=None, min_frac=1.0, circular=False):
+    def map_se(self, batch, exhaustive=0, t_cap=None, min_frac=1.0, circular=False, count_kmers=False):
         """-> (rc_flag, flag, T_off, T), hits dict (n_hits, best_score, flag, tmpl, score, start, end,
         alignment_scores, uniq_alignment_scores). min_frac: proximity matching (-proxi f) in stages 2 and 3a; its sign chooses what a
         kept hit adds to alignment_scores (positive: the read's best score, negative: the hit's own)"""
@@ -841,7 +875,8 @@ class KmaHipDB:
             out = Cands(_p(rc_flag), _p(flag), _p(T_off), _p(T), cap)
             hs = Hits(_p(h["n_hits"]), _p(h["best_score"]), _p(h["flag"]), _p(h["tmpl"]), _p(h["score"]), _p(h["start"]),
                       _p(h["end"]), _p(h["alignment_scores"]), _p(h["uniq_alignment_scores"]), _p(h["rc"]))
-            rc = lib().kmahip_map_se(self.h, self.ws, C.byref(r), C.byref(p), C.byref(out), C.byref(hs))
+            with self._counting(count_kmers):
+                rc = lib().kmahip_map_se(self.h, self.ws, C.byref(r), C.byref(p), C.byref(out), C.byref(hs))
             if rc == -6 and int(T_off[n]) > cap:
                 cap = max(cap * 2, int(T_off[n]) + 16)
                 continue
@@ -1080,7 +1115,7 @@ class KmaHipDB:
             o["consensus"] = {t: raw[coff[t]:raw.index(b"\0", coff[t])].decode() for t in range(D) if coff[t] >= 0}
         return o
 
-    def run_se(self, batch, evalue=0.05, bcd=1, max_frag=0, consensus=True, per_read=True, bc_nano=False, min_frac=1.0, circular=False, conclave=1):
+    def run_se(self, batch, evalue=0.05, bcd=1, max_frag=0, consensus=True, per_read=True, bc_nano=False, min_frac=1.0, circular=False, conclave=1, count_kmers=False):
         """The whole single-end run in one call (kmahip_run_se) -> dict(rows [ResRow], cover, aln_len, depth, asm_len, consensus,
         tmpl, n_hits, rc, trace_stats, ms). min_frac: proximity matching (-proxi f), as map_se. conclave: `-ConClave n`, for this call."""
         n = batch.n
@@ -1108,7 +1143,7 @@ class KmaHipDB:
             p.ca = 1          # -ca: chainSeeds_circular (chain.c:262, kma.c:722)
         if min_frac != 1.0:
             p.minFrac = float(min_frac)
-        with conclave_version(conclave):
+        with conclave_version(conclave), self._counting(count_kmers):
             _check(lib().kmahip_run_se(self.h, self.ws, C.byref(r), C.byref(p), float(evalue), int(bcd), int(max_frag), C.byref(run)))
         o["rows"] = [rows[i] for i in range(run.n_rows)]
         if consensus:
@@ -1216,16 +1251,17 @@ class KmaHipDB:
                                       None if fr is None else _p(fr), blob, _p(noff), int(level), C.byref(rows), per))
         return rows.value, list(per)
 
-    def session(self, evalue=0.05, bcd=1, max_frag=0, reads_hint=0, conclave=1):
-        """a kmahip_session on this database and workspace, for choosing its mode (Session); conclave: `-ConClave n` until it is closed"""
-        return Session(self, evalue, bcd, max_frag, reads_hint, conclave)
+    def session(self, evalue=0.05, bcd=1, max_frag=0, reads_hint=0, conclave=1, count_kmers=False):
+        """a kmahip_session on this database and workspace, for choosing its mode (Session); conclave: `-ConClave n` until it is closed;
+        count_kmers: `-ck`"""
+        return Session(self, evalue, bcd, max_frag, reads_hint, conclave, count_kmers)
 
     def set_pe_chain(self, on=True, minlen=16, coverT=0.1, mrs=0.5):
         """Paired runs on this workspace in the reference's default mode (no -1t1): records that lost their mate go to the chain
         finder (kmahip_ws_set_pe_chain); on=False: back to -1t1."""
         _check(lib().kmahip_ws_set_pe_chain(self.ws, C.byref(ChainParams(int(minlen), 0, float(coverT), float(mrs))) if on else None))
 
-    def run_pe(self, batch, names, pair, evalue=0.05, bcd=1, max_frag=0, frag_path=None, circular=False, conclave=1):
+    def run_pe(self, batch, names, pair, evalue=0.05, bcd=1, max_frag=0, frag_path=None, circular=False, conclave=1, count_kmers=False):
         """The paired run in one call (kmahip_run_pe) on what Ingest.next returned for two mate files -> dict(rows, cover, aln_len,
         depth, asm_len, consensus, ms). conclave: `-ConClave n`, for this call."""
         n = batch.n
@@ -1250,7 +1286,7 @@ class KmaHipDB:
         p = Params.from_buffer_copy(self.params)
         if circular:
             p.ca = 1          # -ca: chainSeeds_circular (chain.c:262, kma.c:722)
-        with conclave_version(conclave):
+        with conclave_version(conclave), self._counting(count_kmers):
             _check(lib().kmahip_run_pe(self.h, self.ws, C.byref(rb), C.byref(p), float(evalue), int(bcd), int(max_frag),
                                        os.fsencode(frag_path) if frag_path else None, C.byref(run)))
         o["rows"] = [rows[i] for i in range(run.n_rows)]
@@ -1382,8 +1418,9 @@ class KmaHipDB:
         return [rows[i] for i in range(n.value)]
 
     # -- paired end stage 2 (-apm p), host buffers ------------------------------------
-    def scan_pe(self, batch, exhaustive=0, t_cap=None):
-        """batch = mates interleaved (read 2i, 2i+1 = pair i) -> mate, rc, rc_flag, flag [2*pairs], R_off, T"""
+    def scan_pe(self, batch, exhaustive=0, t_cap=None, count_kmers=False):
+        """batch = mates interleaved (read 2i, 2i+1 = pair i) -> mate, rc, rc_flag, flag [2*pairs], R_off, T. count_kmers (-ck): the
+        candidates of a mate score one point per k-mer (get_kmers_for_pair_count); the pairing is the same"""
         n = batch.n
         assert n % 2 == 0
         seq = np.ascontiguousarray(batch.seq, np.uint64)
@@ -1398,7 +1435,8 @@ class KmaHipDB:
         for _ in range(6):
             T = np.zeros(cap, np.int32)
             out = PeRecs(_p(mate), _p(rc), _p(rc_flag), _p(flag), _p(R_off), _p(T), cap)
-            rcode = lib().kmahip_scan_pe(self.h, self.ws, C.byref(r), C.byref(p), C.byref(out))
+            with self._counting(count_kmers):
+                rcode = lib().kmahip_scan_pe(self.h, self.ws, C.byref(r), C.byref(p), C.byref(out))
             if rcode == -6:
                 cap = max(cap * 2, int(R_off[n]) + 16)
                 continue
@@ -1406,7 +1444,7 @@ class KmaHipDB:
             return mate[:n], rc[:n], rc_flag[:n], flag[:n], R_off, T[:R_off[n]]
         raise KmaHipError("scan_pe: output capacity kept overflowing")
 
-    def map_pe(self, batch, exhaustive=0, t_cap=None, circular=False):
+    def map_pe(self, batch, exhaustive=0, t_cap=None, circular=False, count_kmers=False):
         """Stages 2 + 3a for interleaved mates -> (mate, rc, rc_flag, flag, R_off, T), hits dict (+ "kind" per pair)"""
         n = batch.n
         assert n % 2 == 0
@@ -1432,7 +1470,8 @@ class KmaHipDB:
             out = PeRecs(_p(mate), _p(rc), _p(rc_flag), _p(flag), _p(R_off), _p(T), cap)
             hs = Hits(_p(h["n_hits"]), _p(h["best_score"]), _p(h["flag"]), _p(h["tmpl"]), _p(h["score"]), _p(h["start"]),
                       _p(h["end"]), _p(h["alignment_scores"]), _p(h["uniq_alignment_scores"]), _p(h["rc"]))
-            rcode = lib().kmahip_map_pe(self.h, self.ws, C.byref(r), C.byref(p), C.byref(out), C.byref(hs), _p(h["kind"]))
+            with self._counting(count_kmers):
+                rcode = lib().kmahip_map_pe(self.h, self.ws, C.byref(r), C.byref(p), C.byref(out), C.byref(hs), _p(h["kind"]))
             if rcode == -6:
                 cap = max(cap * 2, int(R_off[n]) + 16)
                 continue

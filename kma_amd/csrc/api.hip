@@ -22,6 +22,12 @@ extern "C" int kmahip_ws_set_pe_chain(kmahip_ws *ws, const kmahip_chain_params *
 	return KMAHIP_OK;
 }
 
+extern "C" int kmahip_ws_set_count_kmers(kmahip_ws *ws, int on) {
+	if(!ws) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	ws->ck = on != 0;
+	return KMAHIP_OK;
+}
+
 extern "C" int kmahip_ws_set_trace_drops(kmahip_ws *ws, const kmahip_trace_drops *drops) {
 	if(!ws) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	if(drops && (!drops->stats || !drops->ops_off || !drops->n_ops)) { kmahip_set_error("kmahip_ws_set_trace_drops: a drop record needs its three arrays"); return KMAHIP_EINVAL; }

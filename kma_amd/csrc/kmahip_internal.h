@@ -127,6 +127,7 @@ struct kmahip_ws {
 	// paired input in the default mode (kmahip_ws_set_pe_chain): singly loaded reads of a paired stream go to the chain finder
 	int pe_chain_on;
 	kmahip_chain_params pe_chain;
+	int ck;                   // kmahip_ws_set_count_kmers: stage 2 counts k-mers (scan_count_kernel) instead of scoring a pseudo-alignment
 	// paired-end stage 2
 	int32_t *pool_sc, *ppool;
 	void *pe_rec;

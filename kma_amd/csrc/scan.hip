@@ -1187,6 +1187,50 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 // templates of a value list are handled one per lane.
 constexpr int DCH = 512;
 
+// The finish of an item of the wavefront-per-item kernels (scan_dense_kernel and its counting twin), one text for both: `list` holds the
+// item's templates in first-seen order, `score` their scores (counts are scores that are never negative, so the clamps do nothing there).
+// Mode 1: every candidate with its clamped score and the hit count; mode 0: the ties of the best score or, under proximity matching,
+// every score from proxiScore on. Then the planes are put back (score 0, ext -1) and the item's three result words written.
+__device__ __forceinline__ void dense_finish(const ScanArgs &A, int64_t item, int lane, unsigned long long below,
+                                             volatile int32_t *score, volatile int32_t *ext, volatile int32_t *list, int nlist, int hits) {
+	int best = 0, nb = 0;
+	int64_t off = 0;
+	if(hits && A.mode) {
+		best = hits; nb = nlist;
+		if(lane == 0) off = A.pool_tail0 + (int64_t) atomicAdd(&A.counters[C_POOL], (unsigned long long) nb);
+		off = __shfl(off, 0);
+		if(off + nb <= A.pool_cap) {
+			for(int e = lane; e < nlist; e += 64) { A.pool[off + e] = list[e]; A.pool_sc[off + e] = max(0, (int) score[list[e]]); }
+		} else { if(lane == 0) atomicMax(&A.counters[C_STATUS], KMAHIP_ST_POOL); nb = 0; off = 0; }
+	} else if(hits) {
+		for(int e = lane; e < nlist; e += 64) best = max(best, max(0, (int) score[list[e]]));
+		for(int d = 32; d; d >>= 1) best = max(best, __shfl_xor(best, d));
+		if(best > 0) {
+			// proximity matching (uniform across the launch): every template from proxiScore on, in the list's first-seen order
+			const bool px = A.min_frac != 1.0;
+			const int thr = px ? (int) (A.min_frac * (double) best) : best;
+			auto kept = [&](int e) -> bool { const int sc = (int) score[list[e]]; return px ? sc >= thr : max(0, sc) == best; };
+			for(int e = lane; e < nlist; e += 64) nb += kept(e);
+			for(int d = 32; d; d >>= 1) nb += __shfl_xor(nb, d);
+			if(lane == 0) off = A.pool_tail0 + (int64_t) atomicAdd(&A.counters[C_POOL], (unsigned long long) nb);
+			off = __shfl(off, 0);
+			if(off + nb <= A.pool_cap) {
+				int w = 0;
+				for(int e0 = 0; e0 < nlist; e0 += 64) {
+					const int e = e0 + lane;
+					const bool is = e < nlist && kept(e);
+					const unsigned long long m = __ballot(is);
+					if(is) A.pool[off + w + __popcll(m & below)] = list[e];
+					w += __popcll(m);
+				}
+			} else { if(lane == 0) atomicMax(&A.counters[C_STATUS], KMAHIP_ST_POOL); nb = 0; off = 0; }
+		} else nb = 0;
+	}
+	for(int e = lane; e < nlist; e += 64) { const int t = list[e]; score[t] = 0; ext[t] = -1; }
+	__threadfence();
+	if(lane == 0) { A.item_score[item] = best; A.item_n[item] = nb; A.item_off[item] = off; }
+}
+
 __global__ __launch_bounds__(64) void scan_dense_kernel(const ScanArgs A) {
 	__shared__ uint32_t s_vi[DCH];
 	const DevDB &db = A.db;
@@ -1260,47 +1304,294 @@ __global__ __launch_bounds__(64) void scan_dense_kernel(const ScanArgs A) {
 			}
 			__syncthreads();
 		}
-		int best = 0, nb = 0;
-		int64_t off = 0;
 		if(hits) {
 			const int c = (int) value_at(db, last, 0);
 			for(int i = 1 + lane; i <= c; i += 64) score[value_at(db, last, i)] += acc;
 			__threadfence();
 		}
-		if(hits && A.mode) {
-			best = hits; nb = nlist;
-			if(lane == 0) off = A.pool_tail0 + (int64_t) atomicAdd(&A.counters[C_POOL], (unsigned long long) nb);
-			off = __shfl(off, 0);
-			if(off + nb <= A.pool_cap) {
-				for(int e = lane; e < nlist; e += 64) { A.pool[off + e] = list[e]; A.pool_sc[off + e] = max(0, (int) score[list[e]]); }
-			} else { if(lane == 0) atomicMax(&A.counters[C_STATUS], KMAHIP_ST_POOL); nb = 0; off = 0; }
-		} else if(hits) {
-			for(int e = lane; e < nlist; e += 64) best = max(best, max(0, (int) score[list[e]]));
-			for(int d = 32; d; d >>= 1) best = max(best, __shfl_xor(best, d));
-			if(best > 0) {
-				// proximity matching (uniform across the launch): every template from proxiScore on, in the list's first-seen order
-				const bool px = A.min_frac != 1.0;
-				const int thr = px ? (int) (A.min_frac * (double) best) : best;
-				auto kept = [&](int e) -> bool { const int sc = (int) score[list[e]]; return px ? sc >= thr : max(0, sc) == best; };
-				for(int e = lane; e < nlist; e += 64) nb += kept(e);
-				for(int d = 32; d; d >>= 1) nb += __shfl_xor(nb, d);
-				if(lane == 0) off = A.pool_tail0 + (int64_t) atomicAdd(&A.counters[C_POOL], (unsigned long long) nb);
-				off = __shfl(off, 0);
-				if(off + nb <= A.pool_cap) {
-					int w = 0;
-					for(int e0 = 0; e0 < nlist; e0 += 64) {
-						const int e = e0 + lane;
-						const bool is = e < nlist && kept(e);
-						const unsigned long long m = __ballot(is);
-						if(is) A.pool[off + w + __popcll(m & below)] = list[e];
-						w += __popcll(m);
-					}
-				} else { if(lane == 0) atomicMax(&A.counters[C_STATUS], KMAHIP_ST_POOL); nb = 0; off = 0; }
-			} else nb = 0;
+		dense_finish(A, item, lane, below, score, ext, list, nlist, hits);
+	}
+}
+
+// ---- counting scan (-ck, kmahip_ws_set_count_kmers): save_kmers_count (savekmers.c:3067-3365) and get_kmers_for_pair_count (:690-824).
+// Every k-mer start of an N-free stretch whose k-mer is in the index gives ONE point to every template of its value list; there is
+// no pseudo-alignment, so a table slot holds a template id, its count and the first start that brought it in -- no masks, no
+// last-hit state, no queue. The contract is scan_se_kernel's: strand items from in_items, item_score / item_n / item_off / pool
+// (+ pool_sc) out, items whose candidates do not fit the TSLOTS - 2 places of the table to out_over.
+//   MODE 0: item_score = the best count, the list = its ties (getBestMatch) or, PROXI, every count >= (int) (min_frac * best)
+//   MODE 1: item_score = the number of hit starts, the list = every candidate with its count
+// both in first-seen order: ascending (first start whose list holds the template, position in that list) -- the lists ascend by id.
+// A lane takes CSEG consecutive starts: their k-mers lie in ONE 32-base window (CSEG - 1 + k <= 32), fetched from the read's words
+// in global memory (16 lanes of an item read two or three neighbouring words: one line). A lane probes its first start and takes the
+// lists of the starts behind it from vs_id along the template's diagonal, probing only where that fails; equal lists of a lane's
+// segment are merged before they are expanded (the reference's `reps`), so a read that lies along one template expands a list once
+// per lane, not once per start. (Measured, DESIGN.md section 3.1f: nine probes per lane 25.1 ms per 10 M reads, this form 20.6 ms.)
+// The literal stretch rule of save_kmers_count's reverse strand (:3250, end = qseq->N[i] -- the FORWARD strand's N list bounds the
+// stretches of the reverse strand's walk): MODE 0, strand 1 tests the window [p, p + k) of STRAND positions against the forward list.
+constexpr int CSEG = 9;                       // k-mer starts per lane and pass
+constexpr int CPASS = (STHREADS / SG) * CSEG; // starts of an item per pass
+static_assert(CSEG - 1 + 16 <= 32, "one 32-base window holds the k-mers (k <= 16) of a lane's segment");
+
+// forward coordinate the N test of start p takes (see above)
+template <int MODE>
+__device__ __forceinline__ int count_n_coord(int p, int L, int k, int strand) {
+	return (MODE == 0 || !strand) ? p : L - k - p;
+}
+
+template <int MODE, int TSLOTS, bool PROXI = false>
+__global__ __launch_bounds__(STHREADS) void scan_count_kernel(const ScanArgs A) {
+	static_assert(!PROXI || !MODE, "the all-candidates mode keeps every template as it is");
+	__shared__ uint32_t t_id[TSLOTS * SG];
+	__shared__ int32_t t_score[TSLOTS * SG];          // the count
+	__shared__ int32_t t_first[TSLOTS * SG];          // the first k-mer start whose list holds the template
+	__shared__ int32_t t_cnt[SG], s_over[SG], s_hits[SG], s_best[SG], s_nb[SG];
+	__shared__ int64_t s_off[SG];
+	__shared__ int32_t s_len[SG], s_nN[SG];
+	__shared__ int64_t s_soff[SG], s_noff[SG], s_item[SG];
+	__shared__ int32_t s_gmax;
+
+	const DevDB &db = A.db;
+	const int tid = threadIdx.x;
+	const int k = (int) db.kmersize;
+	const int64_t n_active = (int64_t) A.counters[A.in_count];
+	for(int64_t first = (int64_t) blockIdx.x * SG; first < n_active; first += (int64_t) gridDim.x * SG) {
+		const int ng = (int) min((int64_t) SG, n_active - first);
+		if(tid < SG) {
+			int L = 0, nN = 0; int64_t so = 0, no = 0, it = 0;
+			if(tid < ng) {
+				it = A.in_items[first + tid] & ITEM_MASK;
+				const int64_t r = it >> 1;
+				L = A.len[r]; so = A.seq_off[r]; no = A.N_off[r]; nN = (int) (A.N_off[r + 1] - no);
+			}
+			s_len[tid] = L; s_nN[tid] = nN; s_soff[tid] = so; s_noff[tid] = no; s_item[tid] = it;
+			int mx = L;
+#pragma unroll
+			for(int d = SG / 2; d; d >>= 1) mx = max(mx, __shfl_xor(mx, d, SG));
+			if(tid == 0) s_gmax = mx - k + 1;
+			t_cnt[tid] = 0; s_over[tid] = 0; s_hits[tid] = 0; s_best[tid] = 0; s_nb[tid] = 0;
 		}
-		for(int e = lane; e < nlist; e += 64) { const int t = list[e]; score[t] = 0; ext[t] = -1; }
-		__threadfence();
-		if(lane == 0) { A.item_score[item] = best; A.item_n[item] = nb; A.item_off[item] = off; }
+		for(int idx = tid; idx < TSLOTS * SG; idx += STHREADS) { t_id[idx] = T_EMPTY; t_score[idx] = 0; t_first[idx] = INT_MAX; }
+		__syncthreads();
+		{
+			const int g = tid & (SG - 1), sl = tid / SG;
+			const int L = s_len[g], npos = L - k + 1, strand = (int) (s_item[g] & 1), nN = s_nN[g];
+			const int32_t *Nl = A.N + s_noff[g];
+			const uint64_t *rs = A.seq + s_soff[g];
+			const int gmax = s_gmax;
+			for(int c0 = 0; c0 < gmax; c0 += CPASS) {
+				const int p0 = c0 + sl * CSEG;
+				if(g >= ng || p0 >= npos || s_over[g]) continue;
+				const int n = min(CSEG, npos - p0);
+				const uint64_t qw = strand_win(rs, L, strand, p0);
+				uint32_t gp[CSEG], vv[CSEG];
+				uint32_t todo = 0;          // bit i: start p0 + i is in the read, in an N-free stretch, and not resolved yet
+#pragma unroll
+				for(int i = 0; i < CSEG; ++i) {
+					gp[i] = MISS; vv[i] = MISS;
+					if(i < n && !(nN && window_has_N(Nl, nN, count_n_coord<MODE>(p0 + i, L, k, strand), k))) todo |= 1u << i;
+				}
+				// A read that matches a template keeps matching it: the segment's first start is probed, and every start behind it
+				// whose k bases are the template's along that diagonal takes its list from vs_id (the same offset a probe of that
+				// k-mer leads to) -- one gather into the probe table and one issue of sequential loads instead of nine gathers.
+				// Where the template store holds no k-mer (its end) or a base differs, the start is probed like before.
+				if(todo & 1u) {
+					todo &= ~1u;
+					const uint32_t g0 = probe(db, (uint32_t) (qw >> (64 - 2 * k)));
+					if(g0 != MISS) {
+						uint32_t wv[CSEG];
+						const uint32_t *vp = db.vs_id + g0;          // (vs_id carries 64 entries of padding, `cat` two words)
+#pragma unroll
+						for(int i = 0; i < CSEG; ++i) wv[i] = vp[i];
+						const uint64_t x = qw ^ win2(db.cat, (int64_t) g0);
+						const int same = x ? (__clzll((long long) x) >> 1) : 32;
+						vv[0] = wv[0];
+#pragma unroll
+						for(int i = 1; i < CSEG; ++i)
+							if(((todo >> i) & 1u) && same >= k + i && wv[i] != KMAHIP_EMPTY_VI) { vv[i] = wv[i]; todo &= ~(1u << i); }
+					}
+				}
+#pragma unroll
+				for(int i = 0; i < CSEG; ++i)
+					if((todo >> i) & 1u) gp[i] = probe(db, (uint32_t) ((qw << (2 * i)) >> (64 - 2 * k)));
+#pragma unroll
+				for(int i = 0; i < CSEG; ++i) if(gp[i] != MISS) vv[i] = db.vs_id[gp[i]];
+				int hits = 0;
+#pragma unroll
+				for(int i = 0; i < CSEG; ++i) {
+					const uint32_t vi = vv[i];
+					if(vi == MISS) continue;
+					int reps = 1;
+#pragma unroll
+					for(int j = i + 1; j < CSEG; ++j) if(vv[j] == vi) { ++reps; vv[j] = MISS; }
+					hits += reps;
+					if(s_over[g]) continue;
+					const uint32_t cnt = value_at(db, vi, 0);
+#pragma unroll 1
+					for(uint32_t e = 1; e <= cnt; ++e) {
+						const int slot = template_slot<TSLOTS>(value_at(db, vi, (int) e), g, t_id, t_cnt);
+						if(slot < 0) { s_over[g] = 1; break; }
+						atomicAdd(&t_score[slot], reps);
+						atomicMin(&t_first[slot], p0 + i);
+					}
+				}
+				if(hits) atomicAdd(&s_hits[g], hits);
+			}
+		}
+		__syncthreads();
+		// ---- finish, as in scan_se_kernel: the best count of an item by an LDS atomic over its occupied slots, the kept templates
+		// counted the same way, one thread per item takes the result slots, every kept template finds its rank by counting smaller keys
+		auto kept = [&](int j, int best) -> bool {
+			if(PROXI) return t_score[j] >= (int) (A.min_frac * (double) best);
+			return t_score[j] == best;
+		};
+		for(int part = 0; part < TSLOTS * SG; part += STHREADS) {
+			const int idx = part + tid, g = idx & (SG - 1);
+			if(g < ng && !s_over[g] && t_id[idx] != T_EMPTY) {
+				if(MODE) atomicAdd(&s_nb[g], 1);
+				else atomicMax(&s_best[g], t_score[idx]);
+			}
+		}
+		__syncthreads();
+		if(!MODE) {
+			for(int part = 0; part < TSLOTS * SG; part += STHREADS) {
+				const int idx = part + tid, g = idx & (SG - 1);
+				if(g < ng && !s_over[g] && t_id[idx] != T_EMPTY && s_best[g] > 0 && kept(idx, s_best[g])) atomicAdd(&s_nb[g], 1);
+			}
+			__syncthreads();
+		}
+		if(tid < SG) {
+			const int g = tid;
+			const bool mine = g < ng;
+			const int64_t item = s_item[g];
+			int best = 0, nb = 0, want = 0;
+			bool over = false;
+			if(mine && s_over[g]) { over = true; nb = -1; }
+			else if(mine) {
+				best = MODE ? s_hits[g] : s_best[g];
+				nb = (MODE || best > 0) ? s_nb[g] : 0;
+				if(nb && (MODE || nb > INL)) want = nb;
+			}
+			// pool room and places in the overflow list: ONE atomic per workgroup and counter
+			int incl = want, oincl = over ? 1 : 0;
+#pragma unroll
+			for(int d = 1; d < SG; d <<= 1) {
+				const int a = __shfl_up(incl, d, SG), b = __shfl_up(oincl, d, SG);
+				if(tid >= d) { incl += a; oincl += b; }
+			}
+			const int tot = __shfl(incl, SG - 1, SG), otot = __shfl(oincl, SG - 1, SG);
+			unsigned long long pbase = 0, obase = 0;
+			if(tid == 0 && tot) pbase = atomicAdd(&A.counters[C_POOL], (unsigned long long) tot);
+			if(tid == 0 && otot) obase = atomicAdd(&A.counters[A.out_count], (unsigned long long) otot);
+			pbase = __shfl(pbase, 0, SG);
+			obase = __shfl(obase, 0, SG);
+			int64_t off = 0;
+			if(over) { A.out_over[obase + (unsigned long long) (oincl - 1)] = item; s_off[g] = -1; }
+			else if(mine) {
+				if(nb) off = want ? A.pool_tail0 + (int64_t) pbase + (incl - want) : item * INL;
+				// (pool exhausted: the host repeats the call with a larger one; the item is left without a list)
+				if(nb && off + nb > A.pool_cap) { atomicMax(&A.counters[C_STATUS], KMAHIP_ST_POOL); s_off[g] = -1; nb = 0; off = 0; }
+				else s_off[g] = nb ? off : -1;
+			} else s_off[g] = -1;
+			if(mine && !over) {
+				A.item_score[item] = best;
+				A.item_n[item] = nb;
+				A.item_off[item] = off;
+			}
+		}
+		__syncthreads();
+		for(int part = 0; part < TSLOTS * SG; part += STHREADS) {
+			const int idx = part + tid, g = idx & (SG - 1);
+			if(g >= ng || s_off[g] < 0 || t_id[idx] == T_EMPTY) continue;
+			const int best = s_best[g];
+			if(!MODE && !kept(idx, best)) continue;
+			int rank = 0;
+			if(s_nb[g] > 1) {
+				const long long key = ((long long) t_first[idx] << 32) | t_id[idx];
+#pragma unroll 1
+				for(int x = 0; x < TSLOTS; ++x) {
+					const int j = x * SG + g;
+					const uint32_t id = t_id[j];
+					if(id == T_EMPTY || (!MODE && !kept(j, best))) continue;
+					rank += ((((long long) t_first[j] << 32) | id) < key);
+				}
+			}
+			A.pool[s_off[g] + rank] = (int32_t) t_id[idx];
+			if(MODE) A.pool_sc[s_off[g] + rank] = t_score[idx];
+		}
+		__syncthreads();
+	}
+}
+
+// The counting scan's items that fit no LDS tier: save_kmers_count's own sequential walk on the DB_size-wide planes of
+// scan_dense_kernel (count / present / first-seen list; with a decon table the pseudo-template DB_size has its entry too), one
+// wavefront per item: 512 starts are resolved side by side, then walked in order with the reference's `reps`.
+__global__ __launch_bounds__(64) void scan_dense_count_kernel(const ScanArgs A) {
+	__shared__ uint32_t s_vi[DCH];
+	const DevDB &db = A.db;
+	const int k = (int) db.kmersize, lane = threadIdx.x;
+	const int64_t n_over = (int64_t) A.counters[A.in_count];
+	const int64_t slot = blockIdx.x;
+	if(slot >= A.dense_slots) return;
+	const int64_t D = (int64_t) db.DB_size + db.decon;
+	volatile int32_t *score = A.dense + slot * 3 * D;
+	volatile int32_t *ext = score + D;
+	volatile int32_t *list = ext + D;   // list[0..nlist): templates in first-seen order; ext[t] == -1 marks "absent"
+	const unsigned long long below = (1ull << lane) - 1ull;
+	for(int64_t oi = slot; oi < n_over; oi += A.dense_slots) {
+		const int64_t item = A.in_items[oi] & ITEM_MASK;
+		const int64_t r = item >> 1;
+		const int strand = (int) (item & 1);
+		const int L = A.len[r], npos = L - k + 1;
+		const uint64_t *rs = A.seq + A.seq_off[r];
+		const int32_t *Nl = A.N + A.N_off[r];
+		const int nN = (int) (A.N_off[r + 1] - A.N_off[r]);
+		uint32_t last = NONE;
+		int reps = 0, nlist = 0, hits = 0;
+		// `reps` points to every template of list `last`, one per lane; a template that had none enters the first-seen list
+		auto flush = [&]() {
+			const int cnt = (int) value_at(db, last, 0);
+			for(int i0 = 1; i0 <= cnt; i0 += 64) {
+				const int i = i0 + lane;
+				bool fresh = false;
+				uint32_t t = 0;
+				if(i <= cnt) {
+					t = value_at(db, last, i);
+					if(ext[t] != -1) score[t] += reps;
+					else { score[t] = reps; ext[t] = 0; fresh = true; }
+				}
+				const unsigned long long fm = __ballot(fresh);
+				if(fresh) list[nlist + __popcll(fm & below)] = (int32_t) t;
+				nlist += __popcll(fm);
+			}
+			__threadfence();
+			hits += reps;
+		};
+		for(int base = 0; base < npos; base += DCH) {
+			const int n = min(DCH, npos - base);
+			for(int x = lane; x < n; x += 64) {
+				const int p = base + x, q = strand ? (L - k - p) : p;
+				uint32_t vi = MISS;
+				if(nN == 0 || !window_has_N(Nl, nN, A.mode ? q : p, k)) {
+					const int w = q >> 5;
+					uint64_t km = kmer_from(rs[w], rs[w + 1], q, k);
+					if(strand) km = revcomp_kmer(km, k);
+					vi = probe(db, (uint32_t) km);
+					if(vi != MISS) vi = db.vs_id[vi];
+				}
+				s_vi[x] = vi;
+			}
+			__syncthreads();
+			for(int x = 0; x < n; ++x) {
+				const uint32_t vi = s_vi[x];
+				if(vi == MISS) continue;
+				if(vi == last) { ++reps; continue; }
+				if(last != NONE) flush();
+				last = vi; reps = 1;
+			}
+			__syncthreads();
+		}
+		if(last != NONE) flush();
+		dense_finish(A, item, lane, below, score, ext, list, nlist, hits);
 	}
 }
 
@@ -2131,6 +2422,24 @@ static void launch_first_tier(const ScanArgs &A, bool stats, hipStream_t stream)
 	else hipLaunchKernelGGL((scan_se_kernel<false, MODE, TS1, false, true, PROXI>), dim3(bare_grid()), dim3(STHREADS), 0, stream, A);
 }
 
+// the counting scan (kmahip_ws_set_count_kmers): both LDS tiers on looping grids, then the wavefront-per-item kernel. The prefilter has put
+// every live item on the bare list (no records, no diagonals: ScanArgs::recs == NULL, cat_bases == 0).
+template <int MODE>
+static void launch_count_first(const ScanArgs &A, bool proxi, hipStream_t stream) {
+	const unsigned grid = (unsigned) std::min<int64_t>((2 * A.n_reads + SG - 1) / SG, 2 * (int64_t) bare_grid());
+	if(MODE == 0 && proxi) hipLaunchKernelGGL((scan_count_kernel<0, TS1, true>), dim3(grid), dim3(STHREADS), 0, stream, A);
+	else hipLaunchKernelGGL((scan_count_kernel<MODE, TS1>), dim3(grid), dim3(STHREADS), 0, stream, A);
+}
+
+template <int MODE>
+static void launch_count_rest(ScanArgs &A, bool proxi, int64_t *over1, int64_t *over2, int64_t dense_slots, hipStream_t stream) {
+	A.in_items = over1; A.in_count = C_NOVER; A.out_over = over2; A.out_count = C_NOVER2;
+	if(MODE == 0 && proxi) hipLaunchKernelGGL((scan_count_kernel<0, TS2, true>), dim3(TIER2_GRID), dim3(STHREADS), 0, stream, A);
+	else hipLaunchKernelGGL((scan_count_kernel<MODE, TS2>), dim3(TIER2_GRID), dim3(STHREADS), 0, stream, A);
+	A.in_items = over2; A.in_count = C_NOVER2;
+	hipLaunchKernelGGL(scan_dense_count_kernel, dim3((unsigned) dense_slots), dim3(64), 0, stream, A);
+}
+
 static int ws_reserve(kmahip_ws *ws, int64_t n_reads) {
 	kmahip_db *db = ws->db;
 	if(n_reads > ws->cap_reads) {
@@ -2188,14 +2497,16 @@ int kmahip_launch_scan_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	A.item_score = ws->item_score; A.item_n = ws->item_n; A.item_off = ws->item_off;
 	A.pool = ws->pool; A.pool_cap = ws->pool_cap; A.counters = ws->counters; A.overflow_items = ws->overflow_items;
 	A.dense = ws->dense; A.dense_slots = ws->dense_slots; A.active_items = ws->active_items;
-	A.mode = 0; A.pool_sc = nullptr; A.pool_tail0 = 2 * n * INL; A.cat_bases = diag_cat_bases(db);
+	// -ck: the counting scan takes every live item from the bare list and has no use for a diagonal
+	const bool ck = ws->ck != 0;
+	A.mode = 0; A.pool_sc = nullptr; A.pool_tail0 = 2 * n * INL; A.cat_bases = ck ? 0 : diag_cat_bases(db);
 	// proximity matching: stage 2 takes |minFrac| (kma.c:1605; the sign is stage 3a's), and -1 is 1 (kma.c:708)
 	A.min_frac = std::fabs(p->minFrac);
 	const bool proxi = A.min_frac != 1.0;
 	if(!(A.min_frac <= 1.0)) { kmahip_set_error("minFrac %g outside [-1, 1]", p->minFrac); return KMAHIP_EINVAL; }
 	if(kmahip_mem_mode() && (rc = kmahip_refuse_proxi(p, KMAHIP_PROXI_MEM))) return rc;
 	if(kmahip_mem_mode() && (rc = kmahip_refuse_decon(db, KMAHIP_DECON_MEM))) return rc;
-	A.recs = scan_records_on(ws, reads, p) ? ws->recs : nullptr; A.rec_cap = ws->rec_cap;
+	A.recs = !ck && scan_records_on(ws, reads, p) ? ws->recs : nullptr; A.rec_cap = ws->rec_cap;
 	A.refine = scan_refine_on(A.cat_bases); A.pf_stage_words = pf_stage_words();
 	A.ablate = 0;
 #ifdef KMAHIP_DIAG
@@ -2220,7 +2531,8 @@ int kmahip_launch_scan_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	if(ws->timing_on) { HIP_TRY(hipEventRecord(evq, stream)); HIP_TRY(hipEventRecord(ev0, stream)); }
 	int64_t *over1 = ws->overflow_items, *over2 = ws->overflow_items + 2 * ws->cap_reads;
 	A.in_items = ws->active_items; A.in_count = C_NACT; A.out_over = over1; A.out_count = C_NOVER;
-	if(proxi) launch_first_tier<0, true>(A, ws->stats_on != 0, stream);
+	if(ck) launch_count_first<0>(A, proxi, stream);
+	else if(proxi) launch_first_tier<0, true>(A, ws->stats_on != 0, stream);
 	else launch_first_tier<0>(A, ws->stats_on != 0, stream);
 	if(ws->timing_on) {
 		HIP_TRY(hipEventRecord(ev1, stream));
@@ -2229,7 +2541,8 @@ int kmahip_launch_scan_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 		if(!ws->events3) ws->events3 = new std::vector<std::pair<hipEvent_t, hipEvent_t>>();
 		ws->events3->push_back({evp, evq});
 	}
-	{
+	if(ck) launch_count_rest<0>(A, proxi, over1, over2, ws->dense_slots, stream);
+	else {
 		// second tier (64-slot tables, a fixed grid looping over the groups), then whatever is left one wavefront per item
 		A.in_items = over1; A.in_count = C_NOVER; A.out_over = over2; A.out_count = C_NOVER2;
 		if(proxi) {
@@ -2312,8 +2625,9 @@ int kmahip_launch_scan_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	A.item_score = ws->item_score; A.item_n = ws->item_n; A.item_off = ws->item_off;
 	A.pool = ws->pool; A.pool_cap = ws->pool_cap; A.counters = ws->counters; A.overflow_items = ws->overflow_items;
 	A.dense = ws->dense; A.dense_slots = ws->dense_slots; A.active_items = ws->active_items;
-	A.ablate = 0; A.mode = 1; A.pool_sc = ws->pool_sc; A.pool_tail0 = 0; A.cat_bases = diag_cat_bases(db);
-	A.recs = scan_records_on(ws, reads, p) ? ws->recs : nullptr; A.rec_cap = ws->rec_cap;
+	const bool ck = ws->ck != 0;         // -ck: get_kmers_for_pair_count in place of get_kmers_for_pair; the pairing kernels are the same
+	A.ablate = 0; A.mode = 1; A.pool_sc = ws->pool_sc; A.pool_tail0 = 0; A.cat_bases = ck ? 0 : diag_cat_bases(db);
+	A.recs = !ck && scan_records_on(ws, reads, p) ? ws->recs : nullptr; A.rec_cap = ws->rec_cap;
 	A.refine = scan_refine_on(A.cat_bases); A.pf_stage_words = pf_stage_words();
 	A.min_frac = 1.0;
 #ifdef KMAHIP_DIAG
@@ -2332,7 +2646,8 @@ int kmahip_launch_scan_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	if(ws->timing_on) { HIP_TRY(hipEventRecord(evq, stream)); HIP_TRY(hipEventRecord(ev0, stream)); }
 	int64_t *over1 = ws->overflow_items, *over2 = ws->overflow_items + 2 * ws->cap_reads;
 	A.in_items = ws->active_items; A.in_count = C_NACT; A.out_over = over1; A.out_count = C_NOVER;
-	launch_first_tier<1>(A, ws->stats_on != 0, stream);
+	if(ck) launch_count_first<1>(A, false, stream);
+	else launch_first_tier<1>(A, ws->stats_on != 0, stream);
 	if(ws->timing_on) {
 		HIP_TRY(hipEventRecord(ev1, stream));
 		if(!ws->events) ws->events = new std::vector<std::pair<hipEvent_t, hipEvent_t>>();
@@ -2340,10 +2655,13 @@ int kmahip_launch_scan_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 		if(!ws->events3) ws->events3 = new std::vector<std::pair<hipEvent_t, hipEvent_t>>();
 		ws->events3->push_back({evp, evq});
 	}
-	A.in_items = over1; A.in_count = C_NOVER; A.out_over = over2; A.out_count = C_NOVER2;
-	hipLaunchKernelGGL((scan_se_kernel<false, 1, TS2>), dim3(TIER2_GRID), dim3(STHREADS), 0, stream, A);
-	A.in_items = over2; A.in_count = C_NOVER2;
-	hipLaunchKernelGGL(scan_dense_kernel, dim3((unsigned) ws->dense_slots), dim3(64), 0, stream, A);
+	if(ck) launch_count_rest<1>(A, false, over1, over2, ws->dense_slots, stream);
+	else {
+		A.in_items = over1; A.in_count = C_NOVER; A.out_over = over2; A.out_count = C_NOVER2;
+		hipLaunchKernelGGL((scan_se_kernel<false, 1, TS2>), dim3(TIER2_GRID), dim3(STHREADS), 0, stream, A);
+		A.in_items = over2; A.in_count = C_NOVER2;
+		hipLaunchKernelGGL(scan_dense_kernel, dim3((unsigned) ws->dense_slots), dim3(64), 0, stream, A);
+	}
 	PairArgs P;
 	P.S = A; P.n_pairs = np; P.PE = p->rw.PE;
 	P.ppool = ws->ppool; P.ppool_cap = 2 * ws->pool_cap;
