@@ -799,6 +799,14 @@ int kmahip_sam_write(const char *path, kmahip_db *db, const kmahip_reads *reads,
  * log(best)) in double, 0 for best <= 0), evaluated ON THE DEVICE by the one function all of those kernels call, for n triples in HOST
  * arrays. Exposed for tests: the device's log against the libm the reference links. */
 int kmahip_test_mapq(const int32_t *best, const int32_t *second, const int32_t *w, int64_t n, uint32_t *out);
+/* The list table (a second probe table whose value is a k-mer's value-list offset; the scan's queue and the wavefront-per-item kernels
+ * look lists up in it): for n keys in a HOST array, one lane per key, out_list[i] = the list table's answer and out_via_pos[i] = the
+ * list offset filed at the position the probe table answers with; 0xFFFFFFFF = not in the index. The two must agree for every key.
+ * KMAHIP_LTAB_FLAG is honoured as in a scan launch. KMAHIP_EINVAL when the database has no list table. Exposed for tests. */
+int kmahip_test_list_probe(kmahip_db *db, const uint32_t *keys, int64_t n, uint32_t *out_list, uint32_t *out_via_pos);
+/* log2 of the list table's bucket count (the probe table's + 1, or the same with KMAHIP_LTAB_SHIFT=0 in the environment of the
+ * open), 0: the database has none (KMAHIP_SCAN_LTAB=0 at the open, no memory for it, list offsets of 2^31 - 1 or more) */
+int kmahip_db_list_table_log2(const kmahip_db *db);
 /* The neighbour move of the cooperative DP sweep (a DPP row or wavefront shift in place of __shfl_down(x, 1, w)), on one wavefront:
  * out[l] = what lane l receives of in[0..64), w = 8, 16, 32 or 64 lanes per segment. What the last lane of a segment receives is
  * unspecified (the sweep never uses it). Exposed for tests. */
@@ -1064,6 +1072,10 @@ int kmahip_ws_scan_overflow(kmahip_ws *ws, void *stream, unsigned long long out[
  * of them and files that hit's diagonal when fewer bases differ along it (KMAHIP_SCAN_REFINE=0 in the environment: never). Counted
  * only while kmahip_scan_set_stats is on; read it before another stage is launched on the workspace. */
 int kmahip_ws_scan_diag_replaced(kmahip_ws *ws, void *stream, unsigned long long *out);
+/* The queue round of the last scan launch: out[0] the k-mer starts that the lanes of the LDS tiers left to be looked up one by one
+ * (behind a base off the diagonal, a miss or a cut walk), out[1] the rounds -- one per workgroup's group of strand items and pass of 136
+ * starts -- that had any. Counted only while kmahip_scan_set_stats is on; read it before another stage is launched on the workspace. */
+int kmahip_ws_scan_queue_counts(kmahip_ws *ws, void *stream, unsigned long long out[2]);
 /* Stage 3a's device-wide queues after the last alignment launch on the workspace (the register-only route, which hands its DP
  * problems of 2..63 query columns to four class queues that one kernel sweeps): out[0..3] entries of the classes of 33..63,
  * 17..32, 9..16 and 2..8 columns, out[4] tasks that waited for queued problems (the last result to arrive finishes such a task),

@@ -806,6 +806,33 @@ class KmaHipDB:
         _check(lib().kmahip_ws_scan_diag_replaced(self.ws, C.c_void_p(stream or 0), C.byref(out)))
         return int(out.value)
 
+    def get_scan_queue_counts(self, stream=None):
+        """(k-mer starts left to the queue round, rounds that had any) of the last scan launch (counted with set_stats(True))"""
+        out = (C.c_ulonglong * 2)()
+        L = lib()
+        L.kmahip_ws_scan_queue_counts.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]
+        _check(L.kmahip_ws_scan_queue_counts(self.ws, C.c_void_p(stream or 0), out))
+        return int(out[0]), int(out[1])
+
+    def list_table_log2(self) -> int:
+        """log2 of the list table's bucket count, 0: the database was opened without one"""
+        L = lib()
+        L.kmahip_db_list_table_log2.argtypes = [C.c_void_p]
+        L.kmahip_db_list_table_log2.restype = C.c_int
+        return int(L.kmahip_db_list_table_log2(self.h))
+
+    def test_list_probe(self, keys):
+        """kmahip_test_list_probe (a test hook): for every 32-bit key (the list table's answer, the list offset by way of the probe
+        table's position), 0xFFFFFFFF = not in the index -> two uint32 arrays"""
+        k = np.ascontiguousarray(keys, np.uint32)
+        assert k.ndim == 1
+        out_list, out_via_pos = np.zeros(len(k), np.uint32), np.zeros(len(k), np.uint32)
+        L = lib()
+        L.kmahip_test_list_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.kmahip_test_list_probe.restype = C.c_int
+        _check(L.kmahip_test_list_probe(self.h, _p(k), len(k), _p(out_list), _p(out_via_pos)))
+        return out_list, out_via_pos
+
     def get_align_queue_counts(self, stream=None) -> dict:
         """stage 3a's class queues after the last alignment launch: entries per class, pending tasks, hand-ons over the queues"""
         out = (C.c_ulonglong * 6)()

@@ -142,6 +142,16 @@ extern "C" int kmahip_ws_scan_diag_replaced(kmahip_ws *ws, void *stream, unsigne
 	return KMAHIP_OK;
 }
 
+// the queue round of the last scan launch: k-mer starts left to it, and the rounds that had any (counted only with the statistics on)
+extern "C" int kmahip_ws_scan_queue_counts(kmahip_ws *ws, void *stream, unsigned long long out[2]) {
+	if(!ws || !out || !ws->counters) return KMAHIP_EINVAL;
+	unsigned long long c[KMAHIP_N_COUNTERS];
+	HIP_TRY(hipMemcpyAsync(c, ws->counters, sizeof c, hipMemcpyDeviceToHost, (hipStream_t) stream));
+	HIP_TRY(hipStreamSynchronize((hipStream_t) stream));
+	out[0] = c[KMAHIP_C_QENT]; out[1] = c[KMAHIP_C_QWG];
+	return KMAHIP_OK;
+}
+
 // stage 3a's class queues after the last alignment launch: entries of the classes wide (33..63 columns), mid (17..32), narrow (9..16)
 // and tiny (2..8), the tasks left pending on them, and the hand-ons over the queues
 extern "C" int kmahip_ws_align_queue_counts(kmahip_ws *ws, void *stream, unsigned long long out[6]) {

@@ -97,8 +97,10 @@ __global__ __launch_bounds__(256) void table_fill_kernel(unsigned long long *slo
 	if(i < n_slots) slots[i] = (unsigned long long) KMAHIP_EMPTY_VI << 32;
 }
 
+// mark_passed (the list table): a lane that leaves a full bucket sets KMAHIP_LTAB_PASSED in the bucket's fourth value -- that slot is
+// taken by then, no compare-and-swap changes it again, and its list offset lies below the bit.
 __global__ __launch_bounds__(256) void table_insert_kernel(const uint32_t *keys, const uint32_t *vidx, int64_t n, unsigned long long *slots, uint32_t nb_log2,
-                                                           uint32_t *kbits, uint32_t kbits_shift) {
+                                                           uint32_t *kbits, uint32_t kbits_shift, int mark_passed) {
 	const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
 	if(i >= n) return;
 	const uint32_t key = keys[i], nbm = (1u << nb_log2) - 1u;
@@ -111,6 +113,7 @@ __global__ __launch_bounds__(256) void table_insert_kernel(const uint32_t *keys,
 	for(;;) {
 		unsigned long long *s = slots + (size_t) b * KMAHIP_BUCKET_SLOTS;
 		for(int j = 0; j < KMAHIP_BUCKET_SLOTS; ++j) if(atomicCAS(&s[j], empty, mine) == empty) return;
+		if(mark_passed) atomicOr(reinterpret_cast<uint32_t *>(&s[KMAHIP_BUCKET_SLOTS - 1]) + 1, KMAHIP_LTAB_PASSED);
 		b = (b + 1u) & nbm;
 	}
 }
@@ -335,8 +338,31 @@ static int db_open(const char *prefix, bool decon, kmahip_db **out) {
 		if(!bad) {
 			hipLaunchKernelGGL(table_fill_kernel, dim3((unsigned) ((n_slots + 255) / 256)), dim3(256), 0, 0, (unsigned long long *) d_slots, (int64_t) n_slots);
 			if(n) hipLaunchKernelGGL(table_insert_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, d_keys, d_vidx, (int64_t) n, (unsigned long long *) d_slots,
-			                         nb_log2, d_kbits, 32 - kbits_log2);
+			                         nb_log2, d_kbits, 32 - kbits_log2, 0);
 			bad = hipDeviceSynchronize() != hipSuccess;
+		}
+		// The list table (DevDB::lslots), from the same pairs: twice the buckets (KMAHIP_LTAB_SHIFT=0: as many), the list offset as the
+		// value for good, the passed flags set while it fills. KMAHIP_SCAN_LTAB=0: none. Nor when an offset could reach the flag's bit,
+		// and when the memory is not there the database opens without it: every kernel then looks a list up by probe() and vs_id.
+		bool want_ltab = !bad && n > 0 && v_index < 0x7FFFFFFFull;
+		if(const char *e = getenv("KMAHIP_SCAN_LTAB")) if(!atoi(e)) want_ltab = false;
+		if(want_ltab) {
+			uint32_t lb_log2 = nb_log2 + 1;
+			if(const char *e = getenv("KMAHIP_LTAB_SHIFT")) if(!atoi(e)) lb_log2 = nb_log2;
+			if(lb_log2 <= 31) {
+				const size_t l_slots = ((size_t) 1 << lb_log2) * KMAHIP_BUCKET_SLOTS;
+				void *d_l = nullptr;
+				if(hipMalloc(&d_l, l_slots * sizeof(uint2)) != hipSuccess) (void) hipGetLastError();
+				else {
+					db->allocs.push_back(d_l);
+					hipLaunchKernelGGL(table_fill_kernel, dim3((unsigned) ((l_slots + 255) / 256)), dim3(256), 0, 0, (unsigned long long *) d_l, (int64_t) l_slots);
+					hipLaunchKernelGGL(table_insert_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, d_keys, d_vidx, (int64_t) n, (unsigned long long *) d_l,
+					                   lb_log2, (uint32_t *) nullptr, 0u, 1);
+					bad = hipDeviceSynchronize() != hipSuccess;
+					d.lslots = (const uint2 *) d_l; d.lb_log2 = lb_log2;
+					db->info.total_bytes += l_slots * sizeof(uint2);
+				}
+			}
 		}
 		(void) hipFree((void *) d_keys); (void) hipFree((void *) d_vidx);
 		if(bad) { kmahip_db_close(db); kmahip_set_error("building the probe table failed: %s", hipGetErrorString(hipGetLastError())); return KMAHIP_EDEVICE; }

@@ -14,6 +14,9 @@
 #define KMAHIP_C_NACT 8
 #define KMAHIP_C_NREC 21
 #define KMAHIP_C_NREPL 22      // records whose diagonal the prefilter replaced by a better one (counted with the statistics on)
+// the scan's queue (counted with the statistics on): k-mer starts its lanes left to the queue round, and the (group, pass) rounds that had any
+#define KMAHIP_C_QENT 30
+#define KMAHIP_C_QWG 31
 // stage 3a's class queues (align.hip, api.hip): [+0..3] entries of the classes wide, narrow, tiny, mid; [+4] pending
 // tasks; [+5] hand-ons over the queues (tasks punted behind a queued problem, entries that found no room)
 #define KMAHIP_C_ADQ 24
@@ -80,7 +83,18 @@ struct DevDB {
 	// for that id (tlen, cat_off, tseq_off, tpos_*, tmeta all end at DB_size - 1): stage 2 scores it by id alone and takes it out of
 	// every list it hands on, and every entry point that would look a listed template up refuses such a database
 	uint32_t decon;
+	// The list table: a second probe table over the same k-mers whose value is the k-mer's value-list OFFSET (what vs_id holds at the
+	// position `slots` answers with), for the lookups that want nothing but the list: one 32-byte gather where probe() + vs_id[] are
+	// two dependent ones. Same hash, same buckets of four; (1 << lb_log2) buckets, twice the probe table's unless KMAHIP_LTAB_SHIFT=0.
+	// Bit 31 of a bucket's fourth value (KMAHIP_LTAB_PASSED) is set when an insertion went past the (full) bucket, so a lookup of an
+	// absent key ends at the first bucket that is not full OR that no insertion passed; list offsets stay below 2^31 - 1 (else no
+	// table is built). NULL: none was built (KMAHIP_SCAN_LTAB=0, no memory, offsets too large) or the launch switched it off.
+	const uint2 *lslots;
+	uint32_t lb_log2;
+	uint32_t lpass;               // OR-ed to a full bucket's fourth value before its flag is looked at: 0, or KMAHIP_LTAB_PASSED when the
+	                              // flag is to be ignored (KMAHIP_LTAB_FLAG=0: a miss ends at a bucket that is not full, as in probe())
 };
+#define KMAHIP_LTAB_PASSED 0x80000000u
 
 struct kmahip_db {
 	DevDB dev;                    // device pointers
@@ -112,7 +126,8 @@ struct kmahip_ws {
 	int mem_scale;            // MEM slots per (read, template) = the usual 64 (reads up to 1 kb) x this; raised by the runs when a read
 	                          // full of repeats carries more (KMAHIP_ST_SEED_MEMS, KMAHIP_ST_TRACE_MEMS), 0 = 1
 	// counters (KMAHIP_N_COUNTERS): [0] pool top, [1] status, [2] n_overflow, [3] probes, [4] value elems, [5] active strands,
-	// [6] hash probes, [7] pair pool top, [8] live strand items on the bare list, [9] prefilter probes, [21] records, [22] replaced diagonals, [24..29] stage 3a's class queues (KMAHIP_C_ADQ)
+	// [6] hash probes, [7] pair pool top, [8] live strand items on the bare list, [9] prefilter probes, [21] records, [22] replaced diagonals, [24..29] stage 3a's class queues (KMAHIP_C_ADQ),
+	// [30] k-mer starts left to the scan's queue, [31] its rounds that had any
 	unsigned long long *counters;
 	int64_t *overflow_items;
 	int64_t *active_items;    // strand items that passed the prefilter (device-wide compaction)

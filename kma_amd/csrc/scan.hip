@@ -119,7 +119,7 @@ constexpr int64_t DIAG_BIAS = 1ll << 20, DIAG_NONE = 0x7FFFFFFFll;      // (read
 constexpr int REC_WORDS = 8;
 static_assert(REC_WORDS - 2 == SW - 1, "a record carries the staged row but its last, always zero, word");
 
-enum { C_POOL = 0, C_STATUS = 1, C_NOVER = 2, C_PROBES = 3, C_VALS = 4, C_ACTIVE = 5, C_HASH = 6, C_PPOOL = 7, C_NACT = KMAHIP_C_NACT, C_PREF = 9, C_NOVER2 = 10, C_NREC = KMAHIP_C_NREC, C_NREPL = KMAHIP_C_NREPL, N_COUNTERS = KMAHIP_N_COUNTERS };
+enum { C_POOL = 0, C_STATUS = 1, C_NOVER = 2, C_PROBES = 3, C_VALS = 4, C_ACTIVE = 5, C_HASH = 6, C_PPOOL = 7, C_NACT = KMAHIP_C_NACT, C_PREF = 9, C_NOVER2 = 10, C_NREC = KMAHIP_C_NREC, C_NREPL = KMAHIP_C_NREPL, C_QENT = KMAHIP_C_QENT, C_QWG = KMAHIP_C_QWG, N_COUNTERS = KMAHIP_N_COUNTERS };
 
 // two probes whose home buckets travel together (used after a miss: the k-mer starts behind a mismatch miss in a row)
 __device__ __forceinline__ void probe2(const DevDB &db, uint32_t key1, uint32_t key2, uint32_t &r1, uint32_t &r2) {
@@ -165,6 +165,40 @@ __device__ __forceinline__ uint32_t probe(const DevDB &db, uint32_t key) {
 		if(c.w == KMAHIP_EMPTY_VI) return MISS; // bucket not full: the key cannot be further on
 		b = (b + 1u) & nbm;
 	}
+}
+
+// the value-list offset of a k-mer from the list table (DevDB::lslots != NULL): what vs_id[probe(db, key)] gives, in ONE gather. A
+// miss ends at the first bucket that is not full or that no insertion went past (the flag in its fourth value).
+// `pass` is OR-ed to a full bucket's fourth value before the flag is looked at (KMAHIP_LTAB_PASSED: go on past every full bucket) and
+// `vmask` takes the flag out of a fourth value that is the answer: with both all ones this is probe() on a table without flags.
+__device__ __forceinline__ uint32_t probe_flagged(const uint2 *slots, uint32_t log2, uint32_t pass, uint32_t vmask, uint32_t key) {
+	const uint32_t sh = 32u - log2;
+	const uint32_t nbm = (1u << log2) - 1u;
+	uint32_t b = (key * 0x9E3779B1u) >> sh;
+	for(;;) {
+		const uint4 *p = reinterpret_cast<const uint4 *>(slots + (size_t) b * KMAHIP_BUCKET_SLOTS);
+		const uint4 a = p[0], c = p[1];
+		if(a.x == key && a.y != KMAHIP_EMPTY_VI) return a.y;
+		if(a.z == key && a.w != KMAHIP_EMPTY_VI) return a.w;
+		if(c.x == key && c.y != KMAHIP_EMPTY_VI) return c.y;
+		if(c.w == KMAHIP_EMPTY_VI) return MISS; // bucket not full: the key cannot be further on
+		if(c.z == key) return c.w & vmask;
+		if(!((c.w | pass) & KMAHIP_LTAB_PASSED)) return MISS; // full, but no insertion went past it
+		b = (b + 1u) & nbm;
+	}
+}
+
+__device__ __forceinline__ uint32_t probe_list(const DevDB &db, uint32_t key) {
+	return probe_flagged(db.lslots, db.lb_log2, db.lpass, ~KMAHIP_LTAB_PASSED, key);
+}
+
+// the list of a k-mer start that wants nothing else of the k-mer: by the list table where there is one, else by the probe table and
+// vs_id (ONE probe loop in the code for both: the choice is a handful of uniform values)
+__device__ __forceinline__ uint32_t lookup_list(const DevDB &db, uint32_t key) {
+	const bool lt = db.lslots != nullptr;
+	const uint32_t r = probe_flagged(lt ? db.lslots : db.slots, lt ? db.lb_log2 : db.nb_log2, lt ? db.lpass : KMAHIP_LTAB_PASSED,
+	                                 lt ? ~KMAHIP_LTAB_PASSED : ~0u, key);
+	return lt || r == MISS ? r : db.vs_id[r];
 }
 
 // reverse complement of a k-mer held in the low 2k bits
@@ -745,14 +779,14 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 				const uint64_t *wsrc = &w_lds[g * SW];
 				const int w = (p >> 5) - (staged_once ? 0 : (c0 >> 5));
 				const uint64_t km = kmer_from(wsrc[w], wsrc[w + 1], p, k);
-				uint32_t gp;
+				// (the list is all a queued start wants of its k-mer: one gather into the list table, not probe() and then vs_id)
+				uint32_t vi;
 #ifdef KMAHIP_DIAG
-				if(A.ablate & 2) gp = MISS; else
+				if(A.ablate & 2) vi = MISS; else
 #endif
-				gp = probe(db, (uint32_t) km);
+				vi = lookup_list(db, (uint32_t) km);
 				++nprobe; ++nres;
-				if(gp == MISS) return;
-				const uint32_t vi = db.vs_id[gp];
+				if(vi == MISS) return;
 				if(MODE) atomicAdd(&s_hits[g], 1);
 #ifdef KMAHIP_DIAG
 				if(A.ablate & 1) return;
@@ -944,6 +978,8 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 				// the queue: every entry one k-mer start (item, position in the pass), one probe each
 				const uint32_t qn = min(s_qn, (uint32_t) QCAP);
 				const int q_iters = (int) ((qn + STHREADS - 1) / STHREADS);
+				// (the starts left to this round, the lanes' own included, and the rounds that had any)
+				if(STATS && tid == 0 && s_qn) { atomicAdd(&A.counters[C_QENT], (unsigned long long) s_qn); atomicAdd(&A.counters[C_QWG], 1ull); }
 				// (a lane that kept its k-mer starts takes them one by one behind the queue's rounds)
 				for(int it = 0; it < q_iters || own; ++it) {
 					uint32_t v = 0xFFFFu;
@@ -1263,8 +1299,7 @@ __global__ __launch_bounds__(64) void scan_dense_kernel(const ScanArgs A) {
 					const int w = q >> 5;
 					uint64_t km = kmer_from(rs[w], rs[w + 1], q, k);
 					if(strand) km = revcomp_kmer(km, k);
-					vi = probe(db, (uint32_t) km);
-					if(vi != MISS) vi = db.vs_id[vi];
+					vi = lookup_list(db, (uint32_t) km);
 				}
 				s_vi[x] = vi;
 			}
@@ -1575,8 +1610,7 @@ __global__ __launch_bounds__(64) void scan_dense_count_kernel(const ScanArgs A) 
 					const int w = q >> 5;
 					uint64_t km = kmer_from(rs[w], rs[w + 1], q, k);
 					if(strand) km = revcomp_kmer(km, k);
-					vi = probe(db, (uint32_t) km);
-					if(vi != MISS) vi = db.vs_id[vi];
+					vi = lookup_list(db, (uint32_t) km);
 				}
 				s_vi[x] = vi;
 			}
@@ -2359,6 +2393,15 @@ __global__ __launch_bounds__(THREADS, 4) void chain_anchor_kernel(const AnchorAr
 		A.pool[off + i] = a;
 	}
 }
+
+// test hook: probe_list against vs_id[probe()], one lane per key
+__global__ __launch_bounds__(256) void test_list_probe_kernel(const DevDB db, const uint32_t *keys, int64_t n, uint32_t *out_list, uint32_t *out_via_pos) {
+	for(int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t) gridDim.x * blockDim.x) {
+		const uint32_t gp = probe(db, keys[i]);
+		out_via_pos[i] = gp == MISS ? MISS : db.vs_id[gp];
+		out_list[i] = probe_list(db, keys[i]);
+	}
+}
 } // namespace
 
 
@@ -2368,6 +2411,16 @@ static int64_t diag_cat_bases(const kmahip_db *db) {
 	if(const char *e = getenv("KMAHIP_SCAN_DIAG")) if(!atoi(e)) return 0;
 	const int64_t total = db->h_cat_off.empty() ? 0 : db->h_cat_off.back();
 	return total > 0 && total < (1ll << 30) ? total : 0;
+}
+
+// The database as the scan's kernels get it. Both switches are read per launch: KMAHIP_SCAN_LTAB=0 hands them no list table (every
+// list by probe() and vs_id), KMAHIP_LTAB_FLAG=0 has a lookup of the list table continue past every full bucket as probe() does.
+static DevDB scan_dev_db(const kmahip_db *db) {
+	DevDB d = db->dev;
+	d.lpass = 0;
+	if(const char *e = getenv("KMAHIP_SCAN_LTAB")) if(!atoi(e)) d.lslots = nullptr;
+	if(const char *e = getenv("KMAHIP_LTAB_FLAG")) if(!atoi(e)) d.lpass = KMAHIP_LTAB_PASSED;
+	return d;
 }
 
 // the prefilter checks and repairs the diagonal of a record (KMAHIP_SCAN_REFINE=0: it files the first hit's, as found)
@@ -2491,7 +2544,7 @@ int kmahip_launch_scan_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	int rc = ws_reserve(ws, n > 0 ? n : 1);
 	if(rc) return rc;
 	ScanArgs A;
-	A.db = db->dev;
+	A.db = scan_dev_db(db);
 	A.n_reads = n; A.seq = reads->seq; A.seq_off = reads->seq_off; A.len = reads->len; A.N = reads->N; A.N_off = reads->N_off;
 	A.M = p->rw.M; A.MM = p->rw.MM; A.U = p->rw.U; A.W1 = p->rw.W1; A.exhaustive = p->exhaustive;
 	A.item_score = ws->item_score; A.item_n = ws->item_n; A.item_off = ws->item_off;
@@ -2619,7 +2672,7 @@ int kmahip_launch_scan_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 		ws->pe_cap = ws->pool_cap;
 	}
 	ScanArgs A;
-	A.db = db->dev;
+	A.db = scan_dev_db(db);
 	A.n_reads = n; A.seq = reads->seq; A.seq_off = reads->seq_off; A.len = reads->len; A.N = reads->N; A.N_off = reads->N_off;
 	A.M = p->rw.M; A.MM = p->rw.MM; A.U = p->rw.U; A.W1 = p->rw.W1; A.exhaustive = p->exhaustive;
 	A.item_score = ws->item_score; A.item_n = ws->item_n; A.item_off = ws->item_off;
@@ -2676,5 +2729,28 @@ int kmahip_launch_scan_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	hipLaunchKernelGGL(rec_write_kernel, dim3(cgrid), dim3(CB), 0, stream, P.r_n, P.r_off, ws->ppool, n, ws->blk_sums,
 	                   out->R_off, out->T, out->T_cap, ws->counters);
 	HIP_TRY(hipGetLastError());
+	return KMAHIP_OK;
+}
+
+extern "C" int kmahip_db_list_table_log2(const kmahip_db *db) { return db && db->dev.lslots ? (int) db->dev.lb_log2 : 0; }
+
+extern "C" int kmahip_test_list_probe(kmahip_db *db, const uint32_t *keys, int64_t n, uint32_t *out_list, uint32_t *out_via_pos) {
+	if(!db || n < 0 || (n && (!keys || !out_list || !out_via_pos))) { kmahip_set_error("kmahip_test_list_probe: bad argument"); return KMAHIP_EINVAL; }
+	DevDB d = scan_dev_db(db);
+	d.lslots = db->dev.lslots;          // (the hook is about the table: KMAHIP_SCAN_LTAB=0 per launch does not hide it)
+	if(!d.lslots) { kmahip_set_error("kmahip_test_list_probe: the database has no list table"); return KMAHIP_EINVAL; }
+	if(!n) return KMAHIP_OK;
+	uint32_t *dk = nullptr;
+	if(hipMalloc((void **) &dk, (size_t) n * 12) != hipSuccess) { kmahip_set_error("kmahip_test_list_probe: %lld keys do not fit", (long long) n); return KMAHIP_ENOMEM; }
+	hipError_t e = hipMemcpy(dk, keys, (size_t) n * 4, hipMemcpyHostToDevice);
+	if(e == hipSuccess) {
+		const int64_t blocks = (n + 255) / 256;
+		hipLaunchKernelGGL(test_list_probe_kernel, dim3((unsigned) (blocks < 65536 ? blocks : 65536)), dim3(256), 0, 0, d, dk, n, dk + n, dk + 2 * n);
+		e = hipGetLastError();
+	}
+	if(e == hipSuccess) e = hipMemcpy(out_list, dk + n, (size_t) n * 4, hipMemcpyDeviceToHost);
+	if(e == hipSuccess) e = hipMemcpy(out_via_pos, dk + 2 * n, (size_t) n * 4, hipMemcpyDeviceToHost);
+	(void) hipFree(dk);
+	if(e != hipSuccess) { kmahip_set_error("kmahip_test_list_probe: %s", hipGetErrorString(e)); return KMAHIP_EDEVICE; }
 	return KMAHIP_OK;
 }
