@@ -1177,6 +1177,52 @@ int kmahip_sparse_set_timing(kmahip_sparse *sdb, int on);
 int kmahip_sparse_get_timing(kmahip_sparse *sdb, int kernel, double *total_ms, int64_t *launches);
 int kmahip_sparse_set_noadd(kmahip_sparse *sdb, int on);
 
+/* ---- template distances (`kma dist`, dist.c): for every pair of templates the k-mers they share, written as PHYLIP matrices under
+ * thirteen measures. A pipeline of its own (tdist.hip) that reads nothing but <prefix>.comp.b and <prefix>.name and never looks at a
+ * k-mer key, so it serves every form of index the reference writes: hashed and direct-address, k up to 32, sparse / prefix indexes,
+ * minimizer and homopolymer flags -- the forms kmahip_db_open refuses included.
+ *
+ * kmahip_tdist_open reads the file as loadValues does (dist.c:38-162): the header; the direct-address array when size - 1 == mask,
+ * else the bucket array is passed over; the values, 16-bit when DB_size < 65535, else 32-bit; for the hashed form the keys are passed
+ * over (4 or 8 bytes each by mlen) and the n value indexes read; then the optional kmersize / flag. A short or inconsistent file:
+ * KMAHIP_EFORMAT with `Wrong format of DB.` (the reference's words) in kmahip_last_error; so is a list that leaves the value array or
+ * holds a template outside 1 .. DB_size - 1 (the reference walks them unchecked). Offsets beyond 32 bits are not served.
+ * kmahip_tdist_open_lists is the same object over explicit arrays: offsets[n_kmers] are the per-k-mer entries (1 = none, as in the
+ * file), values the [length, ids ...] lists with ids 1 .. n_templates, value_bytes 2 or 4; its templates are named by their ids. */
+typedef struct kmahip_tdist kmahip_tdist;
+typedef struct kmahip_tdist_info {
+	uint32_t DB_size, mlen, kmersize, flag, prefix_len, direct /* 1: the direct-address form */, value_bytes, form /* of the last count: 0 rows, 1 pairs */;
+	uint64_t n_kmers, n_lists /* distinct value lists */, n_values, name_bytes, total_bytes;
+} kmahip_tdist_info;
+int kmahip_tdist_open(const char *prefix, kmahip_tdist **out);
+int kmahip_tdist_open_lists(uint32_t n_templates, uint64_t n_kmers, const uint32_t *offsets, const void *values, int value_bytes, uint64_t n_values,
+                            kmahip_tdist **out);
+void kmahip_tdist_close(kmahip_tdist *td);
+int kmahip_tdist_get_info(const kmahip_tdist *td, kmahip_tdist_info *info);
+/* the name of row t (0 <= t < DB_size - 1) */
+int kmahip_tdist_name(const kmahip_tdist *td, uint32_t t, const char **name);
+/* kmerSimilarity (dist.c:171-225): the per-k-mer entries are walked, entries equal to 1 passed over, the walk ends behind the n-th
+ * live one; a list counts once per k-mer that points to it. N[t] = k-mers whose list holds template t + 1, D[hi][lo] (lower
+ * triangle, hi > lo) = k-mers whose list holds both; int32 like the reference's int. A pair is (max, min) of the two ids.
+ * KMAHIP_TDIST_FORM = rows | pairs chooses between the two forms of the pair sums (both give the same arrays). */
+int kmahip_tdist_count(kmahip_tdist *td);
+/* N (DB_size - 1 entries, may be NULL) and rows row_lo <= hi < row_hi of the triangle, row hi holding hi cells (D may be NULL) */
+int kmahip_tdist_get_counts(kmahip_tdist *td, int32_t *N, int32_t *D, uint32_t row_lo, uint32_t row_hi);
+/* the file of runDist / threadDist (dist.c:659-875): a matrix per bit of methods in the order 1, 2, 4 ... 4096, every cell 11 bytes
+ * (`\t%10d`, `\t%10.6f`, `\t%.8f`), format & 1: names as they are (else `%-10.10s`), format & 4: a method line `# %-35s\n`; sizes as
+ * getPhySize, the 11 NUL bytes behind each matrix with strict names included. The cells are formatted on the device in chunks of
+ * KMAHIP_TDIST_CHUNK bytes (64 MiB). Where a requested measure would divide by zero -- a template with N = 0 under methods 4, 8, 256,
+ * 512, 1024, 2048, two of them under 16, 32, 64, 128, 4096 -- KMAHIP_EINVAL, the template named (the reference prints -nan there, and its
+ * chi-square dies of an integer division). */
+int kmahip_tdist_write(kmahip_tdist *td, const char *path, int methods, int format);
+/* test hook: n cells of `method` (one bit) from explicit triples, formatted on the device into 11 * n bytes */
+int kmahip_test_tdist_cells(int method, const int32_t *Ni, const int32_t *Nj, const int32_t *D, int64_t n, char *out);
+/* event pairs around the kernels; get_timing sums them per kernel (0 tdist_mult_kernel, 1 the inverted index with its scan, 2
+ * tdist_rows_kernel, 3 tdist_pairs_kernel, 4 the write kernels) and resets */
+#define KMAHIP_TDIST_KERNELS 5
+int kmahip_tdist_set_timing(kmahip_tdist *td, int on);
+int kmahip_tdist_get_timing(kmahip_tdist *td, int kernel, double *total_ms, int64_t *launches);
+
 #ifdef __cplusplus
 }
 #endif

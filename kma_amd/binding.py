@@ -1667,3 +1667,120 @@ class SparseDB:
     def set_noadd(self, on=True):
         """timing only: the counting kernel keeps its probes and drops its adds (the counts are wrong by design)"""
         _check(lib().kmahip_sparse_set_noadd(self.h, 1 if on else 0))
+
+
+class TdistInfo(C.Structure):
+    _fields_ = [("DB_size", C.c_uint32), ("mlen", C.c_uint32), ("kmersize", C.c_uint32), ("flag", C.c_uint32), ("prefix_len", C.c_uint32),
+                ("direct", C.c_uint32), ("value_bytes", C.c_uint32), ("form", C.c_uint32),
+                ("n_kmers", C.c_uint64), ("n_lists", C.c_uint64), ("n_values", C.c_uint64), ("name_bytes", C.c_uint64), ("total_bytes", C.c_uint64)]
+
+
+def _tdist_lib():
+    L = lib()
+    if not hasattr(L, "kmahip_tdist_open"):
+        raise KmaHipError("this libkmahip.so has no template distances (kmahip_tdist_open)")
+    L.kmahip_tdist_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+    L.kmahip_tdist_open_lists.argtypes = [C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]
+    L.kmahip_tdist_close.argtypes = [C.c_void_p]
+    L.kmahip_tdist_close.restype = None
+    L.kmahip_tdist_get_info.argtypes = [C.c_void_p, C.POINTER(TdistInfo)]
+    L.kmahip_tdist_name.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_char_p)]
+    L.kmahip_tdist_count.argtypes = [C.c_void_p]
+    L.kmahip_tdist_get_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+    L.kmahip_tdist_write.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int]
+    L.kmahip_tdist_set_timing.argtypes = [C.c_void_p, C.c_int]
+    L.kmahip_tdist_get_timing.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    L.kmahip_test_tdist_cells.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    return L
+
+
+def tdist_cells(method, Ni, Nj, D):
+    """kmahip_test_tdist_cells (a test hook): the cells of one distance measure (`kma dist -d method`) for explicit triples, formatted
+    on the device -> list of 11-byte strings"""
+    a, b, d = (np.ascontiguousarray(x, np.int32) for x in (Ni, Nj, D))
+    assert a.shape == b.shape == d.shape and a.ndim == 1
+    out = np.zeros(11 * max(1, len(a)), np.uint8)
+    _check(_tdist_lib().kmahip_test_tdist_cells(int(method), _p(a), _p(b), _p(d), len(a), _p(out)))
+    raw = out.tobytes()
+    return [raw[11 * i:11 * i + 11] for i in range(len(a))]
+
+
+class TemplateDist:
+    """Template distances (`kma dist`; kmahip_tdist_*): the value lists of <prefix>.comp.b (any form of index the reference writes)
+    resident in HBM. count() counts, for every pair of templates, the k-mers they share; write() formats the PHYLIP matrices."""
+
+    def __init__(self, prefix=None, device: int = 0, _handle=None):
+        L = _tdist_lib()
+        self.h = C.c_void_p()
+        if _handle is not None:
+            self.h = _handle
+        else:
+            _check(L.kmahip_init(device))
+            _check(L.kmahip_tdist_open(os.fsencode(prefix), C.byref(self.h)))
+        self.prefix = prefix
+        self.info = TdistInfo()
+        _check(L.kmahip_tdist_get_info(self.h, C.byref(self.info)))
+        self.n = int(self.info.DB_size) - 1
+
+    @classmethod
+    def from_lists(cls, n_templates, offsets, values, value_bytes=2, device: int = 0):
+        """the same object over explicit arrays: offsets[k] = where k-mer k's list stands in values (1 = none), values the lists as
+        [length, ids ...] with ids 1 .. n_templates, stored 16- or 32-bit; the templates are named by their ids"""
+        L = _tdist_lib()
+        off = np.ascontiguousarray(offsets, np.uint32)
+        val = np.ascontiguousarray(values, np.uint16 if value_bytes == 2 else np.uint32)
+        h = C.c_void_p()
+        _check(L.kmahip_init(device))
+        _check(L.kmahip_tdist_open_lists(int(n_templates), len(off), _p(off) if len(off) else None, _p(val) if len(val) else None, int(value_bytes), len(val), C.byref(h)))
+        return cls(_handle=h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().kmahip_tdist_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def name(self, t):
+        nm = C.c_char_p()
+        _check(lib().kmahip_tdist_name(self.h, int(t), C.byref(nm)))
+        return nm.value
+
+    def count(self):
+        """kmerSimilarity on the device (KMAHIP_TDIST_FORM = rows | pairs) -> the form used"""
+        L = lib()
+        _check(L.kmahip_tdist_count(self.h))
+        _check(L.kmahip_tdist_get_info(self.h, C.byref(self.info)))
+        return "pairs" if self.info.form else "rows"
+
+    def counts(self, row_lo=0, row_hi=None):
+        """-> (N int32[n], the rows row_lo <= hi < row_hi of the lower triangle, row hi holding hi cells, one after the other)"""
+        row_hi = self.n if row_hi is None else int(row_hi)
+        row_lo = int(row_lo)
+        cells = row_hi * max(0, row_hi - 1) // 2 - row_lo * max(0, row_lo - 1) // 2
+        N, D = np.zeros(max(1, self.n), np.int32), np.zeros(max(1, cells), np.int32)
+        _check(lib().kmahip_tdist_get_counts(self.h, _p(N), _p(D), row_lo, row_hi))
+        return N[:self.n], D[:cells]
+
+    def write(self, path, methods=1, fmt=1):
+        """the file of `kma dist -d methods -f fmt`"""
+        _check(lib().kmahip_tdist_write(self.h, os.fsencode(path), int(methods), int(fmt)))
+
+    def set_timing(self, on=True):
+        _check(lib().kmahip_tdist_set_timing(self.h, 1 if on else 0))
+
+    def get_timing(self, kernel):
+        """(milliseconds, launches) of kernel 0 mult, 1 inverted index, 2 rows, 3 pairs, 4 write since the last call"""
+        ms, n = C.c_double(), C.c_int64()
+        _check(lib().kmahip_tdist_get_timing(self.h, int(kernel), C.byref(ms), C.byref(n)))
+        return ms.value, n.value
