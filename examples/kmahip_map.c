@@ -125,6 +125,7 @@ typedef struct stream_job {
 	int s1dev, device, b_dev;
 	kmahip_ingest_dev *dev;
 	long long dev_records, dev_handed;
+	kmahip_qc *qc;                            /* -qc: every reader of the run feeds it, one after the other */
 } stream_job;
 /* the reader of one input file (or couple of mate files): the device reader where -s1dev asks for it and the file is one it covers
  * (plain FASTQ; KMAHIP_EFORMAT from its open, before it touches the device, says it is not), the host reader otherwise */
@@ -134,11 +135,13 @@ static int stream_open(stream_job *j, const char *p1, const char *p2) {
 	if(j->s1dev && !(p2 && !p2[0])) {
 		int rc = kmahip_init(j->device);          /* (this thread's device; the main thread brings the runtime up at the same time) */
 		if(!rc) rc = kmahip_ingest_dev_open(p1, p2, &j->trim, &j->dev);
+		if(!rc && j->qc) rc = kmahip_ingest_dev_set_qc(j->dev, j->qc);
 		if(rc != KMAHIP_EFORMAT) return rc;
 		j->dev = NULL;
 	}
 	int rc = kmahip_ingest_open_part(p1, p2, &j->trim, 0, 1, &j->ing, &whole);
 	if(!rc && j->batch_bases > 0) rc = kmahip_ingest_set_batch_bases(j->ing, j->batch_bases);
+	if(!rc && j->qc) rc = kmahip_ingest_set_qc(j->ing, j->qc);
 	return rc;
 }
 static void stream_close(stream_job *j) {
@@ -217,6 +220,7 @@ static void usage(void) {
 	fprintf(stderr, "usage: kmahip_map (-i reads.fq[.gz] | -ipe r1.fq[.gz] r2.fq[.gz] [-apm p|u] | -int interleaved.fq[.gz] [-apm p|u]) -t_db <index prefix> -o <output prefix> [-1t1] [-Mt1 <template>] [-bcNano] [-bc90] [-bc <support>] [-bcg] [-ref_fsa [n]] [-dense]\n"
 	                "       [-t threads] [-nc] [-na] [-nf] [-mf fragments] [-ml len] [-xl len] [-mp phred] [-mi phred] [-eq q] [-mq q] [-ts bases] [-mrs f] [-mrc f] [-mct f]\n"
 	                "       [-e evalue] [-bcd depth] [-ID id] [-md depth] [-ex_mode] [-gpus N] [-s1dev] [-sam n] [-ef [n]] [-matrix] [-vcf [n]] [-proxi f] [-ill] [-ca] [-ck] [-mint2] [-mint3] [-ConClave n] [-deCon]\n"
+	                "       [-qc] [-5p n] [-3p n]\n"
 	                "       [-reward n] [-gapopen n] [-gapextend n] [-localopen n] [-Npenalty n] [-per n] [-transition n] [-transversion n] [-penalty n] [-cge]\n"
 	                "       (-s1dev, like -gpus not an option of kma: stage 1 of plain FASTQ input on the device; one rank, -1t1 only; its batches close at a quarter\n"
 	                "        of a gigabase of their own accord, KMAHIP_MAP_BATCH_BASES does not apply to them)\n"
@@ -237,6 +241,9 @@ static void usage(void) {
 	                "        the counts (-ss: by score q, coverage c or depth d) and named one by one; only <output prefix>.spa is written. -i takes a list of files,\n"
 	                "        -ipe / -int files are read as single-end files; -ID, -md, -e / -p, -t and the trimming options apply, the other mapping options are\n"
 	                "        taken and ignored; not with -deCon, -gpus N, -s1dev or -o --)\n"
+	                "       (-qc: the QC report <output prefix>.json (print_QCstat): counts, GC content, N50, E(Q), a quality and a length histogram, summed by\n"
+	                "        stage 1 while it trims -- on the device with -s1dev; with it a read is held against -ml by its length less its N's, like kma's. In\n"
+	                "        every run of one rank, -Sparse included; FASTQ input only; not with -ml below 1, a second -qc, -gpus N or -i --)\n"
 	                "(the options of kma 1.5.1 this path implements; -apm takes p or u; everything else is refused)\n");
 }
 
@@ -313,8 +320,10 @@ static int launch_ranks(int gpus, char **argv) {
 /* `kma -Sparse` (kma.c:1483-1538 run_input_sparse, :1607-1612 save_kmers_sparse_batch): every input file is read as single-end records
  * by the host's stage 1, batch by batch; a batch's k-mers are counted on the device against the sparse index (kmahip_sparse_count);
  * then the templates are ranked, named and withdrawn, and <out>.spa is written. Nothing else is written. */
-static int run_sparse(const char *prefix, const char *out, char **files, int n_files, kmahip_trim trim, double ID_t, double Depth_t, double evalue, char ss) {
+static int run_sparse(const char *prefix, const char *out, char **files, int n_files, kmahip_trim trim, double ID_t, double Depth_t, double evalue, char ss,
+                      kmahip_qc *qc, int clip5, int clip3) {
 	kmahip_sparse *sdb = NULL;
+	const kmahip_trim given = trim;          /* (the report prints the options as they were given, kma.c:1533) */
 	/* kma.c:1527-1529 and sparse.c:256-258: the end trimming is at least as strict as the masking and the average quality asked for */
 	if(trim.min_phred < trim.hardmask_q) trim.min_phred = trim.hardmask_q;
 	if(trim.min_phred < trim.min_q) trim.min_phred = trim.min_q;
@@ -325,6 +334,7 @@ static int run_sparse(const char *prefix, const char *out, char **files, int n_f
 		kmahip_ingest *ing = NULL;
 		kmahip_read_batch b;
 		int rc = kmahip_ingest_open(files[f], NULL, &trim, &ing);
+		if(!rc && qc) rc = kmahip_ingest_set_qc(ing, qc);
 		while(!rc) {
 			rc = kmahip_ingest_next(ing, batch_reads, &b);
 			if(rc || b.reads.n_reads == 0) break;
@@ -333,6 +343,14 @@ static int run_sparse(const char *prefix, const char *out, char **files, int n_f
 		if(!rc) rc = kmahip_ingest_status(ing);
 		if(ing) kmahip_ingest_close(ing);
 		if(rc) { fprintf(stderr, "kmahip_map: %s: %s\n", files[f], kmahip_last_error()); kmahip_sparse_close(sdb); return 1; }
+	}
+	if(qc) {	/* kma.c:1532-1536: the report, before the templates are ranked */
+		char *json = malloc(strlen(out) + 8);
+		if(!json) { kmahip_sparse_close(sdb); return 1; }
+		sprintf(json, "%s.json", out);
+		const int qrc = kmahip_qc_write(qc, &given, clip5, clip3, json);
+		free(json);
+		if(qrc) { fprintf(stderr, "kmahip_map: %s\n", kmahip_last_error()); kmahip_sparse_close(sdb); return 1; }
 	}
 	kmahip_sparse_opts so;
 	kmahip_sparse_default_opts(&so);
@@ -365,6 +383,7 @@ int main(int argc, char **argv) {
 	int proxi_opt = 0;                           /* -proxi / -ill given (for the refusals' wording; what counts is par.minFrac) */
 	int decon = 0;                               /* -deCon: map against <t_db>.decon.comp.b and drop what fits the contamination best */
 	int ck = 0;                                  /* -ck (kma.c:689): stage 2 counts k-mers, kmahip_ws_set_count_kmers on the run's workspace */
+	int qc_opt = 0, clip5 = 0, clip3 = 0;        /* -qc (kma.c:653-661): <out>.json; -5p / -3p, which only the report prints */
 	int sparse = 0; char ss = 'q';               /* -Sparse (kma.c:684): count k-mers, write <out>.spa only; -ss q|c|d, the order its templates are named in */
 	int base_call = 0, sig_mode = 0, ref_fsa = 0, dense = 0;      /* as kmahip_assemble_opts.caller (0-2 here) / .sig90; printconsensus.c's ref_fsa */
 	double support = 0;                          /* -bc x: the variable the reference hands updateVcf (kma.c:747, vcf.c:195) ... */
@@ -402,6 +421,9 @@ int main(int argc, char **argv) {
 		else if(!strcmp(o, "-i") || !strcmp(o, "-int") || !strcmp(o, "-ipe")) {                 /* kma.c:371-435: each takes a list of files */
 			const int pe = o[2] == 'p';
 			if(n_files) { fprintf(stderr, "kmahip_map: one of -i, -ipe and -int, once\n"); return 2; }
+			if(a + 1 < argc && !strcmp(argv[a + 1], "--")) {          /* (standard input: never served; with -qc it is refused by that name) */
+				for(int x = 1; x < argc; ++x) if(!strcmp(argv[x], "-qc")) { fprintf(stderr, "kmahip_map: -qc is not built for %s -- (reads on standard input): the report is summed over files\n", o); return 2; }
+			}
 			while(a + 1 < argc && argv[a + 1][0] != '-' && n_files < 256) {
 				list1[n_files] = argv[++a]; list2[n_files] = NULL;
 				if(pe) {
@@ -523,7 +545,8 @@ int main(int argc, char **argv) {
 		}
 		else if(!strcmp(o, "-and")) cmp_mode = 1;                                               /* kma.c:915-920 */
 		else if(!strcmp(o, "-oa")) { cmp_mode = 2; ID_t = 1e-300; Depth_t = 0.0; }               /* (ID_t = 0 there; a row needs 0 < id anyway, and 0 means "the default" to kmahip_shard_opts) */
-		else if(!strcmp(o, "-5p") || !strcmp(o, "-3p")) (void) need_int(argc, argv, &a, o);     /* parsed and handed to run_input*, where nothing reads them (runinput.c:127-368: phredStat never touches fiveClip / threeClip) */
+		else if(!strcmp(o, "-5p") || !strcmp(o, "-3p")) { const int v = (int) need_int(argc, argv, &a, o); if(o[1] == '5') clip5 = v; else clip3 = v; }     /* parsed and handed to run_input*, where nothing reads them (runinput.c:127-368: phredStat never touches fiveClip / threeClip); print_QCstat prints them */
+		else if(!strcmp(o, "-qc")) ++qc_opt;                                                    /* kma.c:653-661: a second one is the verbose form */
 		/* the scoring scheme (kma.c:821-915, 1024-1030): signs are forced like the reference's; -penalty is read and then overwritten
 		 * by the mean of -transition and -transversion below, as there (kma.c:1308) */
 		else if(!strcmp(o, "-reward")) par.rw.M = abs((int) need_int(argc, argv, &a, o));
@@ -549,6 +572,31 @@ int main(int argc, char **argv) {
 		else { fprintf(stderr, "kmahip_map: option %s is not one this program implements\n", o); usage(); return 2; }
 	}
 	if(!prefix || !input || !out) { fprintf(stderr, "kmahip_map: -i (or -ipe / -int), -t_db and -o are required\n"); usage(); return 2; }
+	kmahip_qc *qc = NULL;
+	if(qc_opt) {
+		/* the report is summed by stage 1 of one rank's run, batch by batch. Refused by name, before anything is opened or created, are
+		 * also the three places where the reference's own report breaks: FASTA input (fsastat gives update_QCstat no quality sum, and
+		 * log10(0) indexes the quality histogram), -ml below 1 (a kept read of length 0: 0 / 0) and a second -qc (rescale_ldist_v1
+		 * prints from memory it never cleared) */
+		const char *why = NULL;
+		if(qc_opt > 1) why = "a second -qc (the verbose form: the reference prints it from memory it never cleared)";
+		else if(trim.min_len < 1) why = "-ml below 1 (the reference divides by the length of a kept read)";
+		else if(gpus > 1 || getenv("KMAHIP_RANK") || getenv("RANK")) why = "-gpus N (several ranks: the sums and the order of the reads over ranks are not built)";
+		else if(getenv("KMAHIP_COMM_FORCE_RCCL") && getenv("KMAHIP_COMM_FORCE_RCCL")[0] == '1') why = "KMAHIP_COMM_FORCE_RCCL";
+		else if(getenv("KMAHIP_MAP_ONE_BATCH")) why = "KMAHIP_MAP_ONE_BATCH";
+		if(why) { fprintf(stderr, "kmahip_map: -qc is not built for %s: the QC report serves the runs of one rank on FASTQ input\n", why); return 2; }
+		kmahip_qc *probe_qc = NULL;
+		if(kmahip_qc_open(&qc) || kmahip_qc_open(&probe_qc)) { fprintf(stderr, "kmahip_map: %s\n", kmahip_last_error()); return 1; }
+		for(int f = 0; f < n_files; ++f) for(int m = 0; m < 2; ++m) {          /* (a look at every input's first bytes, by the host reader) */
+			const char *path = m ? list2[f] : list1[f];
+			kmahip_ingest *probe = NULL;
+			if(!path || kmahip_ingest_open(path, NULL, &trim, &probe)) continue;          /* (a file that cannot be read is named by the run itself) */
+			const int prc = kmahip_ingest_set_qc(probe, probe_qc);
+			kmahip_ingest_close(probe);
+			if(prc == KMAHIP_EFORMAT) { fprintf(stderr, "kmahip_map: -qc is not built for FASTA input (%s: the reference's report dies on it): the QC report serves the runs of one rank on FASTQ input\n", path); return 2; }
+		}
+		kmahip_qc_close(probe_qc);
+	}
 	if(sparse) {
 		/* a pipeline of its own (kma.c:1483-1538, 1607-1612): the mapping options its path never reads are taken and ignored, as there */
 		const char *why = NULL;
@@ -563,7 +611,7 @@ int main(int argc, char **argv) {
 		if(input2 && input2[0]) fprintf(stderr, "Paired end information is not considered in Sparse mode.\n");          /* kma.c:1514 */
 		else if(input2) fprintf(stderr, "Interleaved information is not considered in Sparse mode.\n");              /* kma.c:1525 */
 		if(threads) { char v[16]; snprintf(v, sizeof v, "%d", threads); setenv("KMAHIP_INGEST_THREADS", v, 1); }
-		return run_sparse(prefix, out, files, n, trim, ID_t, Depth_t, evalue, ss);
+		return run_sparse(prefix, out, files, n, trim, ID_t, Depth_t, evalue, ss, qc, clip5, clip3);
 	}
 	if(kmahip_set_cmp(cmp_mode)) { fprintf(stderr, "kmahip_map: %s\n", kmahip_last_error()); return 1; }
 	{	/* the substitution matrix (kma.c:1307-1328) */
@@ -741,7 +789,7 @@ int main(int argc, char **argv) {
 		memset(&sj, 0, sizeof sj);
 		sj.in1 = input; sj.in2 = reader2; sj.rc_mates = rc_mates; sj.trim = trim;
 		sj.list1 = list1; sj.list2 = list2; sj.n_files = n_files;
-		sj.s1dev = s1dev; sj.device = local;
+		sj.s1dev = s1dev; sj.device = local; sj.qc = qc;
 		sj.batch_reads = getenv("KMAHIP_MAP_BATCH") ? atoll(getenv("KMAHIP_MAP_BATCH")) : 1000000;
 		if(sj.batch_reads < 1) sj.batch_reads = 1;
 		sj.batch_bases = getenv("KMAHIP_MAP_BATCH_BASES") ? atoll(getenv("KMAHIP_MAP_BATCH_BASES")) : (256ll << 20);
@@ -818,6 +866,11 @@ int main(int argc, char **argv) {
 		}
 		pthread_join(reader, NULL);
 		if(sj.rc) { fprintf(stderr, "kmahip_map: ingest: %s\n", sj.err); finish(1); }
+		if(qc) {	/* kma.c:1573-1577: the report of everything stage 1 read */
+			char json[4096];
+			snprintf(json, sizeof json, "%s.json", out);
+			if(kmahip_qc_write(qc, &trim, clip5, clip3, json)) die("QC report");
+		}
 		const double t_mapped = now_s();
 		double ms[8];
 		int64_t n_reads = 0, n_rows = 0;

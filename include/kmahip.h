@@ -730,6 +730,63 @@ void kmahip_ingest_dev_timing(const kmahip_ingest_dev *in, double ms[3], int64_t
 int kmahip_ingest_dev_copy_out(void *host_dst, const void *dev_src, size_t bytes);
 void kmahip_ingest_dev_close(kmahip_ingest_dev *in);
 
+/* ---- the QC report (`kma ... -qc`, `kma trim -qc`) and the trimmed reads as text (`kma trim`) ------------------------------------
+ * An accumulator that the readers above feed while they trim: what init_QCstat / update_QCstat (qc.c:24-43, 85-104) keep and
+ * print_QCstat (qc.c:167-262) prints. A reader with an accumulator trims by the reference's -qc rule (phredStat with a report,
+ * runinput.c:133-136, 163, 303-312): every read goes through the summing loop whatever -eq and -mi are, and the figure held against
+ * -ml is the trimmed length less its N's (hard-masked bases included) -- so a read with len >= ml > len - ns is kept without an
+ * accumulator and dropped with one. A reader without one does exactly what it did before. */
+typedef struct kmahip_qc kmahip_qc;
+typedef struct kmahip_qc_stats {
+	uint64_t fragcount, org_fragcount;   /* S1 records kept / read, a couple counting once (runinput.c:448-452, 587-593, 712-718) */
+	uint64_t count, org_count;           /* sequences counted by update_QCstat (ml <= len - ns, per mate) / read (runinput.c:133-136) */
+	uint64_t bpcount, org_bpcount;
+	uint64_t totgc, totns;               /* C and G that were not hard-masked; N's and hard-masked bases */
+	double Eeq;                          /* sum of every counted sequence's sum of 10^(-q/10), added up in stream order */
+	int32_t maxlen, qresolution;         /* longest counted sequence; ldist bin = len >> qresolution (rescale_ldist, qc.c:50-65) */
+	int32_t phred_scale, pad_;           /* runinput.c:451, 590-592, 715-717: the last single-end file's, a paired one's once Eeq != 0 */
+	uint32_t qdist[256];                 /* bin (int) ceil(-10 * log10(sp / len)), decided by the host's log10 (qc.c:102) */
+	uint32_t ldist[512];
+} kmahip_qc_stats;
+/* init_QCstat(0) / destroy_QCstat (qc.c:24-48) */
+int kmahip_qc_open(kmahip_qc **out);
+void kmahip_qc_close(kmahip_qc *qc);
+/* Attach an accumulator to a reader, before its first _next (KMAHIP_EINVAL afterwards): from then on the reader trims by the -qc
+ * rule and feeds it (phredStat, runinput.c:127-313; the counts of run_input / _PE / _INT, :448-452, 587-593, 712-718). Readers one
+ * after the other feed one accumulator (`-i a b`; the host reader that the device reader hands odd records to takes it over by
+ * itself). Refused by name, where the reference dies (runinput.c:359-361 with qc.c:102): FASTA input (KMAHIP_EFORMAT) and a
+ * minimum length below 1 (KMAHIP_EINVAL). The accumulator must outlive the reader. */
+int kmahip_ingest_set_qc(kmahip_ingest *in, kmahip_qc *qc);
+int kmahip_ingest_dev_set_qc(kmahip_ingest_dev *in, kmahip_qc *qc);
+/* the sums so far (a copy) */
+int kmahip_qc_get(const kmahip_qc *qc, kmahip_qc_stats *out);
+/* print_QCstat (qc.c:167-262) into `path`: `trim` as the options gave it ("End Trim Q" is -mp raised to -mi, kma.c:1555-1557 /
+ * trim.c:432-434), clip5 / clip3 the -5p / -3p values, which are printed and read by nothing else. The four quality lines, E(Q) and
+ * the Q distribution are left out while Eeq == 0. */
+int kmahip_qc_write(const kmahip_qc *qc, const kmahip_trim *trim, int clip5, int clip3, const char *path);
+/* `kma trim` (printTrimFsa / printTrimFsa_pair, trim.c:28-126): with on != 0, set before the first _next, every batch of the host
+ * reader also carries its records as FASTQ text -- the chomped header line with its '@', the trimmed bases through to2Bit and
+ * "ACGTN" (IUPAC and lower case become A / C / G / T, hard-masked bases N), "+", the trimmed qualities -- single records in stream 0
+ * (<out>.fq), couples in stream 1 (<out>_int.fq), both in stream order. kmahip_ingest_text: the text of the batch delivered last,
+ * valid until the next call on the reader. */
+int kmahip_ingest_set_text(kmahip_ingest *in, int on);
+int kmahip_ingest_text(const kmahip_ingest *in, int stream, const char **text, int64_t *bytes);
+/* the same for the device reader: the text is written on the device (s1_fastq_kernel: a record's size from its trimmed span and its
+ * name, the sizes scanned per stream, a group of lanes per record) and comes back with the batch -- `text` is HOST memory, valid until
+ * the next call. The part of an odd file that the host reader takes is the host reader's text. */
+int kmahip_ingest_dev_set_text(kmahip_ingest_dev *in, int on);
+int kmahip_ingest_dev_text(const kmahip_ingest_dev *in, int stream, const char **text, int64_t *bytes);
+/* what the report cost the device reader so far, ms: [0] fetching the counted sequences' (sp, len), [1] adding and binning them on the host */
+void kmahip_ingest_dev_qc_timing(const kmahip_ingest_dev *in, double ms[2]);
+/* trim_main (trim.c:149-472) over files: single-end files (run_input), then couples of mate files (run_input_PE), then interleaved
+ * files (run_input_INT), FASTQ plain or .gz, into <out_prefix>.fq and -- when there are paired or interleaved files --
+ * <out_prefix>_int.fq; with qc != NULL the report is fed (and written to <out_prefix>.json by the caller, kmahip_qc_write).
+ * s1dev != 0: stage 1 and the text of the files the device reader covers (plain FASTQ, single end or mate files) are made on the
+ * device current at the call, everything else -- .gz, interleaved files, odd records -- by the host reader, as ever.
+ * *fragments: the records written, a couple counting once. FASTA input: KMAHIP_EFORMAT. */
+int kmahip_trim_files(const char *const *se, int n_se, const char *const *pe, int n_pe, const char *const *il, int n_il,
+                      const kmahip_trim *trim, kmahip_qc *qc, int s1dev, const char *out_prefix, int64_t *fragments);
+
 /* `.frag.gz` (updateFrags, assembly.c:49-83): one row per read that passed the stage-3c filter -- the read as aligned, the
  * number of equally good templates, score, start, end, template name (from <prefix>.name), read header -- in the order a
  * single-threaded assemble_KMA writes them: templates ascending, inside a template the pile-up order (see kmahip_assemble).

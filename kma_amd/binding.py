@@ -418,11 +418,88 @@ def index_build(fasta_paths, out_prefix, k=16, decon=None, sparse=None, min_len=
     _check(L.kmahip_index_build(arr, len(paths), os.fsencode(out_prefix), int(k)))
 
 
+class QCStats(C.Structure):
+    _fields_ = [("fragcount", C.c_uint64), ("org_fragcount", C.c_uint64), ("count", C.c_uint64), ("org_count", C.c_uint64),
+                ("bpcount", C.c_uint64), ("org_bpcount", C.c_uint64), ("totgc", C.c_uint64), ("totns", C.c_uint64), ("Eeq", C.c_double),
+                ("maxlen", C.c_int32), ("qresolution", C.c_int32), ("phred_scale", C.c_int32), ("pad_", C.c_int32),
+                ("qdist", C.c_uint32 * 256), ("ldist", C.c_uint32 * 512)]
+
+
+def _qc_lib():
+    L = lib()
+    if not getattr(L, "_qc_ready", False):
+        L.kmahip_qc_open.argtypes = [C.POINTER(C.c_void_p)]
+        L.kmahip_qc_close.argtypes = [C.c_void_p]
+        L.kmahip_qc_close.restype = None
+        L.kmahip_qc_get.argtypes = [C.c_void_p, C.POINTER(QCStats)]
+        L.kmahip_qc_write.argtypes = [C.c_void_p, C.POINTER(Trim), C.c_int, C.c_int, C.c_char_p]
+        L.kmahip_ingest_set_qc.argtypes = [C.c_void_p, C.c_void_p]
+        L.kmahip_ingest_dev_set_qc.argtypes = [C.c_void_p, C.c_void_p]
+        L.kmahip_ingest_set_text.argtypes = [C.c_void_p, C.c_int]
+        L.kmahip_ingest_text.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+        L.kmahip_trim_files.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), C.c_int,
+                                        C.POINTER(Trim), C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_int64)]
+        L.kmahip_ingest_dev_set_text.argtypes = [C.c_void_p, C.c_int]
+        L.kmahip_ingest_dev_text.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+        L._qc_ready = True
+    return L
+
+
+class QC:
+    """The QC report of `kma ... -qc` / `kma trim -qc` (kmahip_qc_*): an accumulator that readers feed while they trim -- Ingest(..., qc=q),
+    IngestDev(..., qc=q), several of them one after the other. A reader with one trims by the reference's -qc rule."""
+
+    def __init__(self):
+        self._h = C.c_void_p()
+        _check(_qc_lib().kmahip_qc_open(C.byref(self._h)))
+
+    def stats(self):
+        """-> dict of the counts, sums, the two histograms (numpy), the resolution and the phred scale"""
+        s = QCStats()
+        _check(_qc_lib().kmahip_qc_get(self._h, C.byref(s)))
+        out = {n: getattr(s, n) for n, _ in QCStats._fields_ if n not in ("pad_", "qdist", "ldist")}
+        out["qdist"] = np.array(s.qdist, np.uint32)
+        out["ldist"] = np.array(s.ldist, np.uint32)
+        return out
+
+    def write(self, path, min_phred=20, min_q=0, hardmask_q=0, min_len=16, max_len=2**31 - 1, clip5=0, clip3=0):
+        """print_QCstat: the JSON file; the trimming options as they were given, -5p / -3p only to be printed"""
+        t = Trim(min_phred, min_q, hardmask_q, min_len, max_len)
+        _check(_qc_lib().kmahip_qc_write(self._h, C.byref(t), int(clip5), int(clip3), os.fsencode(path)))
+
+    def close(self):
+        if self._h:
+            _qc_lib().kmahip_qc_close(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def trim_files(paths, out_prefix, paired=(), interleaved=(), qc=None, s1dev=False, min_phred=20, min_q=0, hardmask_q=0, min_len=16, max_len=2**31 - 1):
+    """`kma trim -i paths -ipe paired -int interleaved -o out_prefix` (kmahip_trim_files): <out_prefix>.fq and, with paired or interleaved
+    files, <out_prefix>_int.fq; qc: a QC to feed (its write() makes <out_prefix>.json); s1dev: stage 1 and the text on the device for
+    the files its reader covers. -> fragments written, a couple counting once"""
+    def arr(xs):
+        xs = [os.fsencode(x) for x in xs]
+        return (C.c_char_p * max(1, len(xs)))(*xs), len(xs)
+    se, n_se = arr(paths)
+    pe, n_pe = arr(paired)
+    il, n_il = arr(interleaved)
+    t = Trim(min_phred, min_q, hardmask_q, min_len, max_len)
+    n = C.c_int64()
+    _check(_qc_lib().kmahip_trim_files(se, n_se, pe, n_pe, il, n_il, C.byref(t), qc._h if qc is not None else None, 1 if s1dev else 0, os.fsencode(out_prefix), C.byref(n)))
+    return n.value
+
+
 class Ingest:
     """Stage 1 on the host (kmahip_ingest_*): FASTQ / FASTA(.gz) -> trimmed, packed formats.ReadBatch batches, the
     records the reference's run_input / run_input_PE write into the S1 stream, in the same order."""
 
-    def __init__(self, path1, path2=None, min_phred=20, min_q=0, hardmask_q=0, min_len=16, max_len=2**31 - 1, interleaved=False):
+    def __init__(self, path1, path2=None, min_phred=20, min_q=0, hardmask_q=0, min_len=16, max_len=2**31 - 1, interleaved=False, qc=None, text=False):
         L = lib()
         t = Trim(min_phred, min_q, hardmask_q, min_len, max_len)
         self._h = C.c_void_p()
@@ -431,8 +508,25 @@ class Ingest:
                 raise ValueError("interleaved input is one file")
             L.kmahip_ingest_open_interleaved.argtypes = [C.c_char_p, C.c_void_p, C.POINTER(C.c_void_p)]
             _check(L.kmahip_ingest_open_interleaved(os.fsencode(path1), C.byref(t), C.byref(self._h)))
-            return
-        _check(L.kmahip_ingest_open(os.fsencode(path1), os.fsencode(path2) if path2 else None, C.byref(t), C.byref(self._h)))
+        else:
+            _check(L.kmahip_ingest_open(os.fsencode(path1), os.fsencode(path2) if path2 else None, C.byref(t), C.byref(self._h)))
+        try:
+            if qc is not None:       # trim by the -qc rule and feed the accumulator (kmahip_ingest_set_qc)
+                _check(_qc_lib().kmahip_ingest_set_qc(self._h, qc._h))
+            if text:                 # the batches also as FASTQ text (kmahip_ingest_set_text): text() after every next()
+                _check(_qc_lib().kmahip_ingest_set_text(self._h, 1))
+        except Exception:
+            self.close()
+            raise
+
+    def text(self):
+        """-> (single records, couples) of the batch delivered last as FASTQ text (bytes), `kma trim`'s <out>.fq and <out>_int.fq"""
+        out = []
+        for k in range(2):
+            p, n = C.c_void_p(), C.c_int64()
+            _check(_qc_lib().kmahip_ingest_text(self._h, k, C.byref(p), C.byref(n)))
+            out.append(C.string_at(p, n.value) if n.value else b"")
+        return tuple(out)
 
     @property
     def phred_scale(self):
@@ -486,11 +580,28 @@ class IngestDev:
     """Stage 1 on the device (kmahip_ingest_dev_*): plain FASTQ file(s) -> the batches of Ingest, made by HIP kernels and resident in HBM.
     Inputs it does not cover (.gz, FASTA) raise KmaHipError from the constructor, before any HIP call: use Ingest for them."""
 
-    def __init__(self, path1, path2=None, min_phred=20, min_q=0, hardmask_q=0, min_len=16, max_len=2**31 - 1):
+    def __init__(self, path1, path2=None, min_phred=20, min_q=0, hardmask_q=0, min_len=16, max_len=2**31 - 1, qc=None, text=False):
         L = lib()
         t = Trim(min_phred, min_q, hardmask_q, min_len, max_len)
         self._h = C.c_void_p()
         _check(L.kmahip_ingest_dev_open(os.fsencode(path1), os.fsencode(path2) if path2 else None, C.byref(t), C.byref(self._h)))
+        try:
+            if qc is not None:       # the records kernel's -qc instantiation and s1_qc_kernel feed the accumulator (kmahip_ingest_dev_set_qc)
+                _check(_qc_lib().kmahip_ingest_dev_set_qc(self._h, qc._h))
+            if text:                 # s1_fastq_kernel writes the batches as FASTQ text as well (kmahip_ingest_dev_set_text): text() after every next()
+                _check(_qc_lib().kmahip_ingest_dev_set_text(self._h, 1))
+        except Exception:
+            self.close()
+            raise
+
+    def text(self):
+        """-> (single records, couples) of the batch delivered last as FASTQ text (bytes), written on the device"""
+        out = []
+        for k in range(2):
+            p, n = C.c_void_p(), C.c_int64()
+            _check(_qc_lib().kmahip_ingest_dev_text(self._h, k, C.byref(p), C.byref(n)))
+            out.append(C.string_at(p, n.value) if n.value else b"")
+        return tuple(out)
 
     @property
     def phred_scale(self):
@@ -511,6 +622,15 @@ class IngestDev:
         ms, n = (C.c_double * 3)(), C.c_int64()
         lib().kmahip_ingest_dev_timing(self._h, ms, C.byref(n))
         return ms[0], ms[1], ms[2], n.value
+
+    def qc_timing(self):
+        """-> (ms fetching the counted sequences' (sp, len), ms adding and binning them on the host) of a reader with a QC"""
+        ms = (C.c_double * 2)()
+        L = lib()
+        L.kmahip_ingest_dev_qc_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        L.kmahip_ingest_dev_qc_timing.restype = None
+        L.kmahip_ingest_dev_qc_timing(self._h, ms)
+        return ms[0], ms[1]
 
     def next_dev(self, max_records=1 << 20):
         """the batch as the library hands it out (ReadBatchC with device pointers; valid until the next call), or None at the end"""

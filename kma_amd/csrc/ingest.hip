@@ -136,6 +136,10 @@ template <class T> struct Arr {
 	T &back() const { return p[n - 1]; }
 };
 
+// one sequence as update_QCstat (qc.c:85-104) takes it: trimmed length, C + G and N's (hard-masked bases are N's), and the sum of
+// 10^(-q/10) over the span, added base by base and less what the -eq loop took off again (runinput.c:170-185, 226-300)
+struct QcSeq { double sp; int32_t len, gc, ns; };
+
 // what one worker thread makes of its share of the records; appended to the batch in thread order
 struct alignas(128) Part {      // own cache lines: neighbouring threads push into neighbouring parts
 	std::vector<uint8_t> codes[2];  // scratch
@@ -146,7 +150,12 @@ struct alignas(128) Part {      // own cache lines: neighbouring threads push in
 	std::vector<uint8_t> pair;
 	int64_t records = 0;
 	int max_len = 0;
-	void clear() { seq.clear(); len.clear(); N.clear(); nN.clear(); names.clear(); name_len.clear(); pair.clear(); records = 0; max_len = 0; }
+	// with a QC accumulator: the sequences update_QCstat counts, in order, and the bases of every sequence read; with the text sink:
+	// the records as FASTQ text, single ones and couples apart
+	std::vector<QcSeq> qc;
+	int64_t org_bp = 0;
+	std::vector<char> fq[2];
+	void clear() { seq.clear(); len.clear(); N.clear(); nN.clear(); names.clear(); name_len.clear(); pair.clear(); records = 0; max_len = 0; qc.clear(); org_bp = 0; fq[0].clear(); fq[1].clear(); }
 };
 
 // A piece of the decompressed input. The bytes [lo, hi) of base are data; a streamed chunk keeps room in front of lo for
@@ -473,6 +482,9 @@ struct kmahip_ingest {
 	Arr<int32_t> len, N;
 	Arr<char> names;
 	Arr<uint8_t> pair;
+	kmahip_qc *qc = nullptr;            // kmahip_ingest_set_qc: trim by the -qc rule and feed it, batch by batch in stream order
+	bool text = false, started = false; // kmahip_ingest_set_text; a first kmahip_ingest_next has been made
+	Arr<char> fq[2];                    // the batch as FASTQ text: single records, couples
 	// kept between batches: the worker threads' parts and the located records (steady state allocates nothing -- eight
 	// threads growing fresh vectors every batch spent 6x the packing time inside the allocator)
 	std::vector<Part> parts;
@@ -608,16 +620,18 @@ bool next_fa(Stream &s, Rec &r) {
 	return true;
 }
 
-// phredStat, runinput.c:127-313 (without a QC report). seq may be modified (hard masking). Returns the length figure the
-// caller compares with minlen: end - start on the plain path, end - start - #N on the -eq / -mi path.
+// phredStat, runinput.c:127-313. seq may be modified (hard masking). Returns the length figure the caller compares with minlen:
+// end - start on the plain path, end - start - #N on the -eq / -mi path. With a QC report (rep != NULL) there is no plain path
+// (:163), and *rep is what update_QCstat is given (:303-306) -- rep->len < 0 when the sequence is not counted.
 int phred_stat(uint8_t *seq, const uint8_t *qual, int len, const double *prob /* indexed by raw byte */, int minPhred /* raw */,
-               int minQ, int hardmaskQ /* as given */, int minlen, int maxlen, int *START, int *END) {
+               int minQ, int hardmaskQ /* as given */, int minlen, int maxlen, int *START, int *END, QcSeq *rep = nullptr) {
+	if(rep) rep->len = -1;
 	if(maxlen < len) { *START = 0; *END = 0; return 0; }
 	int start = 0, end = len;
 	while(start < end && qual[start] < minPhred) ++start;
 	while(start < end && qual[end - 1] < minPhred) --end;
 	len = end - start;
-	if(!minQ && !hardmaskQ) { *START = start; *END = end; return len; }
+	if(!minQ && !hardmaskQ && !rep) { *START = start; *END = end; return len; }
 	unsigned ns = 0, gc = 0;
 	double sp = 0;
 	for(int i = start; i < end; ++i) {
@@ -628,31 +642,32 @@ int phred_stat(uint8_t *seq, const uint8_t *qual, int len, const double *prob /*
 	const double minP = pow(10, (-0.1) * minQ);
 	if(minlen <= (int) (len - ns) && (minP * len) < sp) {
 		// 5' / 3' segments = a run of good bases followed by a run of bad ones, seen from the respective end
-		unsigned ns5 = 0, ns3 = 0, l5 = 0, l3 = 0;
+		unsigned ns5 = 0, ns3 = 0, gc5 = 0, gc3 = 0, l5 = 0, l3 = 0;
 		double sp5 = 0, sp3 = 0;
 		int p5 = start, p3 = end - 1;
+		auto tally = [&](int p, unsigned &n, unsigned &g) { if(seq[p] == 4) ++n; else if(seq[p] == 1 || seq[p] == 2) ++g; };
 		auto grow3 = [&]() {
-			while((int) l3 < len && minPhred <= qual[p3]) { sp3 += prob[qual[p3]]; ++l3; if(seq[p3] == 4) ++ns3; --p3; }
-			while((int) l3 < len && qual[p3] < minPhred) { sp3 += prob[qual[p3]]; ++l3; if(seq[p3] == 4) ++ns3; --p3; }
+			while((int) l3 < len && minPhred <= qual[p3]) { sp3 += prob[qual[p3]]; ++l3; tally(p3, ns3, gc3); --p3; }
+			while((int) l3 < len && qual[p3] < minPhred) { sp3 += prob[qual[p3]]; ++l3; tally(p3, ns3, gc3); --p3; }
 		};
 		auto grow5 = [&]() {
-			while((int) l5 < len && minPhred <= qual[p5]) { sp5 += prob[qual[p5]]; ++l5; if(seq[p5] == 4) ++ns5; ++p5; }
-			while((int) l5 < len && qual[p5] < minPhred) { sp5 += prob[qual[p5]]; ++l5; if(seq[p5] == 4) ++ns5; ++p5; }
+			while((int) l5 < len && minPhred <= qual[p5]) { sp5 += prob[qual[p5]]; ++l5; tally(p5, ns5, gc5); ++p5; }
+			while((int) l5 < len && qual[p5] < minPhred) { sp5 += prob[qual[p5]]; ++l5; tally(p5, ns5, gc5); ++p5; }
 		};
 		grow3();
 		while(minlen <= (int) (len - ns) && (minP * len) < sp) {
 			if((sp5 * l3) < (sp3 * l5)) {
-				end -= (int) l3; ns -= ns3; len -= (int) l3; sp -= sp3;
-				ns3 = 0; l3 = 0; sp3 = 0;
+				end -= (int) l3; ns -= ns3; gc -= gc3; len -= (int) l3; sp -= sp3;
+				ns3 = 0; gc3 = 0; l3 = 0; sp3 = 0;
 				grow3();
 			} else {
-				start += (int) l5; len -= (int) l5; ns -= ns5; sp -= sp5;
-				ns5 = 0; l5 = 0; sp5 = 0;
+				start += (int) l5; len -= (int) l5; ns -= ns5; gc -= gc5; sp -= sp5;
+				ns5 = 0; gc5 = 0; l5 = 0; sp5 = 0;
 				grow5();
 			}
 		}
 	}
-	(void) gc;
+	if(rep && minlen <= (int) (len - ns)) { rep->sp = sp; rep->len = len; rep->gc = (int32_t) gc; rep->ns = (int32_t) ns; }
 	*START = start; *END = end;
 	return len - (int) ns;
 }
@@ -722,7 +737,21 @@ void pack_fastq(const kmahip_ingest *in, const Span *const *spans, size_t a, siz
 	const double *prob = g_prob.p - in->phred;          // indexed by the raw quality byte
 	const int mates = in->paired ? 2 : 1;
 	std::vector<uint8_t> *codes = P.codes;
-	const bool plain = !T.min_q && !T.hardmask_q;       // only the ends are trimmed, by quality alone (runinput.c:144-171)
+	const bool plain = !T.min_q && !T.hardmask_q && !in->qc;      // only the ends are trimmed, by quality alone (runinput.c:144-171)
+	// printTrimFsa / printTrimFsa_pair (trim.c:28-126): header with its '@', bases through "ACGTN", "+", qualities
+	auto put_text = [&](const Span &r, const uint8_t *codes_or_raw, bool raw, int s0, int L, uint8_t pair) {
+		std::vector<char> &o = P.fq[pair ? 1 : 0];
+		const size_t nl = r.got ? r.name_len : 0, at = o.size();
+		o.resize(at + 1 + nl + 1 + (size_t) L + 3 + (size_t) L + 1);
+		char *w = o.data() + at;
+		*w++ = '@';
+		if(nl) memcpy(w, r.name, nl);
+		w += nl; *w++ = '\n';
+		for(int x = 0; x < L; ++x) { const uint8_t c = raw ? g_trans.t[codes_or_raw[x]] : codes_or_raw[x]; *w++ = "ACGTN-"[c < 5 ? c : 5]; }
+		*w++ = '\n'; *w++ = '+'; *w++ = '\n';
+		if(L) memcpy(w, r.qual + s0, (size_t) L);
+		w += L; *w++ = '\n';
+	};
 	const bool il = in->interleaved;                     // (mate m of record i is record 2 i + m of the one file)
 	auto span_of = [&](int m, size_t i) -> const Span & { return il ? spans[0][2 * i + (size_t) m] : spans[m][i]; };
 	for(size_t i = a; i < b; ++i) {
@@ -743,6 +772,7 @@ void pack_fastq(const kmahip_ingest *in, const Span *const *spans, size_t a, siz
 			auto put = [&](int m, uint8_t pair) {
 				const Span &r = span_of(m, i);
 				append_raw(P, r.seq + st[m], en[m] - st[m], (const char *) r.name, r.got ? r.name_len : 0, pair);
+				if(in->text) put_text(r, r.seq + st[m], true, st[m], en[m] - st[m], pair);
 			};
 			if(ok0 && ok1) { put(0, 1); put(1, 2); }
 			else if(ok0) put(0, 0);
@@ -756,13 +786,16 @@ void pack_fastq(const kmahip_ingest *in, const Span *const *spans, size_t a, siz
 			const int L = r.got ? (int) r.seq_len : 0;       // a mate file that ran out yields empty mates (the `|` at :516)
 			codes[m].resize((size_t) L);
 			for(int x = 0; x < L; ++x) codes[m][(size_t) x] = g_trans.t[r.seq[x]];
+			QcSeq rep;
 			len[m] = phred_stat(codes[m].data(), r.qual, L, prob, in->phred + T.min_phred, T.min_q, T.hardmask_q, T.min_len,
-			                    T.max_len, &st[m], &en[m]);
+			                    T.max_len, &st[m], &en[m], in->qc ? &rep : nullptr);
+			if(in->qc) { P.org_bp += L; if(rep.len >= 0) P.qc.push_back(rep); }
 		}
 		const bool ok0 = T.min_len <= len[0], ok1 = in->paired && T.min_len <= len[1];
 		auto put = [&](int m, uint8_t pair) {
 			const Span &r = span_of(m, i);
 			append_read(P, codes[m].data() + st[m], en[m] - st[m], (const char *) r.name, r.got ? r.name_len : 0, pair);
+			if(in->text) put_text(r, codes[m].data() + st[m], false, st[m], en[m] - st[m], pair);
 		};
 		if(ok0 && ok1) { put(0, 1); put(1, 2); }
 		else if(ok0) put(0, 0);
@@ -1066,6 +1099,8 @@ extern "C" int kmahip_ingest_next(kmahip_ingest *in, int64_t max_records, kmahip
 	in->seq.clear(); in->len.clear(); in->N.clear(); in->names.clear(); in->pair.clear();
 	in->seq_off.clear(); in->N_off.clear(); in->name_off.clear();
 	in->seq_off.push_back(0); in->N_off.push_back(0); in->name_off.push_back(0);
+	in->fq[0].clear(); in->fq[1].clear();
+	in->started = true;
 	const kmahip_trim &T = in->trim;
 	const bool il = in->interleaved;
 	const int mates = (in->paired && !il) ? 2 : 1;          // mate FILES
@@ -1119,6 +1154,16 @@ extern "C" int kmahip_ingest_next(kmahip_ingest *in, int64_t max_records, kmahip
 			const auto t2 = std::chrono::steady_clock::now();
 			append_parts(in, parts, nt);
 			for(int t = 0; t < nt; ++t) { records += parts[(size_t) t].records; max_len = std::max(max_len, parts[(size_t) t].max_len); }
+			// the parts in thread order are the records in stream order: the accumulator's Eeq and the text are made here, by one thread
+			for(int t = 0; t < nt && (in->qc || in->text); ++t) {
+				const Part &P = parts[(size_t) t];
+				if(in->qc) {
+					for(const QcSeq &q : P.qc) kmahip_qc_add_seq(in->qc, q.len, q.gc, q.ns, q.sp);
+					kmahip_qc_add_read(in->qc, 0, (uint64_t) P.org_bp, 0, (uint64_t) P.records);
+				}
+				for(int k = 0; k < 2; ++k) in->fq[k].append(P.fq[k].data(), P.fq[k].size());
+			}
+			if(in->qc) kmahip_qc_add_read(in->qc, (uint64_t) n * (in->paired ? 2u : 1u), 0, (uint64_t) n, 0);
 			for(int m = 0; m < mates; ++m) { in->m[m].head += il ? 2 * n : n; release_chunks(in->m[m]); }
 			const auto t3 = std::chrono::steady_clock::now();
 			ms_locate += ms(t0, t1); ms_pack += ms(t1, t2); ms_gather += ms(t2, t3);
@@ -1150,6 +1195,7 @@ extern "C" int kmahip_ingest_next(kmahip_ingest *in, int64_t max_records, kmahip
 		max_len = P.max_len;
 	}
 	in->n_kept += records;
+	if(in->qc) kmahip_qc_end_reader(in->qc, in->paired, in->phred);
 	if(in->N.empty()) in->N.push_back(0);                  // never hand out a null pointer
 	memset(batch, 0, sizeof *batch);
 	batch->reads.n_reads = (int64_t) in->len.size();
@@ -1171,6 +1217,34 @@ extern "C" int kmahip_ingest_next(kmahip_ingest *in, int64_t max_records, kmahip
 		kmahip_set_error("malformed FASTQ input after %lld records", (long long) in->n_read);
 		return KMAHIP_EFORMAT;
 	}
+	return KMAHIP_OK;
+}
+
+// kmahip.h: the reader trims by the -qc rule from now on and feeds the accumulator. FASTA and -ml < 1 are where the reference's own
+// report dies (fsastat hands update_QCstat sp = 0, and a kept read of length 0 makes it 0 / 0: log10 then indexes qdist at INT_MIN)
+extern "C" int kmahip_ingest_set_qc(kmahip_ingest *in, kmahip_qc *qc) {
+	if(!in || !qc) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(in->started) { kmahip_set_error("a QC accumulator is attached before the first batch is read"); return KMAHIP_EINVAL; }
+	if(!in->fastq) { kmahip_set_error("FASTA input has no QC report (the reference's dies on it: fsastat gives update_QCstat no quality sum)"); return KMAHIP_EFORMAT; }
+	if(in->trim.min_len < 1) { kmahip_set_error("a QC report needs a minimum length of 1 at least (the reference divides by the length of a kept read)"); return KMAHIP_EINVAL; }
+	in->qc = qc;
+	kmahip_qc_end_reader(qc, in->paired, in->phred);
+	return KMAHIP_OK;
+}
+
+// kmahip.h: the batches also carry their records as FASTQ text (printTrimFsa / printTrimFsa_pair, trim.c:28-126)
+extern "C" int kmahip_ingest_set_text(kmahip_ingest *in, int on) {
+	if(!in) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(in->started) { kmahip_set_error("the text sink is set before the first batch is read"); return KMAHIP_EINVAL; }
+	if(on && !in->fastq) { kmahip_set_error("FASTA input is not written back as text: the trimmed reads are FASTQ records"); return KMAHIP_EFORMAT; }
+	in->text = on != 0;
+	return KMAHIP_OK;
+}
+
+extern "C" int kmahip_ingest_text(const kmahip_ingest *in, int stream, const char **text, int64_t *bytes) {
+	if(!in || !text || !bytes || stream < 0 || stream > 1) { kmahip_set_error("bad argument"); return KMAHIP_EINVAL; }
+	*text = in->fq[stream].data() ? in->fq[stream].data() : "";
+	*bytes = (int64_t) in->fq[stream].size();
 	return KMAHIP_OK;
 }
 

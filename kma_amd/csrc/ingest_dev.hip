@@ -120,8 +120,14 @@ __device__ __forceinline__ bool is_space(uint8_t c) { return c == ' ' || (c >= 9
 // phred_stat of ingest.hip (phredStat, runinput.c:127-313) on the -eq / -mi path; a base is N when the table says so or when its
 // quality is below -mi (the host writes that into its copy of the read; here it is asked again). Sequential double arithmetic in the
 // reference's order; no product feeds a sum, and contraction is off all the same: one fused rounding would break the byte parity
+//
+// QC: the routine with a report (phredStat's qcreport, runinput.c:133-136, 163, 303-312): C + G are counted beside the N's, through
+// the -eq loop's segments as well, and *rep is what update_QCstat is given -- rep->len < 0 when the sequence is not counted.
+struct QcSlot { double sp; int32_t len, gc, ns, org_len; };
 #pragma clang fp contract(off)
-__device__ int phred_stat_dev(const uint8_t *raw, const uint8_t *qual, int len, const uint8_t *T, const double *prob, const TrimDev P, int *START, int *END) {
+template <bool QC>
+__device__ int phred_stat_dev(const uint8_t *raw, const uint8_t *qual, int len, const uint8_t *T, const double *prob, const TrimDev P, int *START, int *END, QcSlot *rep = nullptr) {
+	if constexpr(QC) { rep->sp = 0; rep->len = -1; rep->gc = 0; rep->ns = 0; rep->org_len = len; }
 	if(P.max_len < len) { *START = 0; *END = 0; return 0; }
 	const int minPhred = P.min_phred_raw;
 	int start = 0, end = len;
@@ -129,35 +135,38 @@ __device__ int phred_stat_dev(const uint8_t *raw, const uint8_t *qual, int len, 
 	while(start < end && qual[end - 1] < minPhred) --end;
 	len = end - start;
 	auto isN = [&](int i) { return T[raw[i]] == 4 || qual[i] < P.hardmask_q; };
-	unsigned ns = 0;
+	unsigned ns = 0, gc = 0;
 	double sp = 0;
-	for(int i = start; i < end; ++i) { sp += prob[qual[i]]; if(isN(i)) ++ns; }
+#define TALLY(p, n_, g_) do { if(isN(p)) ++n_; else if constexpr(QC) { const uint8_t c_ = T[raw[p]]; if(c_ == 1 || c_ == 2) ++g_; } } while(0)
+	for(int i = start; i < end; ++i) { sp += prob[qual[i]]; TALLY(i, ns, gc); }
 	const double minP = P.minP;
 	if(P.min_len <= (int) (len - ns) && (minP * len) < sp) {
-		unsigned ns5 = 0, ns3 = 0, l5 = 0, l3 = 0;
+		unsigned ns5 = 0, ns3 = 0, gc5 = 0, gc3 = 0, l5 = 0, l3 = 0;
 		double sp5 = 0, sp3 = 0;
 		int p5 = start, p3 = end - 1;
 #define GROW3() do { \
-		while((int) l3 < len && minPhred <= qual[p3]) { sp3 += prob[qual[p3]]; ++l3; if(isN(p3)) ++ns3; --p3; } \
-		while((int) l3 < len && qual[p3] < minPhred) { sp3 += prob[qual[p3]]; ++l3; if(isN(p3)) ++ns3; --p3; } } while(0)
+		while((int) l3 < len && minPhred <= qual[p3]) { sp3 += prob[qual[p3]]; ++l3; TALLY(p3, ns3, gc3); --p3; } \
+		while((int) l3 < len && qual[p3] < minPhred) { sp3 += prob[qual[p3]]; ++l3; TALLY(p3, ns3, gc3); --p3; } } while(0)
 #define GROW5() do { \
-		while((int) l5 < len && minPhred <= qual[p5]) { sp5 += prob[qual[p5]]; ++l5; if(isN(p5)) ++ns5; ++p5; } \
-		while((int) l5 < len && qual[p5] < minPhred) { sp5 += prob[qual[p5]]; ++l5; if(isN(p5)) ++ns5; ++p5; } } while(0)
+		while((int) l5 < len && minPhred <= qual[p5]) { sp5 += prob[qual[p5]]; ++l5; TALLY(p5, ns5, gc5); ++p5; } \
+		while((int) l5 < len && qual[p5] < minPhred) { sp5 += prob[qual[p5]]; ++l5; TALLY(p5, ns5, gc5); ++p5; } } while(0)
 		GROW3();
 		while(P.min_len <= (int) (len - ns) && (minP * len) < sp) {
 			if((sp5 * l3) < (sp3 * l5)) {
-				end -= (int) l3; ns -= ns3; len -= (int) l3; sp -= sp3;
-				ns3 = 0; l3 = 0; sp3 = 0;
+				end -= (int) l3; ns -= ns3; gc -= gc3; len -= (int) l3; sp -= sp3;
+				ns3 = 0; gc3 = 0; l3 = 0; sp3 = 0;
 				GROW3();
 			} else {
-				start += (int) l5; len -= (int) l5; ns -= ns5; sp -= sp5;
-				ns5 = 0; l5 = 0; sp5 = 0;
+				start += (int) l5; len -= (int) l5; ns -= ns5; gc -= gc5; sp -= sp5;
+				ns5 = 0; gc5 = 0; l5 = 0; sp5 = 0;
 				GROW5();
 			}
 		}
 #undef GROW3
 #undef GROW5
 	}
+#undef TALLY
+	if constexpr(QC) if(P.min_len <= (int) (len - ns)) { rep->sp = sp; rep->len = len; rep->gc = (int32_t) gc; rep->ns = (int32_t) ns; }
 	*START = start; *END = end;
 	return len - (int) ns;
 }
@@ -166,21 +175,32 @@ struct MateView { const uint8_t *buf; const int32_t *lines; int64_t first; };   
 
 // pack_fastq of ingest.hip for record index blockIdx * 256 + threadIdx of the pass: slots[mates * i + m], and per slot what it adds to
 // the batch (kept reads, words with the pad word, name bytes with the NUL); entry [n_slots] of the three is 0 for the scans
+//
+// The -qc instantiation, s1_records_kernel<true, QcOut>: every read takes the routine with a report, never the plain path; per slot the
+// report (qslots), whether update_QCstat counts it (counted, scanned like kept) and the longest counted sequence so far (*run_max:
+// s1_qc_kernel bins by it). Its three outputs travel in a parameter pack, so that the plain instantiation, s1_records_kernel<false>, has
+// the parameter list -- and the code -- of the kernel that knew no report.
+struct QcOut { QcSlot *qslots; int64_t *counted; int *run_max; };
+template <bool QC, class... Out>
 __global__ __launch_bounds__(256) void s1_records_kernel(MateView M0, MateView M1, int64_t n, const TrimDev P, const uint8_t *tab, const double *prob,
-                                                         Slot *slots, int64_t *kept, int64_t *words, int64_t *nbytes, unsigned long long *couples) {
+                                                         Slot *slots, int64_t *kept, int64_t *words, int64_t *nbytes, unsigned long long *couples, Out... out) {
+	static_assert(sizeof...(Out) == (QC ? 1 : 0), "the -qc instantiation takes one QcOut, the plain one nothing");
 	__shared__ uint8_t T[256];
 	T[threadIdx.x] = tab[threadIdx.x];
 	__syncthreads();
 	const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
 	const int mates = P.paired ? 2 : 1;
 	if(i == 0) { kept[n * mates] = 0; words[n * mates] = 0; nbytes[n * mates] = 0; }
+	if constexpr(QC) if(i == 0) ((out.counted[n * mates] = 0), ...);
 	if(i >= n) return;
 	int len[2] = {0, 0};
 	Slot S[2];
+	QcSlot Q[2];
 	for(int m = 0; m < mates; ++m) {
 		const MateView &V = m ? M1 : M0;
 		Slot &s = S[m];
 		s.seq_pos = s.qual_pos = s.len = s.name_pos = s.name_len = 0; s.pair = 0; s.mate = (uint8_t) m; s.keep = 0; s.pad_ = 0;
+		if constexpr(QC) { Q[m].sp = 0; Q[m].len = -1; Q[m].gc = 0; Q[m].ns = 0; Q[m].org_len = 0; }
 		if(!V.lines) continue;
 		const int32_t *l = V.lines + 4 * (V.first + i);
 		const int l0 = l[0], l1 = l[1], l2 = l[2], l3 = l[3];
@@ -192,14 +212,15 @@ __global__ __launch_bounds__(256) void s1_records_kernel(MateView M0, MateView M
 		const int L = l2 - 1 - l1;
 		const uint8_t *q = V.buf + l3;
 		int st = 0, en = 0;
-		if(P.plain) {
+		if constexpr(QC) len[m] = phred_stat_dev<true>(V.buf + l1, q, L, T, prob, P, &st, &en, &Q[m]);
+		else if(P.plain) {
 			if(P.max_len >= L) {
 				en = L;
 				while(st < en && q[st] < P.min_phred_raw) ++st;
 				while(st < en && q[en - 1] < P.min_phred_raw) --en;
 			}
 			len[m] = en - st;
-		} else len[m] = phred_stat_dev(V.buf + l1, q, L, T, prob, P, &st, &en);
+		} else len[m] = phred_stat_dev<false>(V.buf + l1, q, L, T, prob, P, &st, &en);
 		s.seq_pos = l1 + st; s.qual_pos = l3 + st; s.len = en - st;
 	}
 	const bool ok0 = P.min_len <= len[0], ok1 = P.paired && P.min_len <= len[1];
@@ -216,7 +237,61 @@ __global__ __launch_bounds__(256) void s1_records_kernel(MateView M0, MateView M
 		kept[o] = S[m].keep;
 		words[o] = S[m].keep ? ((S[m].len + 31) >> 5) + 1 : 0;
 		nbytes[o] = S[m].keep ? S[m].name_len + 1 : 0;
+		if constexpr(QC) ((out.qslots[o] = Q[m], out.counted[o] = Q[m].len >= 0), ...);
 	}
+	if constexpr(QC) {	// the running maximum: an atomic only from a thread that still has something to raise (lanes behind the pass's
+		// last record have left, so nothing is exchanged across the wave here)
+		const int mx = max(Q[0].len, mates == 2 ? Q[1].len : -1);
+		((mx > 0 && mx > *(volatile int *) out.run_max ? (void) atomicMax(out.run_max, mx) : (void) 0), ...);
+	}
+}
+
+// ---- QC -----------------------------------------------------------------------------------------------------------------------
+// One pass's share of update_QCstat (qc.c:85-104) for everything that does not depend on floating-point order: the integer sums
+// (sequences counted, their bases, C + G, N's; the bases of every sequence read), the length histogram at len >> res, and the counted
+// sequences' (sp, len) compacted in stream order behind the scan over `counted`. Per workgroup: the sums by wave reductions and one
+// LDS word per wave, the histogram by LDS atomics, then one global atomic per sum and per bin that is not zero. res comes from the
+// running maximum that the records kernel left behind (rescale_ldist, qc.c:50-65: the least res with maxlen >> res < 512), so every
+// bin lies below 512; the host folds the bins of passes with different res together. Eeq and the quality bins are the host's: they
+// depend on the order of the sum and on its log10.
+// stat: [0] counted, [1] bases, [2] C + G, [3] N's, [4] bases read; then int res, int run_max (kept between the passes)
+constexpr int QC_SUMS = 5, QC_BINS = 512;
+struct QcStat { unsigned long long sum[QC_SUMS]; int res, run_max; uint32_t pad_[4]; uint32_t hist[QC_BINS]; };
+__global__ __launch_bounds__(256) void s1_qc_kernel(int64_t n_slots, const QcSlot *qslots, const int64_t *counted_ex, QcStat *stat, KmaQcPair *pairs) {
+	__shared__ uint32_t h[QC_BINS];
+	__shared__ unsigned long long wsum[4][QC_SUMS];
+	for(int b = threadIdx.x; b < QC_BINS; b += 256) h[b] = 0;
+	const int run_max = stat->run_max;
+	int res = 0;
+	while(QC_BINS <= (run_max >> res)) ++res;
+	__syncthreads();
+	const int64_t o = (int64_t) blockIdx.x * 256 + threadIdx.x;
+	unsigned long long v[QC_SUMS] = {0, 0, 0, 0, 0};
+	if(o < n_slots) {
+		const QcSlot q = qslots[o];
+		v[4] = (unsigned long long) q.org_len;
+		if(q.len >= 0) {
+			v[0] = 1; v[1] = (unsigned long long) q.len; v[2] = (unsigned long long) q.gc; v[3] = (unsigned long long) q.ns;
+			const int bin = q.len >> res;
+			if(bin < QC_BINS) atomicAdd(&h[bin], 1u);
+			KmaQcPair p;
+			p.sp = q.sp; p.len = q.len; p.pad_ = 0;
+			pairs[counted_ex[o]] = p;          // (16 bytes, 16-byte aligned: one store)
+		}
+	}
+#pragma unroll
+	for(int k = 0; k < QC_SUMS; ++k) {
+#pragma unroll
+		for(int d = 32; d > 0; d >>= 1) v[k] += __shfl_down(v[k], d, 64);
+	}
+	if((threadIdx.x & 63) == 0) for(int k = 0; k < QC_SUMS; ++k) wsum[threadIdx.x >> 6][k] = v[k];
+	__syncthreads();
+	if(threadIdx.x < QC_SUMS) {
+		const unsigned long long t = wsum[0][threadIdx.x] + wsum[1][threadIdx.x] + wsum[2][threadIdx.x] + wsum[3][threadIdx.x];
+		if(t) atomicAdd(&stat->sum[threadIdx.x], t);
+	}
+	for(int b = threadIdx.x; b < QC_BINS; b += 256) if(h[b]) atomicAdd(&stat->hist[b], h[b]);
+	if(blockIdx.x == 0 && threadIdx.x == 0) stat->res = res;
 }
 
 // ---- pack ---------------------------------------------------------------------------------------------------------------------
@@ -300,6 +375,68 @@ __global__ void s1_ends_kernel(OutView O, int64_t r, int64_t w, int64_t n, int64
 	if(threadIdx.x == 0 && blockIdx.x == 0) { O.seq_off[r] = w; O.N_off[r] = n; O.name_off[r] = c; }
 }
 
+// ---- text ---------------------------------------------------------------------------------------------------------------------
+// `kma trim` (printTrimFsa / printTrimFsa_pair, trim.c:28-126): every kept record as FASTQ text -- '@' and the chomped header line, the
+// trimmed bases through to2Bit and "ACGTN" (a hard-masked base is an N), "+", the trimmed qualities -- single records in stream 0,
+// couples in stream 1, both in stream order. A record's size follows from its Slot alone; the sizes are scanned per stream.
+__device__ __forceinline__ int64_t fastq_bytes(const Slot &s) { return s.keep ? 2 * (int64_t) s.len + s.name_len + 6 : 0; }
+
+__global__ __launch_bounds__(256) void s1_fastq_size_kernel(int64_t n_slots, const Slot *slots, int64_t *size0, int64_t *size1) {
+	const int64_t o = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if(o == 0) { size0[n_slots] = 0; size1[n_slots] = 0; }
+	if(o >= n_slots) return;
+	const Slot s = slots[o];
+	const int64_t b = fastq_bytes(s);
+	size0[o] = s.pair ? 0 : b;
+	size1[o] = s.pair ? b : 0;
+}
+
+// A group of G lanes per slot. The record is a run of bytes at an arbitrary offset of its stream: the bytes before the first
+// 16-byte boundary and behind the last one are stored one by one, everything between as whole 16-byte words, a word per lane and
+// round -- each put together from the chunk (header and qualities as they are, bases through the table).
+__global__ __launch_bounds__(256) void s1_fastq_kernel(const uint8_t *buf0, const uint8_t *buf1, int64_t n_slots, int G, const Slot *slots, const int64_t *off0,
+                                                       const int64_t *off1, int hardmask_q, const uint8_t *tab, char *text0, char *text1) {
+	__shared__ uint8_t T[256];
+	T[threadIdx.x] = tab[threadIdx.x];
+	__syncthreads();
+	const int64_t t = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	const int64_t o = t / G;
+	const int g = (int) (t % G);
+	if(o >= n_slots) return;
+	const Slot s = slots[o];
+	if(!s.keep) return;
+	const uint8_t *buf = s.mate ? buf1 : buf0;
+	const uint8_t *nm = buf + s.name_pos, *raw = buf + s.seq_pos, *q = buf + s.qual_pos;
+	char *dst = s.pair ? text1 + off1[o] : text0 + off0[o];
+	const int64_t L = s.len, nl = s.name_len, size = 2 * L + nl + 6;
+	const int64_t b0 = nl + 2, b1 = b0 + L, q0 = b1 + 3, q1 = q0 + L;          // bases [b0, b1), "\n+\n", qualities [q0, q1), '\n'
+	auto byte_at = [&](int64_t j) -> char {
+		if(j >= q0) return j < q1 ? (char) q[j - q0] : '\n';
+		if(j >= b1) return j == b1 + 1 ? '+' : '\n';
+		if(j >= b0) {
+			uint8_t code = T[raw[j - b0]];
+			if(hardmask_q && q[j - b0] < hardmask_q) code = 4;
+			return "ACGTN-"[code < 5 ? code : 5];
+		}
+		return j == 0 ? '@' : (j <= nl ? (char) nm[j - 1] : '\n');
+	};
+	// [0, head) single bytes, [head, head + 16 * words) aligned words, the rest single bytes
+	const int64_t head = min(size, (int64_t) ((16 - ((uintptr_t) dst & 15)) & 15)), words = (size - head) >> 4, tail = head + (words << 4);
+	for(int64_t j = g; j < head; j += G) dst[j] = byte_at(j);
+	for(int64_t w = g; w < words; w += G) {
+		const int64_t j0 = head + (w << 4);
+		uint32_t x[4];
+#pragma unroll
+		for(int k = 0; k < 4; ++k) {
+			x[k] = 0;
+#pragma unroll
+			for(int b = 0; b < 4; ++b) x[k] |= (uint32_t) (uint8_t) byte_at(j0 + 4 * k + b) << (8 * b);
+		}
+		*(uint4 *) (dst + j0) = make_uint4(x[0], x[1], x[2], x[3]);
+	}
+	for(int64_t j = tail + g; j < size; j += G) dst[j] = byte_at(j);
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 // a device array of the reader's own (never the process-wide block cache: it belongs to the device current at open). Growing one is
 // hipMalloc + copy + hipFree on the reader's thread, and hipFree waits for the whole device -- also for what another thread is running
@@ -362,6 +499,20 @@ struct kmahip_ingest_dev {
 	kmahip_ingest *host = nullptr;       // the host reader, once the rest of the input is its
 	double ms_read = 0, ms_copy = 0, ms_kernel = 0;
 	int64_t bytes_in = 0;
+	// kmahip_ingest_dev_set_qc: the accumulator, the per-slot reports and their scan, the pass's sums + histogram (device and pinned
+	// mirror) and the counted sequences' (sp, len) as they come back; where the report's own time went (KMAHIP_DEBUG_TIMING)
+	// kmahip_ingest_dev_set_text: the per-slot sizes of the two streams and their scans, the batch's text on the device and as it
+	// comes back
+	bool text = false;
+	DBuf tsize[2], tsize_ex[2], d_text[2];
+	int64_t text_tot[2] = {0, 0};
+	std::vector<char> h_text[2];
+	kmahip_qc *qc = nullptr;
+	bool started = false;
+	DBuf qslots, counted, counted_ex, qpairs, qstat;
+	QcStat *h_qstat = nullptr;
+	std::vector<KmaQcPair> h_pairs;
+	double ms_qc_copy = 0, ms_qc_bin = 0;
 };
 
 namespace {
@@ -505,6 +656,8 @@ int run_pass(Reader *R, int64_t take, int64_t tot[4], int *d_max_len, int64_t *r
 	if((rc = R->slots.ensure((size_t) ns * sizeof(Slot), 0, R->s)) || (rc = R->kept.ensure((size_t) (ns + 1) * 8, 0, R->s)) || (rc = R->words.ensure((size_t) (ns + 1) * 8, 0, R->s)) ||
 	   (rc = R->nbytes.ensure((size_t) (ns + 1) * 8, 0, R->s)) || (rc = R->kept_ex.ensure((size_t) (ns + 1) * 8, 0, R->s)) || (rc = R->words_ex.ensure((size_t) (ns + 1) * 8, 0, R->s)) ||
 	   (rc = R->nbytes_ex.ensure((size_t) (ns + 1) * 8, 0, R->s))) return rc;
+	if(R->qc && ((rc = R->qslots.ensure((size_t) ns * sizeof(QcSlot), 0, R->s)) || (rc = R->counted.ensure((size_t) (ns + 1) * 8, 0, R->s)) ||
+	             (rc = R->counted_ex.ensure((size_t) (ns + 1) * 8, 0, R->s)) || (rc = R->qpairs.ensure((size_t) (ns + 1) * sizeof(KmaQcPair), 0, R->s)))) return rc;
 	MateView V[2] = {{nullptr, nullptr, 0}, {nullptr, nullptr, 0}};
 	size_t rec_bytes = 0;          // bytes per record of the chunks: long reads get a wavefront each, short ones eight lanes
 	for(int m = 0; m < mates; ++m) if(!R->m[m].done) {
@@ -513,9 +666,24 @@ int run_pass(Reader *R, int64_t take, int64_t tot[4], int *d_max_len, int64_t *r
 	}
 	unsigned long long *d_couples = (unsigned long long *) (R->small.p + 64);
 	HIP_TRY(hipMemsetAsync(d_couples, 0, 8, R->s));
-	hipLaunchKernelGGL(s1_records_kernel, dim3((unsigned) ((take + 255) / 256)), dim3(256), 0, R->s, V[0], V[1], take, R->P, (const uint8_t *) R->tab.p, R->prob.as<double>(),
+	QcStat *d_stat = R->qstat.as<QcStat>();
+	if(R->qc) {
+		// (the sums and the bins start at zero with every pass; res and the running maximum stay)
+		HIP_TRY(hipMemsetAsync(d_stat->sum, 0, sizeof d_stat->sum, R->s));
+		HIP_TRY(hipMemsetAsync(d_stat->hist, 0, sizeof d_stat->hist, R->s));
+		hipLaunchKernelGGL((s1_records_kernel<true, QcOut>), dim3((unsigned) ((take + 255) / 256)), dim3(256), 0, R->s, V[0], V[1], take, R->P, (const uint8_t *) R->tab.p, R->prob.as<double>(),
+		                   R->slots.as<Slot>(), R->kept.as<int64_t>(), R->words.as<int64_t>(), R->nbytes.as<int64_t>(), d_couples,
+		                   QcOut{R->qslots.as<QcSlot>(), R->counted.as<int64_t>(), &d_stat->run_max});
+	} else
+	hipLaunchKernelGGL(s1_records_kernel<false>, dim3((unsigned) ((take + 255) / 256)), dim3(256), 0, R->s, V[0], V[1], take, R->P, (const uint8_t *) R->tab.p, R->prob.as<double>(),
 	                   R->slots.as<Slot>(), R->kept.as<int64_t>(), R->words.as<int64_t>(), R->nbytes.as<int64_t>(), d_couples);
 	HIP_TRY(hipGetLastError());
+	if(R->qc) {
+		if((rc = scan64(R, R->counted.as<int64_t>(), R->counted_ex.as<int64_t>(), (size_t) ns + 1))) return rc;
+		hipLaunchKernelGGL(s1_qc_kernel, dim3((unsigned) ((ns + 255) / 256)), dim3(256), 0, R->s, ns, R->qslots.as<QcSlot>(), R->counted_ex.as<int64_t>(), d_stat, R->qpairs.as<KmaQcPair>());
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(R->h_qstat, d_stat, sizeof(QcStat), hipMemcpyDeviceToHost, R->s));
+	}
 	if((rc = scan64(R, R->kept.as<int64_t>(), R->kept_ex.as<int64_t>(), (size_t) ns + 1)) || (rc = scan64(R, R->words.as<int64_t>(), R->words_ex.as<int64_t>(), (size_t) ns + 1)) ||
 	   (rc = scan64(R, R->nbytes.as<int64_t>(), R->nbytes_ex.as<int64_t>(), (size_t) ns + 1))) return rc;
 	HIP_TRY(hipMemcpyAsync(R->h_small + 0, R->kept_ex.as<int64_t>() + ns, 8, hipMemcpyDeviceToHost, R->s));
@@ -525,6 +693,42 @@ int run_pass(Reader *R, int64_t take, int64_t tot[4], int *d_max_len, int64_t *r
 	HIP_TRY(hipStreamSynchronize(R->s));
 	const int64_t nk = R->h_small[0], nw = R->h_small[1], nc = R->h_small[2];
 	*records += nk - R->h_small[3];
+	if(R->qc) {
+		// the counted sequences' (sp, len) in stream order: Eeq is their sum in that order and the quality bin the decision of this
+		// host's log10 (qc.hip), everything else of the pass was summed on the device
+		const QcStat &H = *R->h_qstat;
+		const size_t nq = (size_t) H.sum[0];
+		const auto t0 = std::chrono::steady_clock::now();
+		R->h_pairs.resize(nq);
+		if(nq) {
+			HIP_TRY(hipMemcpyAsync(R->h_pairs.data(), R->qpairs.p, nq * sizeof(KmaQcPair), hipMemcpyDeviceToHost, R->s));
+			HIP_TRY(hipStreamSynchronize(R->s));
+		}
+		const auto t1 = std::chrono::steady_clock::now();
+		kmahip_qc_add_pass(R->qc, H.sum[0], H.sum[1], H.sum[2], H.sum[3], H.run_max, H.hist, H.res, R->h_pairs.data(), nq);
+		kmahip_qc_add_read(R->qc, (uint64_t) ns, H.sum[4], (uint64_t) take, (uint64_t) (nk - R->h_small[3]));
+		R->ms_qc_copy += std::chrono::duration<double, std::milli>(t1 - t0).count();
+		R->ms_qc_bin += ms_since(t1);
+	}
+	if(R->text && nk) {
+		// the pass's records as text behind what the batch holds already: sizes, their scans, the bytes
+		for(int k = 0; k < 2; ++k) if((rc = R->tsize[k].ensure((size_t) (ns + 1) * 8, 0, R->s)) || (rc = R->tsize_ex[k].ensure((size_t) (ns + 1) * 8, 0, R->s))) return rc;
+		hipLaunchKernelGGL(s1_fastq_size_kernel, dim3((unsigned) ((ns + 255) / 256)), dim3(256), 0, R->s, ns, R->slots.as<Slot>(), R->tsize[0].as<int64_t>(), R->tsize[1].as<int64_t>());
+		HIP_TRY(hipGetLastError());
+		for(int k = 0; k < 2; ++k) {
+			if((rc = scan64(R, R->tsize[k].as<int64_t>(), R->tsize_ex[k].as<int64_t>(), (size_t) ns + 1))) return rc;
+			HIP_TRY(hipMemcpyAsync(R->h_small + 5 + k, R->tsize_ex[k].as<int64_t>() + ns, 8, hipMemcpyDeviceToHost, R->s));
+		}
+		HIP_TRY(hipStreamSynchronize(R->s));
+		const int64_t nt[2] = {R->h_small[5], R->h_small[6]};
+		for(int k = 0; k < 2; ++k) if((rc = R->d_text[k].ensure((size_t) (R->text_tot[k] + nt[k] + 16), (size_t) R->text_tot[k], R->s))) return rc;
+		const int G = rec_bytes > 600 ? 64 : 8;
+		const int64_t threads = ns * G;
+		hipLaunchKernelGGL(s1_fastq_kernel, dim3((unsigned) ((threads + 255) / 256)), dim3(256), 0, R->s, (const uint8_t *) R->m[0].buf.p, (const uint8_t *) R->m[1].buf.p, ns, G, R->slots.as<Slot>(),
+		                   R->tsize_ex[0].as<int64_t>(), R->tsize_ex[1].as<int64_t>(), R->P.hardmask_q, (const uint8_t *) R->tab.p, R->d_text[0].p + R->text_tot[0], R->d_text[1].p + R->text_tot[1]);
+		HIP_TRY(hipGetLastError());
+		R->text_tot[0] += nt[0]; R->text_tot[1] += nt[1];
+	}
 	if(nk) {
 		if((rc = R->o_seq.ensure((size_t) (tot[1] + nw + 2) * 8, (size_t) tot[1] * 8, R->s)) || (rc = R->o_seq_off.ensure((size_t) (tot[0] + nk + 1) * 8, (size_t) tot[0] * 8, R->s)) ||
 		   (rc = R->o_N_off.ensure((size_t) (tot[0] + nk + 1) * 8, (size_t) tot[0] * 8, R->s)) || (rc = R->o_name_off.ensure((size_t) (tot[0] + nk + 1) * 8, (size_t) tot[0] * 8, R->s)) ||
@@ -578,7 +782,10 @@ int hand_back(Reader *R) {
 		off[m] = std::min(off[m], M.size);
 	}
 	for(int m = 0; m < R->mates; ++m) R->handed += (int64_t) (R->m[m].size - off[m]);
-	return kmahip_ingest_open_at(R->path[0].c_str(), off[0], R->mates == 2 ? R->path[1].c_str() : nullptr, off[1], &R->trim, R->phred, R->n_read, R->n_kept, &R->host);
+	int rc = kmahip_ingest_open_at(R->path[0].c_str(), off[0], R->mates == 2 ? R->path[1].c_str() : nullptr, off[1], &R->trim, R->phred, R->n_read, R->n_kept, &R->host);
+	if(!rc && R->text) rc = kmahip_ingest_set_text(R->host, 1);
+	if(!rc && R->qc) rc = kmahip_ingest_set_qc(R->host, R->qc);          // (the same accumulator goes on, in stream order)
+	return rc;
 }
 
 }  // namespace
@@ -653,6 +860,9 @@ extern "C" int kmahip_ingest_dev_next(kmahip_ingest_dev *R, int64_t max_records,
 	HIP_TRY(hipSetDevice(R->device));
 	int rc = min_out(R);
 	if(rc) return rc;
+	R->started = true;
+	R->text_tot[0] = R->text_tot[1] = 0;
+	R->h_text[0].clear(); R->h_text[1].clear();
 	memset(batch, 0, sizeof *batch);
 	int64_t tot[4] = {0, 0, 0, 0};
 	int max_len = 0;
@@ -680,6 +890,11 @@ extern "C" int kmahip_ingest_dev_next(kmahip_ingest_dev *R, int64_t max_records,
 			tot[0] = n; tot[1] = hb.reads.seq_words; tot[2] = hb.reads.N_total; tot[3] = hb.name_off[n];
 			max_len = hb.reads.max_len;
 			batch->records = hb.records;
+			for(int k = 0; k < 2 && R->text; ++k) {
+				const char *tx = nullptr;
+				int64_t nb = 0;
+				if(!kmahip_ingest_text(R->host, k, &tx, &nb)) R->h_text[k].assign(tx, tx + nb);
+			}
 		}
 		if(rc) return rc;
 	} else {
@@ -712,11 +927,16 @@ extern "C" int kmahip_ingest_dev_next(kmahip_ingest_dev *R, int64_t max_records,
 		R->h_pair.resize((size_t) tot[0]);
 		if(tot[0]) HIP_TRY(hipMemcpyAsync(R->h_pair.data(), R->o_pair.p, (size_t) tot[0], hipMemcpyDeviceToHost, R->s));
 		HIP_TRY(hipMemcpyAsync(R->h_small + 8, d_max_len, sizeof(int), hipMemcpyDeviceToHost, R->s));
+		for(int k = 0; k < 2 && R->text; ++k) {
+			R->h_text[k].resize((size_t) R->text_tot[k]);
+			if(R->text_tot[k]) HIP_TRY(hipMemcpyAsync(R->h_text[k].data(), R->d_text[k].p, (size_t) R->text_tot[k], hipMemcpyDeviceToHost, R->s));
+		}
 		HIP_TRY(hipStreamSynchronize(R->s));
 		max_len = *(const int *) (R->h_small + 8);
 		batch->records = records;
 		R->n_kept += records;
 		R->ms_kernel += ms_since(t0) - (R->ms_read + R->ms_copy - io0);
+		if(R->qc) kmahip_qc_end_reader(R->qc, R->mates == 2, R->phred);
 		if(to_host) {
 			if((rc = hand_back(R))) return rc;
 			// what the device made of the records before the odd one is this batch; with nothing in hand the host reader answers now
@@ -729,6 +949,43 @@ extern "C" int kmahip_ingest_dev_next(kmahip_ingest_dev *R, int64_t max_records,
 	batch->reads.N = R->o_N.as<int32_t>(); batch->reads.N_off = R->o_N_off.as<int64_t>();
 	batch->reads.seq_words = tot[1]; batch->reads.N_total = tot[2]; batch->reads.max_len = max_len;
 	batch->names = R->o_names.p; batch->name_off = R->o_name_off.as<int64_t>(); batch->pair = R->h_pair.data();
+	return KMAHIP_OK;
+}
+
+// kmahip_ingest_set_qc for the device reader: from now on the records kernel's -qc instantiation runs, s1_qc_kernel reduces every pass
+// and the accumulator is fed pass by pass, in stream order; the host reader that takes over at an odd record is given it as well
+extern "C" int kmahip_ingest_dev_set_qc(kmahip_ingest_dev *R, kmahip_qc *qc) {
+	if(!R || !qc) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(R->started) { kmahip_set_error("a QC accumulator is attached before the first batch is read"); return KMAHIP_EINVAL; }
+	if(R->trim.min_len < 1) { kmahip_set_error("a QC report needs a minimum length of 1 at least (the reference divides by the length of a kept read)"); return KMAHIP_EINVAL; }
+	HIP_TRY(hipSetDevice(R->device));
+	int rc = R->qstat.ensure(sizeof(QcStat), 0, R->s);
+	if(rc) return rc;
+	HIP_TRY(hipMemsetAsync(R->qstat.p, 0, sizeof(QcStat), R->s));
+	HIP_TRY(hipStreamSynchronize(R->s));
+	if(!R->h_qstat) HIP_TRY(hipHostMalloc((void **) &R->h_qstat, sizeof(QcStat), hipHostMallocDefault));
+	R->qc = qc;
+	kmahip_qc_end_reader(qc, R->mates == 2, R->phred);
+	return KMAHIP_OK;
+}
+
+extern "C" void kmahip_ingest_dev_qc_timing(const kmahip_ingest_dev *R, double ms[2]) {
+	if(ms) { ms[0] = R ? R->ms_qc_copy : 0; ms[1] = R ? R->ms_qc_bin : 0; }
+}
+
+// kmahip_ingest_set_text / kmahip_ingest_text for the device reader: s1_fastq_kernel writes the text of every pass, the batch's text
+// comes back with the batch (HOST memory, valid until the next call); the host reader's part of an odd file is its own text
+extern "C" int kmahip_ingest_dev_set_text(kmahip_ingest_dev *R, int on) {
+	if(!R) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(R->started) { kmahip_set_error("the text sink is set before the first batch is read"); return KMAHIP_EINVAL; }
+	R->text = on != 0;
+	return KMAHIP_OK;
+}
+
+extern "C" int kmahip_ingest_dev_text(const kmahip_ingest_dev *R, int stream, const char **text, int64_t *bytes) {
+	if(!R || !text || !bytes || stream < 0 || stream > 1) { kmahip_set_error("bad argument"); return KMAHIP_EINVAL; }
+	*text = R->h_text[stream].empty() ? "" : R->h_text[stream].data();
+	*bytes = (int64_t) R->h_text[stream].size();
 	return KMAHIP_OK;
 }
 
@@ -775,6 +1032,8 @@ extern "C" void kmahip_ingest_dev_close(kmahip_ingest_dev *R) {
 		for(int k = 0; k < kmahip_ingest_dev::NPIN; ++k) { if(R->pin[k]) (void) hipHostFree(R->pin[k]); if(R->pin_free[k]) (void) hipEventDestroy(R->pin_free[k]); }
 		if(R->pass_done) (void) hipEventDestroy(R->pass_done);
 		if(R->h_small) (void) hipHostFree(R->h_small);
+		if(R->h_qstat) (void) hipHostFree(R->h_qstat);
+		if(R->qc && getenv("KMAHIP_DEBUG_TIMING")) fprintf(stderr, "[kmahip] ingest_dev: QC report: %.1f ms fetching the counted sequences, %.1f ms summing and binning them on the host\n", R->ms_qc_copy, R->ms_qc_bin);
 	}
 	hipStream_t s = R->s, cs = R->cs;
 	delete R;                                    // (the device arrays)

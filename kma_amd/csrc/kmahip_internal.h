@@ -206,6 +206,18 @@ struct kmahip_ws {
 struct KmaAnk { int score, weight, score_len, len_len; unsigned start, end; uint32_t values; int descend; };
 
 void kmahip_set_error(const char *fmt, ...);
+// The QC accumulator (qc.hip; kmahip_qc_* of kmahip.h) as the two readers feed it, always in stream order.
+//   kmahip_qc_add_seq     update_QCstat (qc.c:85-104) for one counted sequence
+//   kmahip_qc_add_pass    the same for a run of counted sequences whose integer sums and length histogram (512 bins at len >> res)
+//                         were reduced elsewhere (s1_qc_kernel): sp[i] is added to Eeq and binned by the host's log10, in order
+//   kmahip_qc_add_read    what run_input* and the head of phredStat count: sequences read with their bases, records read / kept
+//   kmahip_qc_end_reader  the phred scale a reader leaves behind (runinput.c:451, 590-592, 715-717)
+struct KmaQcPair { double sp; int32_t len, pad_; };
+void kmahip_qc_add_seq(kmahip_qc *qc, int len, int gc, int ns, double sp);
+void kmahip_qc_add_pass(kmahip_qc *qc, uint64_t count, uint64_t bp, uint64_t gc, uint64_t ns, int maxlen, const uint32_t *hist, int res,
+                        const KmaQcPair *pairs, size_t n_pairs);
+void kmahip_qc_add_read(kmahip_qc *qc, uint64_t org_count, uint64_t org_bp, uint64_t org_frag, uint64_t frag);
+void kmahip_qc_end_reader(kmahip_qc *qc, bool paired, int phred);
 // <prefix>.comp.b as read from disk (db.hip: kmahip_comp_read): keys[i] is the i-th k-mer, vidx[i] the offset of its value list in
 // `values` (u16 or u32 elements: count, then the sorted template ids); n_hdr is the header's n, n the k-mers actually there
 struct KmaComp {
