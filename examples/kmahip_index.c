@@ -6,6 +6,11 @@
  *
  *     kmahip_index -i genes.fsa -o genes [-k 16] [-deCon host.fsa phix.fsa]
  *     kmahip_index -i genes.fsa -o genes_sparse -Sparse TG [-ML 100]
+ *     kmahip_index -i genes.fsa -o genes_thin -Sparse TG -hq 0.9 -ht 0.9 -and > clusters.tsv
+ *
+ * -hq / -ht / -and (index.c:309-350, qualcheck.c:81-324): homology reduction of a sparse index over kmahip_index_build_sparse_hom; a
+ * template too similar to those kept before it gets no id, and every template that reaches the gates gets a cluster line on standard
+ * output. Without -Sparse the three options are taken without effect, as in the reference (updateDBs never calls QualCheck).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,7 +19,7 @@
 #include "kmahip.h"
 
 #define USAGE "usage: kmahip_index (-i <fasta> [<fasta> ...] | -batch <file of paths>) -o <index prefix> [-k <k-mer length, 4 ... 16>] " \
-              "[-deCon <fasta> [<fasta> ...]] [-Sparse [<prefix>|-] [-ML <minimum length>]]\n"
+              "[-deCon <fasta> [<fasta> ...]] [-Sparse [<prefix>|-] [-ML <minimum length>] [-hq <query homology, 0 ... 1>] [-ht <template homology, 0 ... 1>] [-and]]\n"
 
 /* index.c:451-474: the letters the reference's table maps to 0 ... 3; anything else, or nothing at all, is no prefix */
 static int valid_prefix(const char *s) {
@@ -28,6 +33,8 @@ int main(int argc, char **argv) {
 	const char *inputs[256], *decon[256], *out = NULL, *sparse = NULL;
 	int n_in = 0, n_decon = 0, decon_opt = 0, k = 16, ml_opt = 0;
 	long min_len = 0;
+	double hom_q = 1.0, hom_t = 1.0;
+	int and_mode = 0;
 	for(int a = 1; a < argc; ++a) {
 		if(!strcmp(argv[a], "-i")) { while(a + 1 < argc && argv[a + 1][0] != '-' && n_in < 256) inputs[n_in++] = argv[++a]; }
 		else if(!strcmp(argv[a], "-batch") && a + 1 < argc) {          /* index.c:351-401: a file that lists the inputs, one path a line */
@@ -63,13 +70,28 @@ int main(int argc, char **argv) {
 			if(min_len <= 0) { fprintf(stderr, "# Invalid minimum length parsed, using default\n"); min_len = 0; }
 			if(min_len > 0x7FFFFFFF) min_len = 0x7FFFFFFF;
 		}
+		else if(!strcmp(argv[a], "-and")) and_mode = 1;          /* index.c:309 */
+		else if(!strcmp(argv[a], "-hq") || !strcmp(argv[a], "-ht")) {          /* index.c:327-350: no value behind it: nothing happens */
+			double *dst = argv[a][2] == 'q' ? &hom_q : &hom_t;
+			if(a + 1 < argc) {
+				char *end;
+				*dst = strtod(argv[a + 1], &end);
+				if(*end) { fprintf(stderr, "Invalid argument at \"%s\".\n", argv[a]); return 1; }
+				if(*dst < 0) { fprintf(stderr, "Invalid -hq\n"); *dst = 1.0; }          /* (these words for both options) */
+				++a;
+			}
+		}
 		else { fprintf(stderr, USAGE); return 2; }
 	}
 	/* what is not built is refused by name, before a file or the device is opened */
 	if(sparse && decon_opt) { fprintf(stderr, "kmahip_index: -Sparse is not built for -deCon (deConNode_sparse)\n"); return 2; }
 	if(ml_opt && !sparse) { fprintf(stderr, "kmahip_index: -ML is not built for a build without -Sparse\n"); return 2; }
+	if(sparse && ml_opt && min_len > 0 && hom_t < 1) {
+		fprintf(stderr, "kmahip_index: -ht is not built with -ML (templateCheck leaves its scores uncleared behind a template below -ML, qualcheck.c:287)\n");
+		return 2;
+	}
 	if(!n_in || !out) { fprintf(stderr, "kmahip_index: -i and -o are required\n"); return 2; }
-	if(kmahip_init(0) || (sparse ? kmahip_index_build_sparse(inputs, n_in, out, k, k, sparse, (int) min_len)
+	if(kmahip_init(0) || (sparse ? kmahip_index_build_sparse_hom(inputs, n_in, out, k, k, sparse, (int) min_len, hom_q, hom_t, and_mode, "-")
 	                      : decon_opt ? kmahip_index_build_decon(inputs, n_in, decon, n_decon, out, k) : kmahip_index_build(inputs, n_in, out, k))) {
 		fprintf(stderr, "kmahip_index: %s\n", kmahip_last_error()); return 1;
 	}

@@ -640,9 +640,37 @@ int kmahip_index_build_decon(const char *const *fasta_paths, int n_files, const 
  * builder's own bucket layout; .seq.b and .name as kmahip_index_build writes them, over the templates that stayed.
  * kmersize <= 0: 16. kmerindex <= 0: kmersize (what -k sets). KMAHIP_EINVAL, the reason in kmahip_last_error: k outside 4 ... 16,
  * a prefix of more than 16 bases, a null prefix, an empty one or one with a letter that is no A, C, G, T (IUPAC codes as the
- * reference folds them) -- "Invalid prefix." as the reference says. Not covered: -deCon on a sparse index, -ht / -hq, appending. */
+ * reference folds them) -- "Invalid prefix." as the reference says. Not covered: -deCon on a sparse index, appending; -ht / -hq
+ * have their own entry point below. */
 int kmahip_index_build_sparse(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize, int kmerindex,
                               const char *prefix_text, int min_len);
+/* `kma index ... -Sparse <prefix | -> -hq x -ht y [-and]` (index.c:309-350, 607-613; qualcheck.c:81-324: queryCheck, templateCheck,
+ * called from updateDBs_sparse alone, updateindex.c:103): homology reduction while the sparse index is built. Templates come in file
+ * order; one that reaches the length gates is scored against the templates kept before it. For a kept template j, Scores_tot[j] =
+ * the windows of the new template, repeats and all, whose k-mer j holds, Scores[j] = its distinct k-mers that j holds; thisQ =
+ * 1.0 * Scores_tot[j] / thisKlen (its windows on both strands), thisT = 1.0 * Scores[j] / ulength[j]; bestQ, bestT their maxima, a tie
+ * going to the template met first in the walk (forward strand, then the reverse complement; inside one value list the lower id).
+ * hom_t < 1 selects templateCheck: the template stays iff cmp(bestT < hom_t, bestQ < hom_q), cmp = OR, AND when and_mode != 0.
+ * Otherwise hom_q < 1 selects queryCheck: it stays iff bestQ < hom_q. Otherwise the build is kmahip_index_build_sparse's. A template
+ * that goes gets no id, and the ids behind it move up. The pairs are counted on the device (homology.hip), the chain of decisions is
+ * the host's; the files are those of kmahip_index_build_sparse over the templates that stayed.
+ * report_path: the cluster lines the reference prints to standard output, one per template whose windows reach MinKlen, in file
+ * order: queryCheck `name\t<its id, or templateQ when it goes>\t%f\t%d` (bestQ, templateQ), templateCheck six fields (`name`, its
+ * id or -- when it goes -- templateQ if bestT < hom_t, else templateT; bestQ, templateQ, bestT, templateT). NULL: no report; "-":
+ * standard output. The lines are written before an empty database is reported (KMAHIP_EFORMAT, "DB is empty"; hom_q = 0 keeps nothing).
+ * KMAHIP_EINVAL besides kmahip_index_build_sparse's: a threshold below 0; hom_t < 1 with a min_len that takes effect (templateCheck
+ * returns at qualcheck.c:287 without clearing its scores, so the reference's later answers rest on stale state).
+ * KMAHIP_HOM_BLOCK (columns a workgroup sums at once) and KMAHIP_HOM_PAIRS (first capacity of the pair list) are test knobs. */
+int kmahip_index_build_sparse_hom(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize, int kmerindex,
+                                  const char *prefix_text, int min_len, double hom_q, double hom_t, int and_mode, const char *report_path);
+/* Test and timing hooks of the homology counts. kmahip_test_index_hom_rows runs the build up to the report and writes no file: out
+ * takes seven words per candidate template (one longer than MinLen) in file order -- stays, thisKlen, max Scores_tot and its template,
+ * Scores and ulength of the best thisT and its template, the templates numbered in file order from 1 (0: none) --, *n_rows how many
+ * there are (KMAHIP_EINVAL with *n_rows set when cap_rows is too small). kmahip_test_index_hom_timing: what the last homology step of
+ * this process took by the host's clock: ms of pass 1, of the host's chain of decisions, of pass 2, and the pairs pass 1 listed. */
+int kmahip_test_index_hom_rows(const char *const *fasta_paths, int n_files, int kmersize, const char *prefix_text, int min_len, double hom_q,
+                               double hom_t, int and_mode, uint32_t *out, int64_t cap_rows, int64_t *n_rows);
+int kmahip_test_index_hom_timing(double *out4);
 
 /* ---- stage 1: FASTQ / FASTA ingest into packed read batches -------------------------------------------
  * Host code (zlib for .gz, plain files read as they are): the record parser of FileBuffgetFq / FileBuffgetFsa

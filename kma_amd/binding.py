@@ -389,11 +389,13 @@ def test_lane_down(values, w):
     return out
 
 
-def index_build(fasta_paths, out_prefix, k=16, decon=None, sparse=None, min_len=0):
+def index_build(fasta_paths, out_prefix, k=16, decon=None, sparse=None, min_len=0, hom_q=1.0, hom_t=1.0, hom_and=False, report=None):
     """kmahip_index_build: the four index files from FASTA file(s) (needs a GPU: the k-mers are sorted on the device).
     decon: contamination FASTA file(s) (`kma index -deCon`) -> kmahip_index_build_decon, which writes <out_prefix>.decon.comp.b too.
     sparse: a prefix such as "TG", or "-" for none (`kma index -Sparse`) -> kmahip_index_build_sparse, the index SparseDB maps against;
-    min_len: its -ML (0: the default). A sparse decon index is not built, and -ML belongs to the sparse build alone."""
+    min_len: its -ML (0: the default). A sparse decon index is not built, and -ML belongs to the sparse build alone.
+    hom_q, hom_t, hom_and, report: `-hq`, `-ht`, `-and` of a sparse build (kmahip_index_build_sparse_hom) and the file that takes the
+    cluster lines the reference prints to standard output; without sparse they have no effect, as in the reference."""
     paths = [os.fsencode(p) for p in ([fasta_paths] if isinstance(fasta_paths, (str, bytes)) else fasta_paths)]
     arr = (C.c_char_p * len(paths))(*paths)
     L = lib()
@@ -402,7 +404,14 @@ def index_build(fasta_paths, out_prefix, k=16, decon=None, sparse=None, min_len=
             raise ValueError("index_build: sparse with decon is not built")
         L.kmahip_index_build_sparse.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int]
         L.kmahip_index_build_sparse.restype = C.c_int
-        _check(L.kmahip_index_build_sparse(arr, len(paths), os.fsencode(out_prefix), int(k), int(k), os.fsencode(sparse), int(min_len)))
+        if hom_q == 1.0 and hom_t == 1.0 and not hom_and and report is None:
+            _check(L.kmahip_index_build_sparse(arr, len(paths), os.fsencode(out_prefix), int(k), int(k), os.fsencode(sparse), int(min_len)))
+            return
+        L.kmahip_index_build_sparse_hom.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double, C.c_double,
+                                                    C.c_int, C.c_char_p]
+        L.kmahip_index_build_sparse_hom.restype = C.c_int
+        _check(L.kmahip_index_build_sparse_hom(arr, len(paths), os.fsencode(out_prefix), int(k), int(k), os.fsencode(sparse), int(min_len), float(hom_q),
+                                               float(hom_t), int(bool(hom_and)), None if report is None else os.fsencode(report)))
         return
     if min_len:
         raise ValueError("index_build: min_len (-ML) is built for sparse indexes only")
@@ -416,6 +425,28 @@ def index_build(fasta_paths, out_prefix, k=16, decon=None, sparse=None, min_len=
     L.kmahip_index_build.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_int]
     L.kmahip_index_build.restype = C.c_int
     _check(L.kmahip_index_build(arr, len(paths), os.fsencode(out_prefix), int(k)))
+
+
+def index_hom_rows(fasta_paths, k=16, sparse="-", min_len=0, hom_q=1.0, hom_t=1.0, hom_and=False):
+    """the test hook of the homology counts (kmahip_test_index_hom_rows): [n candidate templates, 7] uint32 in file order -- stays, thisKlen,
+    max Scores_tot, templateQ, Scores and ulen of the best thisT, templateT (templates by file order, 1 ..; 0: none). No file is written."""
+    paths = [os.fsencode(p) for p in ([fasta_paths] if isinstance(fasta_paths, (str, bytes)) else fasta_paths)]
+    arr = (C.c_char_p * len(paths))(*paths)
+    L = lib()
+    L.kmahip_test_index_hom_rows.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int64,
+                                             C.POINTER(C.c_int64)]
+    L.kmahip_test_index_hom_rows.restype = C.c_int
+    cap = 1 << 16
+    while True:
+        out = np.zeros((cap, 7), np.uint32)
+        n = C.c_int64(0)
+        rc = L.kmahip_test_index_hom_rows(arr, len(paths), int(k), os.fsencode(sparse), int(min_len), float(hom_q), float(hom_t), int(bool(hom_and)), _p(out), cap,
+                                          C.byref(n))
+        if rc and n.value > cap:
+            cap = n.value
+            continue
+        _check(rc)
+        return out[:n.value].copy()
 
 
 class QCStats(C.Structure):

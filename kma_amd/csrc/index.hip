@@ -8,7 +8,9 @@
 // from the growth history of its in-memory hash table and carry no meaning for a reader).
 // Covered: the default hashed form, k <= 16, no minimizers / homopolymer compression, no -batch.
 // -Sparse (kmahip_index_build_sparse; index.c:451-474 / 576-613, updateindex.c:79-199, qualcheck.c:31-79): index_build_sparse below,
-// with its host side in index_host.h. The plain build's kernel, host pass and files are as they were.
+// with its host side in index_host.h. The plain build's kernel, host pass and files are as they were. With -hq / -ht
+// (kmahip_index_build_sparse_hom; qualcheck.c:81-324) the templates too similar to those kept before go as well: the pairs are
+// counted in homology.hip between the windows and the renumbering.
 // -deCon (kmahip_index_build_decon; index.c:676-729, decon.c:77-227): every k-mer of either strand of the contamination records
 // becomes a key of the pseudo-template DB_size and joins the same sort; the host pass runs twice over the sorted pairs, once
 // without those keys (<prefix>.comp.b, as ever) and once with them (<prefix>.decon.comp.b), where a k-mer that only the
@@ -18,6 +20,7 @@
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
+#include <chrono>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -376,8 +379,55 @@ int index_build(const char *const *fasta_paths, int n_files, const char *const *
 // under the ids of the file order (index_sparse_keys_kernel), the host picks the templates that stay from n_t window counts, the keys
 // are renumbered where a template went (index_sparse_remap_kernel) and go through the plain build's sort and unique, and the unique
 // pairs are counted per template (index_sparse_ulen_kernel)
-int index_build_sparse(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize, int kmerindex, const char *prefix_text, int min_len) {
-	if(!fasta_paths || n_files <= 0 || !out_prefix) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+double g_hom_ms[4] = {0, 0, 0, 0};          // the last homology step: pass 1, resolve, pass 2 in ms; pairs listed
+
+// The homology step of a sparse build (QualCheck = queryCheck / templateCheck): the device counts the pairs (homology.hip), the host
+// settles who stays and writes the line of every template that reaches the gate (index_host.h). report_path: NULL none, "-" standard
+// output. capture (the test hook): seven words a candidate template: stays, thisKlen, then the row of pass 2 under file-order ids
+int index_sparse_homology(const unsigned long long *d_keys, int64_t n_keys, const int64_t *d_off, const std::vector<Tmpl> &tm, const std::vector<uint32_t> &slen,
+                          const SparseRule &rule, const HomRule &hom, const char *report_path, std::vector<uint8_t> &kept, std::vector<uint32_t> *capture) {
+	KmaHom *h = nullptr;
+	int rc = kmahip_hom_open(d_keys, n_keys, d_off, slen, rule.prefix_len + rule.k, rule.MinKlen, &h);
+	if(rc) return rc;
+	struct Guard { KmaHom *h; ~Guard() { kmahip_hom_close(h); } } guard{h};
+	std::vector<KmaHomPair> pairs;
+	std::vector<KmaHomRow> rows;
+	// (each step ends with a copy to the host, so the host's clock times it: kmahip_test_index_hom_timing)
+	const auto t0 = std::chrono::steady_clock::now();
+	if((rc = kmahip_hom_pairs(h, hom.homQ, hom.homT, hom.mode() == 2, pairs))) return rc;
+	const auto t1 = std::chrono::steady_clock::now();
+	static_assert(sizeof(KmaHomPair) == 8, "a pair is two words");
+	hom_resolve(slen, rule, hom, (const uint32_t *) pairs.data(), pairs.size(), kept);
+	const auto t2 = std::chrono::steady_clock::now();
+	if((rc = kmahip_hom_best(h, kept, rows))) return rc;
+	const auto t3 = std::chrono::steady_clock::now();
+	g_hom_ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+	g_hom_ms[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
+	g_hom_ms[2] = std::chrono::duration<double, std::milli>(t3 - t2).count();
+	g_hom_ms[3] = (double) pairs.size();
+	FILE *f = nullptr;
+	if(report_path && !(f = strcmp(report_path, "-") ? fopen(report_path, "wb") : stdout)) { kmahip_set_error("cannot create %s", report_path); return KMAHIP_EIO; }
+	uint32_t next = 1;
+	std::vector<uint32_t> id_of(tm.size(), 0);
+	bool agree = true;
+	if(capture) capture->assign(tm.size() * 7, 0);
+	for(size_t t = 0; t < tm.size(); ++t) {
+		if(kept[t]) id_of[t] = next++;
+		const KmaHomRow &r = rows[t];
+		if(capture) { uint32_t *c = capture->data() + 7 * t; c[0] = kept[t]; c[1] = slen[t]; c[2] = r.tot; c[3] = r.jQ; c[4] = r.num; c[5] = r.den; c[6] = r.jT; }
+		if(!hom_eligible(slen[t], rule)) continue;
+		agree = hom_report_line(f, hom, tm[t].name.substr(0, tm[t].head).c_str(), id_of[t], r.tot, slen[t], r.jQ ? id_of[r.jQ - 1] : 0, r.num, r.den, r.jT ? id_of[r.jT - 1] : 0) && agree;
+	}
+	bool ok = true;
+	if(f) ok = (f == stdout ? fflush(f) == 0 : fclose(f) == 0) && !ferror(stdout);
+	if(!ok) { kmahip_set_error("writing the homology report %s failed", report_path); return KMAHIP_EIO; }
+	if(!agree) { kmahip_set_error("homology reduction: the winners of pass 2 contradict the flags of pass 1"); return KMAHIP_EDEVICE; }
+	return KMAHIP_OK;
+}
+
+int index_build_sparse(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize, int kmerindex, const char *prefix_text, int min_len,
+                       const HomRule *hom = nullptr, const char *report_path = nullptr, std::vector<uint32_t> *capture = nullptr) {
+	if(!fasta_paths || n_files <= 0 || (!out_prefix && !capture)) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
 	static const RefTable T;
 	SparseRule rule;
 	rule.k = kmersize > 0 ? kmersize : 16;
@@ -387,6 +437,9 @@ int index_build_sparse(const char *const *fasta_paths, int n_files, const char *
 	int rc = sparse_parse_prefix(prefix_text, T, rule);
 	if(rc) return rc;
 	sparse_set_gates(min_len, rule);
+	// templateCheck leaves at qualcheck.c:287 with its score arrays and found-k-mer set as they are when a template misses -ML's window
+	// count, so what the reference answers afterwards depends on stale state: not a rule to restate
+	if(hom && hom->mode() == 2 && rule.MinKlen > 1) { kmahip_set_error("sparse index: -ht with -ML is not built (templateCheck keeps stale scores behind a template below -ML)"); return KMAHIP_EINVAL; }
 	const int k = rule.k;
 	std::vector<Tmpl> tm;
 	std::vector<uint8_t> codes;
@@ -419,7 +472,13 @@ int index_build_sparse(const char *const *fasta_paths, int n_files, const char *
 	HIP_TRY(hipGetLastError());
 	std::vector<uint32_t> slen((size_t) n_t), new_id;
 	HIP_TRY(hipMemcpy(slen.data(), d_slen, (size_t) n_t * 4, hipMemcpyDeviceToHost));
-	const uint32_t n_kept = sparse_assign_ids(tm, slen, rule, new_id);
+	std::vector<uint8_t> kept;
+	const bool homology = hom && hom->mode();
+	if(homology) {
+		if((rc = index_sparse_homology(d_keys, n_keys, d_off, tm, slen, rule, *hom, report_path, kept, capture))) return rc;
+		if(!out_prefix) return KMAHIP_OK;
+	}
+	const uint32_t n_kept = sparse_assign_ids(tm, slen, rule, new_id, homology ? &kept : nullptr);
 	if(n_kept == 0) { kmahip_set_error("DB is empty: no template holds a k-mer behind the prefix"); return KMAHIP_EFORMAT; }
 	const uint32_t DB_size = n_kept + 1;
 	if(n_kept != (uint32_t) n_t) {
@@ -465,6 +524,44 @@ int index_build_sparse(const char *const *fasta_paths, int n_files, const char *
 extern "C" int kmahip_index_build_sparse(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize, int kmerindex,
                                          const char *prefix_text, int min_len) {
 	return index_build_sparse(fasta_paths, n_files, out_prefix, kmersize, kmerindex, prefix_text, min_len);
+}
+
+extern "C" int kmahip_index_build_sparse_hom(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize, int kmerindex,
+                                             const char *prefix_text, int min_len, double hom_q, double hom_t, int and_mode, const char *report_path) {
+	if(!out_prefix) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	HomRule hom;
+	hom.homQ = hom_q; hom.homT = hom_t; hom.and_mode = and_mode != 0;
+	if(!(hom_q >= 0) || !(hom_t >= 0)) { kmahip_set_error("homology thresholds %g, %g: not below 0", hom_q, hom_t); return KMAHIP_EINVAL; }
+	if(!hom.mode() && report_path && strcmp(report_path, "-")) {
+		// lengthCheck prints nothing: the report is there and empty
+		FILE *f = fopen(report_path, "wb");
+		if(!f || fclose(f)) { kmahip_set_error("cannot create %s", report_path); return KMAHIP_EIO; }
+	}
+	return index_build_sparse(fasta_paths, n_files, out_prefix, kmersize, kmerindex, prefix_text, min_len, &hom, report_path);
+}
+
+// the test hook of the homology counts: no file is written; out: seven words a candidate template in file order (stays, thisKlen, max
+// Scores_tot, its template, Scores and ulen of the max thisT, its template; templates by file order, 1 ..), *n_rows of them
+extern "C" int kmahip_test_index_hom_rows(const char *const *fasta_paths, int n_files, int kmersize, const char *prefix_text, int min_len, double hom_q, double hom_t,
+                                          int and_mode, uint32_t *out, int64_t cap_rows, int64_t *n_rows) {
+	HomRule hom;
+	hom.homQ = hom_q; hom.homT = hom_t; hom.and_mode = and_mode != 0;
+	if(!hom.mode() || !out || !n_rows) { kmahip_set_error("kmahip_test_index_hom_rows: bad argument"); return KMAHIP_EINVAL; }
+	std::vector<uint32_t> capture;
+	const int rc = index_build_sparse(fasta_paths, n_files, nullptr, kmersize, kmersize, prefix_text, min_len, &hom, nullptr, &capture);
+	if(rc) return rc;
+	*n_rows = (int64_t) (capture.size() / 7);
+	if(*n_rows > cap_rows) { kmahip_set_error("kmahip_test_index_hom_rows: %lld rows, room for %lld", (long long) *n_rows, (long long) cap_rows); return KMAHIP_EINVAL; }
+	memcpy(out, capture.data(), capture.size() * 4);
+	return KMAHIP_OK;
+}
+
+// what the last homology step of this process took: ms of pass 1 (with a regrown list: both launches), of the host's resolve and of
+// pass 2, and the pairs pass 1 listed
+extern "C" int kmahip_test_index_hom_timing(double *out4) {
+	if(!out4) return KMAHIP_EINVAL;
+	memcpy(out4, g_hom_ms, sizeof g_hom_ms);
+	return KMAHIP_OK;
 }
 
 extern "C" int kmahip_index_build(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize) {

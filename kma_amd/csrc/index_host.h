@@ -2,6 +2,8 @@
 // plain C++ program: the letter table, the FASTA parser with the sparse build's length gate, the prefix and -ML arithmetic of
 // index.c:451-474 / 576-613, the choice of the templates that stay (makeindex.c:225, updateindex.c:79-167, qualcheck.c:31-79) and
 // the writers of .length.b / .seq.b / .name over the templates that stayed (updateAnnots_sparse, makeindex.c:262-276).
+// With -hq / -ht (queryCheck, templateCheck, qualcheck.c:81-324) also the serial part of homology reduction: who stays, given the pairs
+// the device flagged, and the line each template gets.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -19,6 +21,7 @@ struct Tmpl {
 	std::string name;
 	size_t at = 0;       // first base in the concatenated code array
 	int len = 0;
+	size_t head = 0;     // the bytes of name that are the record's header (" B<n>" may follow)
 };
 
 // index.c:128-170
@@ -94,8 +97,9 @@ int sparse_parse_fasta(const std::vector<uint8_t> &raw, const char *path, const 
 		const size_t len = b - a;
 		if(len > 0x7FFFFFFFu) { kmahip_set_error("%s: a template of %zu bases", path, len); return KMAHIP_EFORMAT; }
 		if(!((size_t) min_len < len)) { codes.resize(at); continue; }              // "# Skipped"
+		const size_t head = name.size();
 		if(bias > 0) name += " B" + std::to_string(bias);
-		Tmpl t; t.name = name; t.at = at; t.len = (int) len;
+		Tmpl t; t.name = name; t.at = at; t.len = (int) len; t.head = head;
 		tm.push_back(t);
 	}
 	return KMAHIP_OK;
@@ -104,15 +108,68 @@ int sparse_parse_fasta(const std::vector<uint8_t> &raw, const char *path, const 
 // The templates that stay, from their window counts over both strands (slen[t], t = 0 .. n_t - 1 in file order): lengthCheck asks
 // for MinKlen windows (without a prefix: of (len - k + 1) * 2, whatever N's there are), update_DB for one at least. new_id[t] = the
 // id of the template in the index, 1 .. , or 0 when it is skipped; every template behind a skipped one moves up. -> how many stay
-inline uint32_t sparse_assign_ids(const std::vector<Tmpl> &tm, const std::vector<uint32_t> &slen, const SparseRule &r, std::vector<uint32_t> &new_id) {
+// kept (a homology build, hom_resolve): the templates that stay are those it marks, which passed queryCheck's / templateCheck's gate
+inline uint32_t sparse_assign_ids(const std::vector<Tmpl> &tm, const std::vector<uint32_t> &slen, const SparseRule &r, std::vector<uint32_t> &new_id,
+                                  const std::vector<uint8_t> *kept = nullptr) {
 	new_id.assign(tm.size(), 0);
 	uint32_t next = 1;
 	for(size_t t = 0; t < tm.size(); ++t) {
+		if(kept) { if((*kept)[t]) new_id[t] = next++; continue; }
 		const int64_t have = r.prefix_len ? (int64_t) slen[t] : ((int64_t) tm[t].len - r.k + 1) * 2;
 		if(have < r.MinKlen || slen[t] == 0) continue;
 		new_id[t] = next++;
 	}
 	return next - 1;
+}
+
+// ---- homology reduction: `-hq x -ht y [-and]` (index.c:309-350, 607-613; queryCheck / templateCheck, qualcheck.c:81-324) -------
+// The reference scores a new template against the templates kept so far and keeps it when its best ratios stay below the thresholds.
+// The device counts every pair (homology.hip); what is here is the serial part: who stays, and the line each template gets.
+struct HomRule {
+	double homQ = 1.0, homT = 1.0;
+	bool and_mode = false;                  // cmp: OR by default, AND under -and
+	int mode() const { return homT < 1 ? 2 : homQ < 1 ? 1 : 0; }          // 2 templateCheck, 1 queryCheck, 0 lengthCheck (index.c:607-613)
+	// does a template stay whose best ratios are below the thresholds as given (qualcheck.c:181, :314)
+	bool stays(bool q_below, bool t_below) const { return mode() == 1 ? q_below : and_mode ? (t_below && q_below) : (t_below || q_below); }
+};
+
+// queryCheck and templateCheck count the windows themselves, N's and all, with a prefix and without (thisKlen < MinKlen: no line, no id)
+inline bool hom_eligible(uint32_t windows, const SparseRule &r) { return windows > 0 && (int64_t) windows >= r.MinKlen; }
+
+// Who stays, in file order. pairs: n_pairs times (row, column * 4 + flags) in any order, the flags of a pair being 1: thisQ >= homQ,
+// 2: thisT >= homT (every pair with a flag is there, whoever is kept). bestQ < homQ fails iff a kept column carries flag 1, bestT <
+// homT iff one carries flag 2: the maxima need not be known. kept[t] = 1 for the templates that get an id
+inline void hom_resolve(const std::vector<uint32_t> &slen, const SparseRule &r, const HomRule &hom, const uint32_t *pairs, size_t n_pairs, std::vector<uint8_t> &kept) {
+	const size_t n_t = slen.size();
+	std::vector<size_t> start(n_t + 1, 0);
+	for(size_t p = 0; p < n_pairs; ++p) ++start[(size_t) pairs[2 * p] + 1];
+	for(size_t t = 0; t < n_t; ++t) start[t + 1] += start[t];
+	std::vector<uint32_t> by_row(n_pairs);
+	{
+		std::vector<size_t> at(start.begin(), start.end() - 1);
+		for(size_t p = 0; p < n_pairs; ++p) by_row[at[pairs[2 * p]]++] = pairs[2 * p + 1];
+	}
+	kept.assign(n_t, 0);
+	for(size_t t = 0; t < n_t; ++t) {
+		if(!hom_eligible(slen[t], r)) continue;
+		unsigned seen = 0;
+		for(size_t p = start[t]; p < start[t + 1]; ++p) if(kept[by_row[p] >> 2]) seen |= by_row[p] & 3u;
+		// (a maximum over no column is 0, which a threshold of 0 does not let pass: -hq 0 keeps nothing)
+		kept[t] = hom.stays(!(seen & 1u) && 0 < hom.homQ, !(seen & 2u) && 0 < hom.homT);
+	}
+}
+
+// The line of one template (qualcheck.c:182-186, :315-318) from the integers of its row: Scores_tot of templateQ over thisKlen, Scores
+// over ulen of templateT; idQ, idT: the winners' ids in the index (0: none). id: the template's own id when it stays, else 0.
+// -> whether the doubles formed here say the same as `id` (the device's flags and these ratios are one expression)
+inline bool hom_report_line(FILE *f, const HomRule &hom, const char *name, uint32_t id, uint32_t tot, uint32_t klen, uint32_t idQ, uint32_t num, uint32_t den, uint32_t idT) {
+	const double bestQ = tot ? 1.0 * tot / klen : 0.0, bestT = num ? 1.0 * num / den : 0.0;
+	const bool stays = hom.stays(bestQ < hom.homQ, bestT < hom.homT);
+	if(f) {
+		if(hom.mode() == 1) fprintf(f, "%s\t%d\t%f\t%d\n", name, (int) (id ? id : idQ), bestQ, (int) idQ);
+		else fprintf(f, "%s\t%d\t%f\t%d\t%f\t%d\n", name, (int) (id ? id : (bestT < hom.homT) ? idQ : idT), bestQ, (int) idQ, bestT, (int) idT);
+	}
+	return stays == (id != 0);
 }
 
 // .length.b of a sparse index (makeindex.c:262-270): DB_size, lengths (slot 0: kmerindex), slengths, ulengths (slot 0: 0).

@@ -229,6 +229,18 @@ struct KmaComp {
 };
 int kmahip_comp_read(const std::string &comp, bool allow_sparse, KmaComp *c);
 int kmahip_cmp(bool t, bool q);          // conclave.hip: the reference's `cmp` (or / and / true, kmahip_set_cmp)
+// The homology counts of a sparse index build (homology.hip; `kma index -Sparse ... -hq / -ht`, qualcheck.c:81-324), over the window
+// keys of index_sparse_keys_kernel as they are before any template is renumbered. Rows and columns are templates in file order.
+//   kmahip_hom_open    sorts the two views of the windows; slen[t]: the windows of template t, w: prefix_len + k, min_klen: MinKlen
+//   kmahip_hom_pairs   pass 1: the pairs whose thisQ / thisT reach a threshold, whatever is kept
+//   kmahip_hom_best    pass 2: every row's winners over the columns with kept[j] != 0
+struct KmaHom;
+struct KmaHomPair { uint32_t row, jf; };                        // jf: column * 4 + (thisQ >= homQ) + 2 * (thisT >= homT)
+struct KmaHomRow { uint32_t tot, jQ, num, den, jT; };           // max Scores_tot and its template; Scores, ulen and template of the max thisT (ids 1 .., 0: none)
+int kmahip_hom_open(const unsigned long long *d_keys, int64_t n_keys, const int64_t *d_off, const std::vector<uint32_t> &slen, int w, int64_t min_klen, KmaHom **out);
+int kmahip_hom_pairs(KmaHom *h, double homQ, double homT, bool use_t, std::vector<KmaHomPair> &pairs);
+int kmahip_hom_best(KmaHom *h, const std::vector<uint8_t> &kept, std::vector<KmaHomRow> &rows);
+void kmahip_hom_close(KmaHom *h);
 #define HIP_TRY(expr) do { hipError_t e__ = (expr); if(e__ != hipSuccess) { \
 	kmahip_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); return KMAHIP_EDEVICE; } } while(0)
 // the workspace's counter block, made (and zeroed) by whichever stage runs first
