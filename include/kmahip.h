@@ -1167,6 +1167,16 @@ int kmahip_ws_scan_queue_counts(kmahip_ws *ws, void *stream, unsigned long long 
  * out[5] hand-ons to the general kernel over the queues: tasks that gave up behind a problem they had queued, plus entries that
  * found no room (KMAHIP_ALIGN_DQ_CAP=<n> in the environment caps the entries per queue: tests and timing only). */
 int kmahip_ws_align_queue_counts(kmahip_ws *ws, void *stream, unsigned long long out[6]);
+/* The traceback of reads up to 1 kb settles in a first pass every read whose DP problems are provably ungapped and puts the others
+ * off to a pass with move matrices: out[0] the reads the last such launch on the workspace put off, out[1] those of them that the pass
+ * with the matrices in LDS (KMAHIP_TRACE_LDS=1 in the environment) put off once more. Both 0 after a launch of that kernel
+ * in one pass (a scheme without the shortcut, KMAHIP_TRACE=lanes1); the long-read pipeline leaves them as they were. Read it before
+ * another stage is launched on the workspace. */
+int kmahip_ws_trace_put_off(kmahip_ws *ws, void *stream, unsigned long long out[2]);
+/* The scoring schemes under which stage 3a and the traceback may take a DP problem's diagonal for its answer without the matrix: the
+ * most mismatches between two seeds up to which they do, -1 for a scheme under which they never do (host arithmetic; both stages call
+ * this one function). */
+int kmahip_diag_gap_m_max(const kmahip_rewards *rw);
 
 /* work figures of the last long-read trace call on this workspace (kmahip_align_trace_mt1*, kmahip_run_mt1, or the trace stage
  * on reads over 1 kb): DP problems solved, their cells (rows x columns; rows x (band + 1) for banded ones), MEMs of the chained

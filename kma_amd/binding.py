@@ -377,6 +377,15 @@ def test_mapq(best, second, w):
     return out
 
 
+def diag_gap_m_max(rw):
+    """kmahip_diag_gap_m_max (host arithmetic): the most mismatches on a link's diagonal up to which stage 3a and the traceback skip the
+    DP matrix under the scoring scheme of a Rewards, -1 where they never do"""
+    L = lib()
+    L.kmahip_diag_gap_m_max.argtypes = [C.POINTER(Rewards)]
+    L.kmahip_diag_gap_m_max.restype = C.c_int
+    return int(L.kmahip_diag_gap_m_max(C.byref(rw)))
+
+
 def test_lane_down(values, w):
     """kmahip_test_lane_down (a test hook): what each of a wavefront's 64 lanes receives from the sweep's neighbour move"""
     v = np.ascontiguousarray(values, np.int32)
@@ -989,6 +998,14 @@ class KmaHipDB:
         out = (C.c_ulonglong * 6)()
         _check(lib().kmahip_ws_align_queue_counts(self.ws, C.c_void_p(stream or 0), out))
         return dict(zip(("wide", "mid", "narrow", "tiny", "pending", "handed_on"), (int(x) for x in out)))
+
+    def get_trace_put_off(self, stream=None):
+        """reads the first pass of the last two-pass traceback launch put off, and those the LDS pass (KMAHIP_TRACE_LDS=1) put off again"""
+        out = (C.c_ulonglong * 2)()
+        L = lib()
+        L.kmahip_ws_trace_put_off.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]
+        _check(L.kmahip_ws_trace_put_off(self.ws, C.c_void_p(stream or 0), out))
+        return int(out[0]), int(out[1])
 
     def get_align_stats(self, stream=None) -> AlignStats:
         st = AlignStats()

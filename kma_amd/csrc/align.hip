@@ -402,6 +402,21 @@ __device__ __forceinline__ bool dp_enqueue(const Lane &L, int cls, int k, int t_
 	return true;
 }
 
+// The scoring schemes under which the diagonal of a DP problem can be proven its only optimum (nw_diagonal here, diag_emit and its
+// proof below), decided once for stage 3a and for the traceback's first pass: a plain match / mismatch table -- every pair of
+// different bases scores MM: with -transition != -transversion MM is their mean and no entry of the table -- and M > 0 > MM > W1,
+// U < 0, MM - M > 2 W1, MM - M > W1 + U, all strict: at equality a gapped alignment ties with the diagonal and the reference's
+// traceback decides. -> the most mismatches a link's diagonal may hold, the largest m with m (M - MM) < M - 2 W1 (the `- 1` keeps a
+// tie such as M 1, MM -2, W1 -4, m = 3 with the matrix: the reference takes the diagonal there too, because it examines the
+// diagonal move last and with <=, but the proof below does not lean on that); -1: no shortcut under this scheme. Wl, Mn and PE do
+// not enter: the shortcut takes no problem with an N in it, none with a free end beyond a tail's template side, and no couple.
+extern "C" int kmahip_diag_gap_m_max(const kmahip_rewards *rw) {
+	const int M = rw->M, MM = rw->MM, W1 = rw->W1, U = rw->U;
+	bool plain = M > 0 && MM < 0 && W1 < 0 && U < 0 && MM > W1 && MM - M > 2 * W1 && MM - M > W1 + U;
+	for(int i = 0; i < 4 && plain; ++i) for(int j = 0; j < 4; ++j) plain = plain && rw->d[i][j] == (i == j ? M : MM);
+	return plain ? (M - 2 * W1 - 1) / (M - MM) : -1;
+}
+
 // mismatches between g read bases from qp and g template bases from tp (neither side holds an N; both word arrays are padded)
 __device__ __forceinline__ int diag_mism(const uint64_t *ts, const QView &q, int tp, int qp, int g) {
 	int m = 0;
@@ -2328,7 +2343,7 @@ struct TLane {
 	int32_t *rows; uint8_t *E; int64_t e_cap;
 	Emit em;
 	int status;     // 1: a DP problem did not fit the per-lane move matrix; 32: put off to the second pass
-	int fast, gap_m_max;
+	int fast, gap_m_max;       // (gap_m_max: kmahip_diag_gap_m_max; read only where fast is set)
 	int ts;                    // -ts: bases trimmed off the front of the chain's seeds (trimSeeds, chain.c:493-528)
 	int ncols;                 // DP columns the rows hold
 	int64_t row_stride;        // distance between neighbouring row elements (the lane count in HBM, 1 in a lane's own LDS)
@@ -2966,13 +2981,9 @@ static int launch_align(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 	A.counters = ws->counters;
 	A.stats = ws->stats_on;
 	A.ablate = 0;
-	{	// nw_diagonal: only with a plain match / mismatch matrix and penalties ordered as its proof needs (KMAHIP_ALIGN_DIAG=0: off)
-		const int M = p->rw.M, MM = p->rw.MM, W1 = p->rw.W1, U = p->rw.U;
-		bool plain = M > 0 && MM < 0 && W1 < 0 && U < 0 && MM > W1 && MM - M > 2 * W1 && MM - M > W1 + U;
-		for(int i = 0; i < 4 && plain; ++i) for(int j = 0; j < 4; ++j) plain = plain && p->rw.d[i][j] == (i == j ? M : MM);
+	{	// nw_diagonal: only under a scheme its proof holds for (KMAHIP_ALIGN_DIAG=0: off)
 		const char *e = getenv("KMAHIP_ALIGN_DIAG");
-		if(e && !atoi(e)) plain = false;
-		A.gap_m_max = plain ? (M - 2 * W1 - 1) / (M - MM) : -1;
+		A.gap_m_max = e && !atoi(e) ? -1 : kmahip_diag_gap_m_max(&p->rw);
 	}
 #ifdef KMAHIP_DIAG
 	if(const char *e = getenv("KMAHIP_ABLATE_ALIGN")) A.ablate = atoi(e);
@@ -3300,15 +3311,13 @@ int kmahip_launch_trace(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *reads,
 	A.counters = ws->counters;
 	// pass 1 settles every read whose DP problems are provably ungapped (diag_proof above) and lists the others; pass 2 runs
 	// the listed ones with their move matrices. KMAHIP_TRACE=lanes1: everything in one pass, as before.
-	const int M = p->rw.M, MM = p->rw.MM, W1 = p->rw.W1, U = p->rw.U;
-	bool plain = M > 0 && MM < 0 && W1 < 0 && U < 0 && MM > W1 && MM - M > 2 * W1 && MM - M > W1 + U;
-	for(int i = 0; i < 4 && plain; ++i) for(int j = 0; j < 4; ++j) plain = plain && p->rw.d[i][j] == (i == j ? M : MM);
+	A.gap_m_max = kmahip_diag_gap_m_max(&p->rw);
 	{
 		const char *mode = getenv("KMAHIP_TRACE");
-		if(mode && !strcmp(mode, "lanes1")) plain = false;
+		if(mode && !strcmp(mode, "lanes1")) A.gap_m_max = -1;
 	}
+	const bool plain = A.gap_m_max >= 0;
 	A.q_in = nullptr; A.q_out = ws->t_queue; A.q_in_cnt = 3; A.q_out_cnt = 3; A.fast = plain ? 1 : 0;
-	A.gap_m_max = plain ? (M - 2 * W1 - 1) / (M - MM) : 0;
 	A.lds_bytes = 0; A.lds_ncols = 0;
 	if(plain) {
 		// the first pass holds no move matrix and no DP rows: it fits five waves per SIMD where the full kernel fits four, and its

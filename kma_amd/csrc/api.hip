@@ -163,6 +163,15 @@ extern "C" int kmahip_ws_align_queue_counts(kmahip_ws *ws, void *stream, unsigne
 	return KMAHIP_OK;
 }
 
+// the reads the first pass of the last two-pass traceback launch put off to a pass with move matrices (out[0]) and, with the LDS
+// pass in between, those that pass put off in turn (out[1])
+extern "C" int kmahip_ws_trace_put_off(kmahip_ws *ws, void *stream, unsigned long long out[2]) {
+	if(!ws || !out || !ws->counters) return KMAHIP_EINVAL;
+	HIP_TRY(hipMemcpyAsync(out, ws->counters + 3, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, (hipStream_t) stream));
+	HIP_TRY(hipStreamSynchronize((hipStream_t) stream));
+	return KMAHIP_OK;
+}
+
 extern "C" int kmahip_align_get_stats(kmahip_ws *ws, kmahip_align_stats *st, void *stream) {
 	if(!ws || !st || !ws->counters) return KMAHIP_EINVAL;
 	unsigned long long c[8];

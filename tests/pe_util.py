@@ -95,11 +95,15 @@ def oracle_pe_lines(g, minlen=16, mq=0, scoreT=0.5, mrc=0.0):
     return exp, kinds
 
 
-def oracle_pe_conclave_records(g, minlen=16, mq=0, scoreT=0.5, mrc=0.0):
+def oracle_pe_conclave_records(g, minlen=16, mq=0, scoreT=0.5, mrc=0.0, set_rewards=None):
     """The frag_raw records of the paired run as ConClave input arrays: one record per proper pair (score negated,
-    updatescores.c:470-488), one per singly written read; plus the two ConClave score vectors."""
+    updatescores.c:470-488), one per singly written read; plus the two ConClave score vectors and, per record, the
+    unit it came from.
+    set_rewards: called with the oracle's Rewards before anything runs (another scoring scheme than the default)"""
     import oracle
     db = oracle.OracleDB(g["prefix"])
+    if set_rewards:
+        set_rewards(db.rw)
     al = oracle.OracleAligner(db, minlen=minlen, mq=mq, scoreT=scoreT, mrc=mrc)
     rec = []        # (n_hits, signed score, q_len, q_len2, tmpl, start, end)
     vec = [np.zeros(len(al.alignment_scores), np.uint64), np.zeros(len(al.alignment_scores), np.uint64)]
@@ -115,7 +119,9 @@ def oracle_pe_conclave_records(g, minlen=16, mq=0, scoreT=0.5, mrc=0.0):
             rec.append((nh, int(res["best_score"][0]), r["seqlen"], 0, res["tmpl"][:nh].tolist(), res["start"][:nh].tolist(),
                         res["end"][:nh].tolist()))
 
+    first = []      # the first record of every unit
     for u in g["units"]:
+        first.append(len(rec))
         if u[0] == "se":
             r = g["s1"][u[1]]
             rf, fl, To, T = db.scan_se(formats.pack_ragged([codes_of(r["seq"], r["seqlen"], r["N"])]))
@@ -151,7 +157,8 @@ def oracle_pe_conclave_records(g, minlen=16, mq=0, scoreT=0.5, mrc=0.0):
     flat = lambda i: np.array([x for r in rec for x in r[i]], np.int32)
     col = lambda i: np.array([r[i] for r in rec], np.int32)
     return dict(n_hits=col(0), score=col(1), q_len=col(2), q_len2=col(3), off=off[:-1], tmpl=flat(4), start=flat(5), end=flat(6),
-                alignment_scores=vec[0], uniq_alignment_scores=vec[1])
+                alignment_scores=vec[0], uniq_alignment_scores=vec[1],
+                unit=np.searchsorted(np.array(first, np.int64), np.arange(len(rec)), side="right") - 1)
 
 
 def hip_pe_conclave(db, g, records_only=False):
