@@ -1161,6 +1161,17 @@ int kmahip_ws_scan_diag_replaced(kmahip_ws *ws, void *stream, unsigned long long
  * (behind a base off the diagonal, a miss or a cut walk), out[1] the rounds -- one per workgroup's group of strand items and pass of 136
  * starts -- that had any. Counted only while kmahip_scan_set_stats is on; read it before another stage is launched on the workspace. */
 int kmahip_ws_scan_queue_counts(kmahip_ws *ws, void *stream, unsigned long long out[2]);
+/* Record items of the last scan launch that the prefilter settled itself: the read lies on the template store along its diagonal
+ * without a mismatch, and the span table (below) says that the k-mers of that stretch leave its template as the only best one. They
+ * are counted among the records of kmahip_ws_scan_routes and never reach the first tier. Always counted. Off (0) outside the
+ * best-templates mode of kmahip_launch_scan_se, under -proxi, -ex_mode, -ck, a decon database, a scoring scheme that is not
+ * M > 0, MM < M, U <= 0, W1 <= 0, and with KMAHIP_PF_SETTLE=0 in the environment. Read it before another stage is launched. */
+int kmahip_ws_scan_settled(kmahip_ws *ws, void *stream, unsigned long long *out);
+/* The span table as it lies on the device, built by kmahip_db_open (KMAHIP_SCAN_SPAN=0: not built): for the first n positions p of
+ * the concatenated templates (template 1 first; at most total bases + 64) t0 = the template p lies in, room = the k-mer starts from p
+ * on inside t0 whose value lists name t0 (capped at 255), need = the fewest of them whose value lists have t0 alone in common (255: never); all 0 where no
+ * k-mer starts. HOST arrays. Returns 1, 0 when the database has no table, or an error. Exposed for tests. */
+int kmahip_test_span_table(kmahip_db *db, int64_t n, uint32_t *out_t0, uint8_t *out_need, uint8_t *out_room);
 /* Stage 3a's device-wide queues after the last alignment launch on the workspace (the register-only route, which hands its DP
  * problems of 2..63 query columns to four class queues that one kernel sweeps): out[0..3] entries of the classes of 33..63,
  * 17..32, 9..16 and 2..8 columns, out[4] tasks that waited for queued problems (the last result to arrive finishes such a task),

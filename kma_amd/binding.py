@@ -974,6 +974,28 @@ class KmaHipDB:
         _check(L.kmahip_ws_scan_queue_counts(self.ws, C.c_void_p(stream or 0), out))
         return int(out[0]), int(out[1])
 
+    def get_scan_settled(self, stream=None) -> int:
+        """record items of the last scan launch that the prefilter settled from the span table (always counted)"""
+        out = C.c_ulonglong(0)
+        L = lib()
+        L.kmahip_ws_scan_settled.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]
+        _check(L.kmahip_ws_scan_settled(self.ws, C.c_void_p(stream or 0), C.byref(out)))
+        return int(out.value)
+
+    def test_span_table(self, n):
+        """kmahip_test_span_table (a test hook): (t0, need, room) of the first n positions of the concatenated templates as the
+        device holds them, or None when the database was opened without the table"""
+        t0, need, room = np.zeros(n, np.uint32), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        L = lib()
+        L.kmahip_test_span_table.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.kmahip_test_span_table.restype = C.c_int
+        rc = L.kmahip_test_span_table(self.h, n, _p(t0), _p(need), _p(room))
+        if rc == 0:
+            return None
+        if rc < 0:
+            _check(rc)
+        return t0, need, room
+
     def list_table_log2(self) -> int:
         """log2 of the list table's bucket count, 0: the database was opened without one"""
         L = lib()

@@ -142,6 +142,16 @@ extern "C" int kmahip_ws_scan_diag_replaced(kmahip_ws *ws, void *stream, unsigne
 	return KMAHIP_OK;
 }
 
+// record items the prefilter of the last scan launch settled itself (KMAHIP_C_NSET; always counted)
+extern "C" int kmahip_ws_scan_settled(kmahip_ws *ws, void *stream, unsigned long long *out) {
+	if(!ws || !out || !ws->counters) return KMAHIP_EINVAL;
+	unsigned long long c = 0;
+	HIP_TRY(hipMemcpyAsync(&c, ws->counters + KMAHIP_C_NSET, sizeof c, hipMemcpyDeviceToHost, (hipStream_t) stream));
+	HIP_TRY(hipStreamSynchronize((hipStream_t) stream));
+	*out = c;
+	return KMAHIP_OK;
+}
+
 // the queue round of the last scan launch: k-mer starts left to it, and the rounds that had any (counted only with the statistics on)
 extern "C" int kmahip_ws_scan_queue_counts(kmahip_ws *ws, void *stream, unsigned long long out[2]) {
 	if(!ws || !out || !ws->counters) return KMAHIP_EINVAL;

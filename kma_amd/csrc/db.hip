@@ -145,6 +145,73 @@ __global__ __launch_bounds__(256) void walk_repoint_kernel(uint2 *slots, int64_t
 	slots[si].y = first[si];
 }
 
+// The span table (DevDB::span), two kernels with one lane per k-mer start p of template t (one workgroup per template, as
+// walk_vsid_kernel). span_mine_kernel: does a k-mer with a value list that names t start at p? One scan of one list per position.
+// Where a template had an N, `cat` holds a base in its place, and a k-mer over it is at best another template's: not t's.
+// span_build_kernel: `room` is the run of such starts from p on, counted along the flags, at most KMAHIP_SPAN_NEVER. `need`: the
+// templates other than t of the list at p are kept in a small array, and every later list inside `room` that is not the one before it
+// takes out those it does not hold; need = the number of starts at which the array first is empty. The lists are compared id by id as
+// the device holds them, in any order. What bounds the work on a database of long lists: a list at p with more than
+// KMAHIP_SPAN_LIST_MAX other templates gives "never" at once, and a later list of more than KMAHIP_SPAN_SCAN_MAX ids is passed over
+// (the array then holds a superset of what the lists have in common, so `need` comes out later or never: both only leave items to the
+// scan). The table was cleared before: need 0 / room 0 where no such k-mer starts.
+__global__ __launch_bounds__(256) void span_mine_kernel(const DevDB d, uint8_t *mine) {
+	const uint32_t t = blockIdx.x + 1;
+	const int64_t g0 = d.cat_off[t];
+	const int tl = d.tlen[t], k = (int) d.kmersize;
+	for(int i = threadIdx.x + blockIdx.y * blockDim.x; i + k <= tl; i += blockDim.x * gridDim.y) {
+		const uint32_t vi = d.vs_id[g0 + i];
+		bool m = false;
+		if(vi != KMAHIP_EMPTY_VI) {
+			const uint32_t cnt = d.values_u16 ? (uint32_t) d.values16[vi] : d.values32[vi];
+			for(uint32_t c = 1; c <= cnt && !m; ++c) m = (d.values_u16 ? (uint32_t) d.values16[vi + c] : d.values32[vi + c]) == t;
+		}
+		mine[g0 + i] = m ? 1 : 0;
+	}
+}
+
+__global__ __launch_bounds__(256) void span_build_kernel(const DevDB d, const uint8_t *mine, uint2 *span) {
+	const uint32_t t = blockIdx.x + 1;
+	const int64_t g0 = d.cat_off[t];
+	const int tl = d.tlen[t], k = (int) d.kmersize;
+	auto value = [&](uint32_t vi, uint32_t c) -> uint32_t { return d.values_u16 ? (uint32_t) d.values16[vi + c] : d.values32[vi + c]; };
+	for(int i = threadIdx.x + blockIdx.y * blockDim.x; i + k <= tl; i += blockDim.x * gridDim.y) {
+		const int64_t p = g0 + i;
+		const int cap = min((int) KMAHIP_SPAN_NEVER, tl - k + 1 - i);
+		int room = 0;
+		while(room < cap && mine[p + room]) ++room;
+		uint32_t others[KMAHIP_SPAN_LIST_MAX];
+		int no = 0;
+		uint32_t need = KMAHIP_SPAN_NEVER, prev = KMAHIP_EMPTY_VI;
+		bool open = true;          // still looking for `need`
+		for(int j = 0; j < room && open; ++j) {
+			const uint32_t vi = d.vs_id[p + j];
+			if(vi == prev) continue;
+			prev = vi;
+			const uint32_t cnt = value(vi, 0);
+			if(j == 0) {
+				for(uint32_t c = 1; c <= cnt && open; ++c) {
+					const uint32_t v = value(vi, c);
+					if(v == t) continue;
+					if(no == KMAHIP_SPAN_LIST_MAX) open = false;
+					else others[no++] = v;
+				}
+				if(!open) break;
+			} else {
+				if(cnt > KMAHIP_SPAN_SCAN_MAX) continue;
+				int kept = 0;
+				for(int x = 0; x < no; ++x) {
+					bool in = false;
+					for(uint32_t c = 1; c <= cnt; ++c) in = in || value(vi, c) == others[x];
+					if(in) others[kept++] = others[x];
+				}
+				no = kept;
+			}
+			if(no == 0) { open = false; if(j + 1 < (int) KMAHIP_SPAN_NEVER) need = (uint32_t) (j + 1); }
+		}
+		span[p] = make_uint2(room ? t : 0u, room ? need | ((uint32_t) room << 8) : 0u);
+	}
+}
 
 // ---- the per-template position index on the device: every k-mer start as (template, k-mer) -> 1-based position, sorted (a stable
 // radix sort keeps the positions of a repeated k-mer ascending), one lane per distinct pair writes its entry -- the position, or a
@@ -447,6 +514,33 @@ static int db_open(const char *prefix, bool decon, kmahip_db **out) {
 			}
 			if(bad) { kmahip_db_close(db); kmahip_set_error("building the walkable template store failed: %s", hipGetErrorString(hipGetLastError())); return KMAHIP_EDEVICE; }
 			if(unplaced) { kmahip_db_close(db); kmahip_set_error("%llu index k-mers do not occur in %s.seq.b", unplaced, prefix); return KMAHIP_EFORMAT; }
+			// The span table (DevDB::span), from vs_id and the value lists as they now lie on the device. It is looked up by the diagonal
+			// that the prefilter files, so a store too large for diagonals (scan.hip: diag_cat_bases) gets none; KMAHIP_SCAN_SPAN=0: none;
+			// and when the memory is not there the database opens without it: every live item is then scanned.
+			bool want_span = total > 0 && total < (1ll << 30) && DB_size > 1 && DB_size < 0xFFFFFFFFu;
+			if(const char *e = getenv("KMAHIP_SCAN_SPAN")) if(!atoi(e)) want_span = false;
+			if(want_span) {
+				const size_t bytes = ((size_t) total + 64) * sizeof(uint2);
+				void *d_span = nullptr;
+				// (the flags of span_mine_kernel: a byte per position, freed again)
+				uint8_t *d_mine = nullptr;
+				if(hipMalloc(&d_span, bytes) != hipSuccess || hipMalloc((void **) &d_mine, (size_t) total + 64) != hipSuccess) {
+					(void) hipGetLastError();
+					if(d_span) (void) hipFree(d_span);
+				} else {
+					db->allocs.push_back(d_span);
+					bool sbad = hipMemsetAsync(d_mine, 0, (size_t) total + 64, 0) != hipSuccess || hipMemsetAsync(d_span, 0, bytes, 0) != hipSuccess;
+					if(!sbad) {
+						hipLaunchKernelGGL(span_mine_kernel, dim3(DB_size - 1, grid_y), dim3(256), 0, 0, d, d_mine);
+						hipLaunchKernelGGL(span_build_kernel, dim3(DB_size - 1, grid_y), dim3(256), 0, 0, d, (const uint8_t *) d_mine, (uint2 *) d_span);
+						sbad = hipDeviceSynchronize() != hipSuccess;
+					}
+					(void) hipFree(d_mine);
+					if(sbad) { kmahip_db_close(db); kmahip_set_error("building the span table failed: %s", hipGetErrorString(hipGetLastError())); return KMAHIP_EDEVICE; }
+					d.span = (const uint2 *) d_span;
+					db->info.total_bytes += bytes;
+				}
+			}
 		}
 
 		stamp("walkable template store (cat / vs_id)");
@@ -532,6 +626,20 @@ extern "C" void kmahip_db_close(kmahip_db *db) {
 	if(!db) return;
 	for(void *p : db->allocs) (void) hipFree(p);
 	delete db;
+}
+
+// test hook: the first n entries of the span table as they lie on the device -> 1, or 0 when the database was opened without one
+extern "C" int kmahip_test_span_table(kmahip_db *db, int64_t n, uint32_t *out_t0, uint8_t *out_need, uint8_t *out_room) {
+	if(!db || n < 0 || (n && (!out_t0 || !out_need || !out_room))) { kmahip_set_error("kmahip_test_span_table: bad argument"); return KMAHIP_EINVAL; }
+	if(!db->dev.span) return 0;
+	const int64_t have = db->h_cat_off.empty() ? 0 : db->h_cat_off.back() + 64;
+	if(n > have) { kmahip_set_error("kmahip_test_span_table: the table has %lld entries", (long long) have); return KMAHIP_EINVAL; }
+	std::vector<uint2> h((size_t) n);
+	if(n && hipMemcpy(h.data(), db->dev.span, (size_t) n * sizeof(uint2), hipMemcpyDeviceToHost) != hipSuccess) {
+		kmahip_set_error("kmahip_test_span_table: %s", hipGetErrorString(hipGetLastError())); return KMAHIP_EDEVICE;
+	}
+	for(int64_t i = 0; i < n; ++i) { out_t0[i] = h[i].x; out_need[i] = (uint8_t) (h[i].y & 255u); out_room[i] = (uint8_t) ((h[i].y >> 8) & 255u); }
+	return 1;
 }
 
 extern "C" int kmahip_db_get_info(const kmahip_db *db, kmahip_db_info *info) {

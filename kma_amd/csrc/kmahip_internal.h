@@ -14,6 +14,11 @@
 #define KMAHIP_C_NACT 8
 #define KMAHIP_C_NREC 21
 #define KMAHIP_C_NREPL 22      // records whose diagonal the prefilter replaced by a better one (counted with the statistics on)
+// KMAHIP_C_NREC counts the items that took the record route; of them the prefilter WRITES the records of those it does not settle
+// itself (DevDB::span), densely, by a counter of their own: what the first tier's launch over records reads as its item count
+// while the route is on (with the route off nothing is added to it: every record item's record is written, and C_NREC is read)
+#define KMAHIP_C_NWRIT 19
+#define KMAHIP_C_NSET 20       // record items the prefilter settled (always counted)
 // the scan's queue (counted with the statistics on): k-mer starts its lanes left to the queue round, and the (group, pass) rounds that had any
 #define KMAHIP_C_QENT 30
 #define KMAHIP_C_QWG 31
@@ -93,7 +98,19 @@ struct DevDB {
 	uint32_t lb_log2;
 	uint32_t lpass;               // OR-ed to a full bucket's fourth value before its flag is looked at: 0, or KMAHIP_LTAB_PASSED when the
 	                              // flag is to be ignored (KMAHIP_LTAB_FLAG=0: a miss ends at a bucket that is not full, as in probe())
+	// The span table: per position p of `cat` (and 64 entries behind it, as vs_id) what a read that lies on `cat` from p on without a
+	// mismatch scores, as far as the database alone decides it. x = t0, the template p lies in; y = need | room << 8:
+	//   room  k-mer starts from p on that lie inside t0 and have a value list that names t0 (a k-mer over a template's N has none, or
+	//         another template's), capped at KMAHIP_SPAN_NEVER (0 where none starts at p);
+	//   need  the smallest n >= 1 for which the value lists at p .. p + n - 1, all inside `room`, have no template but t0 in common;
+	//         KMAHIP_SPAN_NEVER: no such n (or the builder gave up: always safe, the item is then scanned).
+	// A read of npos k-mer starts with need <= npos <= room has t0 as its only best template (scan.hip: settle_allowed has the proof).
+	// NULL: none was built (KMAHIP_SCAN_SPAN=0, no memory, no diagonals to look it up by) or the launch switched the route off.
+	const uint2 *span;
 };
+#define KMAHIP_SPAN_NEVER 255u
+#define KMAHIP_SPAN_LIST_MAX 32      // the builder keeps at most this many other templates of the list at p; a longer list: never
+#define KMAHIP_SPAN_SCAN_MAX 256u    // a later list of more ids than this is passed over by the builder (need comes out later, or never)
 #define KMAHIP_LTAB_PASSED 0x80000000u
 
 struct kmahip_db {
@@ -126,7 +143,7 @@ struct kmahip_ws {
 	int mem_scale;            // MEM slots per (read, template) = the usual 64 (reads up to 1 kb) x this; raised by the runs when a read
 	                          // full of repeats carries more (KMAHIP_ST_SEED_MEMS, KMAHIP_ST_TRACE_MEMS), 0 = 1
 	// counters (KMAHIP_N_COUNTERS): [0] pool top, [1] status, [2] n_overflow, [3] probes, [4] value elems, [5] active strands,
-	// [6] hash probes, [7] pair pool top, [8] live strand items on the bare list, [9] prefilter probes, [21] records, [22] replaced diagonals, [24..29] stage 3a's class queues (KMAHIP_C_ADQ),
+	// [6] hash probes, [7] pair pool top, [8] live strand items on the bare list, [9] prefilter probes, [19] records written, [20] record items settled by the prefilter, [21] records, [22] replaced diagonals, [24..29] stage 3a's class queues (KMAHIP_C_ADQ),
 	// [30] k-mer starts left to the scan's queue, [31] its rounds that had any
 	unsigned long long *counters;
 	int64_t *overflow_items;

@@ -103,10 +103,14 @@ struct ScanArgs {
 	int64_t cat_bases;   // > 0: the prefilter files the template diagonal of its hit with every live strand item (bits 33.. of the
 	                     // list entry: position in `cat` minus strand position of the hit k-mer, + DIAG_BIAS; DIAG_NONE: none) and the
 	                     // scan's lanes try that diagonal before they probe
-	uint64_t *recs;      // the prefilter's records of the plain live items (counters[C_NREC] of them, at most rec_cap); NULL: every
+	uint64_t *recs;      // the prefilter's records of the plain live items (*rec_count of them, at most rec_cap); NULL: every
 	int64_t rec_cap;     // live item goes to active_items
 	int refine;          // the prefilter checks a record's diagonal against `cat` and tries ONE other when it finds two mismatches or more
 	int pf_stage_words;  // the prefilter copies a workgroup's reads into LDS when their words + 2 fit in this many (0: never)
+	const unsigned long long *rec_count;   // the counter that holds the number of records written: &counters[C_NWRIT] when the prefilter
+	                     // settles items, else &counters[C_NREC] (a pointer: the scan reads it in one trip behind its arguments, as it read C_NREC)
+	int settle;          // the prefilter settles a record item whose read lies on `cat` without a mismatch where db.span allows it, and
+	                     // writes no record for it (settle_allowed: the launches and scoring schemes this holds for)
 	double min_frac;     // proximity matching (-proxi, getProxiMatch savekmers.c:296-340): |minFrac|, read by the PROXI finishes only
 };
 
@@ -119,7 +123,7 @@ constexpr int64_t DIAG_BIAS = 1ll << 20, DIAG_NONE = 0x7FFFFFFFll;      // (read
 constexpr int REC_WORDS = 8;
 static_assert(REC_WORDS - 2 == SW - 1, "a record carries the staged row but its last, always zero, word");
 
-enum { C_POOL = 0, C_STATUS = 1, C_NOVER = 2, C_PROBES = 3, C_VALS = 4, C_ACTIVE = 5, C_HASH = 6, C_PPOOL = 7, C_NACT = KMAHIP_C_NACT, C_PREF = 9, C_NOVER2 = 10, C_NREC = KMAHIP_C_NREC, C_NREPL = KMAHIP_C_NREPL, C_QENT = KMAHIP_C_QENT, C_QWG = KMAHIP_C_QWG, N_COUNTERS = KMAHIP_N_COUNTERS };
+enum { C_POOL = 0, C_STATUS = 1, C_NOVER = 2, C_PROBES = 3, C_VALS = 4, C_ACTIVE = 5, C_HASH = 6, C_PPOOL = 7, C_NACT = KMAHIP_C_NACT, C_PREF = 9, C_NOVER2 = 10, C_NREC = KMAHIP_C_NREC, C_NREPL = KMAHIP_C_NREPL, C_QENT = KMAHIP_C_QENT, C_QWG = KMAHIP_C_QWG, C_NWRIT = KMAHIP_C_NWRIT, C_NSET = KMAHIP_C_NSET, N_COUNTERS = KMAHIP_N_COUNTERS };
 
 // two probes whose home buckets travel together (used after a miss: the k-mer starts behind a mismatch miss in a row)
 __device__ __forceinline__ void probe2(const DevDB &db, uint32_t key1, uint32_t key2, uint32_t &r1, uint32_t &r2) {
@@ -341,14 +345,19 @@ __global__ __launch_bounds__(THREADS, 8) void scan_prefilter_kernel(const ScanAr
 	__shared__ int32_t s_len[PF_READS];                   // their lengths
 	__shared__ uint16_t s_woff[PF_READS];                 // staged: the word offset of each in s_words
 	__shared__ uint32_t s_n, s_nr, s_np, s_nt, s_nx, s_nrepl;
-	__shared__ unsigned long long s_base, s_rbase;
+	__shared__ unsigned long long s_base;
 	__shared__ uint32_t s_room;
+	// the places of the records that are written. Route off: the workgroup's reservation on C_NREC is its places, from s_dbase on,
+	// and the scan reads C_NREC (no atomic more than before). Route on: C_NWRIT, one reservation per round of the tail, from the
+	// round's counts per wavefront (two sets: a wavefront may be a round ahead)
+	__shared__ unsigned long long s_dbase, s_wbase[2];
+	__shared__ uint32_t s_wc[2][THREADS / 64], s_sc[2][THREADS / 64], s_nsp;
 	const DevDB &db = A.db;
 	const int tid = threadIdx.x;
 	const int k = (int) db.kmersize;
 	const int plane = tid & (PF_PLANES - 1);
 	const int64_t r0 = (int64_t) blockIdx.x * PF_READS;          // (< n_reads: the grid covers the items and no more)
-	if(tid == 0) { s_n = 0; s_nr = 0; s_np = 0; s_nt = 0; s_nx = 0; s_nrepl = 0; }
+	if(tid == 0) { s_n = 0; s_nr = 0; s_np = 0; s_nt = 0; s_nx = 0; s_nrepl = 0; s_nsp = 0; }
 	// ---- the reads of the workgroup: lengths always, words when the range fits (pf_stage_words: 0 = staging off). A range that is
 	// too long or negative, or a read whose words do not lie inside it, sends the WHOLE workgroup by the unstaged route: the same
 	// text below, its word accessor reading global memory.
@@ -486,8 +495,8 @@ __global__ __launch_bounds__(THREADS, 8) void scan_prefilter_kernel(const ScanAr
 		uint32_t room = 0;
 		if(nrec) {
 			const unsigned long long rb = atomicAdd(&A.counters[C_NREC], (unsigned long long) nrec);
-			s_rbase = rb;
 			room = rb >= (unsigned long long) A.rec_cap ? 0u : (uint32_t) min((unsigned long long) nrec, (unsigned long long) A.rec_cap - rb);
+			s_dbase = rb;
 		}
 		s_room = room;
 		const uint32_t nbare = nact + (nrec - room);
@@ -508,12 +517,21 @@ __global__ __launch_bounds__(THREADS, 8) void scan_prefilter_kernel(const ScanAr
 	// then 64 contiguous bytes in 16-byte stores. (Eight lanes per record, a word and a template window each, the counts summed by
 	// DPP moves and every store instruction writing whole records, took 0.15 ms off the step at 250 M more vector instructions per launch:
 	// short of the rule for a gain, and not kept. DESIGN section 3.1, round 9.)
-	for(uint32_t i = tid; i < room; i += THREADS) {
+	// A lane whose read lies on `cat` along its final diagonal without a mismatch asks the span table (DevDB::span) there: when the
+	// read's k-mer starts are enough to leave the diagonal's template alone (need) and all lie inside it (room), the scan would find
+	// that template with the full score and nothing beside it (settle_allowed has the proof), so the lane writes the item's result
+	// as the scan's finish would and no record. The records that ARE written stay dense: every round of the loop counts its lanes
+	// that write and takes their places with one atomic, so the loop's rounds are those of the whole workgroup.
+	for(uint32_t i0 = 0, round = 0; i0 < room; i0 += THREADS, ++round) {
+		const uint32_t i = i0 + tid;
+		bool writes = false, settled = false;
+		uint64_t w[REC_WORDS];
+		if(i < room) {
+		writes = true;
 		const int64_t ent = s_list[PF_ITEMS - 1 - i];
 		const int64_t it = ent & ITEM_MASK; const int li = (int) (ent & (PF_ITEMS - 1));
 		const int L = s_len[li >> 1], nw = (L + 31) >> 5;
 		const uint64_t *rs = words_of(li >> 1);
-		uint64_t w[REC_WORDS];
 		w[0] = (uint64_t) ent; w[1] = (uint64_t) (uint32_t) L;
 #pragma unroll
 		for(int x = 0; x < SW - 1; ++x) {
@@ -550,6 +568,8 @@ __global__ __launch_bounds__(THREADS, 8) void scan_prefilter_kernel(const ScanAr
 			};
 			int b = -1, b2 = -1;
 			const int m = mismatches(dgf - DIAG_BIAS, b);
+			int64_t af = dgf - DIAG_BIAS;          // the diagonal that is filed, and the bases that differ along it
+			int mf = m;
 			if(m >= 2) {
 				const int st = min(max(0, b - k + 1), L - k);
 				uint64_t lo = 0, hi = 0;
@@ -563,18 +583,56 @@ __global__ __launch_bounds__(THREADS, 8) void scan_prefilter_kernel(const ScanAr
 					if(m1 >= 0 && m1 < m) {
 						w[0] = (uint64_t) (it | ((a1 + DIAG_BIAS) << 33));
 						if(STATS) atomicAdd(&s_nrepl, 1u);
+						af = a1; mf = m1;
 					}
 				}
 			}
+			// (mf == 0: 0 <= af < cat_bases + 32, inside the table's 64 cleared entries behind `cat`. The entry at af names the
+			// template af lies in, so the read begins inside it, and `room` keeps its last k-mer start inside it as well.)
+			if(A.settle && mf == 0) {
+				const uint2 e = db.span[af];
+				const uint32_t npos = (uint32_t) (L - k + 1);
+				if((e.y & 255u) <= npos && npos <= (e.y >> 8)) {
+					settled = true; writes = false;
+					A.item_score[it] = k * A.M + ((int) npos - 1) * A.M;
+					A.item_n[it] = 1;
+					A.item_off[it] = it * INL;
+					A.pool[it * INL] = (int32_t) e.x;
+					if(STATS) atomicAdd(&s_nsp, npos);          // (the k-mer starts it resolved)
+				}
+			}
 		}
-		ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(A.recs + (s_rbase + i) * REC_WORDS);
+		}
+		unsigned long long place = s_dbase + i;
+		if(A.settle) {
+			const int par = (int) (round & 1u), wave = tid >> 6, lane = tid & 63;
+			const unsigned long long bw = __ballot(writes), bs = __ballot(settled);
+			if(lane == 0) { s_wc[par][wave] = (uint32_t) __popcll(bw); s_sc[par][wave] = (uint32_t) __popcll(bs); }
+			__syncthreads();
+			if(tid == 0) {
+				uint32_t nwr = 0, nse = 0;
 #pragma unroll
-		for(int x = 0; x < REC_WORDS / 2; ++x) dst[x] = make_ulonglong2(w[2 * x], w[2 * x + 1]);
+				for(int x = 0; x < THREADS / 64; ++x) { nwr += s_wc[par][x]; nse += s_sc[par][x]; }
+				s_wbase[par] = nwr ? atomicAdd(&A.counters[C_NWRIT], (unsigned long long) nwr) : 0ull;
+				if(nse) atomicAdd(&A.counters[C_NSET], (unsigned long long) nse);
+			}
+			__syncthreads();
+			place = s_wbase[par] + (unsigned long long) __popcll(bw & ((1ull << lane) - 1ull));
+#pragma unroll
+			for(int x = 0; x < THREADS / 64; ++x) if(x < wave) place += s_wc[par][x];
+		}
+		if(writes) {
+			ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(A.recs + place * REC_WORDS);
+#pragma unroll
+			for(int x = 0; x < REC_WORDS / 2; ++x) dst[x] = make_ulonglong2(w[2 * x], w[2 * x + 1]);
+		}
 	}
 	if(STATS && A.refine) {
-		// the repair probes are table gathers (C_HASH); they examine no stride k-mer and resolve no start (C_PREF, C_PROBES)
+		// the repair probes are table gathers (C_HASH); they examine no stride k-mer and resolve no start (C_PREF, C_PROBES); a settled
+		// item resolved its k-mer starts (C_PROBES) with no gather into a probe table
 		__syncthreads();
 		if(tid == 0 && s_nx) { atomicAdd(&A.counters[C_HASH], (unsigned long long) s_nx); atomicAdd(&A.counters[C_NREPL], (unsigned long long) s_nrepl); }
+		if(tid == 0 && s_nsp) atomicAdd(&A.counters[C_PROBES], (unsigned long long) s_nsp);
 	}
 	};
 	if(staged) body(lds_words);
@@ -634,12 +692,12 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 	const DevDB &db = A.db;
 	const int tid = threadIdx.x;
 	const int k = (int) db.kmersize;
-	const int64_t n_active = REC ? min((int64_t) A.counters[C_NREC], A.rec_cap) : (int64_t) A.counters[A.in_count];
+	const int64_t n_active = REC ? min((int64_t) *A.rec_count, A.rec_cap) : (int64_t) A.counters[A.in_count];
 	// all-candidates mode: the first tier's two launches share the fixed places of the pool (see the finish), the records first
 	int64_t place0 = 0, n_places = n_active;
 	if(MODE && TSLOTS == TS1 && A.recs) {
 		if(REC) n_places += (int64_t) A.counters[C_NACT];
-		else { place0 = min((int64_t) A.counters[C_NREC], A.rec_cap); n_places += place0; }
+		else { place0 = min((int64_t) *A.rec_count, A.rec_cap); n_places += place0; }
 	}
 	// first tier: one group of items per workgroup; LOOP: a fixed grid that loops over the (usually few) groups
 	int64_t first = (int64_t) blockIdx.x * SG;
@@ -981,6 +1039,9 @@ __global__ __launch_bounds__(STHREADS, TSLOTS == TS1 ? KMAHIP_SCAN_WAVES : (STHR
 				// (the starts left to this round, the lanes' own included, and the rounds that had any)
 				if(STATS && tid == 0 && s_qn) { atomicAdd(&A.counters[C_QENT], (unsigned long long) s_qn); atomicAdd(&A.counters[C_QWG], 1ull); }
 				// (a lane that kept its k-mer starts takes them one by one behind the queue's rounds)
+				// (With the prefilter's settle route the queues average 196 entries, so most workgroups run a second round. A thread that
+				// takes entries e and e + STHREADS with both list-table gathers in flight before either is entered kept 64 VGPRs and no
+				// scratch, and the step was 10.04-10.07 ms against 10.00-10.02: not kept. DESIGN section 3.1, round 11.)
 				for(int it = 0; it < q_iters || own; ++it) {
 					uint32_t v = 0xFFFFu;
 					if(it < q_iters) { const uint32_t e = (uint32_t) it * STHREADS + tid; if(e < qn) v = s_q[e]; }
@@ -2445,6 +2506,29 @@ static bool scan_records_on(const kmahip_ws *ws, const kmahip_reads *reads, cons
 	return !p->exhaustive && ws->rec_cap > 0 && reads->max_len <= (SW - 1) * 32;
 }
 
+// May the prefilter settle the record items that lie on `cat` without a mismatch (ScanArgs::settle)? Only in the best-templates mode
+// of kmahip_launch_scan_se (the caller passes `best_mode`: not -proxi, not -ck; -ex_mode writes no records; the all-candidates mode
+// of the pairs and the chain finder's prefilter never ask), with records and the diagonal check on, a span table, no decon table
+// (its lists hold an id that is no template), and KMAHIP_PF_SETTLE (read per launch) not 0 -- and under a scoring scheme with
+//     M > 0,  MM < M,  U <= 0,  W1 <= 0.
+// Why that is enough. The read has npos k-mer starts, all N-free, and the k-mer at start i is the one at position a + i of `cat`, so
+// the list it finds is vs_id[a + i]'s. The score machine (scan_se_kernel) gives template t  k*M at its first hit and bridge(g) at every
+// later hit that follows g missed starts, and nothing for starts before its first or behind its last hit. A template that is hit at
+// every start therefore scores S = k*M + (npos - 1)*M > 0. A template that misses a start scores less than S:
+//   a missed start before the first or behind the last hit loses the M > 0 that start gave;
+//   g >= 1 missed starts between two hits are paid bridge(g) where g + 1 hits in a row are paid (g + 1)*M, and bridge(g) < (g + 1)*M:
+//     g < k:   g*M + (k - g)*U + W1 <= g*M < (g + 1)*M                                   (U <= 0, W1 <= 0)
+//     g == k:  k*M + MM < (k + 1)*M                                                      (MM < M)
+//     g > k:   k*M + max(mm*MM + m*M, W1 + (g' - 1)*U), g' = g - k + 1 >= 2, with mm + m <= g' and mm >= 1: the first is at most
+//              (mm + m - 1)*M + MM < g'*M, the second at most 0 < g'*M; and k*M + g'*M = (g + 1)*M.
+// So the best templates are exactly those hit at every start: the templates common to the lists at a .. a + npos - 1. `need` <= npos
+// says that this is t0 alone, `room` >= npos that all those starts lie inside t0 and have a list.
+static int settle_allowed(const kmahip_db *db, const ScanArgs &A, const kmahip_params *p, bool best_mode) {
+	if(const char *e = getenv("KMAHIP_PF_SETTLE")) if(!atoi(e)) return 0;
+	if(!best_mode || !A.recs || !A.refine || !A.db.span || db->decon || p->exhaustive) return 0;
+	return p->rw.M > 0 && p->rw.MM < p->rw.M && p->rw.U <= 0 && p->rw.W1 <= 0;
+}
+
 // the first tier's launch over the bare list: a fixed grid that loops, every wave slot of the device taken once
 static unsigned bare_grid() {
 	static unsigned grid = 0;
@@ -2561,6 +2645,7 @@ int kmahip_launch_scan_se(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	if(kmahip_mem_mode() && (rc = kmahip_refuse_decon(db, KMAHIP_DECON_MEM))) return rc;
 	A.recs = !ck && scan_records_on(ws, reads, p) ? ws->recs : nullptr; A.rec_cap = ws->rec_cap;
 	A.refine = scan_refine_on(A.cat_bases); A.pf_stage_words = pf_stage_words();
+	A.settle = settle_allowed(db, A, p, !ck && !proxi); A.rec_count = ws->counters + (A.settle ? C_NWRIT : C_NREC);
 	A.ablate = 0;
 #ifdef KMAHIP_DIAG
 	if(const char *e = getenv("KMAHIP_ABLATE_SCAN")) A.ablate = atoi(e);
@@ -2636,7 +2721,7 @@ int kmahip_launch_chain_anchors(kmahip_db *db, kmahip_ws *ws, const kmahip_reads
 	S.pool = ws->pool; S.pool_cap = ws->pool_cap; S.counters = ws->counters; S.overflow_items = ws->overflow_items;
 	S.dense = ws->dense; S.dense_slots = ws->dense_slots; S.active_items = ws->active_items;
 	S.mode = 0; S.pool_sc = nullptr; S.pool_tail0 = 2 * n * INL; S.ablate = 0; S.cat_bases = 0;
-	S.recs = nullptr; S.rec_cap = 0; S.refine = 0; S.pf_stage_words = pf_stage_words();          // (the anchor kernel takes every live item from the bare list)
+	S.recs = nullptr; S.rec_cap = 0; S.refine = 0; S.settle = 0; S.rec_count = ws->counters + C_NREC; S.pf_stage_words = pf_stage_words();          // (the anchor kernel takes every live item from the bare list)
 	S.min_frac = 1.0;
 	S.in_items = ws->active_items; S.in_count = C_NACT; S.out_over = ws->overflow_items; S.out_count = C_NOVER;
 	A.pool = pool; A.pool_cap = pool_cap; A.a_off = a_off; A.a_n = a_n; A.slow = slow; A.cnt = cnt;
@@ -2682,6 +2767,7 @@ int kmahip_launch_scan_pe(kmahip_db *db, kmahip_ws *ws, const kmahip_reads *read
 	A.ablate = 0; A.mode = 1; A.pool_sc = ws->pool_sc; A.pool_tail0 = 0; A.cat_bases = ck ? 0 : diag_cat_bases(db);
 	A.recs = !ck && scan_records_on(ws, reads, p) ? ws->recs : nullptr; A.rec_cap = ws->rec_cap;
 	A.refine = scan_refine_on(A.cat_bases); A.pf_stage_words = pf_stage_words();
+	A.settle = 0; A.rec_count = ws->counters + C_NREC;          // (the pairing kernels want every candidate of an item, not its best)
 	A.min_frac = 1.0;
 #ifdef KMAHIP_DIAG
 	if(const char *e = getenv("KMAHIP_ABLATE_SCAN")) A.ablate = atoi(e);

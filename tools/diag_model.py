@@ -49,11 +49,36 @@ def main():
         i = np.searchsorted(ukey, k)
         return int(first[i]) if i < len(ukey) and ukey[i] == k else None
 
+    # round 11, the span table (DevDB::span): the templates of every k-mer, and `need` at a position -- the fewest k-mer starts from
+    # there on, all inside its template, whose template sets have that template alone in common (None: never within the template)
+    tmpl_sorted = (np.searchsorted(off, pos[order], side="right") - 1).astype(np.int64)
+    bounds = np.concatenate([first_i, [len(order)]])
+
+    def templates(p):
+        k = np.uint64(0)
+        for b in cat[p:p + K]:
+            k = (k << np.uint64(2)) | np.uint64(b)
+        i = np.searchsorted(ukey, k)
+        return set(tmpl_sorted[bounds[i]:bounds[i + 1]].tolist())
+
+    def need_at(p):
+        t0 = int(np.searchsorted(off, p, side="right") - 1)
+        room = int(off[t0] + lens[t0] - K + 1 - p)
+        others = None
+        for j in range(min(room, 254)):
+            s = templates(p + j)
+            others = s - {t0} if others is None else others & s
+            if not others:
+                return t0, j + 1, room
+        return t0, None, room
+
     rng = np.random.default_rng(a.seed)
     ok = np.nonzero(lens >= L)[0]
     npos = L - K + 1
     tot = {tries: np.zeros(8) for tries in (0, 1, 2)}
     n = 0
+    zero_mism = settled = own_template = 0
+    needs = []
     for _ in range(a.reads):
         t = int(ok[rng.integers(0, len(ok))])
         st = int(rng.integers(0, lens[t] - L + 1))
@@ -94,6 +119,14 @@ def main():
                 d1 = mism(gp - s0)
                 if d1 is not None and len(d1) < len(d):
                     diag, d = gp - s0, d1
+            if tries == 1 and d is not None and len(d) == 0 and diag + L <= off[-1]:
+                # the prefilter's settle route: no mismatch along the filed diagonal, and the table there says need <= npos <= room
+                zero_mism += 1
+                t0, nd, room = need_at(diag)
+                if nd is not None and nd <= npos <= room:
+                    settled += 1
+                    needs.append(nd)
+                    own_template += t0 == t
             bad = np.zeros(L, bool)
             if d is not None:
                 bad[d] = True
@@ -112,6 +145,10 @@ def main():
     print(f"{'per read':32s}" + "".join(f"{x:>12s}" for x in ("no repair", "one try", "two tries")))
     for i, h in enumerate(head):
         print(f"{h:32s}" + "".join(f"{tot[tries][i] / max(1, n):12.3f}" for tries in (0, 1, 2)))
+    nd = np.array(needs if needs else [0])
+    print(f"one try: {100 * zero_mism / max(1, n):.1f} % of the live reads have no mismatch on the filed diagonal; {100 * settled / max(1, n):.1f} % are settled "
+          f"by the span table (need <= {npos} <= room), {own_template} of {settled} on their own template; need of the settled: mean {nd.mean():.1f}, "
+          f"median {int(np.median(nd))}, 99th percentile {int(np.percentile(nd, 99))}")
 
 
 if __name__ == "__main__":
