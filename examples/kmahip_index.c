@@ -7,7 +7,12 @@
  *     kmahip_index -i genes.fsa -o genes [-k 16] [-deCon host.fsa phix.fsa]
  *     kmahip_index -i genes.fsa -o genes_sparse -Sparse TG [-ML 100]
  *     kmahip_index -i genes.fsa -o genes_thin -Sparse TG -hq 0.9 -ht 0.9 -and > clusters.tsv
+ *     kmahip_index -t_db genes -i new.fsa [-o genes_2] [-deCon host.fsa]
+ *     kmahip_index -t_db genes -deCon host.fsa
  *
+ * -t_db <prefix> (index.c:221-229, 529-557, 616-732): templates are appended to the index that exists, over kmahip_index_append. k and
+ * the sparse prefix are the index's: -k and -Sparse beside -t_db are taken and overridden, as in the reference. Without -o the append
+ * happens in place; without -i, -deCon writes <prefix>.decon.comp.b for the index as it is. -hq / -ht / -ML are not built with it.
  * -hq / -ht / -and (index.c:309-350, qualcheck.c:81-324): homology reduction of a sparse index over kmahip_index_build_sparse_hom; a
  * template too similar to those kept before it gets no id, and every template that reaches the gates gets a cluster line on standard
  * output. Without -Sparse the three options are taken without effect, as in the reference (updateDBs never calls QualCheck).
@@ -19,6 +24,7 @@
 #include "kmahip.h"
 
 #define USAGE "usage: kmahip_index (-i <fasta> [<fasta> ...] | -batch <file of paths>) -o <index prefix> [-k <k-mer length, 4 ... 16>] " \
+              "[-t_db <index to append to> (then -o is optional: in place; -i is optional beside -deCon)] " \
               "[-deCon <fasta> [<fasta> ...]] [-Sparse [<prefix>|-] [-ML <minimum length>] [-hq <query homology, 0 ... 1>] [-ht <template homology, 0 ... 1>] [-and]]\n"
 
 /* index.c:451-474: the letters the reference's table maps to 0 ... 3; anything else, or nothing at all, is no prefix */
@@ -30,11 +36,11 @@ static int valid_prefix(const char *s) {
 }
 
 int main(int argc, char **argv) {
-	const char *inputs[256], *decon[256], *out = NULL, *sparse = NULL;
+	const char *inputs[256], *decon[256], *out = NULL, *sparse = NULL, *t_db = NULL;
 	int n_in = 0, n_decon = 0, decon_opt = 0, k = 16, ml_opt = 0;
 	long min_len = 0;
 	double hom_q = 1.0, hom_t = 1.0;
-	int and_mode = 0;
+	int and_mode = 0, hom_opt = 0;
 	for(int a = 1; a < argc; ++a) {
 		if(!strcmp(argv[a], "-i")) { while(a + 1 < argc && argv[a + 1][0] != '-' && n_in < 256) inputs[n_in++] = argv[++a]; }
 		else if(!strcmp(argv[a], "-batch") && a + 1 < argc) {          /* index.c:351-401: a file that lists the inputs, one path a line */
@@ -57,6 +63,7 @@ int main(int argc, char **argv) {
 			if(n_decon == 0) { fprintf(stderr, "No deCon file specified.\n"); return 1; }
 		}
 		else if(!strcmp(argv[a], "-o") && a + 1 < argc) out = argv[++a];
+		else if(!strcmp(argv[a], "-t_db") && a + 1 < argc) t_db = argv[++a];          /* index.c:221-229 */
 		else if(!strcmp(argv[a], "-k") && a + 1 < argc) k = atoi(argv[++a]);
 		else if(!strcmp(argv[a], "-Sparse")) {         /* index.c:451-474: the next argument whatever it is; none, or "-": no prefix */
 			sparse = a + 1 < argc ? argv[++a] : "-";
@@ -73,6 +80,7 @@ int main(int argc, char **argv) {
 		else if(!strcmp(argv[a], "-and")) and_mode = 1;          /* index.c:309 */
 		else if(!strcmp(argv[a], "-hq") || !strcmp(argv[a], "-ht")) {          /* index.c:327-350: no value behind it: nothing happens */
 			double *dst = argv[a][2] == 'q' ? &hom_q : &hom_t;
+			hom_opt = 1;
 			if(a + 1 < argc) {
 				char *end;
 				*dst = strtod(argv[a + 1], &end);
@@ -84,12 +92,21 @@ int main(int argc, char **argv) {
 		else { fprintf(stderr, USAGE); return 2; }
 	}
 	/* what is not built is refused by name, before a file or the device is opened */
+	if(t_db && hom_opt) { fprintf(stderr, "kmahip_index: -hq / -ht are not built with -t_db (the homology check against the templates already in the index)\n"); return 2; }
+	if(t_db && ml_opt) { fprintf(stderr, "kmahip_index: -ML is not built with -t_db\n"); return 2; }
+	if(t_db) {
+		/* index.c:494-500: what must be there; k and the prefix are the index's, whatever -k and -Sparse said (index.c:535-546) */
+		if(!n_in && !n_decon) { fprintf(stderr, "No inputfiles defined.\n"); return 255; }
+		if(kmahip_init(0) || kmahip_index_append(t_db, inputs, n_in, decon, n_decon, out)) { fprintf(stderr, "kmahip_index: %s\n", kmahip_last_error()); return 1; }
+		return 0;
+	}
 	if(sparse && decon_opt) { fprintf(stderr, "kmahip_index: -Sparse is not built for -deCon (deConNode_sparse)\n"); return 2; }
 	if(ml_opt && !sparse) { fprintf(stderr, "kmahip_index: -ML is not built for a build without -Sparse\n"); return 2; }
 	if(sparse && ml_opt && min_len > 0 && hom_t < 1) {
 		fprintf(stderr, "kmahip_index: -ht is not built with -ML (templateCheck leaves its scores uncleared behind a template below -ML, qualcheck.c:287)\n");
 		return 2;
 	}
+	if(!n_in && n_decon) { fprintf(stderr, "Nothing to update.\n"); return 0; }          /* index.c:498-500 */
 	if(!n_in || !out) { fprintf(stderr, "kmahip_index: -i and -o are required\n"); return 2; }
 	if(kmahip_init(0) || (sparse ? kmahip_index_build_sparse_hom(inputs, n_in, out, k, k, sparse, (int) min_len, hom_q, hom_t, and_mode, "-")
 	                      : decon_opt ? kmahip_index_build_decon(inputs, n_in, decon, n_decon, out, k) : kmahip_index_build(inputs, n_in, out, k))) {

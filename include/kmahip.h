@@ -616,15 +616,15 @@ int kmahip_chain_unpinned_reads(const int32_t *len, const int32_t *N, const int6
  * made unique there (rocPRIM); grouping, list sharing and the bucket directory are one pass on the host. The files hold the
  * same k-mer -> template-list mapping as the reference's (tests compare the two) and the reference maps against them with
  * identical results; bucket count, key order inside a bucket and list order are the builder's own. FASTA input, plain or .gz.
- * Not covered: minimizers (-m), homopolymer compression (-hc), appending (-t_db); -Sparse / prefixes have their own entry point,
- * kmahip_index_build_sparse below; `-batch list` is the
+ * Not covered: minimizers (-m), homopolymer compression (-hc); -Sparse / prefixes have their own entry point,
+ * kmahip_index_build_sparse below, and so has -t_db (kmahip_index_append); `-batch list` is the
  * host program's (examples/kmahip_index: the listed paths become fasta_paths). */
 int kmahip_index_build(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize);
 /* `kma index ... -deCon <fasta ...>` (index.c:676-729, decon.c:77-227): the four files of kmahip_index_build, byte for byte, and
  * <prefix>.decon.comp.b beside them, the same mapping with the pseudo-template DB_size (one past the last template) appended to the
  * list of every database k-mer that occurs in a contamination record or in its reverse complement. A record counts when it is
  * longer than k; N's split it as they split a template. A k-mer that only the contamination holds is not added. decon_paths: FASTA,
- * plain or .gz; "--" (standard input) is refused with KMAHIP_EINVAL. Appending to an existing index is not covered. */
+ * plain or .gz; "--" (standard input) is refused with KMAHIP_EINVAL. Marking an index that exists: kmahip_index_append. */
 int kmahip_index_build_decon(const char *const *fasta_paths, int n_files, const char *const *decon_paths, int n_decon,
                              const char *out_prefix, int kmersize);
 /* `kma index ... -Sparse <prefix | -> [-ML n]` (index.c:451-474, 576-613; makeindex.c:46-48, 167-291; updateindex.c:79-199:
@@ -640,8 +640,8 @@ int kmahip_index_build_decon(const char *const *fasta_paths, int n_files, const 
  * builder's own bucket layout; .seq.b and .name as kmahip_index_build writes them, over the templates that stayed.
  * kmersize <= 0: 16. kmerindex <= 0: kmersize (what -k sets). KMAHIP_EINVAL, the reason in kmahip_last_error: k outside 4 ... 16,
  * a prefix of more than 16 bases, a null prefix, an empty one or one with a letter that is no A, C, G, T (IUPAC codes as the
- * reference folds them) -- "Invalid prefix." as the reference says. Not covered: -deCon on a sparse index, appending; -ht / -hq
- * have their own entry point below. */
+ * reference folds them) -- "Invalid prefix." as the reference says. Not covered: -deCon on a sparse index; -ht / -hq and appending
+ * (kmahip_index_append) have their own entry points below. */
 int kmahip_index_build_sparse(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize, int kmerindex,
                               const char *prefix_text, int min_len);
 /* `kma index ... -Sparse <prefix | -> -hq x -ht y [-and]` (index.c:309-350, 607-613; qualcheck.c:81-324: queryCheck, templateCheck,
@@ -671,6 +671,32 @@ int kmahip_index_build_sparse_hom(const char *const *fasta_paths, int n_files, c
 int kmahip_test_index_hom_rows(const char *const *fasta_paths, int n_files, int kmersize, const char *prefix_text, int min_len, double hom_q,
                                double hom_t, int and_mode, uint32_t *out, int64_t cap_rows, int64_t *n_rows);
 int kmahip_test_index_hom_timing(double *out4);
+/* `kma index -t_db <prefix> [-i <fasta ...>] [-deCon <fasta ...>] [-o <out>]` (index.c:221-229, 529-557, 616-674, 676-732; load_DBs,
+ * loadupdate.c:151-210; hashMapKMA_openChains, loadupdate.c:64-112): templates are added to an index that exists. The result is the
+ * index a fresh build of the old templates followed by the new ones gives: byte for byte the files kmahip_index_build /
+ * _build_sparse / _build_decon write for the concatenated input, and the reference's own append in mapping, header, lengths, names
+ * and sequences. k and the sparse prefix are the old index's (a sparse index is appended sparsely); the new templates get the ids
+ * from the old DB_size on and are parsed as in a fresh build (N trimming, " B<n>", the length gate, IUPAC folding). The k-mers of
+ * the old templates come out of the old .comp.b, not out of .seq.b (which stores N as A): the k-mer -> value-list table is
+ * expanded back into (k-mer << 32 | template) pairs on the device (one thread per k-mer counts, a scan, one lane per pair writes),
+ * joins the keys of the new templates in the sort and goes through the host pass of a fresh build. The list width follows the new
+ * DB_size (16 bits below 65535). The old index may be the reference's or ours, hashed or direct-address.
+ * n_files == 0 with n_decon > 0: decontamination onto the index as it is; only <prefix>.decon.comp.b is written. With both, the
+ * pseudo-template is the new DB_size. out_prefix NULL: in place. Every file is written as <out>.appending<ext> and renamed at the
+ * end, so a failed in-place append leaves the old index whole; with an out_prefix of its own the old files are never touched. An
+ * old <prefix>.decon.comp.b beside an index appended without decon_paths is left as it is, as in the reference: it is stale then.
+ * Before any launch the old index is held to its header: every list inside the value array, not empty, ascending, ids 1 ..
+ * DB_size - 1, .length.b / .name / .seq.b of the sizes DB_size and the lengths ask for; else KMAHIP_EFORMAT, "Wrong format of DB."
+ * KMAHIP_EFORMAT by name also: k > 16, a minimizer / homopolymer flag. KMAHIP_EINVAL: a NULL db_prefix, neither input ("No inputfiles
+ * defined."), "--" among decon_paths, decon_paths on a sparse index (deConNode_sparse). Not covered: -hq / -ht / -ML with an append. */
+int kmahip_index_append(const char *db_prefix, const char *const *fasta_paths, int n_files, const char *const *decon_paths, int n_decon,
+                        const char *out_prefix);
+/* Test and timing hooks of the expansion. kmahip_test_index_expand: the pairs of <prefix>.comp.b (k-mer << 32 | template) as the
+ * device wrote them, in the order of the file's k-mers; *n how many (KMAHIP_EINVAL with *n set when cap is too small); the file is
+ * checked as kmahip_index_append checks it. kmahip_test_index_expand_timing: ms of the count kernel, the scan and the write pass of
+ * the last expansion of this process, by device events. */
+int kmahip_test_index_expand(const char *prefix, uint64_t *out_pairs, int64_t cap, int64_t *n);
+int kmahip_test_index_expand_timing(double *out3);
 
 /* ---- stage 1: FASTQ / FASTA ingest into packed read batches -------------------------------------------
  * Host code (zlib for .gz, plain files read as they are): the record parser of FileBuffgetFq / FileBuffgetFsa

@@ -436,6 +436,47 @@ def index_build(fasta_paths, out_prefix, k=16, decon=None, sparse=None, min_len=
     _check(L.kmahip_index_build(arr, len(paths), os.fsencode(out_prefix), int(k)))
 
 
+def index_append(db_prefix, fasta_paths=None, out_prefix=None, decon=None):
+    """kmahip_index_append (`kma index -t_db`): the templates of fasta_paths behind those of the index db_prefix, as a fresh build of
+    all of them would index them; k and the sparse prefix are the index's. out_prefix None: in place. decon: contamination FASTA
+    file(s); without fasta_paths only <prefix>.decon.comp.b is written, for the index as it is (needs a GPU)."""
+    def arr(x):
+        ps = [] if x is None else [os.fsencode(p) for p in ([x] if isinstance(x, (str, bytes)) else x)]
+        return (C.c_char_p * max(1, len(ps)))(*ps), len(ps)
+    L = lib()
+    L.kmahip_index_append.argtypes = [C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_char_p]
+    L.kmahip_index_append.restype = C.c_int
+    (fa, n_fa), (da, n_da) = arr(fasta_paths), arr(decon)
+    _check(L.kmahip_index_append(os.fsencode(db_prefix), fa, n_fa, da, n_da, None if out_prefix is None else os.fsencode(out_prefix)))
+
+
+def index_expand(prefix):
+    """the test hook of an append's expansion (kmahip_test_index_expand): the (k-mer << 32 | template) pairs of <prefix>.comp.b as
+    the device wrote them, uint64, in the order of the file's k-mers"""
+    L = lib()
+    L.kmahip_test_index_expand.argtypes = [C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    L.kmahip_test_index_expand.restype = C.c_int
+    cap = 1 << 16
+    while True:
+        out = np.zeros(cap, np.uint64)
+        n = C.c_int64(0)
+        rc = L.kmahip_test_index_expand(os.fsencode(prefix), _p(out), cap, C.byref(n))
+        if rc and n.value > cap:
+            cap = n.value
+            continue
+        _check(rc)
+        return out[:n.value].copy()
+
+
+def index_expand_timing():
+    """ms of the count kernel, the scan and the write pass of this process's last expansion (kmahip_test_index_expand_timing)"""
+    out = (C.c_double * 3)()
+    L = lib()
+    L.kmahip_test_index_expand_timing.argtypes = [C.POINTER(C.c_double)]
+    _check(L.kmahip_test_index_expand_timing(out))
+    return list(out)
+
+
 def index_hom_rows(fasta_paths, k=16, sparse="-", min_len=0, hom_q=1.0, hom_t=1.0, hom_and=False):
     """the test hook of the homology counts (kmahip_test_index_hom_rows): [n candidate templates, 7] uint32 in file order -- stays, thisKlen,
     max Scores_tot, templateQ, Scores and ulen of the best thisT, templateT (templates by file order, 1 ..; 0: none). No file is written."""

@@ -15,6 +15,9 @@
 // becomes a key of the pseudo-template DB_size and joins the same sort; the host pass runs twice over the sorted pairs, once
 // without those keys (<prefix>.comp.b, as ever) and once with them (<prefix>.decon.comp.b), where a k-mer that only the
 // contamination holds is dropped: decontamination marks k-mers of the database, it adds none.
+// -t_db (kmahip_index_append; index.c:529-557, 616-674, loadupdate.c:64-210): the old .comp.b is expanded back into pairs on the
+// device (index_expand_count_kernel, a scan, index_expand_pairs_kernel), the new templates' keys are made by the kernels of the fresh
+// builds under ids from the old DB_size on, and everything joins one sort; the host pass and the writers are those of a fresh build.
 #include "kmahip_internal.h"
 #include <zlib.h>
 #include <cstring>
@@ -138,6 +141,39 @@ __global__ __launch_bounds__(256) void index_sparse_ulen_kernel(const unsigned l
 	} else if(has) atomicAdd(&ulen[id], 1u);
 }
 
+// An append (`kma index -t_db`): the k-mer -> value-list table of the old .comp.b back into (k-mer << 32 | template) pairs, what
+// hashMapKMA_openChains (loadupdate.c:64-112) does chain by chain. One thread per stored k-mer: the length of its list, as a 64-bit
+// count for the scan; cnt[n] = 0, so that the exclusive scan over n + 1 counts ends with the number of pairs
+template <typename V>
+__global__ __launch_bounds__(256) void index_expand_count_kernel(const V *values, const uint32_t *vidx, int64_t n, unsigned long long *cnt) {
+	const int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if(i > n) return;
+	cnt[i] = i < n ? (unsigned long long) values[vidx[i]] : 0ull;
+}
+
+// One lane per pair j of the output, so that the stores are plain consecutive 8-byte ones whatever the lists' lengths: its k-mer is
+// the last i with off[i] <= j (off: the scanned counts, n + 1 of them, strictly ascending since no list is empty), found by binary
+// search as index_kmers_kernel finds its template -- over the k-mers of this block alone: the block's first and last lane search all
+// n first and leave their answers in LDS, and lists of a few ids keep what lies between them to a few hundred entries
+template <typename V>
+__global__ __launch_bounds__(256) void index_expand_pairs_kernel(const V *values, const uint32_t *keys, const uint32_t *vidx, const unsigned long long *off, int64_t n,
+                                                                  int64_t total, unsigned long long *pairs) {
+	__shared__ int64_t range[2];
+	const int64_t j0 = (int64_t) blockIdx.x * blockDim.x, j = j0 + threadIdx.x;
+	if(threadIdx.x < 2) {
+		const unsigned long long jj = (unsigned long long) (threadIdx.x == 0 ? j0 : (j0 + blockDim.x - 1 < total ? j0 + blockDim.x - 1 : total - 1));
+		int64_t lo = 0, hi = n;
+		while(hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if(off[mid] <= jj) lo = mid; else hi = mid; }
+		range[threadIdx.x] = lo;
+	}
+	__syncthreads();
+	if(j >= total) return;
+	int64_t lo = range[0], hi = range[1] + 1;
+	while(hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if(off[mid] <= (unsigned long long) j) lo = mid; else hi = mid; }
+	const uint32_t id = (uint32_t) values[(uint64_t) vidx[lo] + 1 + ((unsigned long long) j - off[lo])];
+	pairs[j] = ((unsigned long long) keys[lo] << 32) | id;
+}
+
 struct SameKey { __device__ bool operator()(unsigned long long a, unsigned long long b) const { return a == b; } };
 
 int read_whole(const char *path, std::vector<uint8_t> &buf) {
@@ -229,6 +265,26 @@ int write_comp_b(const std::vector<unsigned long long> &pairs, uint32_t DB_size,
 	return KMAHIP_OK;
 }
 
+// the contamination records of every file behind dcodes, d_roff[r] .. d_roff[r + 1] the bases of record r (d_roff comes in as {0})
+int read_decon_records(const char *const *decon_paths, int n_decon, const RefTable &T, int k, std::vector<uint8_t> &dcodes, std::vector<int64_t> &d_roff) {
+	for(int fi = 0; fi < n_decon; ++fi) {
+		std::vector<uint8_t> raw;
+		const int rc = read_whole(decon_paths[fi], raw);
+		if(rc) return rc;
+		if(raw.empty() || raw[0] != '>') { kmahip_set_error("%s is not a FASTA file", decon_paths[fi]); return KMAHIP_EFORMAT; }
+		size_t p = 0;
+		while(p < raw.size()) {
+			while(p < raw.size() && raw[p] != '\n') ++p;
+			if(p < raw.size()) ++p;
+			const size_t at = dcodes.size();
+			while(p < raw.size() && raw[p] != '>') { const uint8_t c = T.t[raw[p]]; if(c < 8) dcodes.push_back(c); ++p; }
+			if((int64_t) (dcodes.size() - at) > k) d_roff.push_back((int64_t) dcodes.size());
+			else dcodes.resize(at);
+		}
+	}
+	return KMAHIP_OK;
+}
+
 // the build itself: n_decon = 0 is `kma index` without -deCon
 int index_build(const char *const *fasta_paths, int n_files, const char *const *decon_paths, int n_decon, const char *out_prefix, int kmersize) {
 	if(!fasta_paths || n_files <= 0 || !out_prefix) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
@@ -275,21 +331,7 @@ int index_build(const char *const *fasta_paths, int n_files, const char *const *
 	// k (:193), N's and all. Leading and trailing N's need no trimming here: no k-mer holds one
 	std::vector<uint8_t> dcodes;
 	std::vector<int64_t> d_roff(1, 0);
-	for(int fi = 0; fi < n_decon; ++fi) {
-		std::vector<uint8_t> raw;
-		const int rc = read_whole(decon_paths[fi], raw);
-		if(rc) return rc;
-		if(raw.empty() || raw[0] != '>') { kmahip_set_error("%s is not a FASTA file", decon_paths[fi]); return KMAHIP_EFORMAT; }
-		size_t p = 0;
-		while(p < raw.size()) {
-			while(p < raw.size() && raw[p] != '\n') ++p;
-			if(p < raw.size()) ++p;
-			const size_t at = dcodes.size();
-			while(p < raw.size() && raw[p] != '>') { const uint8_t c = T.t[raw[p]]; if(c < 8) dcodes.push_back(c); ++p; }
-			if((int64_t) (dcodes.size() - at) > k) d_roff.push_back((int64_t) dcodes.size());
-			else dcodes.resize(at);
-		}
-	}
+	if(const int rc = read_decon_records(decon_paths, n_decon, T, k, dcodes, d_roff)) return rc;
 	const int64_t dtotal = (int64_t) dcodes.size();
 	const int n_dr = (int) d_roff.size() - 1;
 	const int64_t n_keys = total + 2 * dtotal;
@@ -519,6 +561,215 @@ int index_build_sparse(const char *const *fasta_paths, int n_files, const char *
 	return sparse_write_seq_and_names(base, tm, new_id, codes);
 }
 
+// ---- `kma index -t_db <prefix>`: append to an index that exists ------------------------------------------------------------------
+double g_expand_ms[3] = {0, 0, 0};          // the last expansion: count kernel, scan, pairs kernel in ms (device events)
+
+// <prefix>.comp.b as an append takes it: read, and held to its own header before any of it reaches the device
+struct OldIndex {
+	KmaComp c;
+	bool sparse = false;
+	uint64_t n_pairs = 0;
+};
+
+int append_open(const std::string &base, OldIndex &o) {
+	if(const int rc = kmahip_comp_read(base + ".comp.b", true, &o.c)) return rc;          // (refuses k > 16 and flag != 0 by name)
+	o.sparse = !(o.c.prefix_len == 0 && o.c.prefix == 0);                                  // index.c:542-546
+	if(o.c.prefix_len > 16 || (!o.c.mega && o.c.n != o.c.n_hdr)) { kmahip_set_error(KMAHIP_WRONG_DB " (prefix of %u bases)", o.c.prefix_len); return KMAHIP_EFORMAT; }
+	return append_check_lists(o.c.keys.data(), o.c.vidx.data(), o.c.n, o.c.values.data(), o.c.u16, o.c.v_index, o.c.DB_size, (int) o.c.mlen, &o.n_pairs);
+}
+
+// the pairs of a checked index into d_pairs[0 .. o.n_pairs), in the order of the file's k-mers
+int expand_on_device(const OldIndex &o, unsigned long long *d_pairs) {
+	const KmaComp &c = o.c;
+	const int64_t n = (int64_t) c.n;
+	const size_t vbytes = (size_t) c.v_index * (c.u16 ? 2 : 4);
+	void *d_values = nullptr, *d_tmp = nullptr; uint32_t *d_k = nullptr, *d_vi = nullptr; unsigned long long *d_cnt = nullptr, *d_off = nullptr;
+	hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+	auto release = [&] { (void) hipFree(d_values); (void) hipFree(d_tmp); (void) hipFree(d_k); (void) hipFree(d_vi); (void) hipFree(d_cnt); (void) hipFree(d_off);
+	                     for(hipEvent_t e : ev) if(e) (void) hipEventDestroy(e); };
+	struct Guard { decltype(release) &r; ~Guard() { r(); } } guard{release};
+	HIP_TRY(hipMalloc(&d_values, vbytes));
+	HIP_TRY(hipMalloc((void **) &d_k, (size_t) n * 4));
+	HIP_TRY(hipMalloc((void **) &d_vi, (size_t) n * 4));
+	HIP_TRY(hipMalloc((void **) &d_cnt, ((size_t) n + 1) * 8));
+	HIP_TRY(hipMalloc((void **) &d_off, ((size_t) n + 1) * 8));
+	HIP_TRY(hipMemcpy(d_values, c.values.data(), vbytes, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(d_k, c.keys.data(), (size_t) n * 4, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(d_vi, c.vidx.data(), (size_t) n * 4, hipMemcpyHostToDevice));
+	size_t tmp_bytes = 0;
+	if(rocprim::exclusive_scan(nullptr, tmp_bytes, d_cnt, d_off, 0ull, (size_t) n + 1, rocprim::plus<unsigned long long>(), 0) != hipSuccess) { kmahip_set_error("rocprim size query failed"); return KMAHIP_EDEVICE; }
+	HIP_TRY(hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16));
+	for(hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e));
+	const dim3 g_cnt((unsigned) ((n + 1 + 255) / 256)), g_pairs((unsigned) ((o.n_pairs + 255) / 256));
+	HIP_TRY(hipEventRecord(ev[0], 0));
+	if(c.u16) hipLaunchKernelGGL(index_expand_count_kernel<uint16_t>, g_cnt, dim3(256), 0, 0, (const uint16_t *) d_values, d_vi, n, d_cnt);
+	else hipLaunchKernelGGL(index_expand_count_kernel<uint32_t>, g_cnt, dim3(256), 0, 0, (const uint32_t *) d_values, d_vi, n, d_cnt);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipEventRecord(ev[1], 0));
+	if(rocprim::exclusive_scan(d_tmp, tmp_bytes, d_cnt, d_off, 0ull, (size_t) n + 1, rocprim::plus<unsigned long long>(), 0) != hipSuccess) { kmahip_set_error("rocprim scan failed"); return KMAHIP_EDEVICE; }
+	HIP_TRY(hipEventRecord(ev[2], 0));
+	// the write pass is sized by the host's count of the pairs: the scan must say the same before a lane derives an address from it
+	unsigned long long total = 0;
+	HIP_TRY(hipMemcpy(&total, d_off + n, 8, hipMemcpyDeviceToHost));
+	if(total != o.n_pairs) { kmahip_set_error("index expansion: the scan counts %llu pairs, the host %llu", total, (unsigned long long) o.n_pairs); return KMAHIP_EDEVICE; }
+	HIP_TRY(hipEventRecord(ev[3], 0));
+	if(c.u16) hipLaunchKernelGGL(index_expand_pairs_kernel<uint16_t>, g_pairs, dim3(256), 0, 0, (const uint16_t *) d_values, d_k, d_vi, d_off, n, (int64_t) total, d_pairs);
+	else hipLaunchKernelGGL(index_expand_pairs_kernel<uint32_t>, g_pairs, dim3(256), 0, 0, (const uint32_t *) d_values, d_k, d_vi, d_off, n, (int64_t) total, d_pairs);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipEventRecord(ev[4], 0));
+	HIP_TRY(hipEventSynchronize(ev[4]));
+	float ms[3] = {0, 0, 0};
+	HIP_TRY(hipEventElapsedTime(&ms[0], ev[0], ev[1]));
+	HIP_TRY(hipEventElapsedTime(&ms[1], ev[1], ev[2]));
+	HIP_TRY(hipEventElapsedTime(&ms[2], ev[3], ev[4]));
+	for(int i = 0; i < 3; ++i) g_expand_ms[i] = ms[i];
+	return KMAHIP_OK;
+}
+
+int index_append(const char *db_prefix, const char *const *fasta_paths, int n_files, const char *const *decon_paths, int n_decon, const char *out_prefix) {
+	if(!db_prefix || n_files < 0 || n_decon < 0 || (n_files > 0 && !fasta_paths) || (n_decon > 0 && !decon_paths)) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	if(n_files == 0 && n_decon == 0) { kmahip_set_error("No inputfiles defined."); return KMAHIP_EINVAL; }
+	for(int i = 0; i < n_files; ++i) if(!fasta_paths[i]) { kmahip_set_error("null argument"); return KMAHIP_EINVAL; }
+	for(int i = 0; i < n_decon; ++i)
+		if(!decon_paths[i] || !strcmp(decon_paths[i], "--")) { kmahip_set_error("decontamination from standard input (--) is not built: give a file"); return KMAHIP_EINVAL; }
+	static const RefTable T;
+	const std::string old_base(db_prefix), base(out_prefix ? out_prefix : db_prefix), tmp = base + ".appending";
+	OldIndex o;
+	int rc = append_open(old_base, o);
+	if(rc) return rc;
+	if(o.sparse && n_decon > 0) { kmahip_set_error("index append: -deCon on a sparse index is not built (deConNode_sparse)"); return KMAHIP_EINVAL; }
+	const int k = (int) o.c.mlen;
+	const uint32_t old_DB = o.c.DB_size;
+	OldAnnots ann;
+	if((rc = append_read_annots(old_base, old_DB, o.sparse, n_files > 0, ann))) return rc;
+
+	// the new templates, parsed as a fresh build parses them; k and the prefix are the index's (index.c:535-546)
+	SparseRule rule;
+	rule.k = k; rule.kmerindex = o.sparse && ann.slen[0] ? (int) std::min<uint32_t>(ann.slen[0], 31) : k;          // load_DBs: kmerindex = slengths[0]
+	rule.prefix_len = (int) o.c.prefix_len; rule.prefix = o.c.prefix;
+	sparse_set_gates(0, rule);
+	std::vector<Tmpl> tm;
+	std::vector<uint8_t> codes;
+	for(int fi = 0; fi < n_files; ++fi) {
+		std::vector<uint8_t> raw;
+		if((rc = read_whole(fasta_paths[fi], raw))) return rc;
+		// (a plain build keeps a template of k bases: index_build's `len < k`)
+		if((rc = sparse_parse_fasta(raw, fasta_paths[fi], T, o.sparse ? rule.MinLen : k - 1, codes, tm))) return rc;
+	}
+	const int n_t = (int) tm.size();
+	if(n_files > 0 && n_t == 0) { kmahip_set_error("no template of at least %d bases", k); return KMAHIP_EFORMAT; }
+	std::vector<uint8_t> dcodes;
+	std::vector<int64_t> d_roff(1, 0);
+	if((rc = read_decon_records(decon_paths, n_decon, T, k, dcodes, d_roff))) return rc;
+	const int64_t total = (int64_t) codes.size(), dtotal = (int64_t) dcodes.size(), n_new = o.sparse ? 2 * total : total;
+	const int n_dr = (int) d_roff.size() - 1;
+	const int64_t n_old = (int64_t) o.n_pairs, n_keys = n_new + 2 * dtotal + n_old;
+	std::vector<int64_t> t_off((size_t) n_t + 1);
+	for(int t = 0; t < n_t; ++t) t_off[(size_t) t] = (int64_t) tm[(size_t) t].at;
+	t_off[(size_t) n_t] = total;
+
+	// device: keys[0 .. n_new) the new templates', [n_new .. + 2 dtotal) the contamination's, behind them the old index's pairs
+	uint8_t *d_codes = nullptr, *d_dcodes = nullptr; int64_t *d_off = nullptr, *d_doff = nullptr; unsigned *d_slen = nullptr, *d_ulen = nullptr; uint32_t *d_newid = nullptr;
+	unsigned long long *d_keys = nullptr, *d_sorted = nullptr, *d_uniq = nullptr; size_t *d_count = nullptr; void *d_tmp = nullptr;
+	auto release = [&] { (void) hipFree(d_codes); (void) hipFree(d_dcodes); (void) hipFree(d_off); (void) hipFree(d_doff); (void) hipFree(d_slen); (void) hipFree(d_ulen);
+	                     (void) hipFree(d_newid); (void) hipFree(d_keys); (void) hipFree(d_sorted); (void) hipFree(d_uniq); (void) hipFree(d_count); (void) hipFree(d_tmp); };
+	struct Guard { decltype(release) &r; ~Guard() { r(); } } guard{release};
+	HIP_TRY(hipMalloc((void **) &d_keys, (size_t) n_keys * 8));
+	if((rc = expand_on_device(o, d_keys + n_new + 2 * dtotal))) return rc;
+	std::vector<uint32_t> slen, new_id;
+	uint32_t DB_size = old_DB;
+	if(n_t > 0) {
+		HIP_TRY(hipMalloc((void **) &d_codes, (size_t) total + 32));
+		HIP_TRY(hipMalloc((void **) &d_off, t_off.size() * 8));
+		HIP_TRY(hipMalloc((void **) &d_newid, (size_t) n_t * 4));
+		HIP_TRY(hipMemcpy(d_codes, codes.data(), (size_t) total, hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(d_off, t_off.data(), t_off.size() * 8, hipMemcpyHostToDevice));
+		if(o.sparse) {
+			HIP_TRY(hipMalloc((void **) &d_slen, (size_t) n_t * 4));
+			HIP_TRY(hipMemset(d_slen, 0, (size_t) n_t * 4));
+			hipLaunchKernelGGL(index_sparse_keys_kernel, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, 0, d_codes, d_off, n_t, total, k, rule.prefix_len,
+			                   (unsigned long long) rule.prefix, d_keys, d_slen);
+			HIP_TRY(hipGetLastError());
+			slen.resize((size_t) n_t);
+			HIP_TRY(hipMemcpy(slen.data(), d_slen, (size_t) n_t * 4, hipMemcpyDeviceToHost));
+			if(sparse_assign_ids(tm, slen, rule, new_id) == 0) { kmahip_set_error("no new template holds a k-mer behind the prefix"); return KMAHIP_EFORMAT; }
+		} else {
+			hipLaunchKernelGGL(index_kmers_kernel, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, 0, d_codes, d_off, n_t, total, k, d_keys);
+			HIP_TRY(hipGetLastError());
+			new_id.resize((size_t) n_t);
+			for(int t = 0; t < n_t; ++t) new_id[(size_t) t] = (uint32_t) t + 1;
+		}
+		// the ids of the new templates start at the old DB_size (update_DB with templates->DB_size, makeindex.c:225)
+		if((uint64_t) old_DB + (uint64_t) n_t >= 0xFFFFFFFFull) { kmahip_set_error("more than 2^32 templates"); return KMAHIP_EFORMAT; }
+		for(uint32_t &id : new_id) if(id) { id += old_DB - 1; DB_size = id + 1; }
+		HIP_TRY(hipMemcpy(d_newid, new_id.data(), (size_t) n_t * 4, hipMemcpyHostToDevice));
+		hipLaunchKernelGGL(index_sparse_remap_kernel, dim3((unsigned) ((n_new + 255) / 256)), dim3(256), 0, 0, d_keys, n_new, d_newid);
+		HIP_TRY(hipGetLastError());
+	}
+	if(dtotal > 0) {
+		// the pseudo-template is the NEW DB_size (deConDB runs on the index as it stands after the append, index.c:676-696)
+		HIP_TRY(hipMalloc((void **) &d_dcodes, (size_t) dtotal + 32));
+		HIP_TRY(hipMalloc((void **) &d_doff, d_roff.size() * 8));
+		HIP_TRY(hipMemcpy(d_dcodes, dcodes.data(), (size_t) dtotal, hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(d_doff, d_roff.data(), d_roff.size() * 8, hipMemcpyHostToDevice));
+		hipLaunchKernelGGL(index_decon_kmers_kernel, dim3((unsigned) ((dtotal + 255) / 256)), dim3(256), 0, 0, d_dcodes, d_doff, n_dr, dtotal, k, DB_size, d_keys + n_new);
+		HIP_TRY(hipGetLastError());
+	}
+	HIP_TRY(hipMalloc((void **) &d_sorted, (size_t) n_keys * 8));
+	HIP_TRY(hipMalloc((void **) &d_uniq, (size_t) n_keys * 8));
+	HIP_TRY(hipMalloc((void **) &d_count, sizeof(size_t)));
+	size_t tmp_bytes = 0, tmp2 = 0;
+	if(rocprim::radix_sort_keys(nullptr, tmp_bytes, d_keys, d_sorted, (size_t) n_keys, 0, 64, 0) != hipSuccess ||
+	   rocprim::unique(nullptr, tmp2, d_sorted, d_uniq, d_count, (size_t) n_keys, SameKey(), 0) != hipSuccess) { kmahip_set_error("rocprim size query failed"); return KMAHIP_EDEVICE; }
+	tmp_bytes = std::max(tmp_bytes, tmp2);
+	HIP_TRY(hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16));
+	if(rocprim::radix_sort_keys(d_tmp, tmp_bytes, d_keys, d_sorted, (size_t) n_keys, 0, 64, 0) != hipSuccess ||
+	   rocprim::unique(d_tmp, tmp_bytes, d_sorted, d_uniq, d_count, (size_t) n_keys, SameKey(), 0) != hipSuccess) { kmahip_set_error("rocprim sort / unique failed"); return KMAHIP_EDEVICE; }
+	size_t n_pairs = 0;
+	HIP_TRY(hipMemcpy(&n_pairs, d_count, sizeof n_pairs, hipMemcpyDeviceToHost));
+	if(n_pairs > (size_t) n_keys) { kmahip_set_error("rocprim unique returned %zu of %lld keys", n_pairs, (long long) n_keys); return KMAHIP_EDEVICE; }
+	std::vector<uint32_t> ulen;
+	if(o.sparse && n_pairs) {
+		// (the old templates keep the ulengths their file holds; the count of the new ones is their share of the unique pairs)
+		HIP_TRY(hipMalloc((void **) &d_ulen, (size_t) DB_size * 4));
+		HIP_TRY(hipMemset(d_ulen, 0, (size_t) DB_size * 4));
+		hipLaunchKernelGGL(index_sparse_ulen_kernel, dim3((unsigned) ((n_pairs + 255) / 256)), dim3(256), 0, 0, d_uniq, (int64_t) n_pairs, DB_size, d_ulen);
+		HIP_TRY(hipGetLastError());
+		ulen.resize((size_t) DB_size);
+		HIP_TRY(hipMemcpy(ulen.data(), d_ulen, (size_t) DB_size * 4, hipMemcpyDeviceToHost));
+	}
+	std::vector<unsigned long long> pairs(n_pairs);
+	if(n_pairs) HIP_TRY(hipMemcpy(pairs.data(), d_uniq, n_pairs * 8, hipMemcpyDeviceToHost));
+	if(n_pairs && pairs.back() == ~0ull) pairs.pop_back();         // the starts that hold no k-mer sorted to the end
+	if(pairs.empty()) { kmahip_set_error("the templates hold no k-mer"); return KMAHIP_EFORMAT; }
+
+	// every file under a name of its own beside its target, the names taken at the end: a failed append leaves the old index whole
+	std::vector<const char *> exts;
+	if(n_files > 0) {
+		exts = {".comp.b", ".length.b", ".seq.b", ".name"};
+		rc = write_comp_b(pairs, DB_size, k, false, tmp + ".comp.b", o.c.prefix_len, o.c.prefix);
+		if(!rc) {
+			std::vector<uint32_t> lens(ann.lens), sl(ann.slen), ul(ann.ulen);
+			lens.resize(DB_size, 0);
+			if(o.sparse) { sl.resize(DB_size, 0); ul.resize(DB_size, 0); }
+			for(int t = 0; t < n_t; ++t) {
+				const uint32_t id = new_id[(size_t) t];
+				if(!id) continue;
+				lens[id] = (uint32_t) tm[(size_t) t].len;
+				if(o.sparse) { sl[id] = slen[(size_t) t]; ul[id] = ulen[id]; }
+			}
+			rc = append_write_length_b(tmp + ".length.b", DB_size, lens, o.sparse ? &sl : nullptr, o.sparse ? &ul : nullptr);
+		}
+		if(!rc) rc = sparse_write_seq_and_names(tmp, tm, new_id, codes, &ann.seq, &ann.names);
+	}
+	if(!rc && n_decon > 0) {
+		exts.push_back(".decon.comp.b");
+		rc = write_comp_b(pairs, DB_size, k, true, tmp + ".decon.comp.b", o.c.prefix_len, o.c.prefix);
+	}
+	const int rc2 = append_commit(tmp, base, exts, rc == KMAHIP_OK);
+	return rc ? rc : rc2;
+}
+
 }  // namespace
 
 extern "C" int kmahip_index_build_sparse(const char *const *fasta_paths, int n_files, const char *out_prefix, int kmersize, int kmerindex,
@@ -561,6 +812,36 @@ extern "C" int kmahip_test_index_hom_rows(const char *const *fasta_paths, int n_
 extern "C" int kmahip_test_index_hom_timing(double *out4) {
 	if(!out4) return KMAHIP_EINVAL;
 	memcpy(out4, g_hom_ms, sizeof g_hom_ms);
+	return KMAHIP_OK;
+}
+
+extern "C" int kmahip_index_append(const char *db_prefix, const char *const *fasta_paths, int n_files, const char *const *decon_paths, int n_decon,
+                                   const char *out_prefix) {
+	return index_append(db_prefix, fasta_paths, n_files, decon_paths, n_decon, out_prefix);
+}
+
+// the test hook of the expansion: the pairs of <prefix>.comp.b as the device wrote them, in the order of the file's k-mers
+extern "C" int kmahip_test_index_expand(const char *prefix, uint64_t *out_pairs, int64_t cap, int64_t *n) {
+	if(!prefix || !n || (!out_pairs && cap > 0)) { kmahip_set_error("kmahip_test_index_expand: bad argument"); return KMAHIP_EINVAL; }
+	OldIndex o;
+	int rc = append_open(std::string(prefix), o);
+	if(rc) return rc;
+	*n = (int64_t) o.n_pairs;
+	if(*n > cap) { kmahip_set_error("kmahip_test_index_expand: %lld pairs, room for %lld", (long long) *n, (long long) cap); return KMAHIP_EINVAL; }
+	unsigned long long *d_pairs = nullptr;
+	HIP_TRY(hipMalloc((void **) &d_pairs, (size_t) o.n_pairs * 8));
+	rc = expand_on_device(o, d_pairs);
+	hipError_t e = hipSuccess;
+	if(!rc) e = hipMemcpy(out_pairs, d_pairs, (size_t) o.n_pairs * 8, hipMemcpyDeviceToHost);
+	(void) hipFree(d_pairs);
+	if(e != hipSuccess) { kmahip_set_error("kmahip_test_index_expand: %s", hipGetErrorString(e)); return KMAHIP_EDEVICE; }
+	return rc;
+}
+
+// what the last expansion of this process took on the device: ms of the count kernel, of the scan and of the write pass
+extern "C" int kmahip_test_index_expand_timing(double *out3) {
+	if(!out3) return KMAHIP_EINVAL;
+	memcpy(out3, g_expand_ms, sizeof g_expand_ms);
 	return KMAHIP_OK;
 }
 

@@ -4,6 +4,8 @@
 // the writers of .length.b / .seq.b / .name over the templates that stayed (updateAnnots_sparse, makeindex.c:262-276).
 // With -hq / -ht (queryCheck, templateCheck, qualcheck.c:81-324) also the serial part of homology reduction: who stays, given the pairs
 // the device flagged, and the line each template gets.
+// With -t_db (kmahip_index_append) the host side of an append: the check of the old index's value lists before any of them reaches the
+// device, the readers of its .length.b / .name / .seq.b, the writer of .length.b from whole arrays, and the renaming at the end.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -193,11 +195,14 @@ int sparse_write_length_b(const std::string &path, const std::vector<Tmpl> &tm, 
 	return KMAHIP_OK;
 }
 
-// .seq.b and .name over the templates that stayed: (len >> 5) + 1 words each, 32 bases a word from the top, N as A
-int sparse_write_seq_and_names(const std::string &base, const std::vector<Tmpl> &tm, const std::vector<uint32_t> &new_id, const std::vector<uint8_t> &codes) {
+// .seq.b and .name over the templates that stayed: (len >> 5) + 1 words each, 32 bases a word from the top, N as A.
+// old_seq, old_names (an append): what the index held before, written in front
+int sparse_write_seq_and_names(const std::string &base, const std::vector<Tmpl> &tm, const std::vector<uint32_t> &new_id, const std::vector<uint8_t> &codes,
+                               const std::vector<uint8_t> *old_seq = nullptr, const std::vector<uint8_t> *old_names = nullptr) {
 	FILE *f = fopen((base + ".seq.b").c_str(), "wb");
 	if(!f) { kmahip_set_error("cannot create %s.seq.b", base.c_str()); return KMAHIP_EIO; }
 	bool ok = true;
+	if(old_seq && !old_seq->empty()) ok = fwrite(old_seq->data(), 1, old_seq->size(), f) == old_seq->size();
 	std::vector<uint64_t> words;
 	for(size_t t = 0; t < tm.size(); ++t) {
 		if(!new_id[t]) continue;
@@ -209,10 +214,131 @@ int sparse_write_seq_and_names(const std::string &base, const std::vector<Tmpl> 
 	ok = (fclose(f) == 0) && ok;
 	f = fopen((base + ".name").c_str(), "wb");
 	if(!f) { kmahip_set_error("cannot create %s.name", base.c_str()); return KMAHIP_EIO; }
+	if(old_names && !old_names->empty()) ok = fwrite(old_names->data(), 1, old_names->size(), f) == old_names->size() && ok;
 	for(size_t t = 0; t < tm.size(); ++t) if(new_id[t]) ok = fprintf(f, "%s\n", tm[t].name.c_str()) > 0 && ok;
 	ok = (fclose(f) == 0) && ok;
 	if(!ok) { kmahip_set_error("writing the index under %s failed", base.c_str()); return KMAHIP_EIO; }
 	return KMAHIP_OK;
+}
+
+// ---- appending to an index: `kma index -t_db <prefix>` (index.c:221-229, 529-557, 616-674; load_DBs, loadupdate.c:151-210) -------
+// The old index as an append needs it, apart from .comp.b (which kmahip_comp_read holds): the arrays of .length.b (one, or three
+// for a sparse index), and the bytes of .name and .seq.b, which go in front of the new templates'.
+struct OldAnnots {
+	std::vector<uint32_t> lens, slen, ulen;          // DB_size entries each; slen, ulen: a sparse index alone
+	std::vector<uint8_t> names, seq;
+};
+
+#define KMAHIP_WRONG_DB "Wrong format of DB."          // (what the reference says, loadupdate.c:163)
+
+inline bool append_slurp(const std::string &path, std::vector<uint8_t> &buf) {
+	FILE *f = fopen(path.c_str(), "rb");
+	if(!f) return false;
+	buf.clear();
+	uint8_t chunk[1 << 16];
+	for(size_t got; (got = fread(chunk, 1, sizeof chunk, f)) > 0;) buf.insert(buf.end(), chunk, chunk + got);
+	const bool ok = !ferror(f);
+	fclose(f);
+	return ok;
+}
+
+// The value lists of an index before anything of it reaches the device: every list lies inside `values` (v_index elements of 2 or 4
+// bytes: count, then the ids), holds at least one id, ascends, and names templates 1 .. DB_size - 1; every k-mer fits 2 k bits. Each
+// list is walked once however many k-mers share it. *n_pairs = the (k-mer, template) pairs the index holds
+inline int append_check_lists(const uint32_t *keys, const uint32_t *vidx, uint64_t n, const void *values, bool u16, uint64_t v_index, uint32_t DB_size, int k,
+                              uint64_t *n_pairs) {
+	const uint16_t *v16 = (const uint16_t *) values;
+	const uint32_t *v32 = (const uint32_t *) values;
+	const uint64_t kmask = (1ull << (2 * k)) - 1;
+	std::vector<uint8_t> seen((size_t) v_index, 0);
+	uint64_t total = 0;
+	if(DB_size < 2 || n == 0) { kmahip_set_error(KMAHIP_WRONG_DB " (%u templates, %llu k-mers)", DB_size ? DB_size - 1 : 0, (unsigned long long) n); return KMAHIP_EFORMAT; }
+	for(uint64_t i = 0; i < n; ++i) {
+		const uint64_t at = vidx[i];
+		if(keys[i] > kmask) { kmahip_set_error(KMAHIP_WRONG_DB " (k-mer %llu of %d bases: 0x%x)", (unsigned long long) i, k, keys[i]); return KMAHIP_EFORMAT; }
+		if(at >= v_index) { kmahip_set_error(KMAHIP_WRONG_DB " (k-mer %llu: its list starts at %llu of %llu)", (unsigned long long) i, (unsigned long long) at, (unsigned long long) v_index); return KMAHIP_EFORMAT; }
+		const uint64_t cnt = u16 ? v16[at] : v32[at];
+		if(cnt == 0 || cnt >= DB_size || at + 1 + cnt > v_index) {
+			kmahip_set_error(KMAHIP_WRONG_DB " (k-mer %llu: a list of %llu at %llu of %llu)", (unsigned long long) i, (unsigned long long) cnt, (unsigned long long) at, (unsigned long long) v_index);
+			return KMAHIP_EFORMAT;
+		}
+		total += cnt;
+		if(seen[(size_t) at]) continue;
+		seen[(size_t) at] = 1;
+		uint32_t last = 0;
+		for(uint64_t j = at + 1; j <= at + cnt; ++j) {
+			const uint32_t id = u16 ? v16[j] : v32[j];
+			if(id <= last || id >= DB_size) { kmahip_set_error(KMAHIP_WRONG_DB " (k-mer %llu: template %u behind %u, %u in the index)", (unsigned long long) i, id, last, DB_size - 1); return KMAHIP_EFORMAT; }
+			last = id;
+		}
+	}
+	*n_pairs = total;
+	return KMAHIP_OK;
+}
+
+// <prefix>.length.b, and with `all` <prefix>.name and .seq.b: sizes held against DB_size and the lengths. The words of .seq.b are
+// brought to the form this builder writes: the bits behind a template's last base are 0 (where a length is a multiple of 32 the
+// reference's last word is whatever its buffer held, updateindex.c:187), so an appended index does not depend on who built the old one
+inline int append_read_annots(const std::string &base, uint32_t DB_size, bool sparse, bool all, OldAnnots &o) {
+	std::vector<uint8_t> raw;
+	if(!append_slurp(base + ".length.b", raw)) { kmahip_set_error("cannot read %s.length.b", base.c_str()); return KMAHIP_EIO; }
+	const size_t arrays = sparse ? 3 : 1;
+	uint32_t first = 0;
+	if(raw.size() >= 4) memcpy(&first, raw.data(), 4);
+	if(raw.size() != 4 + arrays * 4 * (size_t) DB_size || first != DB_size) {
+		kmahip_set_error(KMAHIP_WRONG_DB " (%s.length.b: %zu bytes, %u templates; .comp.b: %u)", base.c_str(), raw.size(), first ? first - 1 : 0, DB_size - 1);
+		return KMAHIP_EFORMAT;
+	}
+	o.lens.resize(DB_size);
+	memcpy(o.lens.data(), raw.data() + 4, 4 * (size_t) DB_size);
+	if(sparse) {
+		o.slen.resize(DB_size); o.ulen.resize(DB_size);
+		memcpy(o.slen.data(), raw.data() + 4 + 4 * (size_t) DB_size, 4 * (size_t) DB_size);
+		memcpy(o.ulen.data(), raw.data() + 4 + 8 * (size_t) DB_size, 4 * (size_t) DB_size);
+	}
+	if(!all) return KMAHIP_OK;
+	if(!append_slurp(base + ".name", o.names)) { kmahip_set_error("cannot read %s.name", base.c_str()); return KMAHIP_EIO; }
+	if(!append_slurp(base + ".seq.b", o.seq)) { kmahip_set_error("cannot read %s.seq.b", base.c_str()); return KMAHIP_EIO; }
+	size_t lines = 0, words = 0;
+	for(uint8_t c : o.names) lines += c == '\n';
+	for(uint32_t t = 1; t < DB_size; ++t) words += ((size_t) o.lens[t] >> 5) + 1;
+	if(lines != DB_size - 1 || (!o.names.empty() && o.names.back() != '\n') || o.seq.size() != 8 * words) {
+		kmahip_set_error(KMAHIP_WRONG_DB " (%s: %zu names, %zu bytes of .seq.b; %u templates of %zu words)", base.c_str(), lines, o.seq.size(), DB_size - 1, words);
+		return KMAHIP_EFORMAT;
+	}
+	size_t w = 0;
+	for(uint32_t t = 1; t < DB_size; ++t) {
+		const uint32_t len = o.lens[t], rest = len & 31;
+		uint64_t last;
+		uint8_t *p = o.seq.data() + 8 * (w + (len >> 5));
+		memcpy(&last, p, 8);
+		last = rest ? last & ~(~0ull >> (2 * rest)) : 0;
+		memcpy(p, &last, 8);
+		w += ((size_t) len >> 5) + 1;
+	}
+	return KMAHIP_OK;
+}
+
+// .length.b of an appended index from whole arrays (makeindex.c:262-273): DB_size, lengths, and for a sparse index slengths, ulengths
+inline int append_write_length_b(const std::string &path, uint32_t DB_size, const std::vector<uint32_t> &lens, const std::vector<uint32_t> *slen,
+                                 const std::vector<uint32_t> *ulen) {
+	FILE *f = fopen(path.c_str(), "wb");
+	if(!f) { kmahip_set_error("cannot create %s", path.c_str()); return KMAHIP_EIO; }
+	bool ok = fwrite(&DB_size, 4, 1, f) == 1 && fwrite(lens.data(), 4, DB_size, f) == DB_size;
+	if(slen) ok = ok && fwrite(slen->data(), 4, DB_size, f) == DB_size && fwrite(ulen->data(), 4, DB_size, f) == DB_size;
+	ok = (fclose(f) == 0) && ok;
+	if(!ok) { kmahip_set_error("writing %s failed", path.c_str()); return KMAHIP_EIO; }
+	return KMAHIP_OK;
+}
+
+// the files of an append are written under <prefix>.appending<ext> and take their names at the end, all of them or none
+inline int append_commit(const std::string &tmp, const std::string &out, const std::vector<const char *> &exts, bool keep) {
+	int rc = KMAHIP_OK;
+	for(const char *e : exts) {
+		if(keep && !rc && rename((tmp + e).c_str(), (out + e).c_str())) { kmahip_set_error("cannot rename %s%s to %s%s", tmp.c_str(), e, out.c_str(), e); rc = KMAHIP_EIO; }
+		if(!keep || rc) remove((tmp + e).c_str());
+	}
+	return rc;
 }
 
 }  // namespace

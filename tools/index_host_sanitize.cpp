@@ -10,6 +10,12 @@
 #include <random>
 
 void kmahip_set_error(const char *fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc('\n', stderr); }
+// what index.hip calls in other files of the library (the homology counts, the reader of .comp.b): never reached from here
+int kmahip_hom_open(const unsigned long long *, int64_t, const int64_t *, const std::vector<uint32_t> &, int, int64_t, KmaHom **) { return KMAHIP_EDEVICE; }
+int kmahip_hom_pairs(KmaHom *, double, double, bool, std::vector<KmaHomPair> &) { return KMAHIP_EDEVICE; }
+int kmahip_hom_best(KmaHom *, const std::vector<uint8_t> &, std::vector<KmaHomRow> &) { return KMAHIP_EDEVICE; }
+void kmahip_hom_close(KmaHom *) {}
+int kmahip_comp_read(const std::string &, bool, KmaComp *) { return KMAHIP_EIO; }
 
 static bool read_file(const std::string &path, std::vector<uint8_t> &buf) {
 	FILE *f = fopen(path.c_str(), "rb");
